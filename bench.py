@@ -27,6 +27,9 @@ One JSON line on rank 0: metric/value/unit/... as the driver's contract says, pl
                 NumPy global RNG; oracle/py_ref_style.py) in P = usable CPUs processes; `c_oracle` = the
                 vectorised C oracle (OpenMP) on a working set that does not fit the last-level cache
   rccl / rccl_ranks   N > 1: whether the RCCL process group came up and what all_reduce(ones) returned
+
+--dump-outputs DIR: right after the timed passes, the arrays step_many handed back for the last timed step (rank 0) go to
+DIR/<name>.npy in float32.  Tables, actions and env draws are seeded (--seed), so the same arguments give the same arrays.
 """
 import argparse
 import gc
@@ -107,7 +110,38 @@ def parse():
     ap.add_argument("--exchange-selftest", action="store_true",
                     help="N>1 control flow (process group, watchdog, pack -> all-gather -> unpack, MAX over ranks) on "
                          "fabricated CPU records, no GPU and no stepping: a functional test, not a measurement")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="anymdp workload: after the timed passes, write what the timed path handed back for its LAST step (the "
+                         "step_many ring slot of that step: obs, reward, reward_gt, terminated, truncated, final_obs of rank 0's "
+                         "envs) as DIR/<name>.npy in float32, so that two builds can be compared output for output")
+    args = ap.parse_args()
+    if args.dump_outputs and (args.workload != "anymdp" or args.sweep_envs or args.exchange_selftest):
+        ap.error("--dump-outputs: the anymdp bench line only (not --workload mixed, --sweep-envs or --exchange-selftest)")
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    return args
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, ring, slot, seed=0):
+    """--dump-outputs: ring slot `slot` of every array of the step_many output ring (the last timed step) as
+    out_dir/<name>.npy, float32 (observations and flags are small integers: exact).  Past DUMP_MAX_BYTES in all, a fixed
+    seeded sample of the envs is written, the same for every array, and its env indices as env_index.npy (float64)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    names = sorted(ring)
+    n_env = int(ring[names[0]].shape[1])
+    idx = None
+    if len(names) * n_env * 4 > DUMP_MAX_BYTES:
+        keep = DUMP_MAX_BYTES // (len(names) * 4 + 8)
+        idx = np.sort(np.random.RandomState(seed).choice(n_env, keep, replace=False))
+        np.save(os.path.join(out_dir, "env_index.npy"), idx.astype(np.float64))
+    for k in names:
+        a = ring[k][slot].cpu().numpy().astype(np.float32)
+        np.save(os.path.join(out_dir, k + ".npy"), a if idx is None else a[idx])
+    return names
 
 
 # -----------------------------------------------------------------------------------------------------------
@@ -466,6 +500,16 @@ def init_distributed(args, torch, local, wd, cpu_only):
     return dist, info
 
 
+def rank_barrier(dist, cpu_only):
+    """dist.barrier() first looks the accelerator up (torch._C._get_accelerator: hipGetDeviceCount), which brings the HIP
+    runtime up in the calling process; the CPU-only ranks of --exchange-selftest meet through gloo's monitored_barrier
+    instead, so that they never open a GPU of the machine they run on"""
+    if cpu_only:
+        dist.monitored_barrier()
+    else:
+        dist.barrier()
+
+
 def spin_sync(torch, ev):
     """device synchronisation without the wake-up latency of a blocking wait: poll the last event, then synchronise"""
     if ev is not None:
@@ -564,7 +608,7 @@ def main():
             print(json.dumps(out), flush=True)
         if dist is not None:
             wd.arm("final barrier")
-            dist.barrier()
+            rank_barrier(dist, selftest)
             dist.destroy_process_group()
             wd.cancel()
         if selftest and rank == 0 and out.get("selftest") != "ok":
@@ -682,7 +726,7 @@ def main():
         if gpu:
             spin_sync(torch, ev)
         if dist is not None:
-            dist.barrier()
+            rank_barrier(dist, selftest)
         if gpu:
             torch.cuda.synchronize()
 
@@ -728,6 +772,8 @@ def main():
 
     # pass 1 (the reported value): sharded stepping, no data-path collective — envs are independent
     wall, ev_ms, walls = timed_pass(False, R)
+    if args.dump_outputs and env is not None and rank == 0:     # before any later pass steps the same envs into the ring
+        dump_outputs(args.dump_outputs, ring, (args.steps - 1) % P, seed=args.seed)
     state["errs"] = env.check_errors() if env is not None else 0
     state["graph"] = 0
     state["overlap"] = 0
@@ -1074,7 +1120,7 @@ def main():
         env.close()
     if dist is not None:
         wd.arm("final barrier")
-        dist.barrier()
+        rank_barrier(dist, selftest)
         dist.destroy_process_group()
         wd.cancel()
     if selftest and rank == 0 and state["selftest"] != "ok":

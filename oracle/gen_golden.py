@@ -708,9 +708,41 @@ def gen_anymdp_sampled(n=int(os.environ.get("XV_REFPOP_N", "128")), seed0=100):
     print("sampler_refpop_16x4.npz", os.path.getsize(path) // 1024, "KiB")
 
 
+def gen_anymdp_accept(seeds=(11, 12, 13)):
+    """The reference's acceptance test (check_valuefunction, solver.py:105-148) and its greedy / uniform-policy values at
+    gamma = 2^(-1/ns) on tasks of THIS project's AnyMDPTaskSampler(16, 4, seed): with the task tensors, so that a test sees
+    that the sampler still makes the very tasks the reference judged."""
+    _refimport.setup()
+    from xenoverse.anymdp.solver import check_valuefunction, update_value_matrix
+    from xenoverse_amd.anymdp import AnyMDPTaskSampler
+    out = {"seed": np.asarray(seeds, np.int64)}
+    for k, seed in enumerate(seeds):
+        task = AnyMDPTaskSampler(16, 4, seed=seed)
+        T, R = np.asarray(task["transition"], np.float64), np.asarray(task["reward"], np.float64)
+        ns, na, _ = T.shape
+        gamma = float(np.power(2, -1.0 / ns))
+        out["transition%d" % k], out["reward%d" % k] = T, R
+        out["vm_opt%d" % k] = update_value_matrix(T, R, gamma, np.zeros((ns, na)), is_greedy=True)
+        out["vm_rnd%d" % k] = update_value_matrix(T, R, gamma, np.zeros((ns, na)), is_greedy=False)
+        out["accepted%d" % k] = np.bool_(check_valuefunction(task))
+    path = os.path.join(GOLD, "sampler_accept_ref_16x4.npz")
+    np.savez_compressed(path, **out)
+    print("sampler_accept_ref_16x4.npz", os.path.getsize(path) // 1024, "KiB")
+
+
+def gen_maze_texture_names():
+    """The file names of the reference's texture folder (xenoverse/mazeworld/envs/img; names only, no image): what its
+    task sampler's library sizes follow from (37 wall*, 29 ground*, 21 ceiling*)."""
+    names = sorted(os.listdir(os.path.join(_refimport.REF_ROOT, "xenoverse", "mazeworld", "envs", "img")))
+    path = os.path.join(GOLD, "sampler_reftexture_names.npz")
+    np.savez_compressed(path, names=np.asarray(names))
+    print("sampler_reftexture_names.npz", len(names), "names")
+
+
 FAMILIES = {"anymdp": gen_anymdp, "linds": gen_linds, "maze": gen_maze, "acrobot": gen_acrobot, "garnet": gen_garnet,
             "anymdp_vi": gen_anymdp_vi, "anymdp_sampled": gen_anymdp_sampled, "maze_sampled": gen_maze_sampled,
-            "linds_sampled": gen_linds_sampled, "maze_agent": gen_maze_agent, "maze_refcounts": gen_maze_refcounts}
+            "linds_sampled": gen_linds_sampled, "maze_agent": gen_maze_agent, "maze_refcounts": gen_maze_refcounts,
+            "anymdp_accept": gen_anymdp_accept, "maze_texture_names": gen_maze_texture_names}
 
 if __name__ == "__main__":
     os.makedirs(GOLD, exist_ok=True)

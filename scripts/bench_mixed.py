@@ -180,8 +180,8 @@ def _run_mixed(args, torch, dist, dinfo, rank, world, local, wd, selftest, scale
     def barrier():
         if gpu:
             torch.cuda.synchronize()
-        if dist is not None:
-            dist.barrier()
+        if dist is not None:      # (CPU-only ranks: monitored_barrier, which does not bring up the HIP runtime; bench.rank_barrier)
+            dist.barrier() if gpu else dist.monitored_barrier()
         if gpu:
             torch.cuda.synchronize()
 

@@ -161,7 +161,7 @@ def _worker(rank, world, port, n_total, T, q, uneven=None):
         t = torch.tensor([float(rank + 1)], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         q.put((rank, ok, float(t[0])))
-        dist.barrier()
+        dist.monitored_barrier()      # (dist.barrier() would bring up the HIP runtime in every rank: bench.rank_barrier)
     finally:
         dist.destroy_process_group()
 

@@ -66,3 +66,24 @@ def test_bench_line_shared_tasks_claims_no_hbm_fraction():
     assert d["roofline"]["traffic_live"] is None
     assert d["roofline"]["bound"] == "cache" and d["roofline"]["frac"] is None and d["roofline"]["frac_survey_bytes"] > 0
     assert "long_call" not in d
+
+
+def test_dump_outputs_are_the_last_timed_step_and_repeat_run_to_run(tmp_path):
+    """--dump-outputs: the step_many ring slot of the last timed step, float32, one value per env; the same arguments give
+    the same arrays (seeded tables, actions and draws), which is what lets two builds be compared output for output"""
+    import numpy as np
+    quick = ["--no-cpu-baseline", "--no-live-pmc", "--long-steps", "0", "--no-variants", "--sustain-seconds", "0"]
+    got = []
+    for d in ("a", "b"):
+        line = _line(quick + ["--dump-outputs", str(tmp_path / d)])
+        assert line["steps"] == 20 and line["ms_per_step"] > 0
+        got.append({f[:-4]: np.load(tmp_path / d / f) for f in os.listdir(tmp_path / d)})
+    a, b = got
+    assert sorted(a) == ["final_obs", "obs", "reward", "reward_gt", "terminated", "truncated"]
+    for k in a:
+        assert a[k].dtype == np.float32 and a[k].shape == (4096,), k
+        assert np.array_equal(a[k], b[k]), k
+    assert a["obs"].min() >= 0 and a["obs"].max() < 64 and np.all(a["obs"] == np.round(a["obs"]))
+    assert set(np.unique(a["terminated"])) <= {0.0, 1.0} and set(np.unique(a["truncated"])) <= {0.0, 1.0}
+    assert np.all(np.isfinite(a["reward"])) and np.all(np.isfinite(a["reward_gt"]))
+    assert np.all((a["final_obs"] == -1) | ((a["terminated"] + a["truncated"]) > 0))

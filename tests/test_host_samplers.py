@@ -251,31 +251,35 @@ def test_seeded_sampler_reproduces_32_reference_sampled_tasks():
 
 
 def test_acceptance_rule_agrees_with_reference_when_available():
-    """container-only cross-check: the reference's check_valuefunction and value iteration vs this restatement"""
-    import os
-    import pickle
-    import sys
-    import pytest
-    cache = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_cache")
-    if not (os.path.isdir("/root/reference/xenoverse") and os.path.isdir(cache)):
-        pytest.skip("reference tree / sampled-task cache not present (build container only)")
-    sys.path.insert(0, os.path.join(os.path.dirname(cache)))
-    import _refimport
-    _refimport.setup()
-    from xenoverse.anymdp.solver import check_valuefunction, update_value_matrix
+    """the reference's check_valuefunction and value iteration vs this restatement, on the reference's stored results
+    (oracle/gen_golden.py anymdp, anymdp_vi, anymdp_accept): every task the reference sampled passes check_task here,
+    value_iteration agrees with its update_value_matrix, and the tasks sampled here are the ones its own test accepted"""
     from xenoverse_amd.anymdp import AnyMDPTaskSampler
     from xenoverse_amd.anymdp.task_sampler import check_task, value_iteration
-    for f in sorted(os.listdir(cache)):
-        if "mdp_16_4" not in f:
-            continue
-        task = pickle.load(open(os.path.join(cache, f), "rb"))
-        assert check_task(task)                       # every task the reference accepted passes here too
-        gamma = 2.0 ** (-1.0 / 16)
-        q_ref = update_value_matrix(task["transition"], task["reward"], gamma, np.zeros((16, task["na"])))
-        q = value_iteration(task["transition"], task["reward"], gamma)
-        assert np.max(np.abs(q - q_ref)) < 5e-3 * (1 + np.abs(q_ref).max())
-    mine = AnyMDPTaskSampler(16, 4, seed=11)
-    assert check_valuefunction(mine)                  # and a task sampled here passes the reference's own test
+    gold = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+    gamma = 2.0 ** (-1.0 / 16)
+    vi = np.load(os.path.join(gold, "sampler_vi_ref.npz"))
+    for seed in range(4):
+        g = np.load(os.path.join(gold, "anymdp_16x4_seed%d.npz" % seed))
+        task = {k: g[k] for k in ("transition", "reward", "max_steps", "s_0", "s_0_prob", "s_e")}
+        assert check_task(task), seed                 # every task the reference accepted passes here too
+        if seed in (0, 2):                            # the reference's update_value_matrix at check_valuefunction's gamma
+            assert np.array_equal(vi["T%d" % seed], task["transition"])
+            assert vi["gamma%d" % seed][1] == gamma
+            q_ref = vi["vm_s%d_g1_1" % seed]
+            q = value_iteration(task["transition"], task["reward"], gamma)
+            assert np.max(np.abs(q - q_ref)) < 5e-3 * (1 + np.abs(q_ref).max())
+    acc = np.load(os.path.join(gold, "sampler_accept_ref_16x4.npz"))
+    for k, seed in enumerate(acc["seed"]):
+        mine = AnyMDPTaskSampler(16, 4, seed=int(seed))
+        T, R = np.asarray(mine["transition"], np.float64), np.asarray(mine["reward"], np.float64)
+        assert _same(T, acc["transition%d" % k], False) and _same(R, acc["reward%d" % k], False), seed
+        assert bool(acc["accepted%d" % k]), seed     # and a task sampled here passes the reference's own test
+        assert check_task(mine), seed
+        for key, greedy in (("vm_opt", True), ("vm_rnd", False)):
+            q_ref = acc["%s%d" % (key, k)]
+            q = value_iteration(T, R, gamma, greedy=greedy)
+            assert np.max(np.abs(q - q_ref)) < 5e-3 * (1 + np.abs(q_ref).max()), (seed, key)
 
 
 def test_sample_batch_returns_stacked_tables():
@@ -420,9 +424,16 @@ def test_load_texture_library_reads_a_folder_like_the_reference(tmp_path):
     (tmp_path / "sub").mkdir()
     with pytest.raises(ValueError, match="no wall"):
         load_texture_library(str(tmp_path / "sub"))
-    ref_dir = "/root/reference/xenoverse/mazeworld/envs/img"
-    if os.path.isdir(ref_dir):                                      # build container only: the reference's own folder
-        assert texture_counts(load_texture_library(ref_dir)) == (37, 29, 21)
+    # the reference's own folder, by its file names (tests/golden/sampler_reftexture_names.npz; the images are not kept)
+    ref_dir = tmp_path / "ref"
+    ref_dir.mkdir()
+    blank = Image.fromarray(np.zeros((256, 256, 3), np.uint8))
+    for name in np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "sampler_reftexture_names.npz"))["names"]:
+        if str(name).startswith(("wall", "ground", "ceiling")):
+            blank.save(ref_dir / str(name))
+        else:                                                       # (.DS_Store, .gitattributes: not read)
+            (ref_dir / str(name)).write_bytes(b"")
+    assert texture_counts(load_texture_library(str(ref_dir))) == (37, 29, 21)
 
 
 def test_texture_libraries_of_another_size_are_refused_or_resampled(tmp_path):
