@@ -571,6 +571,46 @@ int xv_linds_rollout(xv_linds* h, int T, const float* action, float* obs, float*
 int xv_linds_get_state(xv_linds* h, float* x, int32_t* steps, uint8_t* need_reset);
 int xv_linds_set_state(xv_linds* h, const float* x, const int32_t* steps, const uint8_t* need_reset);
 
+/* LinDS MPC teacher — reference: xenoverse/linds/solver.py LTISystemMPC
+ *   __init__ / _pre_build_matrices :20-92 -> xv_linds_mpc_create (the QP data built on the host in fp64:
+ *                                           xenoverse_amd/linds/teacher.py device_tables)
+ *   solve :94-125                         -> xv_linds_mpc_solve (explicit x, ref), xv_linds_mpc_action (x = the env's
+ *                                           state, ref = get_future_inner_cmds(K), as test_mpc :127-150 drives it)
+ *   test_mpc's loop :138-157              -> xv_linds_rollout_mpc
+ * The reference hands the QP min 1/2 U^T P U + q^T U, -1 <= U <= 1 (U = [u_0; ...; u_{K-1}], n = K * action_dim) to OSQP;
+ * the device runs OSQP's ADMM (A = I) per env with a per-task rho and operator M = (P + (sigma + rho) I)^-1 and freezes an
+ * env once its residuals pass (checked every 10 iterations), so an env's result depends on its own (task, x, ref) only.
+ * U rows are U[k * Nu + a] of the task's action_dim Nu, zero past n; the action is u_0 zero-padded to NA.  status: 1
+ * converged, 0 stopped at max_iter (the returned U is the projected iterate either way, so always feasible).  n <= 512
+ * (XV_ERR_UNSUPPORTED beyond).  The handle keeps its own device copies of the tables; it refers to the xv_linds handle,
+ * which must outlive it. */
+typedef struct xv_linds_mpc xv_linds_mpc;
+typedef struct xv_linds_mpc_tables {
+  int n_pad;                /* max over tasks of K * action_dim, rounded up to 16 */
+  int n_in;                 /* NS + K * NOc rounded up to 16: rows of the input w = [x; vec(ref)] */
+  int NOc;                  /* command columns read (multiple of 4, <= NO) */
+  const float* mfrag;       /* [n_task][n_pad/16][n_pad/16][64][4]  M in v_mfma_f32_16x16x4_f32 A-operand order */
+  const float* gfrag;       /* [n_task][n_pad/16][n_in/16][64][4]   [G_x | -G_r], same order */
+  const float* g0;          /* [n_task][n_pad]   q = G_x x + g_0 - G_r vec(ref) */
+  const float* rho;         /* [n_task] */
+  const float* mnorm;       /* [n_task]  |M|_inf of the fp32 operator: scales the stopping test's allowance for rounding */
+  const int32_t* nu;        /* [n_task] action_dim */
+  float sigma, alpha, eps_abs, eps_rel;
+} xv_linds_mpc_tables;
+int xv_linds_mpc_create(xv_linds* l, int K, double gamma, const xv_linds_mpc_tables* tables, int max_iter,
+                        xv_linds_mpc** out);
+int xv_linds_mpc_destroy(xv_linds_mpc* m);
+/* action float[n_env][NA] for the current state, without stepping; U float[n_env][n_pad] (the whole plan), status / iters
+ * int32[n_env]: nullable */
+int xv_linds_mpc_action(xv_linds_mpc* m, float* action, float* U, int32_t* status, int32_t* iters);
+/* x float[n_env][NS], ref float[n_env][K][NO] (ref[j] is the command tracked j steps ahead) -> U float[n_env][n_pad] */
+int xv_linds_mpc_solve(xv_linds_mpc* m, const float* x, const float* ref, float* U, int32_t* status, int32_t* iters);
+/* T x (xv_linds_mpc_action, xv_linds_step) with SAME_STEP auto-reset, issued from C: the outputs of xv_linds_rollout
+ * ([T][n_env](...), cmd and error required, final_obs nullable) plus action float[T][n_env][NA], status / iters int32[T][n_env]
+ * (nullable); equals T such pairs of calls bit for bit. */
+int xv_linds_rollout_mpc(xv_linds_mpc* m, int T, float* action, float* obs, float* reward, uint8_t* terminated,
+                         uint8_t* truncated, float* cmd, float* error, float* final_obs, int32_t* status, int32_t* iters);
+
 /* ------------------------------------------------------------------------------------------------
  * CartPole — reference: xenoverse/metacontrol/random_cartpole.py (set_task :46-50, step :52-61, reset
  * :63-75).  The physics is gymnasium's CartPoleEnv.step (third-party dependency, `gymnasium>=1.0.0` in the

@@ -98,6 +98,11 @@ SIGNATURES = {
     "xv_linds_rollout": [c_void_p, c_int] + [c_void_p] * 8,
     "xv_linds_get_state": [c_void_p, c_void_p, c_void_p, c_void_p],
     "xv_linds_set_state": [c_void_p, c_void_p, c_void_p, c_void_p],
+    "xv_linds_mpc_create": [c_void_p, c_int, C.c_double, c_void_p, c_int, C.POINTER(c_void_p)],
+    "xv_linds_mpc_destroy": [c_void_p],
+    "xv_linds_mpc_action": [c_void_p] * 5,
+    "xv_linds_mpc_solve": [c_void_p] + [c_void_p] * 5,
+    "xv_linds_rollout_mpc": [c_void_p, c_int] + [c_void_p] * 10,
     "xv_cartpole_create": [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, C.POINTER(c_void_p)],
     "xv_cartpole_destroy": [c_void_p],
     "xv_cartpole_reset": [c_void_p, c_void_p, c_void_p],

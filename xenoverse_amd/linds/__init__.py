@@ -2,3 +2,4 @@
 from .tables import build_dynamics_matrices, build_tables  # noqa: F401
 from .vec_env import LinDSVecEnv, pad_tables  # noqa: F401
 from .task_sampler import LinearDSSampler, LinearDSSamplerRandomDim, RandomFourier  # noqa: F401
+from .teacher import LTISystemMPC  # noqa: F401

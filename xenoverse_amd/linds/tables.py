@@ -59,6 +59,7 @@ def build_tables(tasks, dt=0.1, pad_observation_dim=16, pad_action_dim=8, pad_co
     scal = np.zeros((n_task, 8), np.float32)
     ints = np.zeros((n_task, 4), np.int32)
     init = np.zeros((n_task, NI, NS), np.float32)
+    action_dims = np.zeros(n_task, np.int32)      # host only (the MPC teacher's n = K * action_dim)
     for i, t in enumerate(tasks):
         ns, na, no = int(t["state_dim"]), int(t["action_dim"]), int(t["observation_dim"])
         phi, gam, xdt = build_dynamics_matrices(np.asarray(t["ld_A"], np.float64), np.asarray(t["ld_B"], np.float64),
@@ -86,8 +87,9 @@ def build_tables(tasks, dt=0.1, pad_observation_dim=16, pad_action_dim=8, pad_co
         scal[i, :6] = [t["action_cost"], t["reward_base"], t["terminate_punish"], t["reward_factor"],
                        float(t["noise_drift"]) * dt, dt]
         ints[i] = [int(t["max_steps"]), int(t["target_delay"]), len(t["initial_states"]), n_terms]
+        action_dims[i] = na
         for k, x0 in enumerate(t["initial_states"]):
             init[i, k, :ns] = np.asarray(x0, np.float64)
     return dict(NS=NS, NA=NA, NO=NO, NI=NI, dt=float(dt), phiT=phiT, gamT=gamT, cT=cT, xt=xt, y0=y0, valid=valid,
                 cmd0=cmd0, four_coef=four_coef, four_omega=four_omega, four_period=four_period, scal=scal,
-                ints=ints, init=init)
+                ints=ints, init=init, action_dims=action_dims)

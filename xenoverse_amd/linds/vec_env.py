@@ -25,6 +25,12 @@ class _Tables(C.Structure):   # xv_linds_tables (include/xeno.h)
                                           "four_omega", "four_period", "scal", "ints", "init")]
 
 
+class _MPCTables(C.Structure):   # xv_linds_mpc_tables (include/xeno.h)
+    _fields_ = [("n_pad", C.c_int), ("n_in", C.c_int), ("NOc", C.c_int)] + \
+        [(k, C.c_void_p) for k in ("mfrag", "gfrag", "g0", "rho", "mnorm", "nu")] + \
+        [(k, C.c_float) for k in ("sigma", "alpha", "eps_abs", "eps_rel")]
+
+
 def _pad_to(n, choices):
     for c in choices:
         if n <= c:
@@ -73,9 +79,13 @@ class LinDSVecEnv(VectorEnv):
 
     def set_task(self, tasks, env_task_index=None):
         """tasks: one reference task dict, a list of them, or prebuilt tables (linds.tables.build_tables)."""
+        self._drop_mpc()
         if isinstance(tasks, dict) and "phiT" in tasks:
             tab = tasks
+            self._mpc_src = None if any(torch.is_tensor(tab[k]) for k in ("phiT", "gamT", "cT", "xt", "y0", "valid", "scal")) \
+                else tab
         else:
+            self._mpc_src = [tasks] if isinstance(tasks, dict) else list(tasks)
             tab = build_tables(tasks, dt=self.dt, pad_observation_dim=self.pad_observation_dim,
                                pad_action_dim=self.pad_action_dim, pad_command_dim=self.pad_command_dim)
         self.user_dims = (int(tab["NA"]), int(tab["NO"]))
@@ -446,7 +456,108 @@ class LinDSVecEnv(VectorEnv):
         self.engine.sync()
         self.need_reset = False
 
+    # -- MPC teacher (linds/teacher.py, csrc/linds_mpc.hip) --------------------------------------------
+    MPC_MAX_ITER = 4000
+
+    def mpc_models(self):
+        """the fp64 LTI model of every task (linds.teacher._Model): from the task dicts given to set_task, or from host
+        tables (their fp32 values)"""
+        from . import teacher
+        src = getattr(self, "_mpc_src", None)
+        if src is None:
+            raise ValueError("the MPC teacher needs the task dicts or host (numpy) tables given to set_task")
+        if isinstance(src, dict):
+            return [teacher.model_from_tables(src, t) for t in range(self.n_task)]
+        memo = {}      # a task dict repeated over many task indices is discretised once
+        for t in src:
+            if id(t) not in memo:
+                memo[id(t)] = teacher.model_from_task(t, dt=self.dt, pad_action_dim=self.pad_action_dim)
+        return [memo[id(t)] for t in src]
+
+    def _drop_mpc(self):
+        c = getattr(self, "_mpc_cache", None)
+        if c is not None and getattr(self, "lib", None) is not None:
+            self.lib.xv_linds_mpc_destroy(c[1])
+        self._mpc_cache = None
+
+    def _mpc(self, K, gamma, max_iter=None):
+        """the device teacher's handle for (K, gamma), built once per set_task (cached like AnyMDP's greedy table)"""
+        from . import teacher
+        max_iter = self.MPC_MAX_ITER if max_iter is None else int(max_iter)
+        key = (id(self._tab), int(K), float(gamma), max_iter)
+        c = getattr(self, "_mpc_cache", None)
+        if c is not None and c[0] == key:
+            return c[1], c[2]
+        self._drop_mpc()
+        dt = teacher.device_tables(self.mpc_models(), K, gamma, self.NS, self.NO)
+        ct = _MPCTables(dt["n_pad"], dt["n_in"], dt["NOc"], dt["mfrag"].ctypes.data, dt["gfrag"].ctypes.data,
+                        dt["g0"].ctypes.data, dt["rho"].ctypes.data, dt["mnorm"].ctypes.data, dt["nu"].ctypes.data, teacher.SIGMA, teacher.ALPHA,
+                        teacher.EPS_ABS, teacher.EPS_REL)
+        h = C.c_void_p()
+        _lib.check(self.lib.xv_linds_mpc_create(self._h, int(K), float(gamma), C.byref(ct), max_iter, C.byref(h)))
+        info = dict(n_pad=dt["n_pad"], n_in=dt["n_in"], NOc=dt["NOc"], nu=dt["nu"], rho=dt["rho"])
+        self._mpc_cache = (key, h, info)
+        return h, info
+
+    def mpc_action(self, K=20, gamma=0.99, return_info=False, max_iter=None):
+        """The reference's MPC teacher (LTISystemMPC(env, K, gamma).solve(env.state, env.get_future_inner_cmds(K)),
+        xenoverse/linds/solver.py:94-125) for every env, on the device, without stepping: float32[N, action_dim]
+        (+ dict(status=int32[N] 1 converged / 0 max_iter, iters=int32[N], U=float32[N, n_pad] the whole plan U[k * Nu + a])
+        with return_info)."""
+        self._check_step()
+        h, info = self._mpc(K, gamma, max_iter)
+        n, d = self.num_envs, self.device
+        a = torch.empty((n, self.NA), dtype=torch.float32, device=d)
+        st = torch.empty(n, dtype=torch.int32, device=d)
+        it = torch.empty(n, dtype=torch.int32, device=d)
+        U = torch.empty((n, info["n_pad"]), dtype=torch.float32, device=d) if return_info else None
+        _lib.check(self.lib.xv_linds_mpc_action(h, _lib.ptr(a), _lib.ptr(U), _lib.ptr(st), _lib.ptr(it)))
+        a = a[:, :self.user_dims[0]]
+        return (a, dict(status=st, iters=it, U=U)) if return_info else a
+
+    def mpc_solve(self, x, ref, K=20, gamma=0.99, max_iter=None):
+        """Parity hook (xv_linds_mpc_solve): x float[N, <=NS], ref float[N, K, <=NO] -> (U float32[N, n_pad] with
+        U[k * Nu + a], status int32[N], iters int32[N]) for each env's task"""
+        self._require_task()
+        h, _ = self._mpc(K, gamma, max_iter)
+        n, d = self.num_envs, self.device
+        xs = torch.zeros((n, self.NS), dtype=torch.float32, device=d)
+        xi = self._dev(x, torch.float32)
+        xs[:, :xi.shape[1]] = xi
+        rs = torch.zeros((n, K, self.NO), dtype=torch.float32, device=d)
+        ri = self._dev(ref, torch.float32)
+        rs[:, :, :ri.shape[2]] = ri
+        info = self._mpc_cache[2]
+        U = torch.empty((n, info["n_pad"]), dtype=torch.float32, device=d)
+        st = torch.empty(n, dtype=torch.int32, device=d)
+        it = torch.empty(n, dtype=torch.int32, device=d)
+        _lib.check(self.lib.xv_linds_mpc_solve(h, _lib.ptr(xs), _lib.ptr(rs), _lib.ptr(U), _lib.ptr(st), _lib.ptr(it)))
+        return U, st, it
+
+    def rollout_teacher(self, T, K=20, gamma=0.99, max_iter=None):
+        """T steps driven by the device MPC teacher (xv_linds_rollout_mpc), SAME_STEP auto-reset: dict of [T, N(, ...)]
+        device tensors — the outputs of rollout() plus "action" [T, N, NA], "status" and "iters" [T, N].  Equals T x
+        (mpc_action(K, gamma) + step) bit for bit."""
+        self._check_step()
+        T = int(T)
+        h, _ = self._mpc(K, gamma, max_iter)
+        d, n = self.device, self.num_envs
+        out = dict(action=torch.empty((T, n, self.NA), dtype=torch.float32, device=d),
+                   obs=torch.empty((T, n, self.NO), dtype=torch.float32, device=d),
+                   reward=torch.empty((T, n), dtype=torch.float32, device=d),
+                   terminated=torch.empty((T, n), dtype=torch.uint8, device=d),
+                   truncated=torch.empty((T, n), dtype=torch.uint8, device=d),
+                   command=torch.empty((T, n, self.NO), dtype=torch.float32, device=d),
+                   error=torch.empty((T, n), dtype=torch.float32, device=d),
+                   final_obs=torch.zeros((T, n, self.NO), dtype=torch.float32, device=d),
+                   status=torch.empty((T, n), dtype=torch.int32, device=d),
+                   iters=torch.empty((T, n), dtype=torch.int32, device=d))
+        _lib.check(self.lib.xv_linds_rollout_mpc(h, T, *[_lib.ptr(out[k]) for k in (
+            "action", "obs", "reward", "terminated", "truncated", "command", "error", "final_obs", "status", "iters")]))
+        return out
+
     def close_extras(self, **kwargs):
+        self._drop_mpc()
         if self._h is not None:
             self.lib.xv_linds_destroy(self._h)
             self._h = None
