@@ -413,6 +413,32 @@ int xv_anymdp_rollout_teacher(xv_anymdp* h, int T, const uint8_t* greedy, float 
                               int32_t* obs, float* reward, float* reward_gt, uint8_t* terminated,
                               uint8_t* truncated, int32_t* final_obs);
 
+/* AnyMDP Q-learning agents — reference: xenoverse/anymdp/anymdp_solver_q.py AnyMDPSolverQ, driven by the training loop of
+ * anymdp/test_utils.py (epoch_run :42-60), one agent per env of an MDP handle, in fp64 (xenoverse_amd/anymdp/qlearner.py)
+ *   __init__ :8-27   -> xv_anymdp_qlearn_create / xv_anymdp_qlearn_reset (Q = 1 / (1 - gamma), visit counts 1)
+ *   learner :30-49, policy :51-59 -> xv_anymdp_rollout_qlearn
+ * Agent state on the device: Q double[n_env][S][A] (rows indexed by observation id), sa_visits uint32[n_env][S][A],
+ * s_visits uint32[n_env][S].  The learner learns from the step's fp32 reward widened to fp64 (the reference's is fp64).
+ * create: XV_ERR_UNSUPPORTED for POMDP / multi-token handles (the reference asserts task_type == "MDP", :17), for views and
+ * for observation ids >= S; XV_ERR_NOMEM when the tables do not fit.  max_steps (M) is the learner's constant of the lr and
+ * stiffness schedules, not the env's.  get / set_state copy device arrays (each nullable) on the engine's stream.  A learner
+ * borrows its xv_anymdp handle: destroy the learner first (destroy synchronises the handle's stream). */
+typedef struct xv_anymdp_qlearn xv_anymdp_qlearn;
+int xv_anymdp_qlearn_create(xv_anymdp* h, double gamma, double alpha, int max_steps, xv_anymdp_qlearn** out);
+int xv_anymdp_qlearn_destroy(xv_anymdp_qlearn* ql);
+int xv_anymdp_qlearn_reset(xv_anymdp_qlearn* ql, const uint8_t* mask);   /* mask uint8[n_env] or nullptr (all) */
+int xv_anymdp_qlearn_get_state(xv_anymdp_qlearn* ql, double* q, uint32_t* sa_visits, uint32_t* s_visits);
+int xv_anymdp_qlearn_set_state(xv_anymdp_qlearn* ql, const double* q, const uint32_t* sa_visits, const uint32_t* s_visits);
+/* T steps of [policy -> step (SAME_STEP auto-reset) -> learner] for every env, issued from C: the first action is chosen
+ * from the env's current observation, whatever produced it.  greedy != 0: argmax actions (is_test epochs; the learner still
+ * learns).  Draws: u (transition uniforms), z (reward normals), u_reset [T][n_env] all given (xv_anymdp_step_injected per
+ * step) or all nullptr (Philox); u_policy [T][n_env] the policy's uniforms, given exactly when u is (ignored when greedy).
+ * Free-running policy draws are keyed by (seed, global env id, launch tick of the step that takes the action): splitting T
+ * over calls changes nothing.  Outputs [T][n_env] in the layout of xv_anymdp_rollout_teacher; all required. */
+int xv_anymdp_rollout_qlearn(xv_anymdp* h, xv_anymdp_qlearn* ql, int T, int greedy, const double* u_policy, const double* u,
+                             const float* z, const double* u_reset, int32_t* action_out, int32_t* obs, float* reward,
+                             float* reward_gt, uint8_t* terminated, uint8_t* truncated, int32_t* final_obs);
+
 /* Value iteration for every task of the handle, one workgroup per task (the reference's ground-truth teacher,
  * anymdp_solver_opt.py:30-51, for whole task batches): synchronous sweeps
  *   Q[s,a] <- sum_s' T[s,a,s'] (R[s,a,s'] + gamma max_a' Q[s',a'])   until rms(Q_new - Q) <= tol or max_iter sweeps,

@@ -4,3 +4,4 @@ from .vec_env import AnyMDPVecEnv  # noqa: F401
 from .task_sampler import (AnyMDPTaskSampler, AnyPOMDPTaskSampler, GarnetTaskSampler,  # noqa: F401
                            MultiTokensAnyPOMDPTaskSampler)
 from .device_sampler import sample_tasks_device  # noqa: F401,E402
+from .qlearner import AnyMDPQLearner, QLearnerHost  # noqa: F401,E402

@@ -5,6 +5,7 @@ reset :81-90, step :112-132, properties :134-165) behind gymnasium's VectorEnv s
 same exception types/messages for misuse, same info keys (`steps`, `reward_gt`, optional `transition_gt`).
 """
 import ctypes as C
+import weakref
 
 import numpy as np
 import torch
@@ -56,6 +57,7 @@ class AnyMDPVecEnv(VectorEnv):
         self._many_cache = None
         self._tab = None
         self._views = []            # sub-batch envs made by split(): they borrow this env's tables
+        self._learners = weakref.WeakSet()   # AnyMDPQLearner objects on this env's handle
         self._parent = None
 
     # ---- set_task ---------------------------------------------------------------------------------
@@ -118,6 +120,7 @@ class AnyMDPVecEnv(VectorEnv):
         if self._parent is not None:
             raise ValueError("set_task on a sub-batch made by split(): set the task on the env it was split from")
         self._drop_views()
+        self._release_learners("AnyMDPQLearner: its env was given new tasks; make a new learner")
         if self._h is not None:
             self.lib.xv_anymdp_destroy(self._h)
             self._h = None
@@ -570,6 +573,51 @@ class AnyMDPVecEnv(VectorEnv):
         self.engine.sync()
         return out
 
+    _DRAW_KEYS = ("u_policy", "u", "z", "u_reset")
+
+    def rollout_learner(self, learner, T, greedy=False, draws=None):
+        """T steps of the reference's training loop (anymdp/test_utils.py: epoch_run :42-60) for every env at once, on the
+        device: action = learner's policy(obs) -> step -> learner.learner(s, a, ns, r, terminated, truncated), SAME_STEP
+        auto-reset, starting from the env's current observation.  learner: an AnyMDPQLearner of this env.  greedy: argmax
+        actions (the reference's is_test epochs; the agents still learn).  draws: None (Philox) or a dict of [T, N] arrays
+        u_policy (float64, the policy's uniforms), u (float64), z (float32), u_reset (float64) — the step's draws as in
+        step_injected.  -> dict of [T, N] device tensors in rollout_teacher's layout ("action" included)."""
+        self._check_step()
+        if self._parent is not None:
+            raise ValueError("rollout_learner on a sub-batch made by split(): roll the env it was split from")
+        if self.autoreset_mode != "same_step":
+            raise ValueError("rollout_learner needs autoreset_mode='same_step' (got %r)" % (self.autoreset_mode,))
+        if getattr(learner, "env", None) is not self:
+            raise ValueError("rollout_learner: the learner belongs to another env")
+        learner._live()
+        T, n, d = int(T), self.num_envs, self.device
+        if T < 1:
+            raise ValueError("rollout_learner: T must be >= 1")
+        dr = [None] * 4
+        if draws is not None:
+            dts = dict(u_policy=torch.float64, u=torch.float64, z=torch.float32, u_reset=torch.float64)
+            for j, k in enumerate(self._DRAW_KEYS):
+                if k == "u_policy" and greedy and draws.get(k) is None:
+                    continue
+                if draws.get(k) is None:
+                    raise ValueError("rollout_learner: draws[%r] missing" % k)
+                dr[j] = self._dev(draws[k], dts[k])
+                if tuple(dr[j].shape) != (T, n):
+                    raise ValueError("rollout_learner: draws[%r] has shape %s, expected %s" % (k, tuple(dr[j].shape), (T, n)))
+        out = dict(action=torch.empty((T, n), dtype=torch.int32, device=d),
+                   obs=torch.empty((T, n), dtype=torch.int32, device=d),
+                   reward=torch.empty((T, n), dtype=torch.float32, device=d),
+                   reward_gt=torch.empty((T, n), dtype=torch.float32, device=d),
+                   terminated=torch.empty((T, n), dtype=torch.uint8, device=d),
+                   truncated=torch.empty((T, n), dtype=torch.uint8, device=d),
+                   final_obs=torch.empty((T, n), dtype=torch.int32, device=d))
+        _lib.check(self.lib.xv_anymdp_rollout_qlearn(
+            self._h, learner._h, T, 1 if greedy else 0, *(_lib.ptr(x) for x in dr), _lib.ptr(out["action"]),
+            _lib.ptr(out["obs"]), _lib.ptr(out["reward"]), _lib.ptr(out["reward_gt"]), _lib.ptr(out["terminated"]),
+            _lib.ptr(out["truncated"]), _lib.ptr(out["final_obs"])))
+        self.engine.sync()
+        return out
+
     _MANY_KEYS = ("obs", "reward", "reward_gt", "terminated", "truncated", "final_obs")
 
     def step_many(self, n_steps, actions, out=None, chains=1, how="streams"):
@@ -792,8 +840,15 @@ class AnyMDPVecEnv(VectorEnv):
         self.engine.sync()   # the temporaries above must outlive the copies
         self.need_reset = False
 
+    def _release_learners(self, why):
+        """the learners borrow this env's handle: they go first (their device tables are freed, later use raises `why`)"""
+        for ql in list(self._learners):
+            ql.close(why)
+        self._learners = weakref.WeakSet()
+
     def close_extras(self, **kwargs):
         self._drop_views()
+        self._release_learners("AnyMDPQLearner: its env was closed")
         if self._h is not None:
             self.lib.xv_anymdp_destroy(self._h)
             self._h = None
