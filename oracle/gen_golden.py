@@ -424,6 +424,104 @@ def gen_maze():
         gen_maze_one("maze_15_seed%d" % k, task, max_steps=(5000 if k else 230), seed0=100 + k)
 
 
+RAYCAST_REF_SIZES = ((256, 256), (320, 320), (320, 200), (200, 320), (40, 72), (72, 40))
+RAYCAST_REF_CIO = ((40, 72), (72, 40))       # command bar clipped by the frame: whole observations stored too
+
+
+def _raycast_ref_poses(k, g):
+    """the seven poses of task k (tests/golden/maze_15_seed<k>.npz): kind, pos, ori, cmd_idx"""
+    walls = g["cell_walls"]
+    cs = float(g["cell_size"])
+    n_cmd = len(g["commands_sequence"])
+    NG = walls.shape[0]
+    rng = np.random.RandomState(500 + k)
+    cells = [(i, j) for i in range(1, NG - 1) for j in range(1, NG - 1) if walls[i, j] == 0]
+    cells = [cells[q] for q in rng.permutation(len(cells))]
+    out = []
+    for t in (45, 171):                                   # recorded poses
+        out.append(("recorded_%d" % t, g["tr_pos"][t], float(g["tr_ori"][t]), int(g["tr_cmd_idx"][t])))
+    s = g["start"]
+    p = [(s[0] + 0.5 + 0.23) * cs, (s[1] + 0.5 - 0.17) * cs]
+    out.append(("ori_0", p, 0.0, int(rng.randint(n_cmd))))            # axis-parallel rays
+    out.append(("ori_half_pi", p, np.pi / 2, int(rng.randint(n_cmd))))
+    i, j = next((i, j) for i, j in cells if walls[i - 1, j] == 0)
+    out.append(("cell_boundary", [i * cs, (j + 0.37) * cs], 0.6 + 0.9 * k, int(rng.randint(n_cmd))))
+    # 0.05 cell from a wall, facing it (+x, +y, -x for the three tasks): the wall texture magnified
+    d = [(1, 0, 0.0), (0, 1, np.pi / 2), (-1, 0, np.pi)][k % 3]
+    i, j = next((i, j) for i, j in cells if walls[i + d[0], j + d[1]] != 0)
+    q = [(i + 0.5 + 0.45 * d[0]) * cs, (j + 0.5 + 0.45 * d[1]) * cs]
+    out.append(("near_wall", q, d[2] + 0.07, int(rng.randint(n_cmd))))
+    # one cell away from a landmark, facing it (a little off axis)
+    lm = g["cell_landmarks"]
+    found = None
+    for (a, b) in zip(*np.nonzero(lm >= 0)):
+        for dx, dy, ang in ((-1, 0, 0.0), (1, 0, np.pi), (0, -1, np.pi / 2), (0, 1, -np.pi / 2)):
+            if walls[a + dx, b + dy] == 0:
+                found = ([(a + dx + 0.5) * cs, (b + dy + 0.5) * cs], ang + 0.21)
+                break
+        if found:
+            break
+    out.append(("landmark", found[0], found[1], int(rng.randint(n_cmd))))
+    return [(kind, np.asarray(pp, np.float64), float(o), c) for kind, pp, o, c in out]
+
+
+def _raycast_ref_one(args):
+    """maze_view frames (and, at the clipped sizes, whole observations with the command bar) of one task at one size"""
+    k, W, H = args
+    Maze, mts, dyn, rc = _refimport.mazeworld()
+    M = mts.MAZE_TASK_MANAGER
+    g = dict(np.load(os.path.join(GOLD, "maze_15_seed%d.npz" % k)))
+    task = mts.MazeTaskSampler(n_range=(15, 16), seed=k, verbose=False)
+    assert np.array_equal(np.asarray(task["cell_walls"]), g["cell_walls"])
+    poses = _raycast_ref_poses(k, g)
+    frames = np.zeros((len(poses), W, H, 3), np.uint8)
+    for q, (kind, p, o, c) in enumerate(poses):
+        img, _ = rc.maze_view(np.array(p, dtype=np.float32), o, task["agent_height"], task["cell_walls"],
+                              task["cell_landmarks"], task["cell_texts"], task["cell_size"], M.textlib_walls,
+                              M.textlib_grounds[task["ground_text"]], M.textlib_ceilings[task["ceiling_text"]],
+                              task["wall_height"], 1.0, 12.0, 0.20, task["fol_angle"], W, H, rc.landmarks_rgb_arr)
+        frames[q] = img.astype("uint8")
+    out = dict(W=np.int64(W), H=np.int64(H), task=np.int64(k), kind=np.array([x[0] for x in poses]),
+               pos=np.array([x[1] for x in poses]), ori=np.array([x[2] for x in poses]),
+               cmd_idx=np.array([x[3] for x in poses], np.int64), frames=frames)
+    if (W, H) in RAYCAST_REF_CIO:
+        env = Maze(enable_render=False, resolution=(W, H), max_steps=5000, visibility_3D=12.0,
+                   command_in_observation=True, action_space_type="Discrete16")
+        env.set_task(task)
+        env.reset()
+        core = env.maze_core
+        obs = np.zeros_like(frames)
+        for q, (kind, p, o, c) in enumerate(poses):
+            core._agent_loc = [float(p[0]), float(p[1])]
+            core._agent_ori = o
+            core._commands_sequence_idx = c
+            core._command = core._commands_sequence[c]
+            core.update_observation()
+            obs[q] = core.get_observation()
+        out["obs_cio"] = obs
+    return out
+
+
+def gen_raycast_ref():
+    """tests/golden/raycast_ref_<W>x<H>_seed<k>.npz: the reference's maze_view at the frame sizes users get (256 x 256
+    registered, 320 x 320 default, non-square, the command bar clipped by a small frame) on the three maze_15 tasks, seven
+    poses each: two recorded ones, ori exactly 0 and pi/2, a cell boundary, 0.05 cell from a wall, a landmark in view.
+    One file per size and task keeps each under 1 MB."""
+    import multiprocessing
+    Maze, mts, dyn, rc = _refimport.mazeworld()
+    from xenoverse_amd.mazeworld.textures import make_texture_library
+    lib = make_texture_library(8, 4, 4, seed=0)
+    M = mts.MAZE_TASK_MANAGER
+    M.textlib_walls, M.textlib_grounds, M.textlib_ceilings = lib["walls"], lib["grounds"], lib["ceilings"]
+    jobs = [(k, W, H) for W, H in RAYCAST_REF_SIZES for k in range(3)]
+    with multiprocessing.get_context("fork").Pool(min(len(jobs), os.cpu_count() or 1, 16)) as pool:
+        res = pool.map(_raycast_ref_one, jobs, chunksize=1)
+    for (k, W, H), out in zip(jobs, res):
+        path = os.path.join(GOLD, "raycast_ref_%dx%d_seed%d.npz" % (W, H, k))
+        np.savez_compressed(path, **out)
+        print("wrote", path, os.path.getsize(path) // 1024, "KiB")
+
+
 def gen_maze_agent_one(name, task, T, action_space, agent_kind, res=32, seed0=0, expose_all=False):
     """The reference's SmartSLAMAgent / OracleAgent driving its own MazeWorldContinuous3D: per agent.step() the env
     state it read (pose, cell, command, maze_core._cell_exposed) and what it produced (action, _mask_info, _cost_map,
@@ -742,7 +840,8 @@ def gen_maze_texture_names():
 FAMILIES = {"anymdp": gen_anymdp, "linds": gen_linds, "maze": gen_maze, "acrobot": gen_acrobot, "garnet": gen_garnet,
             "anymdp_vi": gen_anymdp_vi, "anymdp_sampled": gen_anymdp_sampled, "maze_sampled": gen_maze_sampled,
             "linds_sampled": gen_linds_sampled, "maze_agent": gen_maze_agent, "maze_refcounts": gen_maze_refcounts,
-            "anymdp_accept": gen_anymdp_accept, "maze_texture_names": gen_maze_texture_names}
+            "anymdp_accept": gen_anymdp_accept, "maze_texture_names": gen_maze_texture_names,
+            "raycast_ref": gen_raycast_ref}
 
 if __name__ == "__main__":
     os.makedirs(GOLD, exist_ok=True)

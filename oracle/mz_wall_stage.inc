@@ -62,7 +62,7 @@
       const int ti = (int)((REAL)256 * d_i), tj = (int)(256 * d_j);
       const double eff_ps = eff_distance * pixel_size / l_focal; /* stale eff_distance: quirk (i) */
       double col[3];
-      mz_interpolate(wt, (double)ti, (double)tj, eff_ps, tps, tps, col);
+      mz_interpolate(wt, (double)ti, (double)tj, eff_ps, tps, tps, col, !typing_f64);
       int32_t* px = rgb + ((size_t)d_h * H + d_v) * 3;
       for (int c = 0; c < 3; ++c) {
         const double blend = (double)(REAL)(alpha * (REAL)1) + (double)((REAL)1 - alpha) * col[c];

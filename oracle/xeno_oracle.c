@@ -1047,14 +1047,20 @@ static const float MZ_LANDMARK_RGB[XO_MAZE_LMAX][3] = {
     {128, 255, 128}, {255, 128, 128}, {0, 96, 128}, {96, 0, 128}, {0, 128, 96}, {96, 128, 0}, {128, 96, 0},
     {128, 0, 96}};
 
-/* interpolate, ray_caster_utils.py:123-140: 4x4 taps, distance-weighted, wrap-around; sum_r is a float32
- * array accumulated as float32(float64(sum_r) + wht * tex), the return value is float64 */
+/* interpolate, ray_caster_utils.py:123-140: 4x4 taps, distance-weighted, wrap-around.  `weak`: the types the source takes
+ * as plain Python under NumPy 2, where they follow the VALUES: wht = max(0.01, min(w, 1.0)) is numpy's float64 w inside
+ * the ramp but the python float 0.01 (weak, i.e. float32 next to a float32 array) where it clamps (w <= 0.01; w > 1.0
+ * does not occur off the texel centres, and the wall stage's integer centre tap has w == 1.0 exactly, which min() keeps).
+ * So a ramp tap accumulates float32(float64(sum_r) + wht * tex), a clamped one float32(sum_r + float32(0.01f * tex)),
+ * and when all 16 clamp, sum_wht stays a python float and sum_r / sum_wht is a float32 division (a magnified ground or
+ * ceiling texture).  weak = 0 (numba's typing): every weight float64, the return value float64. */
 static void mz_interpolate(const float* tex /*[256][256][3]*/, double i, double j, double d, double px, double py,
-                           double out[3]) {
+                           double out[3], int weak) {
   double d2 = d * d;
   if (d2 < 1.0e-8) d2 = 1.0e-8;
   const int ib = (int)i, jb = (int)j;
   double sum_wht = 0.0;
+  int all_weak = weak;
   float sr[3] = {0.0f, 0.0f, 0.0f};
   for (int x = ib - 1; x < ib + 3; ++x)
     for (int y = jb - 1; y < jb + 3; ++y) {
@@ -1062,13 +1068,27 @@ static void mz_interpolate(const float* tex /*[256][256][3]*/, double i, double 
       const double dist = a * a + b * b;
       double wht = 1.0 - 10 * dist / d2;
       if (wht > 1.0) wht = 1.0;
-      if (wht < 0.01) wht = 0.01;
+      const int clamped = wht <= 0.01;
+      if (clamped) wht = 0.01;
       sum_wht += wht;
       const int xv = ((x % 256) + 256) % 256, yv = ((y % 256) + 256) % 256;
       const float* tp = tex + ((size_t)xv * 256 + yv) * 3;
-      for (int c = 0; c < 3; ++c) sr[c] = (float)((double)sr[c] + wht * (double)tp[c]);
+      if (weak && clamped) {
+        for (int c = 0; c < 3; ++c) {
+          const float prod = 0.01f * tp[c];
+          sr[c] = sr[c] + prod;
+        }
+      } else {
+        all_weak = 0;
+        for (int c = 0; c < 3; ++c) sr[c] = (float)((double)sr[c] + wht * (double)tp[c]);
+      }
     }
-  for (int c = 0; c < 3; ++c) out[c] = (double)sr[c] / sum_wht;
+  if (all_weak) {
+    const float sw = (float)sum_wht;
+    for (int c = 0; c < 3; ++c) out[c] = (double)(sr[c] / sw);
+  } else {
+    for (int c = 0; c < 3; ++c) out[c] = (double)sr[c] / sum_wht;
+  }
 }
 
 static inline int32_t mz_clip_int(double v) { /* numpy.clip(v, 0, 255) stored into an int32 array */
@@ -1139,7 +1159,7 @@ static void mz_view(const xo_maze* h, int e, int32_t* rgb /*[W][H][3]*/, int typ
         d_i -= floor(d_i); d_j -= floor(d_j);
         d_i *= 256; d_j *= 256;
         double col[3];
-        mz_interpolate(ground, d_i, d_j, eff_ps, tps, tps, col);
+        mz_interpolate(ground, d_i, d_j, eff_ps, tps, tps, col, !typing_f64);
         int32_t* px = rgb + ((size_t)d_h * H + d_v) * 3;
         for (int c = 0; c < 3; ++c) px[c] = mz_clip_int(light * (alpha * 1.0 + (1.0 - alpha) * col[c]));
       }
@@ -1167,7 +1187,7 @@ static void mz_view(const xo_maze* h, int e, int32_t* rgb /*[W][H][3]*/, int typ
         d_i -= floor(d_i); d_j -= floor(d_j);
         d_i *= 256; d_j *= 256;
         double col[3];
-        mz_interpolate(ceil_t, d_i, d_j, eff_ps, tps, tps, col);
+        mz_interpolate(ceil_t, d_i, d_j, eff_ps, tps, tps, col, !typing_f64);
         int32_t* px = rgb + ((size_t)d_h * H + d_v) * 3;
         for (int c = 0; c < 3; ++c) px[c] = mz_clip_int(light * (alpha * 1.0 + (1.0 - alpha) * col[c]));
       }

@@ -6,9 +6,10 @@ import pytest
 import oracle
 from xenoverse_amd.mazeworld.tables import DEFAULT_ACTION_SPACE_16, build_tables
 from xenoverse_amd.mazeworld.textures import make_texture_library
-from util import frame_mismatch, golden_files, load_maze_golden
+from util import golden_files, load_maze_golden, load_raycast_ref
 
 FILES = golden_files("maze_")
+RC_FILES = golden_files("raycast_ref_")
 TEX = None
 
 
@@ -83,7 +84,7 @@ def test_pose_rules_rewards_trajectory(path):
 
 @pytest.mark.parametrize("path", FILES)
 def test_frames_at_reference_poses(path):
-    """frames rendered at the reference's recorded poses: the bar is +-1 LSB on <= 0.5 % of the values"""
+    """frames rendered at the reference's recorded poses: byte for byte"""
     g, task = load_maze_golden(path)
     tab = build_tables([task])
     for res, frames, steps in ((int(g["res"]), g["frames"], g["frame_steps"]), (64, g["frames64"], g["frames64_steps"])):
@@ -94,8 +95,7 @@ def test_frames_at_reference_poses(path):
         o.ori[:] = g["tr_ori"][steps]
         o.cmd_idx[:] = g["tr_cmd_idx"][steps]
         f, c = o.render(n_threads=4)
-        frac, worst = frame_mismatch(f, frames)
-        assert frac <= 0.005 and worst <= 1, (res, frac, worst)
+        assert f.shape == frames.shape and np.array_equal(f, frames), (res, int((f != frames).sum()))
         assert np.array_equal(c, g["tr_cmd_rgb"][steps])
 
 
@@ -106,8 +106,37 @@ def test_reset_frame(path):
     o = oracle.MazeOracle(tab, textures(), [0], resolution=(int(g["res"]),) * 2)
     o.reset()
     f, _ = o.render()
-    frac, worst = frame_mismatch(f[0], g["frame0"])
-    assert frac <= 0.005 and worst <= 1
+    assert np.array_equal(f[0], g["frame0"]), int((f[0] != g["frame0"]).sum())
+
+
+def test_raycast_ref_fixtures_present():
+    sizes = {tuple(int(x) for x in np.load(p)["frames"].shape[1:3]) for p in RC_FILES}
+    assert sizes == {(256, 256), (320, 320), (320, 200), (200, 320), (40, 72), (72, 40)}, sizes
+    assert len(RC_FILES) == 18
+
+
+@pytest.mark.parametrize("path", RC_FILES, ids=lambda p: p.split("raycast_ref_")[-1][:-4])
+def test_oracle_renders_the_reference_frames_at_large_and_clipped_sizes(path):
+    """tests/golden/raycast_ref_*.npz: the reference's maze_view at 256 x 256 (registered), 320 x 320 (the default),
+    320 x 200 / 200 x 320 and the small frames whose command bar the frame clips; recorded poses, ori exactly 0 and pi/2,
+    a cell boundary, 0.05 cell from a wall, a landmark in view.  Frames and whole observations (command_in_observation)
+    byte for byte."""
+    g, task = load_raycast_ref(path)
+    W, H = int(g["W"]), int(g["H"])
+    n = len(g["ori"])
+    assert g["frames"].shape == (n, W, H, 3)
+    for cio in ((False, True) if "obs_cio" in g else (False,)):
+        o = oracle.MazeOracle(build_tables([task]), textures(), np.zeros(n, np.int32), resolution=(W, H),
+                              command_in_observation=cio)
+        o.reset()
+        o.pos[:] = g["pos"].T; o.ori[:] = g["ori"]; o.cmd_idx[:] = g["cmd_idx"]
+        f, c = o.render(n_threads=4)
+        ref = g["obs_cio"] if cio else g["frames"]
+        assert np.array_equal(f, ref), (cio, int((f != ref).sum()))
+    if "obs_cio" in g:      # where the reference's bar lies: first axis from H alone, second from H and W, clipped by numpy
+        xs, ys = np.nonzero((g["obs_cio"] != g["frames"]).any(-1).any(0))
+        assert (xs.min(), xs.max() + 1) == (int(0.25 * H), min(int(0.25 * H + 0.50 * H), W))
+        assert (ys.min(), ys.max() + 1) == (int(0.10 * H), min(int(0.10 * H + 0.05 * W), H))
 
 
 def test_distance_between_the_two_typings_of_the_ray_caster():

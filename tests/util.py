@@ -94,3 +94,10 @@ def load_anymdp_tok_golden(path):
     else:
         task["observation_transition"] = g["observation_transition"][0]
     return g, task
+
+
+def load_raycast_ref(path):
+    """tests/golden/raycast_ref_<W>x<H>_seed<k>.npz (oracle/gen_golden.py raycast_ref) and the maze_15 task its poses are in"""
+    g = dict(np.load(path, allow_pickle=False))
+    _, task = load_maze_golden(os.path.join(GOLD, "maze_15_seed%d.npz" % int(g["task"])))
+    return g, task

@@ -624,7 +624,10 @@ __device__ __forceinline__ void mz_fetch_window(const void* __restrict__ texv, i
 // [~1e-40, 1e4]): mz_div, 3 instructions per tap instead of 14.
 // dist >= 0 and d2 > 0 make the reference's upper clamp (wht > 1 -> 1) unreachable; the lower one is a v_max_f64.
 // W: the 4 x 4 window is already in registers (`win`, mz_fetch_window); otherwise PACKED says which copy `texv` is.
-template <bool PACKED, bool W = false>
+// WEAK (the reference's source as plain Python under NumPy 2, not numba's typing): a weight clamped at 0.01 is the python float
+// 0.01, weak next to the float32 sums, so that tap adds fl32(0.01f * t) in float32; when all 16 clamp, sum_wht stays a python
+// float and the colour is a float32 division (oracle mz_interpolate).
+template <bool PACKED, bool W = false, bool WEAK = true>
 __device__ __forceinline__ void mz_interpolate(const void* __restrict__ texv, double i, double j, double d,
                                                double px, double py, double (&out)[3], const uint32_t (*win)[4] = nullptr) {
   double d2 = d * d;
@@ -632,6 +635,7 @@ __device__ __forceinline__ void mz_interpolate(const void* __restrict__ texv, do
   const MzDivisor D2 = mz_divisor(d2);
   const int ib = (int)i, jb = (int)j;
   double sum_wht = 0.0;
+  bool all_weak = WEAK;
   float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f;
   double bb[4];
 #pragma unroll
@@ -650,7 +654,9 @@ __device__ __forceinline__ void mz_interpolate(const void* __restrict__ texv, do
 #pragma unroll
     for (int yy = -1; yy < 3; ++yy) {
       const double dist = aa + bb[yy + 1];
-      const double wht = __builtin_fmax(1.0 - mz_div(10 * dist, D2), 0.01);
+      const double w0 = 1.0 - mz_div(10 * dist, D2);
+      const bool weak = WEAK && !(w0 > 0.01);
+      const double wht = __builtin_fmax(w0, 0.01);
       sum_wht += wht;
       float t0, t1, t2;
       if (PACKED || W) {
@@ -660,10 +666,20 @@ __device__ __forceinline__ void mz_interpolate(const void* __restrict__ texv, do
         const float* tp = static_cast<const float*>(texv) + ((size_t)xv * 256 + ((jb + yy) & 255)) * 3;
         t0 = tp[0]; t1 = tp[1]; t2 = tp[2];
       }
-      s0 = (float)((double)s0 + wht * (double)t0);
-      s1 = (float)((double)s1 + wht * (double)t1);
-      s2 = (float)((double)s2 + wht * (double)t2);
+      if (weak) {      // (-ffp-contract=off: product and sum each rounded to float32)
+        s0 = s0 + 0.01f * t0; s1 = s1 + 0.01f * t1; s2 = s2 + 0.01f * t2;
+      } else {
+        all_weak = false;
+        s0 = (float)((double)s0 + wht * (double)t0);
+        s1 = (float)((double)s1 + wht * (double)t1);
+        s2 = (float)((double)s2 + wht * (double)t2);
+      }
     }
+  }
+  if (WEAK && all_weak) {
+    const float sw = (float)sum_wht;
+    out[0] = (double)(s0 / sw); out[1] = (double)(s1 / sw); out[2] = (double)(s2 / sw);
+    return;
   }
   const MzDivisor SW = mz_divisor(sum_wht);   // in [0.16, 16]
   out[0] = mz_div((double)s0, SW); out[1] = mz_div((double)s1, SW); out[2] = mz_div((double)s2, SW);
@@ -698,8 +714,12 @@ __device__ __forceinline__ void mz_interpolate(const void* __restrict__ texv, do
 //     the third channel): |sw' - sum w'| <= 17 * 2^-24 (1 + 2e-6) sum w' likewise.
 //   * 10 / d2 and 1 / sw' come from v_rcp_f64 + one Newton step (mz_rcp_spec: within 1e-12; the weights then move by < 1e-10 of
 //     themselves, the colour by 1e-12): 12 instructions fewer than two correctly rounded divisor set-ups and three quotients.
-//   so c' = s' / sw' has |c' - c| <= (2 * 1.0133e-6 + 9.5368e-7 * 1.000001 + 3e-10) c < 2.981e-6 c'(1 + 4e-6): KAPPA = 3.0e-6 (0.97e-6
-//     for the float64 sums), and about one pixel in 100 instead of one in 300 is re-run in the reference's typing.
+//   so c' = s' / sw' has |c' - c| <= (2 * 1.0133e-6 + 9.5368e-7 * 1.000001 + 3e-10) c < 2.981e-6 c'(1 + 4e-6), and about one pixel
+//     in 100 instead of one in 300 is re-run in the reference's typing.
+//   * a weight clamped at 0.01 is the python float 0.01 in the reference (mz_interpolate WEAK): its term is fl32(fl32(0.01) t), within
+//     (2.3e-8 + 2^-24) 1.0000001 <= 8.3e-8 of 0.01 t, so s_ref moves by at most 8.3e-8 more of the sum; when all 16 clamp, the
+//     float32 division by fl32(sum_wht) adds 2 * 2^-24 (1.2e-7) relative: |c' - c| < (2.981 + 0.083 + 0.12) 1e-6 c'(1 + 4e-6) < 3.19e-6 c'.
+//   KAPPA = 3.3e-6 (1.2e-6 for the float64 sums).
 //   * byte: v' = fma(L B, c', L A) instead of L (A + B c') (three roundings of values < 2^9 either way: inside the absolute 1e-9),
 //     bound e = fma(v', KAPPA, 1e-9) >= L B c' KAPPA + 1e-9 (L, A, B >= 0).  0 <= v' <= 255 (L <= 1, A + B = 1, c' <= 255 (1 + 3e-6);
 //     a v' above 255 by that much truncates to 255 as the reference's clip does): no clamp instructions.
@@ -708,9 +728,9 @@ __device__ __forceinline__ void mz_interpolate(const void* __restrict__ texv, do
 #define XV_MAZE_SPEC32 1
 #endif
 #if XV_MAZE_SPEC32
-#define MZ_SPEC_KAPPA 3.0e-6
+#define MZ_SPEC_KAPPA 3.3e-6
 #else
-#define MZ_SPEC_KAPPA 9.7e-7
+#define MZ_SPEC_KAPPA 1.2e-6
 #endif
 typedef float mz_f2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ void mz_interpolate_spec(const uint32_t (&qw)[4][4], double i, double j, double d, double ps,
@@ -1215,7 +1235,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MZ_RC_WAVES
               (void)pixel(C, dv2, tx, f_i, f_j, f_d, L, A, B);
               uint32_t qw[4][4];
               mz_fetch_window<PP>(tx, (int)f_i, (int)f_j, qw);
-              mz_interpolate<true, true>(nullptr, f_i, f_j, f_d, tps, tps, c, qw);
+              mz_interpolate<true, true, !NB>(nullptr, f_i, f_j, f_d, tps, tps, c, qw);
               uint8_t* px = lds + (size_t)cc * cstride + (dv2 - c0) * 3;
               px[0] = mz_clip_u8(L * (A + B * c[0]));
               px[1] = mz_clip_u8(L * (A + B * c[1]));
@@ -1233,7 +1253,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MZ_RC_WAVES
               (void)pixel(C, d_v, tx, f_i, f_j, f_d, L, A, B);
               uint32_t qw[4][4];
               mz_fetch_window<PP>(tx, (int)f_i, (int)f_j, qw);
-              mz_interpolate<true, true>(nullptr, f_i, f_j, f_d, tps, tps, c, qw);
+              mz_interpolate<true, true, !NB>(nullptr, f_i, f_j, f_d, tps, tps, c, qw);
               uint8_t* px = lds + (size_t)cc * cstride + (d_v - c0) * 3;
               px[0] = mz_clip_u8(L * (A + B * c[0]));
               px[1] = mz_clip_u8(L * (A + B * c[1]));
@@ -1297,7 +1317,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MZ_RC_WAVES
               redo |= (unsigned long long)doubt << (d_v - r0);
             } else {
               if (F32) mz_interpolate_f32<PACKED>(tx, f_i, f_j, f_d, tps, c);
-              else mz_interpolate<PACKED>(tx, f_i, f_j, f_d, tps, tps, c);
+              else mz_interpolate<PACKED, false, !NB>(tx, f_i, f_j, f_d, tps, tps, c);
               px[0] = mz_clip_u8(L * (A + B * c[0]));
               px[1] = mz_clip_u8(L * (A + B * c[1]));
               px[2] = mz_clip_u8(L * (A + B * c[2]));
@@ -1316,7 +1336,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MZ_RC_WAVES
             (void)pixel(C, dv2, tx, f_i, f_j, f_d, L, A, B);
             uint32_t qw[4][4];
             mz_fetch_window<PP>(tx, (int)f_i, (int)f_j, qw);
-            mz_interpolate<true, true>(nullptr, f_i, f_j, f_d, tps, tps, c, qw);
+            mz_interpolate<true, true, !NB>(nullptr, f_i, f_j, f_d, tps, tps, c, qw);
             uint8_t* px = lds + (size_t)((threadIdx.x & ~63u) + (unsigned)src_lane) * cstride + (dv2 - c0) * 3;
             px[0] = mz_clip_u8(L * (A + B * c[0]));
             px[1] = mz_clip_u8(L * (A + B * c[1]));
@@ -1332,7 +1352,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MZ_RC_WAVES
             (void)pixel(me, d_v, tx, f_i, f_j, f_d, L, A, B);
             uint32_t qw[4][4];
             mz_fetch_window<PP>(tx, (int)f_i, (int)f_j, qw);
-            mz_interpolate<true, true>(nullptr, f_i, f_j, f_d, tps, tps, c, qw);
+            mz_interpolate<true, true, !NB>(nullptr, f_i, f_j, f_d, tps, tps, c, qw);
             uint8_t* px = col + (d_v - c0) * 3;
             px[0] = mz_clip_u8(L * (A + B * c[0]));
             px[1] = mz_clip_u8(L * (A + B * c[1]));
