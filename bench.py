@@ -16,15 +16,21 @@ bracketed by a barrier + device synchronisation on both sides and by HIP events 
 ranks is taken per repetition and the MEDIAN repetition is reported (`steps` stays K; `repeats` = R).  With the
 driver's K = 20 one repetition is a 0.15 ms region, which a single sample cannot resolve.
 
+A plain run does only what the headline needs: set-up, warm-up, the timed passes, --dump-outputs, the line.  Everything
+else the benchmark measures takes runs of its own and is done with --full only (the opt-out flags below still apply there):
+the child counter passes of `roofline.traffic_live`, `search_variants`, `long_call`, `sustain`, `cpu_baseline`, `families`
+and, N > 1, the all-gather pass (`with_allgather`; --exchange-selftest always runs it, it is what that mode checks).
+
 One JSON line on rank 0: metric/value/unit/... as the driver's contract says, plus
-  roofline      HBM bound for the step kernel.  `traffic` = bytes the kernel really moved per launch (PMC counters of the
-                committed profile of THIS kernel source, else null).  `achieved` / `frac` price those bytes when they are below
-                SURVEY.md §8(d)'s algorithmic 562 B per env-step (the search reads one 128-byte line of the 512-byte row) — a
-                fraction above 1 is never printed; the survey's figure stays as `achieved_survey_bytes` / `frac_survey_bytes`
-  long_call     SURVEY.md §8(d)'s own definition (>= 2,000 back-to-back steps after >= 100 warm-up, median of 5, both clocks)
-                for the three issue modes on the same tables: one stream, overlapped, fused roll-out
-  cpu_baseline  SURVEY.md §8(d): the reference's execution style (one env per Python object, one step() per call,
-                NumPy global RNG; oracle/py_ref_style.py) in P = usable CPUs processes; `c_oracle` = the
+  roofline      HBM bound for the step kernel.  `traffic` = bytes the kernel really moved per launch (PMC counters: with --full
+                this run's own child passes, else the committed profile of THIS kernel source, else null).  `achieved` / `frac`
+                price those bytes when they are below SURVEY.md §8(d)'s algorithmic 562 B per env-step (the search reads one
+                128-byte line of the 512-byte row) — a fraction above 1 is never printed; the survey's figure stays as
+                `achieved_survey_bytes` / `frac_survey_bytes`
+  long_call     --full: SURVEY.md §8(d)'s own definition (>= 2,000 back-to-back steps after >= 100 warm-up, median of 5, both
+                clocks) for the three issue modes on the same tables: one stream, overlapped, fused roll-out
+  cpu_baseline  --full (null otherwise): SURVEY.md §8(d): the reference's execution style (one env per Python object, one
+                step() per call, NumPy global RNG; oracle/py_ref_style.py) in P = usable CPUs processes; `c_oracle` = the
                 vectorised C oracle (OpenMP) on a working set that does not fit the last-level cache
   rccl / rccl_ranks   N > 1: whether the RCCL process group came up and what all_reduce(ones) returned
 
@@ -66,6 +72,10 @@ def parse():
     ap.add_argument("--tasks", type=int, default=0, help="tasks per GPU (0 = one per env, config 2a)")
     ap.add_argument("--period", type=int, default=32, help="rollout-chunk ring length T")
     ap.add_argument("--seed", type=int, default=1234)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, everything else the benchmark measures (~1 min at the default sizes): the CPU "
+                         "baselines, the live counter passes, search_variants, long_call, sustain, families and, N > 1, the "
+                         "all-gather pass; without it a run sets up, warms up, times the steps and prints the line")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--cpu-table-gib", type=float, default=16.0, help="working set of the C-oracle CPU line")
@@ -566,7 +576,7 @@ def main():
         return self_launch(args)
     selftest = args.exchange_selftest
     cpu = None
-    if world == 1 and rank == 0 and not args.no_cpu_baseline and not selftest and not args.sweep_envs \
+    if args.full and world == 1 and rank == 0 and not args.no_cpu_baseline and not selftest and not args.sweep_envs \
             and not under_profiler():
         if args.workload == "mixed":
             sys.path.insert(0, os.path.join(ROOT, "scripts"))
@@ -579,8 +589,8 @@ def main():
             cpu = cpu_baseline(args.cpu_seconds, args.seed, args.cpu_table_gib)      # before the GPU is touched
 
     live = None
-    if world == 1 and rank == 0 and not selftest and not args.sweep_envs and not under_profiler() and not args.no_live_pmc \
-            and args.workload == "anymdp" and not os.environ.get("XV_BENCH_SHARE_GPU"):
+    if args.full and world == 1 and rank == 0 and not selftest and not args.sweep_envs and not under_profiler() \
+            and not args.no_live_pmc and args.workload == "anymdp" and not os.environ.get("XV_BENCH_SHARE_GPU"):
         live = live_pmc_traffic(args)      # child processes; this one has not touched the GPU yet
 
     import torch
@@ -668,7 +678,7 @@ def main():
     # exchange step: all-gather of each finished T-step rollout chunk (8-byte records) on a side
     # stream so that it overlaps the next chunk's stepping.  Stepping itself needs no collective.  On GPUs the
     # all-gather runs over RCCL only (gloo would stage 16 MB per rank through the host).
-    do_gather = world > 1 and not args.no_allgather and dinfo["note"] is None and \
+    do_gather = world > 1 and (args.full or selftest) and not args.no_allgather and dinfo["note"] is None and \
         (selftest or dist.get_backend() == "nccl" or bool(os.environ.get("XV_BENCH_FORCE_GATHER")))
     gather = None
     gather_note = dinfo["note"] or "none"
@@ -783,7 +793,7 @@ def main():
 
     # the other searches on the same workload (`value` above is the AUTO choice): each timed with min(R, 5) repetitions
     variants = None
-    if env is not None and world == 1 and not args.no_variants and not under_profiler():   # (N = 1: no collective in here)
+    if args.full and env is not None and world == 1 and not args.no_variants and not under_profiler():   # (N = 1: no collective)
         def vrow(w, e, is_value):      # both clocks side by side: events (us_per_step, env_steps_per_s) and host wall (wall_*)
             return {"us_per_step": e * 1e3 / args.steps, "env_steps_per_s": n_env * args.steps / (e * 1e-3),
                     "wall_us_per_step": w * 1e6 / args.steps, "wall_env_steps_per_s": n_env * args.steps / w, "is_value": is_value}
@@ -836,7 +846,7 @@ def main():
     PL = max(2, args.period - args.period % 2)
     KL = (max(args.long_steps, PL) + PL - 1) // PL * PL if args.long_steps > 0 else 0
     ring_l = actions_l = None
-    if env is not None and KL > 0 and not under_profiler():
+    if args.full and env is not None and KL > 0 and not under_profiler():
         try:
             g2 = torch.Generator(device=device)
             g2.manual_seed(args.seed + 17 * rank + 5)
@@ -887,7 +897,7 @@ def main():
     # milliseconds).  Excluded from `value`; `sustain_s` says how long it ran.  Issued the way `long_call.overlapped` (or, with
     # --overlap off, `.one_stream`) is: calls of `long_call` length on the long ring, so that the two figures can be compared.
     sustain = None
-    if env is not None and args.sustain_seconds > 0 and not under_profiler():
+    if args.full and env is not None and args.sustain_seconds > 0 and not under_profiler():
         ks, al, rl = (KL, actions_l, ring_l) if (KL > 0 and ring_l is not None) else (8 * P, actions, ring)
         t0 = time.perf_counter()
         done = calls = 0
@@ -1066,7 +1076,7 @@ def main():
         state["fused"] = n_env * T * reps / (f0.elapsed_time(f1) * 1e-3)
 
     # N = 1: configs 3, 4 and the per-GPU share of config 5 beside the headline, in the same JSON line (`families`)
-    if world == 1 and env is not None and not args.no_families and not args.sweep_envs:
+    if args.full and world == 1 and env is not None and not args.no_families and not args.sweep_envs:
         try:
             env.close()
             env = None
@@ -1078,7 +1088,7 @@ def main():
         except Exception as ex:
             state["families"] = {"error": repr(ex)}
 
-    if world > 1 and env is not None and not args.no_families and not selftest:
+    if args.full and world > 1 and env is not None and not args.no_families and not selftest:
         # N > 1: BASELINE configs[4] on the same ranks (the N = 1 line carries one GPU's share as `families.mixed_share`)
         try:
             sys.path.insert(0, os.path.join(ROOT, "scripts"))

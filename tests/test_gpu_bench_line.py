@@ -1,5 +1,6 @@
 """The bench line as a GPU run prints it (small sizes): the contract keys, the `roofline` and `cpu_baseline` objects, the
-`long_call` block — a renamed key or a fraction above 1 fails here before a judge reads the line."""
+`long_call` block of a --full run, and a plain run that measures the headline only — a renamed key or a fraction above 1
+fails here before a judge reads the line."""
 import json
 import os
 import subprocess
@@ -25,7 +26,7 @@ def _line(extra):
 
 
 def test_bench_line_schema_at_the_drivers_flags():
-    d = _line([])
+    d = _line(["--full"])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
               "dtype", "data", "config", "roofline", "cpu_baseline", "long_call", "sustain"):
         assert k in d, k
@@ -59,6 +60,23 @@ def test_bench_line_schema_at_the_drivers_flags():
     # the sustain leg is issued the way long_call.overlapped is (round 5 left it on one stream by a bench bug)
     assert d["sustain"]["overlap_requested"] is True and d["sustain"]["steps_per_call"] == 256
     assert d["sustain"]["overlap_state"] == lc["overlapped"]["overlap_state"] or d["sustain"]["overlap_state"] in (1, 0, -2)
+
+
+def test_plain_run_is_the_headline_only():
+    """without --full a run sets up, warms up, times the steps and prints the line: the contract keys and the roofline (traffic
+    from a committed counter profile where one matches), none of the blocks that take runs of their own (the flags that size
+    them are ignored)"""
+    d = _line([])
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "config",
+              "roofline"):
+        assert k in d, k
+    assert d["steps"] == 20 and d["warmup"] == 5 and d["repeats"] == 5 and d["dtype"] == "f64" and d["higher_is_better"] is True
+    assert d["value"] > 0 and d["ms_per_step"] > 0 and d["config"]["device_error_flags"] == 0
+    for k in bench.ROOFLINE_KEYS:
+        assert k in d["roofline"], k
+    assert d["roofline"]["traffic_live"] is None and d["cpu_baseline"] is None
+    for k in ("long_call", "sustain", "sustain_s", "search_variants", "families", "with_allgather", "fused_rollout_env_steps_per_s_rank0"):
+        assert k not in d, k
 
 
 def test_bench_line_shared_tasks_claims_no_hbm_fraction():
