@@ -439,6 +439,34 @@ int xv_anymdp_rollout_qlearn(xv_anymdp* h, xv_anymdp_qlearn* ql, int T, int gree
                              const float* z, const double* u_reset, int32_t* action_out, int32_t* obs, float* reward,
                              float* reward_gt, uint8_t* terminated, uint8_t* truncated, int32_t* final_obs);
 
+/* AnyMDP model-based agents — reference: xenoverse/anymdp/anymdp_solver_mbrl.py AnyMDPSolverMBRL, driven by the training
+ * loop of anymdp/test_utils.py (epoch_run :42-60), one agent per env of an MDP handle, in fp64 (xenoverse_amd/anymdp/mbrl.py)
+ *   __init__ :13-40  -> xv_anymdp_mbrl_create / xv_anymdp_mbrl_reset (est_r = 0, vis_cnt = 0.01, vis_cnt_sa = 1, vm = 0,
+ *                       b = c / (1 - gamma) * 0.01)
+ *   learner :57-71, update_estimator :42-55 (one Gauss-Seidel sweep of solver.py update_value_matrix, max_iteration = 1),
+ *   policy :73-78 -> xv_anymdp_rollout_mbrl
+ * Agent state on the device: est_r, vis_cnt double[n_env][S][A][S], vis_cnt_sa, vm, b double[n_env][S][A] (rows indexed by
+ * observation id); b is the snapshot the last episode end took.  The learner learns from the step's fp32 reward widened to
+ * fp64 (the reference's is fp64).  create: XV_ERR_UNSUPPORTED for POMDP / multi-token handles, for views and for observation
+ * ids >= S; XV_ERR_NOMEM, before allocating, when the tables do not fit the free device memory less 2 GiB.  get / set_state
+ * copy device arrays (each nullable) on the engine's stream.  A learner borrows its xv_anymdp handle: destroy the learner
+ * first (destroy synchronises the handle's stream). */
+typedef struct xv_anymdp_mbrl xv_anymdp_mbrl;
+int xv_anymdp_mbrl_create(xv_anymdp* h, double gamma, double c, xv_anymdp_mbrl** out);
+int xv_anymdp_mbrl_destroy(xv_anymdp_mbrl* m);
+int xv_anymdp_mbrl_reset(xv_anymdp_mbrl* m, const uint8_t* mask);   /* mask uint8[n_env] or nullptr (all) */
+int xv_anymdp_mbrl_get_state(xv_anymdp_mbrl* m, double* est_r, double* vis_cnt, double* vis_cnt_sa, double* vm, double* b);
+int xv_anymdp_mbrl_set_state(xv_anymdp_mbrl* m, const double* est_r, const double* vis_cnt, const double* vis_cnt_sa,
+                             const double* vm, const double* b);
+/* T steps of [policy -> step (SAME_STEP auto-reset) -> learner] for every env, issued from C, as xv_anymdp_rollout_qlearn;
+ * per step one learn launch (envs whose episode goes on also pick their next action) and one estimator launch over the
+ * envs whose episode ended, listed on the device.  u_policy [T][n_env][A]: the policy's A uniforms per step, given exactly
+ * when u is (ignored when greedy); free-running draws are keyed by (seed, global env id, launch tick of the step that takes
+ * the action): splitting T over calls changes nothing.  Outputs [T][n_env] in the layout of xv_anymdp_rollout_teacher. */
+int xv_anymdp_rollout_mbrl(xv_anymdp* h, xv_anymdp_mbrl* m, int T, int greedy, const double* u_policy, const double* u,
+                           const float* z, const double* u_reset, int32_t* action_out, int32_t* obs, float* reward,
+                           float* reward_gt, uint8_t* terminated, uint8_t* truncated, int32_t* final_obs);
+
 /* Value iteration for every task of the handle, one workgroup per task (the reference's ground-truth teacher,
  * anymdp_solver_opt.py:30-51, for whole task batches): synchronous sweeps
  *   Q[s,a] <- sum_s' T[s,a,s'] (R[s,a,s'] + gamma max_a' Q[s',a'])   until rms(Q_new - Q) <= tol or max_iter sweeps,

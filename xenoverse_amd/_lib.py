@@ -82,6 +82,12 @@ SIGNATURES = {
     "xv_anymdp_qlearn_get_state": [c_void_p] * 4,
     "xv_anymdp_qlearn_set_state": [c_void_p] * 4,
     "xv_anymdp_rollout_qlearn": [c_void_p, c_void_p, c_int, c_int] + [c_void_p] * 11,
+    "xv_anymdp_mbrl_create": [c_void_p, C.c_double, C.c_double, C.POINTER(c_void_p)],
+    "xv_anymdp_mbrl_destroy": [c_void_p],
+    "xv_anymdp_mbrl_reset": [c_void_p, c_void_p],
+    "xv_anymdp_mbrl_get_state": [c_void_p] * 6,
+    "xv_anymdp_mbrl_set_state": [c_void_p] * 6,
+    "xv_anymdp_rollout_mbrl": [c_void_p, c_void_p, c_int, c_int] + [c_void_p] * 11,
     "xv_anymdp_get_state": [c_void_p, c_void_p, c_void_p, c_void_p],
     "xv_anymdp_set_state": [c_void_p, c_void_p, c_void_p, c_void_p],
     "xv_anymdp_transition_gt": [c_void_p, c_void_p, c_void_p],

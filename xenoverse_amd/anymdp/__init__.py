@@ -5,3 +5,4 @@ from .task_sampler import (AnyMDPTaskSampler, AnyPOMDPTaskSampler, GarnetTaskSam
                            MultiTokensAnyPOMDPTaskSampler)
 from .device_sampler import sample_tasks_device  # noqa: F401,E402
 from .qlearner import AnyMDPQLearner, QLearnerHost  # noqa: F401,E402
+from .mbrl import AnyMDPMBRLLearner, MBRLHost  # noqa: F401,E402

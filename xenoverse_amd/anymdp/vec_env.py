@@ -15,6 +15,7 @@ from ..engine import AUTORESET
 from ..spaces import Discrete, MultiDiscrete
 from ..vector import OutputSlabs, VectorEnv
 from .tables import build_obs_tables, build_tables, build_tables_device, device_buildable
+from .mbrl import AnyMDPMBRLLearner
 
 _TABLE_KEYS = ("rows", "state_map", "term_mask", "s0_cdf", "s0_ids", "max_steps")
 _TABLE_DTYPES = dict(rows=torch.float64, state_map=torch.int32, term_mask=torch.int64,
@@ -57,7 +58,7 @@ class AnyMDPVecEnv(VectorEnv):
         self._many_cache = None
         self._tab = None
         self._views = []            # sub-batch envs made by split(): they borrow this env's tables
-        self._learners = weakref.WeakSet()   # AnyMDPQLearner objects on this env's handle
+        self._learners = weakref.WeakSet()   # the learners (Q, MBRL) on this env's handle
         self._parent = None
 
     # ---- set_task ---------------------------------------------------------------------------------
@@ -120,7 +121,7 @@ class AnyMDPVecEnv(VectorEnv):
         if self._parent is not None:
             raise ValueError("set_task on a sub-batch made by split(): set the task on the env it was split from")
         self._drop_views()
-        self._release_learners("AnyMDPQLearner: its env was given new tasks; make a new learner")
+        self._release_learners("its env was given new tasks; make a new learner")
         if self._h is not None:
             self.lib.xv_anymdp_destroy(self._h)
             self._h = None
@@ -578,7 +579,8 @@ class AnyMDPVecEnv(VectorEnv):
     def rollout_learner(self, learner, T, greedy=False, draws=None):
         """T steps of the reference's training loop (anymdp/test_utils.py: epoch_run :42-60) for every env at once, on the
         device: action = learner's policy(obs) -> step -> learner.learner(s, a, ns, r, terminated, truncated), SAME_STEP
-        auto-reset, starting from the env's current observation.  learner: an AnyMDPQLearner of this env.  greedy: argmax
+        auto-reset, starting from the env's current observation.  learner: an AnyMDPQLearner or an AnyMDPMBRLLearner of this
+        env (for the latter draws["u_policy"] is [T, N, A]: the policy's A uniforms per step).  greedy: argmax
         actions (the reference's is_test epochs; the agents still learn).  draws: None (Philox) or a dict of [T, N] arrays
         u_policy (float64, the policy's uniforms), u (float64), z (float32), u_reset (float64) — the step's draws as in
         step_injected.  -> dict of [T, N] device tensors in rollout_teacher's layout ("action" included)."""
@@ -593,6 +595,7 @@ class AnyMDPVecEnv(VectorEnv):
         T, n, d = int(T), self.num_envs, self.device
         if T < 1:
             raise ValueError("rollout_learner: T must be >= 1")
+        mbrl = isinstance(learner, AnyMDPMBRLLearner)
         dr = [None] * 4
         if draws is not None:
             dts = dict(u_policy=torch.float64, u=torch.float64, z=torch.float32, u_reset=torch.float64)
@@ -602,8 +605,9 @@ class AnyMDPVecEnv(VectorEnv):
                 if draws.get(k) is None:
                     raise ValueError("rollout_learner: draws[%r] missing" % k)
                 dr[j] = self._dev(draws[k], dts[k])
-                if tuple(dr[j].shape) != (T, n):
-                    raise ValueError("rollout_learner: draws[%r] has shape %s, expected %s" % (k, tuple(dr[j].shape), (T, n)))
+                shape = (T, n, self.A) if (mbrl and k == "u_policy") else (T, n)
+                if tuple(dr[j].shape) != shape:
+                    raise ValueError("rollout_learner: draws[%r] has shape %s, expected %s" % (k, tuple(dr[j].shape), shape))
         out = dict(action=torch.empty((T, n), dtype=torch.int32, device=d),
                    obs=torch.empty((T, n), dtype=torch.int32, device=d),
                    reward=torch.empty((T, n), dtype=torch.float32, device=d),
@@ -611,7 +615,8 @@ class AnyMDPVecEnv(VectorEnv):
                    terminated=torch.empty((T, n), dtype=torch.uint8, device=d),
                    truncated=torch.empty((T, n), dtype=torch.uint8, device=d),
                    final_obs=torch.empty((T, n), dtype=torch.int32, device=d))
-        _lib.check(self.lib.xv_anymdp_rollout_qlearn(
+        rollout = self.lib.xv_anymdp_rollout_mbrl if mbrl else self.lib.xv_anymdp_rollout_qlearn
+        _lib.check(rollout(
             self._h, learner._h, T, 1 if greedy else 0, *(_lib.ptr(x) for x in dr), _lib.ptr(out["action"]),
             _lib.ptr(out["obs"]), _lib.ptr(out["reward"]), _lib.ptr(out["reward_gt"]), _lib.ptr(out["terminated"]),
             _lib.ptr(out["truncated"]), _lib.ptr(out["final_obs"])))
@@ -841,14 +846,15 @@ class AnyMDPVecEnv(VectorEnv):
         self.need_reset = False
 
     def _release_learners(self, why):
-        """the learners borrow this env's handle: they go first (their device tables are freed, later use raises `why`)"""
+        """the learners borrow this env's handle: they go first (their device tables are freed, later use raises
+        "<learner class>: `why`")"""
         for ql in list(self._learners):
-            ql.close(why)
+            ql.close("%s: %s" % (type(ql).__name__, why))
         self._learners = weakref.WeakSet()
 
     def close_extras(self, **kwargs):
         self._drop_views()
-        self._release_learners("AnyMDPQLearner: its env was closed")
+        self._release_learners("its env was closed")
         if self._h is not None:
             self.lib.xv_anymdp_destroy(self._h)
             self._h = None
