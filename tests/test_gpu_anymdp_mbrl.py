@@ -1,16 +1,14 @@
 """The device model-based learner (csrc/anymdp_mbrl.hip: AnyMDPMBRLLearner, AnyMDPVecEnv.rollout_learner) against the
 reference's own training loop (tests/golden/mbrl_anymdp_*.npz), against the host restatement (xenoverse_amd/anymdp/mbrl.py)
-and against itself."""
-import ctypes as C
+and against itself.  The tests that are the same for every learner are in test_gpu_anymdp_learners.py."""
 import os
 
 import numpy as np
 import pytest
-import torch
 
-from util import close_f32, golden_files, load_anymdp_golden, load_anymdp_tok_golden
-from xenoverse_amd import _lib
-from xenoverse_amd.anymdp import AnyMDPMBRLLearner, AnyMDPVecEnv, MBRLHost
+from util import anymdp_env as _env, anymdp_fixture_task as _fixture_task, anymdp_tasks16 as _tasks16, to_np as _np
+from util import close_f32, golden_files, load_anymdp_golden
+from xenoverse_amd.anymdp import AnyMDPMBRLLearner, MBRLHost
 
 pytestmark = pytest.mark.gpu
 FILES = golden_files("mbrl_anymdp_")
@@ -21,32 +19,12 @@ REPLAY_TXT = os.path.join(ROOT, "profiles", "anymdp_mbrl_replay.txt")
 _replay_lines = []
 
 
-def _np(t):
-    return t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
-
-
-def _fixture_task(g):
-    return dict(ns=int(g["ns"]), na=int(g["na"]), max_steps=float(g["max_steps"]), state_mapping=g["state_mapping"],
-                task_type="MDP", s_0=g["s_0"], s_0_prob=g["s_0_prob"], s_e=g["s_e"], transition=g["transition"],
-                reward=g["reward"], reward_noise=g["reward_noise"])
-
-
-def _tasks16():
-    return [load_anymdp_golden(p)[1] for p in golden_files("anymdp_16x4")[:4]]
-
-
 def _tasks(cfg):
     if cfg == "16x4":
         return _tasks16()
     if cfg == "64x8":
         return [load_anymdp_golden(golden_files("anymdp_64x8")[0])[1]]
     return [_fixture_task(dict(np.load(f))) for f in FILES if cfg in f]
-
-
-def _env(tasks, n, seed, mode="same_step"):
-    env = AnyMDPVecEnv(n, seed=seed, autoreset_mode=mode)
-    env.set_task(tasks)
-    return env
 
 
 def _close(a, b):
@@ -212,47 +190,6 @@ def test_scale_65536_envs_sampled_against_host():
     assert n_term + n_trunc > 0
 
 
-def test_rollout_equals_stepping_its_actions():
-    n, T = 256, 160
-    a_env = _env(_tasks16(), n, seed=9)
-    a_env.reset()
-    ml = AnyMDPMBRLLearner(a_env, c=0.05)
-    ro = {k: _np(v) for k, v in a_env.rollout_learner(ml, T).items()}
-    b_env = _env(_tasks16(), n, seed=9)
-    b_env.reset()
-    for t in range(T):
-        obs, r, term, trunc, info = b_env.step(ro["action"][t])
-        assert np.array_equal(_np(obs), ro["obs"][t]), t
-        assert np.array_equal(_np(r), ro["reward"][t]) and np.array_equal(_np(info["reward_gt"]), ro["reward_gt"][t])
-        assert np.array_equal(_np(term).astype(np.uint8), ro["terminated"][t])
-        assert np.array_equal(_np(trunc).astype(np.uint8), ro["truncated"][t])
-    assert len(np.unique(ro["action"])) == 4 and (ro["terminated"] | ro["truncated"]).sum() > 0
-    assert a_env.check_errors() == 0 and b_env.check_errors() == 0
-    ml.close()
-    a_env.close()
-    b_env.close()
-
-
-def test_splitting_T_changes_nothing():
-    n, T = 512, 240
-    res = []
-    for parts in (1, 3):
-        env = _env(_tasks16(), n, seed=21)
-        env.reset()
-        ml = AnyMDPMBRLLearner(env, c=0.05)
-        outs = [env.rollout_learner(ml, T // parts) for _ in range(parts)]
-        res.append(({k: np.concatenate([_np(o[k]) for o in outs]) for k in outs[0]}, [_np(x) for x in ml.get_state()]))
-        assert env.check_errors() == 0
-        ml.close()
-        env.close()
-    (o1, s1), (o2, s2) = res
-    assert (o1["terminated"] | o1["truncated"]).sum() > 0
-    for k in o1:
-        assert np.array_equal(o1[k], o2[k]), k
-    for x, y in zip(s1, s2):
-        assert np.array_equal(x, y)
-
-
 def test_learning_is_real():
     """greedy reward per step over 100 steps, of agents trained for 1,500 steps against that of freshly made ones (vm = 0:
     action 0 until their first episode end), same tasks and seed, on the scale of the random and the optimal teacher.
@@ -315,85 +252,3 @@ def test_state_round_trip_and_masked_reset():
     assert env.check_errors() == 0
     ml.close()
     env.close()
-
-
-def test_refusals_before_any_launch():
-    tasks = _tasks16()
-    _, ptask = load_anymdp_tok_golden(golden_files("anymdptok_pomdp")[0])
-    penv = AnyMDPVecEnv(4, autoreset_mode="same_step")
-    penv.set_task(ptask)
-    with pytest.raises(ValueError):
-        AnyMDPMBRLLearner(penv)
-    h = C.c_void_p()
-    assert penv.lib.xv_anymdp_mbrl_create(penv._h, 0.99, 1.0, C.byref(h)) == _lib.XV_ERR_UNSUPPORTED
-    assert not h.value
-    penv.close()
-    for mode in ("disabled", "next_step"):
-        env = _env(tasks, 8, seed=1, mode=mode)
-        env.reset()
-        ml = AnyMDPMBRLLearner(env)
-        with pytest.raises(ValueError):
-            env.rollout_learner(ml, 4)
-        ml.close()
-        env.close()
-    env = _env(tasks, 8, seed=1)
-    env.reset()
-    ml = AnyMDPMBRLLearner(env)
-    tick = env.engine.tick
-    good = dict(u_policy=np.zeros((4, 8, 4)), u=np.zeros((4, 8)), z=np.zeros((4, 8), np.float32), u_reset=np.zeros((4, 8)))
-    for k in good:
-        bad = dict(good)
-        bad[k] = np.zeros((4, 8)) if k == "u_policy" else np.zeros((4, 7))
-        with pytest.raises(ValueError):
-            env.rollout_learner(ml, 4, draws=bad)
-        bad.pop(k)
-        with pytest.raises(ValueError):
-            env.rollout_learner(ml, 4, draws=bad)
-    with pytest.raises(ValueError):
-        env.rollout_learner(ml, 0)
-    subs = env.split(2)
-    with pytest.raises(ValueError):
-        AnyMDPMBRLLearner(subs[0])
-    with pytest.raises(ValueError):
-        subs[0].rollout_learner(ml, 4)
-    assert env.engine.tick == tick
-    assert np.all(_np(ml.vis_cnt_sa) == 1)
-    env._drop_views()
-    # too large N S A S: refused with XV_ERR_NOMEM before anything is allocated
-    big = AnyMDPVecEnv(1 << 20, seed=1, autoreset_mode="same_step")     # 2^20 x 64 x 8 x 64 x 16 B = 512 GiB of tables
-    big.set_task([load_anymdp_golden(golden_files("anymdp_64x8")[0])[1]])
-    free = torch.cuda.mem_get_info()[0]
-    with pytest.raises(_lib.XenoError) as ex:
-        AnyMDPMBRLLearner(big)
-    assert ex.value.code == _lib.XV_ERR_NOMEM
-    assert abs(torch.cuda.mem_get_info()[0] - free) < (1 << 30)
-    big.close()
-    assert env.check_errors() == 0
-    ml.close()
-    env.close()
-
-
-def test_learner_does_not_outlive_its_env_tasks():
-    tasks = _tasks16()
-    env = _env(tasks, 8, seed=2)
-    env.reset()
-    ml = AnyMDPMBRLLearner(env)
-    env.rollout_learner(ml, 4)
-    for _ in range(2):
-        env.set_task(tasks)
-        env.reset()
-    uses = (lambda: env.rollout_learner(ml, 4), ml.get_state, ml.reset, lambda: ml.vm, lambda: ml.est_r,
-            lambda: ml.set_state(vm=np.zeros((8, 16, 4))))
-    for use in uses:
-        with pytest.raises(ValueError, match="new tasks"):
-            use()
-    ml2 = AnyMDPMBRLLearner(env)
-    out = env.rollout_learner(ml2, 8)
-    assert out["action"].shape == (8, 8)
-    assert np.array_equal(_np(ml2.vis_cnt_sa).sum(axis=(1, 2)), np.full(8, 16 * 4 + 8.0))
-    assert env.check_errors() == 0
-    env.close()
-    for use in (lambda: ml2.get_state(), ml2.reset):
-        with pytest.raises(ValueError, match="closed"):
-            use()
-    ml2.close()

@@ -1,39 +1,16 @@
 """The device Q-learner (csrc/anymdp_qlearn.hip: AnyMDPQLearner, AnyMDPVecEnv.rollout_learner) against the reference's own
 training loop (tests/golden/qlearn_anymdp_*.npz), against the host restatement (xenoverse_amd/anymdp/qlearner.py) and
-against itself."""
-import ctypes as C
-
+against itself.  The tests that are the same for every learner are in test_gpu_anymdp_learners.py."""
 import numpy as np
 import pytest
-import torch
 
-from util import close_f32, golden_files, load_anymdp_golden, load_anymdp_tok_golden
-from xenoverse_amd import _lib
-from xenoverse_amd.anymdp import AnyMDPQLearner, AnyMDPVecEnv, QLearnerHost
+from util import anymdp_env as _env, anymdp_fixture_task as _fixture_task, anymdp_tasks16 as _tasks16, to_np as _np
+from util import close_f32, golden_files, load_anymdp_golden
+from xenoverse_amd.anymdp import AnyMDPQLearner, QLearnerHost
 
 pytestmark = pytest.mark.gpu
 FILES = golden_files("qlearn_anymdp_")
 MARGIN = 1e-4
-
-
-def _np(t):
-    return t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
-
-
-def _fixture_task(g):
-    return dict(ns=int(g["ns"]), na=int(g["na"]), max_steps=float(g["max_steps"]), state_mapping=g["state_mapping"],
-                task_type="MDP", s_0=g["s_0"], s_0_prob=g["s_0_prob"], s_e=g["s_e"], transition=g["transition"],
-                reward=g["reward"], reward_noise=g["reward_noise"])
-
-
-def _tasks16():
-    return [load_anymdp_golden(p)[1] for p in golden_files("anymdp_16x4")[:4]]
-
-
-def _env(tasks, n, seed, mode="same_step"):
-    env = AnyMDPVecEnv(n, seed=seed, autoreset_mode=mode)
-    env.set_task(tasks)
-    return env
 
 
 @pytest.mark.parametrize("path", FILES, ids=lambda p: p.rsplit("/", 1)[-1])
@@ -117,50 +94,6 @@ def test_device_equals_host_restatement(cfg):
     env.close()
 
 
-def test_rollout_equals_stepping_its_actions():
-    """a twin env with the same seed and tasks stepped through step() with the rollout's actions returns the same outputs"""
-    n, T = 256, 96
-    a_env = _env(_tasks16(), n, seed=9)
-    a_env.reset()
-    ql = AnyMDPQLearner(a_env)
-    ro = {k: _np(v) for k, v in a_env.rollout_learner(ql, T).items()}
-    b_env = _env(_tasks16(), n, seed=9)
-    b_env.reset()
-    for t in range(T):
-        obs, r, term, trunc, info = b_env.step(ro["action"][t])
-        assert np.array_equal(_np(obs), ro["obs"][t]), t
-        assert np.array_equal(_np(r), ro["reward"][t]) and np.array_equal(_np(info["reward_gt"]), ro["reward_gt"][t])
-        assert np.array_equal(_np(term).astype(np.uint8), ro["terminated"][t])
-        assert np.array_equal(_np(trunc).astype(np.uint8), ro["truncated"][t])
-        done = (ro["terminated"][t] | ro["truncated"][t]).astype(bool)
-        assert np.array_equal(_np(info["final_obs"])[done], ro["final_obs"][t][done])
-    assert len(np.unique(ro["action"])) == 4
-    assert a_env.check_errors() == 0 and b_env.check_errors() == 0
-    ql.close()
-    a_env.close()
-    b_env.close()
-
-
-def test_splitting_T_changes_nothing():
-    """two calls of T / 2 equal one call of T bit for bit (free-running draws), agent state included"""
-    n, T = 512, 128
-    res = []
-    for parts in (1, 2):
-        env = _env(_tasks16(), n, seed=21)
-        env.reset()
-        ql = AnyMDPQLearner(env)
-        outs = [env.rollout_learner(ql, T // parts) for _ in range(parts)]
-        res.append(({k: np.concatenate([_np(o[k]) for o in outs]) for k in outs[0]}, [_np(x) for x in ql.get_state()]))
-        assert env.check_errors() == 0
-        ql.close()
-        env.close()
-    (o1, s1), (o2, s2) = res
-    for k in o1:
-        assert np.array_equal(o1[k], o2[k]), k
-    for x, y in zip(s1, s2):
-        assert np.array_equal(x, y)
-
-
 def test_learning_is_real():
     """greedy reward per step after 3,000 steps of learning: far above the random agent, most of the way to the optimal
     teacher.  Thresholds from the host restatement on the same tasks (mean gap closed 0.55-0.74 over 16 runs)"""
@@ -210,97 +143,3 @@ def test_state_round_trip_and_masked_reset():
     assert env.check_errors() == 0
     ql.close()
     env.close()
-
-
-def test_refusals_before_any_launch():
-    tasks = _tasks16()
-    # POMDP: the reference asserts task_type == "MDP" (anymdp_solver_q.py:17); the C-ABI refuses as well
-    _, ptask = load_anymdp_tok_golden(golden_files("anymdptok_pomdp")[0])
-    penv = AnyMDPVecEnv(4, autoreset_mode="same_step")
-    penv.set_task(ptask)
-    with pytest.raises(AssertionError):
-        AnyMDPQLearner(penv)
-    h = C.c_void_p()
-    assert penv.lib.xv_anymdp_qlearn_create(penv._h, 0.99, 0.5, 4000, C.byref(h)) == _lib.XV_ERR_UNSUPPORTED
-    assert not h.value
-    penv.close()
-    # auto-reset modes other than SAME_STEP
-    for mode in ("disabled", "next_step"):
-        env = _env(tasks, 8, seed=1, mode=mode)
-        env.reset()
-        ql = AnyMDPQLearner(env)
-        with pytest.raises(ValueError):
-            env.rollout_learner(ql, 4)
-        ql.close()
-        env.close()
-    env = _env(tasks, 8, seed=1)
-    env.reset()
-    ql = AnyMDPQLearner(env)
-    tick = env.engine.tick
-    # wrong shapes, a missing draw, T < 1, another env's learner
-    good = dict(u_policy=np.zeros((4, 8)), u=np.zeros((4, 8)), z=np.zeros((4, 8), np.float32), u_reset=np.zeros((4, 8)))
-    for k in good:
-        bad = dict(good)
-        bad[k] = np.zeros((4, 7))
-        with pytest.raises(ValueError):
-            env.rollout_learner(ql, 4, draws=bad)
-        bad.pop(k)
-        with pytest.raises(ValueError):
-            env.rollout_learner(ql, 4, draws=bad)
-    with pytest.raises(ValueError):
-        env.rollout_learner(ql, 0)
-    other = _env(tasks, 8, seed=1)
-    other.reset()
-    oql = AnyMDPQLearner(other)
-    with pytest.raises(ValueError):
-        env.rollout_learner(oql, 4)
-    # sub-batches (split) are refused: learners live on the whole env
-    subs = env.split(2)
-    with pytest.raises(ValueError):
-        AnyMDPQLearner(subs[0])
-    with pytest.raises(ValueError):
-        subs[0].rollout_learner(ql, 4)
-    assert env.engine.tick == tick     # nothing was launched
-    q, sa, sv = (_np(x) for x in ql.get_state())
-    assert np.all(sa == 1) and np.all(sv == 1)
-    # a learner of an env that was given new tasks is refused
-    env._drop_views()
-    env.set_task(tasks)
-    env.reset()
-    with pytest.raises(ValueError):
-        env.rollout_learner(ql, 4)
-    assert env.check_errors() == 0 and other.check_errors() == 0
-    oql.close()
-    ql.close()
-    other.close()
-    env.close()
-
-
-def test_learner_does_not_outlive_its_env_tasks():
-    """set_task (twice: a recycled handle address must not revive the learner) and close release the learner before the
-    env's handle goes; every later use raises, a new learner works"""
-    tasks = _tasks16()
-    env = _env(tasks, 8, seed=2)
-    env.reset()
-    ql = AnyMDPQLearner(env)
-    env.rollout_learner(ql, 4)
-    for _ in range(2):
-        env.set_task(tasks)
-        env.reset()
-    uses = (lambda: env.rollout_learner(ql, 4), ql.get_state, ql.reset, lambda: ql.q, lambda: ql.s_visits,
-            lambda: ql.set_state(q=np.zeros((8, 16, 4))))
-    for use in uses:
-        with pytest.raises(ValueError, match="new tasks"):
-            use()
-    ql2 = AnyMDPQLearner(env)
-    out = env.rollout_learner(ql2, 8)
-    assert out["action"].shape == (8, 8)
-    sv = _np(ql2.s_visits)
-    assert sv.shape == (8, 16) and int(sv.sum()) == 8 * 16 + 8 * 8      # one visit per env-step on top of the ones
-    assert np.array_equal(_np(ql2.sa_visits).sum(axis=(1, 2)), 64 + np.full(8, 8))
-    assert env.check_errors() == 0
-    env.close()
-    for use in (lambda: ql2.get_state(), ql2.reset):
-        with pytest.raises(ValueError, match="closed"):
-            use()
-    ql2.close()

@@ -11,13 +11,32 @@ def golden_files(prefix):
     return sorted(glob.glob(os.path.join(GOLD, prefix + "*.npz")))
 
 
+def anymdp_fixture_task(g):
+    """the MDP task dict of a loaded anymdp_* / qlearn_anymdp_* / mbrl_anymdp_* fixture"""
+    return dict(ns=int(g["ns"]), na=int(g["na"]), max_steps=float(g["max_steps"]), state_mapping=g["state_mapping"],
+                task_type="MDP", s_0=g["s_0"], s_0_prob=g["s_0_prob"], s_e=g["s_e"], transition=g["transition"],
+                reward=g["reward"], reward_noise=g["reward_noise"])
+
+
 def load_anymdp_golden(path):
     g = dict(np.load(path, allow_pickle=False))
-    task = dict(ns=int(g["ns"]), na=int(g["na"]), max_steps=float(g["max_steps"]),
-                state_mapping=g["state_mapping"], task_type="MDP", s_0=g["s_0"], s_0_prob=g["s_0_prob"],
-                s_e=g["s_e"], transition=g["transition"], reward=g["reward"],
-                reward_noise=g["reward_noise"])
-    return g, task
+    return g, anymdp_fixture_task(g)
+
+
+def anymdp_tasks16():
+    return [load_anymdp_golden(p)[1] for p in golden_files("anymdp_16x4")[:4]]
+
+
+def anymdp_env(tasks, n, seed, mode="same_step"):
+    from xenoverse_amd.anymdp import AnyMDPVecEnv
+    env = AnyMDPVecEnv(n, seed=seed, autoreset_mode=mode)
+    env.set_task(tasks)
+    return env
+
+
+def to_np(t):
+    import torch
+    return t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
 
 
 def close_f32(a, b, rel=1e-5, abs_=1e-6):

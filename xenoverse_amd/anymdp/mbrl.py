@@ -17,46 +17,15 @@ what the golden fixtures are replayed with.  Per agent (states are observations,
                              vm[s, a] += exp_q - vm[s, a]   (max(vm[sn]) reads the rows this sweep already moved)
     policy :73-78            greedy: the first argmax of vm[o];  else the first argmax of vm[o] + b[o] u, u = A uniforms
 
-The row sum is numpy's pairwise sum of a length-S row (`pairwise_sum`).  np.std of the whole [S, A, S] tensor runs in
+The row sum is numpy's pairwise sum of a length-S row (`pairwise_sum`, learner.py).  np.std of the whole [S, A, S] tensor runs in
 buffered chunks of 8192 elements: each chunk is pairwise-summed and the chunks are added in order (`np_tensor_sum`), for
 the mean and again for the squared deviations.  Everything is + - * / sqrt max, so the device can be bit-exact.
 """
 import numpy as np
 
+from .learner import _DeviceLearner, np_rowsum, pairwise_sum  # noqa: F401
+
 NP_BUFSIZE = 8192    # numpy's default ufunc buffer: the inner-loop length of a whole-array reduction
-
-
-def pairwise_sum(x):
-    """numpy's pairwise_sum of each row of x[..., n] (any n): a plain loop below 8 elements, eight partial sums up to 128,
-    above that split at n / 2 rounded down to a multiple of 8"""
-    n = x.shape[-1]
-    if n < 8:
-        res = np.zeros(x.shape[:-1])
-        for i in range(n):
-            res = res + x[..., i]
-        return res
-    if n <= 128:
-        r = [x[..., j].copy() for j in range(8)]
-        i = 8
-        while i < n - (n % 8):
-            for j in range(8):
-                r[j] = r[j] + x[..., i + j]
-            i += 8
-        res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]))
-        for k in range(i, n):
-            res = res + x[..., k]
-        return res
-    n2 = n // 2
-    n2 -= n2 % 8
-    if 2 * n2 == n:      # two equal halves: one call over both
-        h = pairwise_sum(x.reshape(x.shape[:-1] + (2, n2)))
-        return h[..., 0] + h[..., 1]
-    return pairwise_sum(x[..., :n2]) + pairwise_sum(x[..., n2:])
-
-
-def np_rowsum(x):
-    """numpy.sum(x, axis=-1) of a contiguous x: add.reduce of each row onto the identity 0"""
-    return 0.0 + pairwise_sum(x)
 
 
 def np_tensor_sum(x):
@@ -168,7 +137,7 @@ class MBRLHost(object):
                 dst[...] = src
 
 
-class AnyMDPMBRLLearner(object):
+class AnyMDPMBRLLearner(_DeviceLearner):
     """One AnyMDPSolverMBRL agent per env of an AnyMDPVecEnv, on the device (csrc/anymdp_mbrl.hip): the reference's
     AnyMDPSolverMBRL(env, gamma, c) for every env at once (the reference's train() passes c = 0.05; the class default is 1).
     Drive it with `env.rollout_learner(learner, T)`; there draws["u_policy"] is [T, N, A].
@@ -178,112 +147,16 @@ class AnyMDPMBRLLearner(object):
     bonus the last episode end computed.  The learner lives as long as its env's tasks: `env.set_task` and `env.close` close
     it (any later use raises).  Rows are indexed by observation id, so MDP tasks only; the env must have been set a task, and
     a sub-batch made by split() cannot carry learners (make them on the env it was split from)."""
+    _ABI = "xv_anymdp_mbrl"
+    _ROLLOUT = "xv_anymdp_rollout_mbrl"
+    _TABLES = (("est_r", "float64", "NSAS"), ("vis_cnt", "float64", "NSAS"), ("vis_cnt_sa", "float64", "NSA"),
+               ("vm", "float64", "NSA"), ("b", "float64", "NSA"))
+    _U_POLICY = "TNA"
+    _NOT_MDP = (ValueError, "AnyMDPMBRLLearner: MDP tasks only (the model's states are observation ids)")
 
     def __init__(self, env, gamma=0.99, c=1.0):
-        import ctypes as C
-
-        from .. import _lib
-        env._require_task()
-        if getattr(env, "_parent", None) is not None:
-            raise ValueError("AnyMDPMBRLLearner: a sub-batch made by split() cannot carry learners; "
-                             "make them on the env it was split from")
-        if env.task_type != "MDP":
-            raise ValueError("AnyMDPMBRLLearner: MDP tasks only (the model's states are observation ids)")
+        self._check_env(env)
         if not (0.0 <= gamma < 1.0) or c != c:
             raise ValueError("AnyMDPMBRLLearner: need 0 <= gamma < 1 and a number c")
-        self.env, self.lib = env, env.lib
         self.gamma, self.c = float(gamma), float(c)
-        self.num_envs, self.S, self.A = env.num_envs, env.S, env.A
-        # the env's handle object itself: set_task makes a new one, and holding it keeps `is` from ever matching a recycled one
-        self._env_h = env._h
-        self._h, self._closed_why = None, "AnyMDPMBRLLearner: closed"
-        h = C.c_void_p()
-        _lib.check(self.lib.xv_anymdp_mbrl_create(env._h, self.gamma, self.c, C.byref(h)))
-        self._h = h
-        env._learners.add(self)      # released before the env's handle goes (set_task, close)
-
-    def _shapes(self):
-        n, S, A = self.num_envs, self.S, self.A
-        return ((n, S, A, S), (n, S, A, S), (n, S, A), (n, S, A), (n, S, A))
-
-    def _live(self):
-        if self._h is None:
-            raise ValueError(self._closed_why)
-        if self.env._h is not self._env_h:
-            raise ValueError("AnyMDPMBRLLearner: its env was closed or given new tasks; make a new learner")
-
-    def reset(self, mask=None):
-        """__init__'s state for the agents where mask (bool[N]) is set (None: all)"""
-        import torch
-
-        from .. import _lib
-        self._live()
-        m = None if mask is None else self.env._dev(mask, torch.uint8)
-        if m is not None and tuple(m.shape) != (self.num_envs,):
-            raise ValueError("reset mask must have shape (num_envs,)")
-        _lib.check(self.lib.xv_anymdp_mbrl_reset(self._h, _lib.ptr(m)))
-        self.env.engine.sync()
-
-    def _get(self, which):
-        import torch
-
-        from .. import _lib
-        self._live()
-        out = [torch.empty(shp, dtype=torch.float64, device=self.env.device) if j in which else None
-               for j, shp in enumerate(self._shapes())]
-        _lib.check(self.lib.xv_anymdp_mbrl_get_state(self._h, *(_lib.ptr(t) for t in out)))
-        self.env.engine.sync()
-        return out
-
-    def get_state(self):
-        """-> (est_r, vis_cnt float64[N, S, A, S], vis_cnt_sa, vm, b float64[N, S, A]) device tensors (copies)"""
-        return tuple(self._get(range(5)))
-
-    def set_state(self, est_r=None, vis_cnt=None, vis_cnt_sa=None, vm=None, b=None):
-        import torch
-
-        from .. import _lib
-        self._live()
-        args = []
-        for x, shp in zip((est_r, vis_cnt, vis_cnt_sa, vm, b), self._shapes()):
-            if x is None:
-                args.append(None)
-                continue
-            t = self.env._dev(x, torch.float64)
-            if tuple(t.shape) != shp:
-                raise ValueError("set_state: expected shape %s, got %s" % (shp, tuple(t.shape)))
-            args.append(t)
-        _lib.check(self.lib.xv_anymdp_mbrl_set_state(self._h, *(_lib.ptr(t) for t in args)))
-        self.env.engine.sync()      # the temporaries above must outlive the copies
-
-    @property
-    def est_r(self):
-        return self._get((0,))[0]
-
-    @property
-    def vis_cnt(self):
-        return self._get((1,))[1]
-
-    @property
-    def vis_cnt_sa(self):
-        return self._get((2,))[2]
-
-    @property
-    def vm(self):
-        return self._get((3,))[3]
-
-    @property
-    def b(self):
-        return self._get((4,))[4]
-
-    def close(self, why="AnyMDPMBRLLearner: closed"):
-        if self._h is not None:
-            self.lib.xv_anymdp_mbrl_destroy(self._h)
-            self._h = None
-            self._closed_why = why
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._create(env, self.gamma, self.c)

@@ -13,33 +13,13 @@ what the golden fixtures are replayed with.  Per agent (states are observations,
                      p = exp(v) / sum(exp(v));  numpy.random.choice(A, p=p) = #{cumsum(p) / cumsum(p)[-1] <= u}
 
 with M the learner's own max_steps (4000), not the env's.  Sums, means and the population std follow numpy's pairwise
-summation of a length-A row (`np_sum`): a plain loop below 8 elements, eight partial sums from 8 up (A <= 64 < 128).
+summation of a length-A row (`np_sum`, learner.py): a plain loop below 8 elements, eight partial sums from 8 up (A <= 64 < 128).
 """
 import numpy as np
 
+from .learner import _DeviceLearner, np_rowsum as np_sum  # noqa: F401  (np_sum: numpy's sum of each row of x[..., n])
+
 A_MAX = 64   # the widest row the device learner takes (xv_anymdp_create: A <= 64)
-
-
-def np_sum(x):
-    """numpy's sum of each row of x[..., n] (add.reduce over a contiguous row: pairwise_sum, initial 0), n <= 128"""
-    n = x.shape[-1]
-    if n < 8:
-        res = np.zeros(x.shape[:-1])
-        for i in range(n):
-            res = res + x[..., i]
-        return 0.0 + res
-    if n > 128:
-        raise ValueError("np_sum: rows of more than 128 elements are not restated")
-    r = [x[..., j].copy() for j in range(8)]
-    i = 8
-    while i < n - (n % 8):
-        for j in range(8):
-            r[j] = r[j] + x[..., i + j]
-        i += 8
-    res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]))
-    for k in range(i, n):
-        res = res + x[..., k]
-    return 0.0 + res
 
 
 def policy_cdf(q_rows, s_visits, max_steps):
@@ -112,123 +92,24 @@ class QLearnerHost(object):
         self.s_visits[...] = s_visits
 
 
-class AnyMDPQLearner(object):
+class AnyMDPQLearner(_DeviceLearner):
     """One AnyMDPSolverQ agent per env of an AnyMDPVecEnv, on the device (csrc/anymdp_qlearn.hip): the reference's
     AnyMDPSolverQ(env, gamma, alpha, max_steps) for every env at once.  Drive it with `env.rollout_learner(learner, T)`.
 
     `q` (float64[N, S, A]), `sa_visits` (int32[N, S, A]) and `s_visits` (int32[N, S]) are device copies of one table of the
-    agent state taken when read; `get_state` copies all three, `set_state` writes them.  The learner lives as long as its
-    env's tasks: `env.set_task` and `env.close` close it (any later use raises).  Rows are indexed by observation id.  MDP tasks only (the reference asserts
-    task_type == "MDP"); the env must have been set a task, and a sub-batch made by split() cannot carry learners (make them
-    on the env it was split from)."""
+    agent state taken when read; `get_state` copies all three, `set_state` writes them; `reset` restores __init__'s state
+    (Q = 1 / (1 - gamma), counts 1).  The learner lives as long as its env's tasks: `env.set_task` and `env.close` close it
+    (any later use raises).  Rows are indexed by observation id.  MDP tasks only (the reference asserts task_type == "MDP");
+    the env must have been set a task, and a sub-batch made by split() cannot carry learners (make them on the env it was
+    split from)."""
+    _ABI = "xv_anymdp_qlearn"
+    _ROLLOUT = "xv_anymdp_rollout_qlearn"
+    _TABLES = (("q", "float64", "NSA"), ("sa_visits", "int32", "NSA"), ("s_visits", "int32", "NS"))
+    _NOT_MDP = (AssertionError, "The solver only works for MDP")       # anymdp_solver_q.py:17
 
     def __init__(self, env, gamma=0.99, alpha=0.5, max_steps=4000):
-        import ctypes as C
-
-        from .. import _lib
-        env._require_task()
-        if getattr(env, "_parent", None) is not None:
-            raise ValueError("AnyMDPQLearner: a sub-batch made by split() cannot carry learners; "
-                             "make them on the env it was split from")
-        if env.task_type != "MDP":
-            raise AssertionError("The solver only works for MDP")       # anymdp_solver_q.py:17
+        self._check_env(env)
         if not (0.0 <= gamma < 1.0) or int(max_steps) < 0:
             raise ValueError("AnyMDPQLearner: need 0 <= gamma < 1 and max_steps >= 0")
-        self.env, self.lib = env, env.lib
         self.gamma, self.alpha, self.max_steps = float(gamma), float(alpha), int(max_steps)
-        self.num_envs, self.S, self.A = env.num_envs, env.S, env.A
-        # the env's handle object itself: set_task makes a new one, and holding it keeps `is` from ever matching a recycled one
-        self._env_h = env._h
-        self._h, self._closed_why = None, "AnyMDPQLearner: closed"
-        h = C.c_void_p()
-        _lib.check(self.lib.xv_anymdp_qlearn_create(env._h, self.gamma, self.alpha, self.max_steps, C.byref(h)))
-        self._h = h
-        env._learners.add(self)      # released before the env's handle goes (set_task, close)
-
-    def _live(self):
-        if self._h is None:
-            raise ValueError(self._closed_why)
-        if self.env._h is not self._env_h:
-            raise ValueError("AnyMDPQLearner: its env was closed or given new tasks; make a new learner")
-
-    def reset(self, mask=None):
-        """__init__'s state (Q = 1 / (1 - gamma), counts 1) for the agents where mask (bool[N]) is set (None: all)"""
-        import torch
-
-        from .. import _lib
-        self._live()
-        m = None if mask is None else self.env._dev(mask, torch.uint8)
-        if m is not None and tuple(m.shape) != (self.num_envs,):
-            raise ValueError("reset mask must have shape (num_envs,)")
-        _lib.check(self.lib.xv_anymdp_qlearn_reset(self._h, _lib.ptr(m)))
-        self.env.engine.sync()
-
-    def get_state(self):
-        """-> (q float64[N, S, A], sa_visits int32[N, S, A], s_visits int32[N, S]) device tensors (copies)"""
-        import torch
-
-        from .. import _lib
-        self._live()
-        n, S, A, d = self.num_envs, self.S, self.A, self.env.device
-        q = torch.empty((n, S, A), dtype=torch.float64, device=d)
-        sa = torch.empty((n, S, A), dtype=torch.int32, device=d)
-        sv = torch.empty((n, S), dtype=torch.int32, device=d)
-        _lib.check(self.lib.xv_anymdp_qlearn_get_state(self._h, _lib.ptr(q), _lib.ptr(sa), _lib.ptr(sv)))
-        self.env.engine.sync()
-        return q, sa, sv
-
-    def set_state(self, q=None, sa_visits=None, s_visits=None):
-        import torch
-
-        from .. import _lib
-        self._live()
-        n, S, A = self.num_envs, self.S, self.A
-        args = []
-        for x, dt, shp in ((q, torch.float64, (n, S, A)), (sa_visits, torch.int32, (n, S, A)), (s_visits, torch.int32, (n, S))):
-            if x is None:
-                args.append(None)
-                continue
-            t = self.env._dev(x, dt)
-            if tuple(t.shape) != shp:
-                raise ValueError("set_state: expected shape %s, got %s" % (shp, tuple(t.shape)))
-            args.append(t)
-        _lib.check(self.lib.xv_anymdp_qlearn_set_state(self._h, *(_lib.ptr(t) for t in args)))
-        self.env.engine.sync()      # the temporaries above must outlive the copies
-
-    def _table(self, j):
-        """a device copy of one table: 0 q, 1 sa_visits, 2 s_visits"""
-        import torch
-
-        from .. import _lib
-        self._live()
-        n, S, A, d = self.num_envs, self.S, self.A, self.env.device
-        t = torch.empty((n, S, A) if j < 2 else (n, S), dtype=torch.float64 if j == 0 else torch.int32, device=d)
-        p = [None, None, None]
-        p[j] = t
-        _lib.check(self.lib.xv_anymdp_qlearn_get_state(self._h, *(_lib.ptr(x) for x in p)))
-        self.env.engine.sync()
-        return t
-
-    @property
-    def q(self):
-        return self._table(0)
-
-    @property
-    def sa_visits(self):
-        return self._table(1)
-
-    @property
-    def s_visits(self):
-        return self._table(2)
-
-    def close(self, why="AnyMDPQLearner: closed"):
-        if self._h is not None:
-            self.lib.xv_anymdp_qlearn_destroy(self._h)
-            self._h = None
-            self._closed_why = why
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._create(env, self.gamma, self.alpha, self.max_steps)

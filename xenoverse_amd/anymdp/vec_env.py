@@ -15,7 +15,6 @@ from ..engine import AUTORESET
 from ..spaces import Discrete, MultiDiscrete
 from ..vector import OutputSlabs, VectorEnv
 from .tables import build_obs_tables, build_tables, build_tables_device, device_buildable
-from .mbrl import AnyMDPMBRLLearner
 
 _TABLE_KEYS = ("rows", "state_map", "term_mask", "s0_cdf", "s0_ids", "max_steps")
 _TABLE_DTYPES = dict(rows=torch.float64, state_map=torch.int32, term_mask=torch.int64,
@@ -595,7 +594,6 @@ class AnyMDPVecEnv(VectorEnv):
         T, n, d = int(T), self.num_envs, self.device
         if T < 1:
             raise ValueError("rollout_learner: T must be >= 1")
-        mbrl = isinstance(learner, AnyMDPMBRLLearner)
         dr = [None] * 4
         if draws is not None:
             dts = dict(u_policy=torch.float64, u=torch.float64, z=torch.float32, u_reset=torch.float64)
@@ -605,7 +603,7 @@ class AnyMDPVecEnv(VectorEnv):
                 if draws.get(k) is None:
                     raise ValueError("rollout_learner: draws[%r] missing" % k)
                 dr[j] = self._dev(draws[k], dts[k])
-                shape = (T, n, self.A) if (mbrl and k == "u_policy") else (T, n)
+                shape = learner._shape(learner._U_POLICY, T) if k == "u_policy" else (T, n)
                 if tuple(dr[j].shape) != shape:
                     raise ValueError("rollout_learner: draws[%r] has shape %s, expected %s" % (k, tuple(dr[j].shape), shape))
         out = dict(action=torch.empty((T, n), dtype=torch.int32, device=d),
@@ -615,8 +613,7 @@ class AnyMDPVecEnv(VectorEnv):
                    terminated=torch.empty((T, n), dtype=torch.uint8, device=d),
                    truncated=torch.empty((T, n), dtype=torch.uint8, device=d),
                    final_obs=torch.empty((T, n), dtype=torch.int32, device=d))
-        rollout = self.lib.xv_anymdp_rollout_mbrl if mbrl else self.lib.xv_anymdp_rollout_qlearn
-        _lib.check(rollout(
+        _lib.check(getattr(self.lib, learner._ROLLOUT)(
             self._h, learner._h, T, 1 if greedy else 0, *(_lib.ptr(x) for x in dr), _lib.ptr(out["action"]),
             _lib.ptr(out["obs"]), _lib.ptr(out["reward"]), _lib.ptr(out["reward_gt"]), _lib.ptr(out["terminated"]),
             _lib.ptr(out["truncated"]), _lib.ptr(out["final_obs"])))

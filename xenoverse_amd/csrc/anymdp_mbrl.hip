@@ -27,6 +27,7 @@
 #define XV_KERNELS_ONLY
 #include "anymdp.hip"
 #undef XV_KERNELS_ONLY
+#include "anymdp_learner.h"
 
 #define XV_DRAW_MBRL_POLICY 7u   // sub = a >> 1: words 0,1 (a even) or 2,3 (a odd) -> the policy's uniform u[a]
 #define MBRL_CHUNK 8192          // numpy's ufunc buffer: a whole-array sum runs over chunks of this many elements
@@ -66,6 +67,7 @@ struct xv_anymdp_mbrl {
   double* scratch;     // [grid][A][S] the row's products when they do not fit LDS, else nullptr
   int grid;            // estimator workgroups (one wave each)
   size_t lds;          // estimator LDS bytes
+  int u_per_env() const { return A; }   // the policy's uniforms per env and step: one per action
 };
 
 struct MBArgs {
@@ -82,42 +84,26 @@ struct MBArgs {
   const MBRLPlan* plan;
   double* scratch;
   double gamma, cc;
-  int n_env, S, A;
-  uint64_t seed, gid_base, tick;
-  const uint64_t* tick_dev;
-};
-
-struct MBStepIO {
-  // the step just made (learning launches)
-  const int32_t* act_prev;
-  const int32_t* obs;        // also where the next action is chosen from; nullptr: the env's current state (first launch)
-  const int32_t* final_obs;
-  const float* reward;
-  const uint8_t* terminated;
-  const uint8_t* truncated;
-  // the next action
-  const double* u_policy;    // injected uniforms [n_env][A] or nullptr (Philox)
-  int32_t* action_out;
-  int greedy;
+  XvLearnerBind B;
 };
 
 // policy() :73-78 of env i from observation o: the first argmax of vm[o] (greedy) or of vm[o] + b[o] u
 template <bool INJECT>
-__device__ int mbrl_policy(const MBArgs& L, const MBStepIO& io, int i, int o) {
-  const size_t row = ((size_t)i * L.S + o) * L.A;
-  const uint64_t tick = xv_launch_tick(L.tick, L.tick_dev);
+__device__ int mbrl_policy(const MBArgs& L, const XvLearnStepIO& io, int i, int o) {
+  const size_t row = ((size_t)i * L.B.S + o) * L.B.A;
+  const uint64_t tick = xv_launch_tick(L.B.tick, L.B.tick_dev);
   int best = 0;
   double m = 0.0;
   xv_u32x4 w{0u, 0u, 0u, 0u};
-  for (int k = 0; k < L.A; ++k) {
+  for (int k = 0; k < L.B.A; ++k) {
     double v = L.vm[row + k];
     if (!io.greedy) {
       double u;
       if (INJECT) {
-        u = io.u_policy[(size_t)i * L.A + k];
+        u = io.u_policy[(size_t)i * L.B.A + k];
       } else {
         if ((k & 1) == 0)
-          w = xv_env_draw_sub(L.seed, L.gid_base + (uint64_t)i, tick, XV_DRAW_MBRL_POLICY, (uint32_t)(k >> 1));
+          w = xv_env_draw_sub(L.B.seed, L.B.gid_base + (uint64_t)i, tick, XV_DRAW_MBRL_POLICY, (uint32_t)(k >> 1));
         u = (k & 1) ? xv_u53(w.z, w.w) : xv_u53(w.x, w.y);
       }
       v = v + L.b[row + k] * u;
@@ -128,11 +114,11 @@ __device__ int mbrl_policy(const MBArgs& L, const MBStepIO& io, int i, int o) {
 }
 
 template <bool LEARN, bool ACT, bool INJECT>
-__global__ __launch_bounds__(256) void anymdp_mbrl_learn_kernel(AnyMDPArgs P, MBArgs L, MBStepIO io) {
+__global__ __launch_bounds__(256) void anymdp_mbrl_learn_kernel(AnyMDPArgs P, MBArgs L, XvLearnStepIO io) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (LEARN && i == 0) *L.count_next = 0u;      // its last readers (the previous step's estimator) have finished
-  if (i >= L.n_env) return;
-  const int S = L.S, A = L.A;
+  if (i >= L.B.n_env) return;
+  const int S = L.B.S, A = L.B.A;
   if (LEARN) {   // learner(s, a, ns, r, terminated, truncated) :57-71
     const int s = L.cur_obs[i], a = io.act_prev[i];
     const bool term = io.terminated[i] != 0, done = term || io.truncated[i] != 0;
@@ -153,13 +139,7 @@ __global__ __launch_bounds__(256) void anymdp_mbrl_learn_kernel(AnyMDPArgs P, MB
     }
   }
   if (ACT) {
-    int o;
-    if (io.obs) {
-      o = io.obs[i];
-    } else {
-      const int t = P.env_task[i], st = (int)(P.sr[i].x & 0xFFFFu);
-      o = P.state_map[(size_t)t * P.S + st];
-    }
+    const int o = xv_learner_act_obs(P, io.obs, i);
     L.cur_obs[i] = o;
     io.action_out[i] = (unsigned)o < (unsigned)S ? mbrl_policy<INJECT>(L, io, i, o) : 0;
   } else if (LEARN) {
@@ -243,9 +223,9 @@ __device__ double mbrl_tensor_sum(const F& f, const MBRLPlan* plan, double* leaf
 // update_estimator() :42-55 (after the terminal reset of :64-66) for the envs on this step's list, one wave each; then the
 // policy from the observation the step returned
 template <bool ACT, bool INJECT, bool LDS_P>
-__global__ __launch_bounds__(64) void anymdp_mbrl_estimator_kernel(MBArgs L, MBStepIO io) {
+__global__ __launch_bounds__(64) void anymdp_mbrl_estimator_kernel(MBArgs L, XvLearnStepIO io) {
   extern __shared__ double sm[];
-  const int S = L.S, A = L.A, lane = threadIdx.x;
+  const int S = L.B.S, A = L.B.A, lane = threadIdx.x;
   double* M = sm;                      // [S] max(vm[sn]) as the sweep stands
   double* den = M + S;                 // [A] clip(rowsum(vis_cnt[s, a]), 0.01) of the current row
   double* pre = den + A;               // [A] 0 + the products of sn < s
@@ -352,7 +332,7 @@ __global__ __launch_bounds__(64) void anymdp_mbrl_estimator_kernel(MBArgs L, MBS
 // __init__ :13-40 for the masked agents (nullptr: all): est_r = 0, vis_cnt = 0.01, vis_cnt_sa = 1, and what the first
 // update_estimator() makes of that: vm = 0, b = (_c max(std(0), 0.01)) / sqrt(1)
 static __global__ __launch_bounds__(256) void anymdp_mbrl_reset_kernel(MBArgs L, const uint8_t* mask) {
-  const size_t per = (size_t)L.S * L.A * L.S, per_sa = (size_t)L.S * L.A, total = (size_t)L.n_env * per;
+  const size_t per = (size_t)L.B.S * L.B.A * L.B.S, per_sa = (size_t)L.B.S * L.B.A, total = (size_t)L.B.n_env * per;
   const double b0 = (L.cc * 0.01) / sqrt(1.0);
   for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
     const size_t i = idx / per;
@@ -375,12 +355,7 @@ static MBArgs mbrl_args(xv_anymdp_mbrl* m) {
   L.count = m->count + m->parity; L.count_next = m->count + (m->parity ^ 1);
   L.plan = m->plan; L.scratch = m->scratch;
   L.gamma = m->gamma; L.cc = m->cc;
-  L.n_env = m->n_env; L.S = m->S; L.A = m->A;
-  xv_engine* e = m->h->eng;
-  L.seed = e->seed; L.gid_base = e->env_id_base;
-  // the tick the NEXT step launch will draw with (no advance: that launch advances it)
-  const XvTickBind b = xv_engine_bind_tick(e, 0);
-  L.tick = b.tick; L.tick_dev = b.tick_dev;
+  L.B = xv_learner_bind(m->h);
   return L;
 }
 
@@ -415,9 +390,7 @@ static void mbrl_free(xv_anymdp_mbrl* m) {
 
 extern "C" int xv_anymdp_mbrl_reset(xv_anymdp_mbrl* m, const uint8_t* mask) {
   XV_CHECK_ARG(m != nullptr);
-  const size_t n = (size_t)m->n_env * m->S * m->A * m->S, blocks = (n + 255) / 256;
-  // grid-stride: n_env S A S may exceed what one grid dimension holds
-  hipLaunchKernelGGL(anymdp_mbrl_reset_kernel, dim3((unsigned)(blocks < (1u << 20) ? blocks : (1u << 20))), dim3(256), 0,
+  hipLaunchKernelGGL(anymdp_mbrl_reset_kernel, dim3(xv_learner_blocks((size_t)m->n_env * m->S * m->A * m->S)), dim3(256), 0,
                      m->h->eng->stream, mbrl_args(m), mask);
   XV_LAUNCH_CHECK();
   return XV_OK;
@@ -427,38 +400,12 @@ extern "C" int xv_anymdp_mbrl_create(xv_anymdp* h, double gamma, double c, xv_an
   XV_CHECK_ARG(out != nullptr);
   *out = nullptr;
   XV_CHECK_ARG(h != nullptr && gamma >= 0.0 && gamma < 1.0 && c == c);
-  if (h->obs_cdf != nullptr) {
-    xv_set_error("xv_anymdp_mbrl_create: the model-based learner takes MDP tasks only (its states are observation ids)");
-    return XV_ERR_UNSUPPORTED;
-  }
-  if (h->parent != nullptr) {
-    xv_set_error("xv_anymdp_mbrl_create: a view (xv_anymdp_view) cannot carry learners; create them on the whole handle");
-    return XV_ERR_UNSUPPORTED;
-  }
-  xv_engine* e = h->eng;
-  XV_HIP(hipSetDevice(e->device));
-  const int n_env = h->a.n_env, S = h->a.S, A = h->a.A;
   // the tables are indexed by observation id: every id of the task tables must be a row
-  const size_t n_map = (size_t)h->a.n_task * S;
-  int* d_max = nullptr;
-  int h_max = 0;
-  XV_HIP(hipMalloc(&d_max, sizeof(int)));
-  hipError_t r = hipMemsetAsync(d_max, 0, sizeof(int), e->stream);
-  if (r == hipSuccess) {
-    hipLaunchKernelGGL(anymdp_max_obs_kernel, dim3((unsigned)((n_map + 255) / 256)), dim3(256), 0, e->stream,
-                       h->a.state_map, n_map, d_max);
-    r = hipMemcpyAsync(&h_max, d_max, sizeof(int), hipMemcpyDeviceToHost, e->stream);
-  }
-  if (r == hipSuccess) r = hipStreamSynchronize(e->stream);
-  (void)hipFree(d_max);
-  if (r != hipSuccess) {
-    xv_set_error("xv_anymdp_mbrl_create: %s", hipGetErrorString(r));
-    return XV_ERR_HIP;
-  }
-  if (h_max >= S) {
-    xv_set_error("xv_anymdp_mbrl_create: observation id %d does not index the S = %d rows of the model", h_max, S);
-    return XV_ERR_UNSUPPORTED;
-  }
+  int rc = xv_anymdp_learner_check(h, __func__, "the model-based learner takes MDP tasks only (its states are observation ids)",
+                                   "the model");
+  if (rc != XV_OK) return rc;
+  xv_engine* e = h->eng;
+  const int n_env = h->a.n_env, S = h->a.S, A = h->a.A;
   // the estimator: one wave per workgroup, 12 per CU (3 per SIMD: what its ~150 VGPRs leave resident); the row's products
   // in LDS when they fit, else a global slab per workgroup
   int cus = 0;
@@ -492,7 +439,7 @@ extern "C" int xv_anymdp_mbrl_create(xv_anymdp* h, double gamma, double c, xv_an
   m->n_env = n_env; m->S = S; m->A = A; m->parity = 0; m->grid = grid;
   m->lds = lds_base + (lds_p ? prod : 0);
   const size_t nsas = (size_t)n_env * S * A * S, nsa = (size_t)n_env * S * A, n = (size_t)n_env;
-  r = hipMalloc(&m->est_r, sizeof(double) * nsas);
+  hipError_t r = hipMalloc(&m->est_r, sizeof(double) * nsas);
   if (r == hipSuccess) r = hipMalloc(&m->vis_cnt, sizeof(double) * nsas);
   if (r == hipSuccess) r = hipMalloc(&m->vis_cnt_sa, sizeof(double) * nsa);
   if (r == hipSuccess) r = hipMalloc(&m->vm, sizeof(double) * nsa);
@@ -525,7 +472,7 @@ extern "C" int xv_anymdp_mbrl_create(xv_anymdp* h, double gamma, double c, xv_an
     mbrl_free(m);
     return XV_ERR_HIP;
   }
-  const int rc = xv_anymdp_mbrl_reset(m, nullptr);
+  rc = xv_anymdp_mbrl_reset(m, nullptr);
   if (rc != XV_OK) {
     mbrl_free(m);
     return rc;
@@ -534,50 +481,37 @@ extern "C" int xv_anymdp_mbrl_create(xv_anymdp* h, double gamma, double c, xv_an
   return XV_OK;
 }
 
-extern "C" int xv_anymdp_mbrl_destroy(xv_anymdp_mbrl* m) {
-  if (!m) return XV_OK;
-  (void)hipSetDevice(m->device);
-  (void)hipStreamSynchronize(m->h->eng->stream);   // the handle outlives its learners (xeno.h)
-  mbrl_free(m);
-  return XV_OK;
-}
+extern "C" int xv_anymdp_mbrl_destroy(xv_anymdp_mbrl* m) { return xv_learner_destroy(m, mbrl_free); }
 
-static int mbrl_copy(xv_anymdp_mbrl* m, bool to_learner, double* const* dev, const double* const* user) {
-  const size_t nsas = (size_t)m->n_env * m->S * m->A * m->S, nsa = (size_t)m->n_env * m->S * m->A;
-  const size_t sizes[5] = {nsas, nsas, nsa, nsa, nsa};
-  hipStream_t st = m->h->eng->stream;
-  for (int k = 0; k < 5; ++k) {
-    if (!user[k]) continue;
-    if (to_learner) XV_HIP(hipMemcpyAsync(dev[k], user[k], sizeof(double) * sizes[k], hipMemcpyDeviceToDevice, st));
-    else XV_HIP(hipMemcpyAsync((void*)user[k], dev[k], sizeof(double) * sizes[k], hipMemcpyDeviceToDevice, st));
-  }
-  return XV_OK;
+static int mbrl_copy(xv_anymdp_mbrl* m, bool to_learner, const double* est_r, const double* vis_cnt, const double* vis_cnt_sa,
+                     const double* vm, const double* b) {
+  const size_t nsa = sizeof(double) * (size_t)m->n_env * m->S * m->A, nsas = nsa * m->S;
+  void* const dev[5] = {m->est_r, m->vis_cnt, m->vis_cnt_sa, m->vm, m->b};
+  const size_t bytes[5] = {nsas, nsas, nsa, nsa, nsa};
+  const void* const user[5] = {est_r, vis_cnt, vis_cnt_sa, vm, b};
+  return xv_learner_copy(m->h, to_learner, 5, dev, bytes, user);
 }
 
 extern "C" int xv_anymdp_mbrl_get_state(xv_anymdp_mbrl* m, double* est_r, double* vis_cnt, double* vis_cnt_sa, double* vm,
                                         double* b) {
   XV_CHECK_ARG(m != nullptr);
-  double* const dev[5] = {m->est_r, m->vis_cnt, m->vis_cnt_sa, m->vm, m->b};
-  const double* const user[5] = {est_r, vis_cnt, vis_cnt_sa, vm, b};
-  return mbrl_copy(m, false, dev, user);
+  return mbrl_copy(m, false, est_r, vis_cnt, vis_cnt_sa, vm, b);
 }
 
 extern "C" int xv_anymdp_mbrl_set_state(xv_anymdp_mbrl* m, const double* est_r, const double* vis_cnt,
                                         const double* vis_cnt_sa, const double* vm, const double* b) {
   XV_CHECK_ARG(m != nullptr);
-  double* const dev[5] = {m->est_r, m->vis_cnt, m->vis_cnt_sa, m->vm, m->b};
-  const double* const user[5] = {est_r, vis_cnt, vis_cnt_sa, vm, b};
-  return mbrl_copy(m, true, dev, user);
+  return mbrl_copy(m, true, est_r, vis_cnt, vis_cnt_sa, vm, b);
 }
 
 template <bool LEARN, bool ACT, bool INJECT>
-static void mbrl_launch_learn(xv_anymdp_mbrl* m, const MBArgs& L, const MBStepIO& io) {
+static void mbrl_launch_learn(xv_anymdp_mbrl* m, const MBArgs& L, const XvLearnStepIO& io) {
   hipLaunchKernelGGL((anymdp_mbrl_learn_kernel<LEARN, ACT, INJECT>), dim3(xv_div_up(m->n_env, 256)), dim3(256), 0,
                      m->h->eng->stream, m->h->a, L, io);
 }
 
 template <bool ACT, bool INJECT>
-static void mbrl_launch_estimator(xv_anymdp_mbrl* m, const MBArgs& L, const MBStepIO& io) {
+static void mbrl_launch_estimator(xv_anymdp_mbrl* m, const MBArgs& L, const XvLearnStepIO& io) {
   if (m->scratch)
     hipLaunchKernelGGL((anymdp_mbrl_estimator_kernel<ACT, INJECT, false>), dim3(m->grid), dim3(MBRL_WAVE), m->lds,
                        m->h->eng->stream, L, io);
@@ -588,7 +522,7 @@ static void mbrl_launch_estimator(xv_anymdp_mbrl* m, const MBArgs& L, const MBSt
 
 // the first launch: the policy from every env's current observation
 template <bool INJECT>
-static int mbrl_launch_first(xv_anymdp_mbrl* m, const MBStepIO& io) {
+static int mbrl_launch_first(xv_anymdp_mbrl* m, const XvLearnStepIO& io) {
   const MBArgs L = mbrl_args(m);
   mbrl_launch_learn<false, true, INJECT>(m, L, io);
   XV_LAUNCH_CHECK();
@@ -597,7 +531,7 @@ static int mbrl_launch_first(xv_anymdp_mbrl* m, const MBStepIO& io) {
 
 // after a step: learn (the next action for envs whose episode goes on), then the estimator for those whose episode ended
 template <bool ACT, bool INJECT>
-static int mbrl_launch_step(xv_anymdp_mbrl* m, const MBStepIO& io) {
+static int mbrl_launch_step(xv_anymdp_mbrl* m, const XvLearnStepIO& io) {
   const MBArgs L = mbrl_args(m);
   mbrl_launch_learn<true, ACT, INJECT>(m, L, io);
   mbrl_launch_estimator<ACT, INJECT>(m, L, io);
@@ -606,34 +540,18 @@ static int mbrl_launch_step(xv_anymdp_mbrl* m, const MBStepIO& io) {
   return XV_OK;
 }
 
+static int mbrl_first(xv_anymdp_mbrl* m, const XvLearnStepIO& io) {
+  return io.u_policy ? mbrl_launch_first<true>(m, io) : mbrl_launch_first<false>(m, io);
+}
+static int mbrl_after(xv_anymdp_mbrl* m, const XvLearnStepIO& io, bool act) {
+  if (!act) return mbrl_launch_step<false, false>(m, io);
+  return io.u_policy ? mbrl_launch_step<true, true>(m, io) : mbrl_launch_step<true, false>(m, io);
+}
+
 extern "C" int xv_anymdp_rollout_mbrl(xv_anymdp* h, xv_anymdp_mbrl* m, int T, int greedy, const double* u_policy,
                                       const double* u, const float* z, const double* u_reset, int32_t* action_out,
                                       int32_t* obs, float* reward, float* reward_gt, uint8_t* terminated,
                                       uint8_t* truncated, int32_t* final_obs) {
-  XV_CHECK_ARG(h != nullptr && m != nullptr && m->h == h && T > 0);
-  XV_CHECK_ARG(action_out && obs && reward && reward_gt && terminated && truncated && final_obs);
-  const bool inject = u != nullptr;
-  XV_CHECK_ARG((z != nullptr) == inject && (u_reset != nullptr) == inject);
-  XV_CHECK_ARG(greedy || (u_policy != nullptr) == inject);
-  const size_t n = (size_t)h->a.n_env, na = n * (size_t)m->A;
-  const double* up = greedy ? nullptr : u_policy;
-  MBStepIO first{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, up, action_out, greedy};
-  int rc = up ? mbrl_launch_first<true>(m, first) : mbrl_launch_first<false>(m, first);
-  for (int t = 0; t < T && rc == XV_OK; ++t) {
-    const size_t o = (size_t)t * n;
-    if (inject)
-      rc = xv_anymdp_step_injected(h, action_out + o, u + o, z + o, u_reset + o, obs + o, reward + o, reward_gt + o,
-                                   terminated + o, truncated + o, final_obs + o, XV_AUTORESET_SAME_STEP);
-    else
-      rc = xv_anymdp_step_info(h, action_out + o, obs + o, reward + o, reward_gt + o, terminated + o, truncated + o,
-                               final_obs + o, nullptr, nullptr, XV_AUTORESET_SAME_STEP);
-    if (rc != XV_OK) break;
-    const bool act = t + 1 < T;
-    const double* un = (up && act) ? up + (size_t)(t + 1) * na : nullptr;
-    MBStepIO io{action_out + o, obs + o, final_obs + o, reward + o, terminated + o, truncated + o, un,
-                act ? action_out + o + n : nullptr, greedy};
-    if (act) rc = un ? mbrl_launch_step<true, true>(m, io) : mbrl_launch_step<true, false>(m, io);
-    else rc = mbrl_launch_step<false, false>(m, io);
-  }
-  return rc;
+  return xv_learner_rollout(__func__, mbrl_first, mbrl_after, h, m, T, greedy, u_policy, u, z, u_reset, action_out, obs,
+                            reward, reward_gt, terminated, truncated, final_obs);
 }

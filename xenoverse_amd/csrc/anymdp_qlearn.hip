@@ -22,6 +22,7 @@
 #define XV_KERNELS_ONLY
 #include "anymdp.hip"
 #undef XV_KERNELS_ONLY
+#include "anymdp_learner.h"
 
 #define XV_DRAW_QPOLICY 4u   // words 0,1 -> the uniform numpy.random.choice searches in the Q-learner's policy
 
@@ -35,6 +36,7 @@ struct xv_anymdp_qlearn {
   uint32_t* sa;        // [n_env][S][A]
   uint32_t* sv;        // [n_env][S]
   int32_t* cur_obs;    // [n_env]
+  int u_per_env() const { return 1; }   // the policy's uniforms per env and step (random.choice draws one)
 };
 
 struct QLArgs {
@@ -43,23 +45,7 @@ struct QLArgs {
   uint32_t* sv;
   int32_t* cur_obs;
   double gamma, alpha, M;
-  int n_env, S, A;
-  uint64_t seed, gid_base, tick;
-  const uint64_t* tick_dev;
-};
-
-struct QLStepIO {
-  // the step just made (learning launches)
-  const int32_t* act_prev;
-  const int32_t* obs;        // also where the next action is chosen from; nullptr: the env's current state (first launch)
-  const int32_t* final_obs;
-  const float* reward;
-  const uint8_t* terminated;
-  const uint8_t* truncated;
-  // the next action
-  const double* u_policy;    // injected uniforms [n_env] or nullptr (Philox)
-  int32_t* action_out;
-  int greedy;
+  XvLearnerBind B;
 };
 
 // numpy's sum of the n <= AM values f(0..n-1): add.reduce of a contiguous row (pairwise_sum: a plain loop below 8, eight
@@ -121,10 +107,10 @@ __device__ __forceinline__ int qlearn_choice(const double* row, int A, uint32_t 
 }
 
 template <bool LEARN, bool ACT, bool INJECT, int AM>
-__global__ __launch_bounds__(256) void anymdp_qlearn_kernel(AnyMDPArgs P, QLArgs L, QLStepIO io) {
+__global__ __launch_bounds__(256) void anymdp_qlearn_kernel(AnyMDPArgs P, QLArgs L, XvLearnStepIO io) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= L.n_env) return;
-  const int S = L.S, A = L.A;
+  if (i >= L.B.n_env) return;
+  const int S = L.B.S, A = L.B.A;
   double* Qe = L.q + (size_t)i * S * A;
   uint32_t* SAe = L.sa + (size_t)i * S * A;
   uint32_t* SVe = L.sv + (size_t)i * S;
@@ -154,13 +140,7 @@ __global__ __launch_bounds__(256) void anymdp_qlearn_kernel(AnyMDPArgs P, QLArgs
     }
   }
   if (ACT) {
-    int o;
-    if (io.obs) {
-      o = io.obs[i];      // what the step returned: the next episode's first observation when it ended
-    } else {
-      const int t = P.env_task[i], st = (int)(P.sr[i].x & 0xFFFFu);
-      o = P.state_map[(size_t)t * P.S + st];
-    }
+    const int o = xv_learner_act_obs(P, io.obs, i);
     L.cur_obs[i] = o;
     int a = 0;
     if ((unsigned)o < (unsigned)S) {
@@ -174,7 +154,7 @@ __global__ __launch_bounds__(256) void anymdp_qlearn_kernel(AnyMDPArgs P, QLArgs
         if (INJECT) {
           u = io.u_policy[i];
         } else {
-          const xv_u32x4 w = xv_env_draw(L.seed, L.gid_base + (uint64_t)i, xv_launch_tick(L.tick, L.tick_dev), XV_DRAW_QPOLICY);
+          const xv_u32x4 w = xv_env_draw(L.B.seed, L.B.gid_base + (uint64_t)i, xv_launch_tick(L.B.tick, L.B.tick_dev), XV_DRAW_QPOLICY);
           u = xv_u53(w.x, w.y);
         }
         a = qlearn_choice<AM>(row, A, SVe[o], L.M, u);
@@ -186,14 +166,14 @@ __global__ __launch_bounds__(256) void anymdp_qlearn_kernel(AnyMDPArgs P, QLArgs
 
 // __init__ :8-27 for the masked agents (nullptr: all)
 static __global__ __launch_bounds__(256) void anymdp_qlearn_reset_kernel(QLArgs L, const uint8_t* mask) {
-  const size_t per = (size_t)L.S * L.A, total = (size_t)L.n_env * per;
+  const size_t per = (size_t)L.B.S * L.B.A, total = (size_t)L.B.n_env * per;
   for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
     const size_t i = idx / per;
     if (mask && !mask[i]) continue;
     L.q[idx] = 1.0 / (1.0 - L.gamma);
     L.sa[idx] = 1u;
     const size_t j = idx - i * per;
-    if (j < (size_t)L.S) L.sv[i * L.S + j] = 1u;
+    if (j < (size_t)L.B.S) L.sv[i * L.B.S + j] = 1u;
   }
 }
 
@@ -201,12 +181,7 @@ static QLArgs qlearn_args(xv_anymdp_qlearn* ql) {
   QLArgs L;
   L.q = ql->q; L.sa = ql->sa; L.sv = ql->sv; L.cur_obs = ql->cur_obs;
   L.gamma = ql->gamma; L.alpha = ql->alpha; L.M = (double)ql->max_steps;
-  L.n_env = ql->n_env; L.S = ql->S; L.A = ql->A;
-  xv_engine* e = ql->h->eng;
-  L.seed = e->seed; L.gid_base = e->env_id_base;
-  // the tick the NEXT step launch will draw with (no advance: that launch advances it)
-  const XvTickBind b = xv_engine_bind_tick(e, 0);
-  L.tick = b.tick; L.tick_dev = b.tick_dev;
+  L.B = xv_learner_bind(ql->h);
   return L;
 }
 
@@ -220,11 +195,8 @@ static void qlearn_free(xv_anymdp_qlearn* ql) {
 
 extern "C" int xv_anymdp_qlearn_reset(xv_anymdp_qlearn* ql, const uint8_t* mask) {
   XV_CHECK_ARG(ql != nullptr);
-  const size_t n = (size_t)ql->n_env * ql->S * ql->A, blocks = (n + 255) / 256;
-  // grid-stride: n_env S A may exceed what one grid dimension holds
-  hipLaunchKernelGGL(anymdp_qlearn_reset_kernel, dim3((unsigned)(blocks < (1u << 20) ? blocks : (1u << 20))), dim3(256), 0,
-                     ql->h->eng->stream,
-                     qlearn_args(ql), mask);
+  hipLaunchKernelGGL(anymdp_qlearn_reset_kernel, dim3(xv_learner_blocks((size_t)ql->n_env * ql->S * ql->A)), dim3(256), 0,
+                     ql->h->eng->stream, qlearn_args(ql), mask);
   XV_LAUNCH_CHECK();
   return XV_OK;
 }
@@ -233,37 +205,11 @@ extern "C" int xv_anymdp_qlearn_create(xv_anymdp* h, double gamma, double alpha,
   XV_CHECK_ARG(out != nullptr);
   *out = nullptr;
   XV_CHECK_ARG(h != nullptr && gamma >= 0.0 && gamma < 1.0 && alpha == alpha && max_steps >= 0);
-  if (h->obs_cdf != nullptr) {      // anymdp_solver_q.py:17: assert env.task_type == "MDP"
-    xv_set_error("xv_anymdp_qlearn_create: the Q-learner takes MDP tasks only (the reference asserts task_type == \"MDP\")");
-    return XV_ERR_UNSUPPORTED;
-  }
-  if (h->parent != nullptr) {
-    xv_set_error("xv_anymdp_qlearn_create: a view (xv_anymdp_view) cannot carry learners; create them on the whole handle");
-    return XV_ERR_UNSUPPORTED;
-  }
+  // anymdp_solver_q.py:17: assert env.task_type == "MDP"; Q rows are indexed by observation id: every id must be a row
+  int rc = xv_anymdp_learner_check(h, __func__,
+                                   "the Q-learner takes MDP tasks only (the reference asserts task_type == \"MDP\")", "Q");
+  if (rc != XV_OK) return rc;
   xv_engine* e = h->eng;
-  XV_HIP(hipSetDevice(e->device));
-  // Q rows are indexed by observation id: every id of the tables must be a row
-  const size_t n_map = (size_t)h->a.n_task * h->a.S;
-  int* d_max = nullptr;
-  int h_max = 0;
-  XV_HIP(hipMalloc(&d_max, sizeof(int)));
-  hipError_t r = hipMemsetAsync(d_max, 0, sizeof(int), e->stream);
-  if (r == hipSuccess) {
-    hipLaunchKernelGGL(anymdp_max_obs_kernel, dim3((unsigned)((n_map + 255) / 256)), dim3(256), 0, e->stream,
-                       h->a.state_map, n_map, d_max);
-    r = hipMemcpyAsync(&h_max, d_max, sizeof(int), hipMemcpyDeviceToHost, e->stream);
-  }
-  if (r == hipSuccess) r = hipStreamSynchronize(e->stream);
-  (void)hipFree(d_max);
-  if (r != hipSuccess) {
-    xv_set_error("xv_anymdp_qlearn_create: %s", hipGetErrorString(r));
-    return XV_ERR_HIP;
-  }
-  if (h_max >= h->a.S) {
-    xv_set_error("xv_anymdp_qlearn_create: observation id %d does not index the S = %d rows of Q", h_max, h->a.S);
-    return XV_ERR_UNSUPPORTED;
-  }
   xv_anymdp_qlearn* ql = new (std::nothrow) xv_anymdp_qlearn();
   if (!ql) {
     xv_set_error("xv_anymdp_qlearn_create: out of host memory");
@@ -272,7 +218,7 @@ extern "C" int xv_anymdp_qlearn_create(xv_anymdp* h, double gamma, double alpha,
   ql->h = h; ql->device = e->device; ql->gamma = gamma; ql->alpha = alpha; ql->max_steps = max_steps;
   ql->n_env = h->a.n_env; ql->S = h->a.S; ql->A = h->a.A;
   const size_t nsa = (size_t)ql->n_env * ql->S * ql->A, ns = (size_t)ql->n_env * ql->S;
-  r = hipMalloc(&ql->q, sizeof(double) * nsa);
+  hipError_t r = hipMalloc(&ql->q, sizeof(double) * nsa);
   if (r == hipSuccess) r = hipMalloc(&ql->sa, sizeof(uint32_t) * nsa);
   if (r == hipSuccess) r = hipMalloc(&ql->sv, sizeof(uint32_t) * ns);
   if (r == hipSuccess) r = hipMalloc(&ql->cur_obs, sizeof(int32_t) * (size_t)ql->n_env);
@@ -289,7 +235,7 @@ extern "C" int xv_anymdp_qlearn_create(xv_anymdp* h, double gamma, double alpha,
     qlearn_free(ql);
     return XV_ERR_HIP;
   }
-  const int rc = xv_anymdp_qlearn_reset(ql, nullptr);
+  rc = xv_anymdp_qlearn_reset(ql, nullptr);
   if (rc != XV_OK) {
     qlearn_free(ql);
     return rc;
@@ -298,44 +244,36 @@ extern "C" int xv_anymdp_qlearn_create(xv_anymdp* h, double gamma, double alpha,
   return XV_OK;
 }
 
-extern "C" int xv_anymdp_qlearn_destroy(xv_anymdp_qlearn* ql) {
-  if (!ql) return XV_OK;
-  (void)hipSetDevice(ql->device);
-  (void)hipStreamSynchronize(ql->h->eng->stream);   // the handle outlives its learners (xeno.h)
-  qlearn_free(ql);
-  return XV_OK;
-}
+extern "C" int xv_anymdp_qlearn_destroy(xv_anymdp_qlearn* ql) { return xv_learner_destroy(ql, qlearn_free); }
 
-static int qlearn_copy(xv_anymdp_qlearn* ql, void* dst_q, void* dst_sa, void* dst_sv, const void* src_q, const void* src_sa,
-                       const void* src_sv) {
+static int qlearn_copy(xv_anymdp_qlearn* ql, bool to_learner, const void* q, const void* sa_visits, const void* s_visits) {
   const size_t nsa = (size_t)ql->n_env * ql->S * ql->A, ns = (size_t)ql->n_env * ql->S;
-  hipStream_t st = ql->h->eng->stream;
-  if (dst_q && src_q) XV_HIP(hipMemcpyAsync(dst_q, src_q, sizeof(double) * nsa, hipMemcpyDeviceToDevice, st));
-  if (dst_sa && src_sa) XV_HIP(hipMemcpyAsync(dst_sa, src_sa, sizeof(uint32_t) * nsa, hipMemcpyDeviceToDevice, st));
-  if (dst_sv && src_sv) XV_HIP(hipMemcpyAsync(dst_sv, src_sv, sizeof(uint32_t) * ns, hipMemcpyDeviceToDevice, st));
-  return XV_OK;
+  void* const dev[3] = {ql->q, ql->sa, ql->sv};
+  const size_t bytes[3] = {sizeof(double) * nsa, sizeof(uint32_t) * nsa, sizeof(uint32_t) * ns};
+  const void* const user[3] = {q, sa_visits, s_visits};
+  return xv_learner_copy(ql->h, to_learner, 3, dev, bytes, user);
 }
 
 extern "C" int xv_anymdp_qlearn_get_state(xv_anymdp_qlearn* ql, double* q, uint32_t* sa_visits, uint32_t* s_visits) {
   XV_CHECK_ARG(ql != nullptr);
-  return qlearn_copy(ql, q, sa_visits, s_visits, ql->q, ql->sa, ql->sv);
+  return qlearn_copy(ql, false, q, sa_visits, s_visits);
 }
 
 extern "C" int xv_anymdp_qlearn_set_state(xv_anymdp_qlearn* ql, const double* q, const uint32_t* sa_visits,
                                           const uint32_t* s_visits) {
   XV_CHECK_ARG(ql != nullptr);
-  return qlearn_copy(ql, ql->q, ql->sa, ql->sv, q, sa_visits, s_visits);
+  return qlearn_copy(ql, true, q, sa_visits, s_visits);
 }
 
 template <bool LEARN, bool ACT, bool INJECT, int AM>
-static void qlearn_launch_am(xv_anymdp_qlearn* ql, const QLArgs& L, const QLStepIO& io) {
+static void qlearn_launch_am(xv_anymdp_qlearn* ql, const QLArgs& L, const XvLearnStepIO& io) {
   hipLaunchKernelGGL((anymdp_qlearn_kernel<LEARN, ACT, INJECT, AM>), dim3(xv_div_up(ql->n_env, 256)), dim3(256), 0,
                      ql->h->eng->stream, ql->h->a, L, io);
 }
 
 // the policy's register row: the smallest of 8, 16, 32, 64 doubles that holds A (a launch that only learns needs none)
 template <bool LEARN, bool ACT, bool INJECT>
-static void qlearn_launch_inj(xv_anymdp_qlearn* ql, const QLArgs& L, const QLStepIO& io) {
+static void qlearn_launch_inj(xv_anymdp_qlearn* ql, const QLArgs& L, const XvLearnStepIO& io) {
   if constexpr (!ACT) qlearn_launch_am<LEARN, ACT, INJECT, 8>(ql, L, io);
   else if (ql->A <= 8) qlearn_launch_am<LEARN, ACT, INJECT, 8>(ql, L, io);
   else if (ql->A <= 16) qlearn_launch_am<LEARN, ACT, INJECT, 16>(ql, L, io);
@@ -344,7 +282,7 @@ static void qlearn_launch_inj(xv_anymdp_qlearn* ql, const QLArgs& L, const QLSte
 }
 
 template <bool LEARN, bool ACT>
-static int qlearn_launch(xv_anymdp_qlearn* ql, const QLStepIO& io) {
+static int qlearn_launch(xv_anymdp_qlearn* ql, const XvLearnStepIO& io) {
   const QLArgs L = qlearn_args(ql);
   if (io.u_policy) qlearn_launch_inj<LEARN, ACT, true>(ql, L, io);
   else qlearn_launch_inj<LEARN, ACT, false>(ql, L, io);
@@ -352,31 +290,15 @@ static int qlearn_launch(xv_anymdp_qlearn* ql, const QLStepIO& io) {
   return XV_OK;
 }
 
+static int qlearn_first(xv_anymdp_qlearn* ql, const XvLearnStepIO& io) { return qlearn_launch<false, true>(ql, io); }
+static int qlearn_after(xv_anymdp_qlearn* ql, const XvLearnStepIO& io, bool act) {
+  return act ? qlearn_launch<true, true>(ql, io) : qlearn_launch<true, false>(ql, io);
+}
+
 extern "C" int xv_anymdp_rollout_qlearn(xv_anymdp* h, xv_anymdp_qlearn* ql, int T, int greedy, const double* u_policy,
                                         const double* u, const float* z, const double* u_reset, int32_t* action_out,
                                         int32_t* obs, float* reward, float* reward_gt, uint8_t* terminated,
                                         uint8_t* truncated, int32_t* final_obs) {
-  XV_CHECK_ARG(h != nullptr && ql != nullptr && ql->h == h && T > 0);
-  XV_CHECK_ARG(action_out && obs && reward && reward_gt && terminated && truncated && final_obs);
-  const bool inject = u != nullptr;
-  XV_CHECK_ARG((z != nullptr) == inject && (u_reset != nullptr) == inject);
-  XV_CHECK_ARG(greedy || (u_policy != nullptr) == inject);
-  const size_t n = (size_t)h->a.n_env;
-  const double* up = greedy ? nullptr : u_policy;
-  QLStepIO first{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, up, action_out, greedy};
-  int rc = qlearn_launch<false, true>(ql, first);
-  for (int t = 0; t < T && rc == XV_OK; ++t) {
-    const size_t o = (size_t)t * n;
-    if (inject)
-      rc = xv_anymdp_step_injected(h, action_out + o, u + o, z + o, u_reset + o, obs + o, reward + o, reward_gt + o,
-                                   terminated + o, truncated + o, final_obs + o, XV_AUTORESET_SAME_STEP);
-    else
-      rc = xv_anymdp_step_info(h, action_out + o, obs + o, reward + o, reward_gt + o, terminated + o, truncated + o,
-                               final_obs + o, nullptr, nullptr, XV_AUTORESET_SAME_STEP);
-    if (rc != XV_OK) break;
-    QLStepIO io{action_out + o, obs + o, final_obs + o, reward + o, terminated + o, truncated + o,
-                (up && t + 1 < T) ? up + o + n : nullptr, action_out + o + n, greedy};
-    rc = t + 1 < T ? qlearn_launch<true, true>(ql, io) : qlearn_launch<true, false>(ql, io);
-  }
-  return rc;
+  return xv_learner_rollout(__func__, qlearn_first, qlearn_after, h, ql, T, greedy, u_policy, u, z, u_reset, action_out, obs,
+                            reward, reward_gt, terminated, truncated, final_obs);
 }
