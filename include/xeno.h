@@ -899,6 +899,39 @@ int xv_mixed_step_many(xv_anymdp* a, xv_linds* l, xv_cartpole* c, const xv_mixed
  * overlapped, a hand-off expired and the call was replayed (results are right). */
 int xv_mixed_step_many_overlap_state(xv_anymdp* a);
 
+/* ------------------------------------------------------------------------------------------------
+ * MetaLangV2 — reference: xenoverse/metalang/metalangv2.py (RandomNGram.forward :31-77, MetaLangV2 :79-110), tasks from
+ * metalang/task_sampler.py TaskSamplerV2 :22-50.  Sequence generation, not an env step: a handle holds n_group GROUPS of
+ * seqs_per_group sequences; a group is one call of forward(l, batch = seqs_per_group) under one task, and its sequences
+ * share one mean and one standard deviation of the logits per step (mean_var_norm :37-41).  fp64 throughout.  New symbols
+ * only: no ABI bump.
+ *   set_task :94-96                 -> xv_metalang_set_task (tables of n_task tasks and one task index per group; n_gram is
+ *                                      per task, the input-layer tables are padded to n_gram_max rows)
+ *   forward :31-77 (data_generator  -> xv_metalang_generate: tokens int32[n_group][seqs_per_group][L + 1] (token 0 first);
+ *   :98-103, batch_generator           logp float64[n_group][seqs_per_group][L], nullable: log of the chosen token's
+ *   :105-110)                          probability (:70-71; the printed perplexity is the mean of -logp over a group);
+ *                                      u float64[n_group][seqs_per_group][L]: the uniforms of :69 (numpy.random.rand(batch)
+ *                                      per step), or NULL: Philox, keyed by (engine seed, env_id_base + group *
+ *                                      seqs_per_group + b, the call's tick, position); the call advances the tick by one
+ *   (no reference counterpart)      -> xv_metalang_log_prob: teacher forcing, the log-probability of tokens[.][.][t + 1] given
+ *                                      its predecessors, with the group statistics forward would have formed along them
+ * Limits (XV_ERR_UNSUPPORTED beyond, the text names the limit): n_vocab <= 1024, n_hidden <= 128, n_emb <= 64,
+ * n_gram <= 8, seqs_per_group <= 64.  Table pointers are borrowed until the next set_task / destroy.  A token outside
+ * [0, n_vocab) handed to log_prob, a task index or n_gram outside its range: XV_DEVERR_ACTION_RANGE; a standard deviation
+ * or a sum of exponentials that is not finite and positive: XV_DEVERR_NONFINITE. */
+typedef struct xv_metalang xv_metalang;
+int xv_metalang_create(xv_engine* e, int n_group, int seqs_per_group, int n_vocab, int n_emb, int n_hidden, int n_gram_max,
+                       xv_metalang** out);
+int xv_metalang_destroy(xv_metalang* h);
+/* word_emb [n_task][V][E], weights_inputlayer [n_task][n_gram_max][E][H], bias_inputlayer [n_task][n_gram_max][H],
+ * weights_outputlayer [n_task][H][V], bias_outputlayer [n_task][V], lambda [n_task]: float64; n_gram int32[n_task];
+ * group_task int32[n_group] */
+int xv_metalang_set_task(xv_metalang* h, int n_task, const double* word_emb, const double* weights_inputlayer,
+                         const double* bias_inputlayer, const double* weights_outputlayer, const double* bias_outputlayer,
+                         const double* lambda, const int32_t* n_gram, const int32_t* group_task);
+int xv_metalang_generate(xv_metalang* h, int L, const double* u, int32_t* tokens, double* logp);
+int xv_metalang_log_prob(xv_metalang* h, int L, const int32_t* tokens, double* logp);
+
 #ifdef __cplusplus
 }
 #endif

@@ -151,6 +151,11 @@ SIGNATURES = {
     "xv_maze_agent_destroy": [c_void_p],
     "xv_maze_agent_act": [c_void_p, c_void_p, c_void_p],
     "xv_maze_agent_get": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    "xv_metalang_create": [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, C.POINTER(c_void_p)],
+    "xv_metalang_destroy": [c_void_p],
+    "xv_metalang_set_task": [c_void_p, c_int] + [c_void_p] * 8,
+    "xv_metalang_generate": [c_void_p, c_int, c_void_p, c_void_p, c_void_p],
+    "xv_metalang_log_prob": [c_void_p, c_int, c_void_p, c_void_p],
 }
 _RESTYPE = {"xv_last_error": C.c_char_p, "xv_engine_stream": c_void_p}
 
