@@ -73,6 +73,7 @@ extern "C" {
 #define XV_DEVERR_STEP_TERMINAL 2u  /* reference: raise "given an terminated state" (anymdp_env.py:95-96) */
 #define XV_DEVERR_NONFINITE 4u      /* a float state left the finite range */
 #define XV_DEVERR_HANDOFF 8u        /* overlapped xv_anymdp_step_many: a wave's bounded wait for the step before it expired */
+#define XV_DEVERR_LENGTH 16u        /* xv_metalm_*: a pass reached max_len tokens without the stop token and was cut there */
 
 #define XV_STREAM_OWN ((void*)(intptr_t)-1)
 
@@ -931,6 +932,56 @@ int xv_metalang_set_task(xv_metalang* h, int n_task, const double* word_emb, con
                          const double* lambda, const int32_t* n_gram, const int32_t* group_task);
 int xv_metalang_generate(xv_metalang* h, int L, const double* u, int32_t* tokens, double* logp);
 int xv_metalang_log_prob(xv_metalang* h, int L, const int32_t* tokens, double* logp);
+
+/* ------------------------------------------------------------------------------------------------
+ * MetaLMV3 — reference: xenoverse/metalang/metalangv3.py (MetaLMV3Env :4-42) over xenoverse/utils/random_nn.py RandomLM
+ * :218-344 and its decoders softmax_sampling :193-198, rnd_sampling :200-206, high_sampling :208-216; tasks from
+ * metalang/task_sampler.py TaskSamplerV3 :86-98.  A handle holds n_env envs; an env is one task index, the current query
+ * and the hidden state that query left (the reference's rnn.cache_states), and a step counter.  fp64 throughout.  New
+ * symbols only: no ABI bump.
+ *   set_task :11-19                  -> xv_metalm_set_task (tables of n_task tasks, one task index per env)
+ *   reset :21-26 (generate_query     -> xv_metalm_reset: a query from the zero state, T = 10 for the first token and 1 after;
+ *   random_nn.py:306-309)               steps = 0
+ *   policy :40-42 (generate_answer_  -> xv_metalm_policy: a softmax answer from the cached state at a per-env temperature
+ *   softmax random_nn.py:317-321)
+ *   step :28-38 (label_answer        -> xv_metalm_step: in ONE launch the teacher-forced label pass over the given answer, the
+ *   :329-344, generate_answer_greedy    greedy pass (ppl_min), the rnd pass (ppl_max), the next query unless cached[env], and
+ *   :311-315, generate_answer_low       reward = (ppl_max - ppl_min) / max(ppl - ppl_min + 0.1, 1e-3) - 2 (:32)
+ *   :323-327)
+ * Tokens are int32 rows of max_len (label: max_len + 1, one per answer position and one for the stop position), padded
+ * with 0 behind their length.  Every drawing pass takes u float64[n_env][max_len + 1], the uniforms numpy.random.choice
+ * would consume (one per token, the stop step included), or NULL: Philox, keyed by (engine seed, env_id_base + env, the
+ * call's tick, pass, position).  Every reset / policy / step advances the tick by one.
+ * Limits (XV_ERR_UNSUPPORTED beyond, the text names the limit): 12 <= n_vocab <= 256, n_hidden <= 128, n_emb <= 64,
+ * max_len <= 1024.  Table pointers are borrowed until the next set_task / destroy.  A token of the answer outside
+ * [0, n_vocab), an answer length outside [0, max_len] or a task index outside its range: XV_DEVERR_ACTION_RANGE; a sum of
+ * exponentials or a temperature that is not finite and positive: XV_DEVERR_NONFINITE; a pass that emitted max_len tokens
+ * and then did not draw the stop token is cut there: XV_DEVERR_LENGTH (a flagged result, the call completes). */
+typedef struct xv_metalm xv_metalm;
+/* function_tokens: n_function HOST ints, the tokens whose logit is always -1e6 (the reference's function_vocab but 's') */
+int xv_metalm_create(xv_engine* e, int n_env, int n_vocab, int n_emb, int n_hidden, int max_len, int stop_token,
+                     const int32_t* function_tokens, int n_function, xv_metalm** out);
+int xv_metalm_destroy(xv_metalm* h);
+/* emb [n_task][V][E] (layer_norm of the encoder's column per token), w_h_t [n_task][H + E][H] (the RNN's weights
+ * TRANSPOSED), b_h [n_task][H], w_d_t [n_task][H][V] (the decoder's weights TRANSPOSED), b_d [n_task][V]: float64;
+ * env_task int32[n_env] */
+int xv_metalm_set_task(xv_metalm* h, int n_task, const double* emb, const double* w_h_t, const double* b_h,
+                       const double* w_d_t, const double* b_d, const int32_t* env_task);
+/* query int32[n_env][max_len], query_len int32[n_env]: nullable copies of the new state */
+int xv_metalm_reset(xv_metalm* h, const double* u_query, int32_t* query, int32_t* query_len);
+/* temperature float64[n_env]; answer int32[n_env][max_len], answer_len int32[n_env] */
+int xv_metalm_policy(xv_metalm* h, const double* temperature, const double* u_policy, int32_t* answer, int32_t* answer_len);
+/* answer int32[n_env][max_len], answer_len int32[n_env]; cached uint8[n_env] or NULL (none); reward float64[n_env];
+ * nullable: query / query_len (the query after the step), steps int32[n_env], label int32[n_env][max_len + 1],
+ * ppl float64[3][n_env] (ppl, ppl_min, ppl_max), greedy / low int32[n_env][max_len] with their lengths */
+int xv_metalm_step(xv_metalm* h, const int32_t* answer, const int32_t* answer_len, const uint8_t* cached,
+                   const double* u_greedy, const double* u_low, const double* u_query, int32_t* query, int32_t* query_len,
+                   double* reward, int32_t* steps, int32_t* label, double* ppl, int32_t* greedy, int32_t* greedy_len,
+                   int32_t* low, int32_t* low_len);
+/* query int32[n_env][max_len], query_len int32[n_env], cache float64[n_env][H], steps int32[n_env]: device pointers */
+int xv_metalm_get_state(xv_metalm* h, int32_t* query, int32_t* query_len, double* cache, int32_t* steps);
+int xv_metalm_set_state(xv_metalm* h, const int32_t* query, const int32_t* query_len, const double* cache,
+                        const int32_t* steps);
 
 #ifdef __cplusplus
 }

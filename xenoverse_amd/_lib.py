@@ -156,6 +156,14 @@ SIGNATURES = {
     "xv_metalang_set_task": [c_void_p, c_int] + [c_void_p] * 8,
     "xv_metalang_generate": [c_void_p, c_int, c_void_p, c_void_p, c_void_p],
     "xv_metalang_log_prob": [c_void_p, c_int, c_void_p, c_void_p],
+    "xv_metalm_create": [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, C.POINTER(c_void_p)],
+    "xv_metalm_destroy": [c_void_p],
+    "xv_metalm_set_task": [c_void_p, c_int] + [c_void_p] * 6,
+    "xv_metalm_reset": [c_void_p] + [c_void_p] * 3,
+    "xv_metalm_policy": [c_void_p] + [c_void_p] * 4,
+    "xv_metalm_step": [c_void_p] + [c_void_p] * 16,
+    "xv_metalm_get_state": [c_void_p] * 5,
+    "xv_metalm_set_state": [c_void_p] * 5,
 }
 _RESTYPE = {"xv_last_error": C.c_char_p, "xv_engine_stream": c_void_p}
 
