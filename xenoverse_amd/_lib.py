@@ -115,26 +115,6 @@ SIGNATURES = {
     "xv_linds_mpc_action": [c_void_p] * 5,
     "xv_linds_mpc_solve": [c_void_p] + [c_void_p] * 5,
     "xv_linds_rollout_mpc": [c_void_p, c_int] + [c_void_p] * 10,
-    "xv_cartpole_create": [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, C.POINTER(c_void_p)],
-    "xv_cartpole_destroy": [c_void_p],
-    "xv_cartpole_reset": [c_void_p, c_void_p, c_void_p],
-    "xv_cartpole_reset_injected": [c_void_p, c_void_p, c_void_p, c_void_p],
-    "xv_cartpole_step": [c_void_p] + [c_void_p] * 6 + [c_int],
-    "xv_cartpole_step_info": [c_void_p] + [c_void_p] * 7 + [c_int],
-    "xv_cartpole_rollout": [c_void_p, c_int] + [c_void_p] * 6 + [c_int],
-    "xv_cartpole_step_injected": [c_void_p] + [c_void_p] * 7 + [c_int],
-    "xv_cartpole_get_state": [c_void_p, c_void_p, c_void_p, c_void_p],
-    "xv_cartpole_set_state": [c_void_p, c_void_p, c_void_p, c_void_p],
-    "xv_acrobot_create": [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, C.POINTER(c_void_p)],
-    "xv_acrobot_destroy": [c_void_p],
-    "xv_acrobot_reset": [c_void_p, c_void_p, c_void_p],
-    "xv_acrobot_reset_injected": [c_void_p, c_void_p, c_void_p, c_void_p],
-    "xv_acrobot_step": [c_void_p] + [c_void_p] * 6 + [c_int],
-    "xv_acrobot_step_info": [c_void_p] + [c_void_p] * 7 + [c_int],
-    "xv_acrobot_rollout": [c_void_p, c_int] + [c_void_p] * 6 + [c_int],
-    "xv_acrobot_step_injected": [c_void_p] + [c_void_p] * 7 + [c_int],
-    "xv_acrobot_get_state": [c_void_p, c_void_p, c_void_p, c_void_p],
-    "xv_acrobot_set_state": [c_void_p, c_void_p, c_void_p, c_void_p],
     "xv_maze_create": [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, C.c_double, C.c_double,
                        c_void_p, c_void_p, C.POINTER(c_void_p)],
     "xv_maze_destroy": [c_void_p],
@@ -165,7 +145,21 @@ SIGNATURES = {
     "xv_metalm_get_state": [c_void_p] * 5,
     "xv_metalm_set_state": [c_void_p] * 5,
 }
-_RESTYPE = {"xv_last_error": C.c_char_p, "xv_engine_stream": c_void_p}
+for _p in ("xv_cartpole", "xv_acrobot"):      # the control families share one set of entry points (csrc/xv_control.h)
+    SIGNATURES.update({
+        # acrobot's extra int: scale_is_vector
+        _p + "_create": [c_void_p] + [c_int] * 4 + [c_void_p] * 2 + [c_int] * (_p == "xv_acrobot") + [c_void_p, C.POINTER(c_void_p)],
+        _p + "_destroy": [c_void_p],
+        _p + "_reset": [c_void_p, c_void_p, c_void_p],
+        _p + "_reset_injected": [c_void_p, c_void_p, c_void_p, c_void_p],
+        _p + "_step": [c_void_p] + [c_void_p] * 6 + [c_int],
+        _p + "_step_info": [c_void_p] + [c_void_p] * 7 + [c_int],
+        _p + "_rollout": [c_void_p, c_int] + [c_void_p] * 6 + [c_int],
+        _p + "_step_injected": [c_void_p] + [c_void_p] * 7 + [c_int],
+        _p + "_get_state": [c_void_p, c_void_p, c_void_p, c_void_p],
+        _p + "_set_state": [c_void_p, c_void_p, c_void_p, c_void_p],
+    })
+_RESTYPE ={"xv_last_error": C.c_char_p, "xv_engine_stream": c_void_p}
 
 _lib = None
 

@@ -221,7 +221,7 @@ extern "C" int xv_mixed_step(xv_anymdp* a, xv_linds* l, xv_cartpole* c, const xv
   if (dev3 && !a->eng->tick_batch) xv_engine_advance_device_tick3(a->eng, l->eng, c->eng, n_tot[0], n_tot[1], n_tot[2]);
   anymdp_bind_rng(a, 1, !dev3);
   linds_bind_rng(l, 1, !dev3);
-  cartpole_bind_rng(c, 1, !dev3);
+  xv_control_bind_rng(c, 1, !dev3);
   if (dev3 && !a->eng->tick_batch) {      // relative to the advanced word: -n, -n + 1, ... for the handles that share it
     a->a.tick = (uint64_t)0 - n_tot[0] + n_before[0];
     l->a.tick = (uint64_t)0 - n_tot[1] + n_before[1];
@@ -498,7 +498,7 @@ static int mixed_pipe_run(xv_anymdp* a, xv_linds* l, xv_cartpole* c, const xv_mi
   const int n_lw = xv_div_up(l->a.n_slot, 16), n_cw = xv_div_up(c->a.n_env, 64);
   anymdp_bind_rng(a, 0, false);
   linds_bind_rng(l, 0, false);
-  cartpole_bind_rng(c, 0, false);
+  xv_control_bind_rng(c, 0, false);
   const int U = mixed_pipe_setup(M, st, (size_t)(n_lw + n_cw), D) ? mixed_pipe_graphs(M, a, l, c, ring, period, ring_cycles, mode, v, n_lw, D) : -1;
   if (U < 0) {
     (void)hipGetLastError();
