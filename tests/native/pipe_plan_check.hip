@@ -1,16 +1,44 @@
-// host-only check of the planning helpers of csrc/xv_pipe.h (built and run by tests/test_pipe_plan.py; no GPU needed:
-// nothing here calls the HIP runtime)
+// host-only check of the planning and step-enumeration helpers of csrc/xv_pipe.h (built and run by tests/test_pipe_plan.py;
+// no GPU needed: nothing here calls the HIP runtime)
 #include <cstdio>
+#include <vector>
 
 #include "xv_pipe.h"
 
 static int fails = 0;
 #define CHECK(cond, ...) do { if (!(cond)) { ++fails; printf("FAIL %s: ", #cond); printf(__VA_ARGS__); printf("\n"); } } while (0)
 
+// the steps of a graph set as the lanes get them (xv_pipe_lane_step / xv_pipe_step_slot): every step of the U ring cycles
+// once, the same number on every lane, and the `depth` steps in flight together on distinct ring slots
+static void check_lanes(int depth, int period, int U) {
+  const int n = U * period;
+  std::vector<int> seen(n, 0);
+  for (int q = 0; q < depth; ++q) {
+    int n_lane = 0, last = -1;
+    for (int i = 0, g; (g = xv_pipe_lane_step(q, i, depth, U, period)) >= 0; ++i) {
+      CHECK(g < n && g > last && g % depth == q, "depth %d period %d U %d: lane %d step %d is %d after %d", depth, period, U, q, i, g, last);
+      if (g >= n) break;
+      seen[g] += 1; last = g; ++n_lane;
+    }
+    CHECK(n_lane == n / depth && n % depth == 0, "depth %d period %d U %d: lane %d has %d of %d steps", depth, period, U, q, n_lane, n);
+    CHECK(xv_pipe_lane_step(q, n_lane + 1, depth, U, period) < 0, "depth %d period %d U %d: lane %d goes on past its end", depth, period, U, q);
+  }
+  for (int g = 0; g < n; ++g) CHECK(seen[g] == 1, "depth %d period %d U %d: step %d is on %d lanes", depth, period, U, g, seen[g]);
+  for (int g0 = 0; g0 + depth <= n; ++g0)
+    for (int x = 0; x < depth; ++x) {
+      const int sx = xv_pipe_step_slot(g0 + x, period);
+      CHECK(sx >= 0 && sx < period, "period %d: step %d on slot %d", period, g0 + x, sx);
+      for (int y = x + 1; y < depth; ++y)
+        CHECK(sx != xv_pipe_step_slot(g0 + y, period), "depth %d period %d U %d: steps %d and %d share ring slot %d", depth, period, U,
+              g0 + x, g0 + y, sx);
+    }
+}
+
 int main() {
   const int periods[] = {2, 4, 6, 8, 10, 16, 20, 32, 64, 128, 200};
   for (int depth = 2; depth <= 4; ++depth)
-    for (int period : periods)
+    for (int period : periods) {
+      int lanes_checked = 0;      // (the unroll last handed to check_lanes)
       for (int n_steps = 1; n_steps <= 3000; n_steps += (n_steps < 300 ? 1 : 37)) {
         const int cycles = n_steps / period;
         const int U = xv_pipe_pick_unroll(period, cycles, 0, depth);
@@ -24,6 +52,7 @@ int main() {
         }
         CHECK(U >= 1 && U <= cycles, "depth %d period %d steps %d: U = %d", depth, period, n_steps, U);
         CHECK((U * period) % depth == 0, "depth %d period %d: U = %d leaves a ragged stream", depth, period, U);
+        if (depth <= period && U != lanes_checked) { check_lanes(depth, period, U); lanes_checked = U; }
         CHECK(U * period / depth <= (period > XV_PIPE_GRAPH_STEPS_BIG ? period : XV_PIPE_GRAPH_STEPS_BIG),
               "depth %d period %d: %d steps per stream", depth, period, U * period / depth);
         // sticky: what was chosen is kept for the same call, and for any call it serves within 3 % of the best
@@ -38,6 +67,7 @@ int main() {
           }
         }
       }
+    }
   // the documented cases
   CHECK(xv_pipe_pick_unroll(32, 62, 0, 2) == 4, "2,000 steps, ring of 32, two streams: %d", xv_pipe_pick_unroll(32, 62, 0, 2));
   CHECK(xv_pipe_pick_unroll(32, 62, 0, 3) % 3 == 0, "2,000 steps, three streams: %d", xv_pipe_pick_unroll(32, 62, 0, 3));

@@ -1,6 +1,7 @@
 """Host logic of the overlapped step_many paths (csrc/xv_pipe.h): how many ring cycles a cycle graph holds for a call of a
-given length — whole steps per stream, never more cycles than the call has, sticky within 3 % of the best choice.  A small
-host program built with hipcc (it calls nothing of the HIP runtime: no GPU needed)."""
+given length — whole steps per stream, never more cycles than the call has, sticky within 3 % of the best choice — and
+which steps of such a graph set each stream gets: every step once, the same number per stream, the steps in flight together
+on distinct ring slots.  A small host program built with hipcc (it calls nothing of the HIP runtime: no GPU needed)."""
 import os
 import shutil
 import subprocess

@@ -1661,34 +1661,37 @@ static void anymdp_pipe_clear(xv_anymdp* h) {      // fields of the overlapped s
   h->backoff_mixed.fell_known = 0; h->backoff_mixed.left = 0; h->backoff_mixed.len = 0;
   memset(&h->pipe_key, 0, sizeof(h->pipe_key));
 }
-static void anymdp_pipe_drop_graphs(xv_anymdp* h) {
+// where this handle keeps its lanes (xv_pipe.h): lanes 0 and 1 in its own fields — the graph slots of the MDP steps' set or
+// of the token steps' (at most one of the two sets is built at a time) —, lanes 2 and 3 in gate.deep
+static XvPipeLanes anymdp_pipe_lanes(xv_anymdp* h, bool tokens, int D = 0) {
+  XvPipeLanes L;
+  L.D = D; L.main = h->eng->stream; L.side_for = &h->side_for; L.fork = &h->side_ev[0];
+  L.side[0] = &h->side; L.join[0] = &h->side_ev[1];
   for (int q = 0; q < 2; ++q) {
-    if (h->pgraph_exec[q]) { (void)hipGraphExecDestroy(h->pgraph_exec[q]); h->pgraph_exec[q] = nullptr; }
-    if (h->pgraph[q]) { (void)hipGraphDestroy(h->pgraph[q]); h->pgraph[q] = nullptr; }
-    if (h->tgraph_exec[q]) { (void)hipGraphExecDestroy(h->tgraph_exec[q]); h->tgraph_exec[q] = nullptr; }
-    if (h->tgraph[q]) { (void)hipGraphDestroy(h->tgraph[q]); h->tgraph[q] = nullptr; }
+    L.graph[q] = tokens ? &h->tgraph[q] : &h->pgraph[q];
+    L.exec[q] = tokens ? &h->tgraph_exec[q] : &h->pgraph_exec[q];
   }
+  for (int i = 0; i < XV_PIPE_DEPTH_MAX - 2; ++i) {
+    XvPipeDeepLanes& X = h->gate.deep;
+    L.side[1 + i] = &X.side[i]; L.join[1 + i] = &X.join[i]; L.graph[2 + i] = &X.graph[i]; L.exec[2 + i] = &X.exec[i];
+  }
+  return L;
+}
+static void anymdp_pipe_drop_graphs(xv_anymdp* h) {      // both sets (every lane drained first)
+  xv_pipe_drop_set(anymdp_pipe_lanes(h, false));
+  xv_pipe_drop_set(anymdp_pipe_lanes(h, true));
   memset(&h->pipe_key, 0, sizeof(h->pipe_key));
   memset(&h->tpipe_key, 0, sizeof(h->tpipe_key));
   h->gate.unroll[0] = h->gate.unroll[1] = 0;
-  for (int i = 0; i < 2; ++i) {
-    if (h->gate.exec_n[i]) { (void)hipGraphExecDestroy(h->gate.exec_n[i]); h->gate.exec_n[i] = nullptr; }
-    if (h->gate.graph_n[i]) { (void)hipGraphDestroy(h->gate.graph_n[i]); h->gate.graph_n[i] = nullptr; }
-  }
   h->gate.depth = 0;
   h->ptick_valid = false;
 }
 static void anymdp_pipe_release(xv_anymdp* h) {
   anymdp_pipe_drop_graphs(h);
-  if (h->side) { (void)hipStreamSynchronize(h->side); (void)hipStreamDestroy(h->side); }
-  for (int q = 0; q < 2; ++q) if (h->side_ev[q]) (void)hipEventDestroy(h->side_ev[q]);
+  xv_pipe_release_streams(anymdp_pipe_lanes(h, false));
   if (h->d_ptick) (void)hipFree(h->d_ptick);
   if (h->d_snap) (void)hipFree(h->d_snap);
   if (h->d_snap_w) (void)hipFree(h->d_snap_w);
-  for (int i = 0; i < 2; ++i) {
-    if (h->gate.side_n[i]) { (void)hipStreamSynchronize(h->gate.side_n[i]); (void)hipStreamDestroy(h->gate.side_n[i]); h->gate.side_n[i] = nullptr; }
-    if (h->gate.ev_n[i]) { (void)hipEventDestroy(h->gate.ev_n[i]); h->gate.ev_n[i] = nullptr; }
-  }
   xv_pipe_gate_destroy(&h->gate);
   anymdp_pipe_clear(h);
 }
@@ -1902,43 +1905,47 @@ extern "C" int xv_anymdp_reset_injected(xv_anymdp* h, const uint8_t* mask, const
   return XV_OK;
 }
 
+// The ONE list of the step kernel's instantiations over (G, BK) — G: blocks per fence entry, 0 = the binary search; BK: 0 fence
+// (or binary) search, 1 / 2 the bucket lines' packing (AnyMDPArgs::bfmt) — for the step, graph-node, HAND and replay kernels
+// alike:  BK == 0: G = 0 .. 5;  BK == 1 (7 cuts per line: S <= 256, i.e. G <= 3): G = 1 .. 3;  BK == 2: G = 1 .. 5.  A larger G
+// takes the last of its row.  f gets the pair as a type with compile-time members g and bk.  (G = 0 has no HAND kernel and
+// no replay kernel: those callers leave it out with `if constexpr`.)
+template <int G, int BK> struct AnyMDPVariant { static constexpr int g = G, bk = BK; };
+template <class F>
+static auto anymdp_select_variant(int G, int bk, F&& f) {
+  if (bk == 1) return G == 1 ? f(AnyMDPVariant<1, 1>{}) : G == 2 ? f(AnyMDPVariant<2, 1>{}) : f(AnyMDPVariant<3, 1>{});
+  if (bk == 2)
+    return G == 1 ? f(AnyMDPVariant<1, 2>{}) : G == 2 ? f(AnyMDPVariant<2, 2>{}) : G == 3 ? f(AnyMDPVariant<3, 2>{})
+           : G == 4 ? f(AnyMDPVariant<4, 2>{}) : f(AnyMDPVariant<5, 2>{});
+  return G == 0 ? f(AnyMDPVariant<0, 0>{}) : G == 1 ? f(AnyMDPVariant<1, 0>{}) : G == 2 ? f(AnyMDPVariant<2, 0>{})
+         : G == 3 ? f(AnyMDPVariant<3, 0>{}) : G == 4 ? f(AnyMDPVariant<4, 0>{}) : f(AnyMDPVariant<5, 0>{});
+}
+// (G, BK) of a handle under the search in effect, as anymdp_select_variant takes them
+static inline int anymdp_variant_g(const xv_anymdp* h, int eff) { return eff == XV_ANYMDP_SEARCH_BINARY ? 0 : h->a.G; }
+static inline int anymdp_variant_bk(const xv_anymdp* h, int eff) { return eff == XV_ANYMDP_SEARCH_BUCKET ? h->a.bfmt : 0; }
+
+// the same for the cooperative token kernel over (FMT, PAIR) — FMT: the transition bucket lines' packing (1: 7 cuts per line,
+// else 2); PAIR: observations of more than one token — for its step, HAND and replay kernels
+template <int FMT, bool PAIR> struct AnyMDPTokVariant { static constexpr int fmt = FMT; static constexpr bool pair = PAIR; };
+template <class F>
+static auto anymdp_select_tok_variant(const xv_anymdp* h, F&& f) {
+  const bool pair = h->d_obs > 1;
+  if (h->a.bfmt == 1) return pair ? f(AnyMDPTokVariant<1, true>{}) : f(AnyMDPTokVariant<1, false>{});
+  return pair ? f(AnyMDPTokVariant<2, true>{}) : f(AnyMDPTokVariant<2, false>{});
+}
+
 template <bool INJECT>
 static int anymdp_launch_step(xv_anymdp* h, const AnyMDPStepIO& io, int T, int mode) {
   const dim3 grid(xv_div_up(h->a.n_env, 256)), block(256);
-#define XV_LAUNCH_STEP(GV, ROLL)                                                                  \
-  hipLaunchKernelGGL((anymdp_step_kernel<INJECT, GV, ROLL>), grid, block, 0, h->eng->stream, h->a, io, T, mode)
-#define XV_LAUNCH_STEP_G(GV) do { if (roll) XV_LAUNCH_STEP(GV, true); else XV_LAUNCH_STEP(GV, false); } while (0)
   const bool roll = T > 1 || io.greedy != nullptr;
   const int eff = anymdp_effective_search(h);
-  if (eff == XV_ANYMDP_SEARCH_BUCKET) {
-#define XV_LAUNCH_BK(GV, FV)                                                                                              \
-  do {                                                                                                                     \
-    if (roll) hipLaunchKernelGGL((anymdp_step_kernel<INJECT, GV, true, false, FV>), grid, block, 0, h->eng->stream, h->a, io, T, mode);  \
-    else hipLaunchKernelGGL((anymdp_step_kernel<INJECT, GV, false, false, FV>), grid, block, 0, h->eng->stream, h->a, io, T, mode);      \
-  } while (0)
-    if (h->a.bfmt == 1) {        // 7 cuts per line: S <= 256, i.e. G <= 3
-      if (h->a.G == 1) XV_LAUNCH_BK(1, 1);
-      else if (h->a.G == 2) XV_LAUNCH_BK(2, 1);
-      else XV_LAUNCH_BK(3, 1);
-    } else {
-      if (h->a.G == 1) XV_LAUNCH_BK(1, 2);
-      else if (h->a.G == 2) XV_LAUNCH_BK(2, 2);
-      else if (h->a.G == 3) XV_LAUNCH_BK(3, 2);
-      else if (h->a.G == 4) XV_LAUNCH_BK(4, 2);
-      else XV_LAUNCH_BK(5, 2);
-    }
-#undef XV_LAUNCH_BK
-  } else if (eff == XV_ANYMDP_SEARCH_FENCE) {
-    if (h->a.G == 1) XV_LAUNCH_STEP_G(1);
-    else if (h->a.G == 2) XV_LAUNCH_STEP_G(2);
-    else if (h->a.G == 3) XV_LAUNCH_STEP_G(3);
-    else if (h->a.G == 4) XV_LAUNCH_STEP_G(4);
-    else XV_LAUNCH_STEP_G(5);
-  } else {
-    XV_LAUNCH_STEP_G(0);
-  }
-#undef XV_LAUNCH_STEP_G
-#undef XV_LAUNCH_STEP
+  // (bucket search: any packing but the 7-cut one is served by the 6-cut kernels here)
+  const int bk = eff == XV_ANYMDP_SEARCH_BUCKET ? (h->a.bfmt == 1 ? 1 : 2) : 0;
+  anymdp_select_variant(anymdp_variant_g(h, eff), bk, [&](auto v) {
+    using V = decltype(v);
+    if (roll) hipLaunchKernelGGL((anymdp_step_kernel<INJECT, V::g, true, false, V::bk>), grid, block, 0, h->eng->stream, h->a, io, T, mode);
+    else hipLaunchKernelGGL((anymdp_step_kernel<INJECT, V::g, false, false, V::bk>), grid, block, 0, h->eng->stream, h->a, io, T, mode);
+  });
   XV_LAUNCH_CHECK();
   return XV_OK;
 }
@@ -1981,53 +1988,51 @@ extern "C" int xv_anymdp_step_injected(xv_anymdp* h, const int32_t* action, cons
 // `stride`: elements between two ring slots (n_env for the handle's own rings; the parent's n_env when a view steps its
 // columns of the parent's rings, xv_anymdp_step_many_chains).
 static void* anymdp_graph_step_fn(const xv_anymdp* h, int eff, bool hand = false) {
-  const bool fast = eff != XV_ANYMDP_SEARCH_BINARY;
-  const int bk = eff == XV_ANYMDP_SEARCH_BUCKET ? h->a.bfmt : 0;
-  const int Gv = h->a.G;
-  if (hand) {      // the hand-off kernels: fence and bucket searches
-#define XV_STEP_FN(GV, BKV) reinterpret_cast<void*>(&anymdp_step_kernel<false, GV, false, true, BKV, true>)
-    if (!fast) return nullptr;
-    return bk == 1 ? (Gv == 1 ? XV_STEP_FN(1, 1) : Gv == 2 ? XV_STEP_FN(2, 1) : XV_STEP_FN(3, 1))
-           : bk == 2 ? (Gv == 1 ? XV_STEP_FN(1, 2) : Gv == 2 ? XV_STEP_FN(2, 2) : Gv == 3 ? XV_STEP_FN(3, 2)
-                        : Gv == 4 ? XV_STEP_FN(4, 2) : XV_STEP_FN(5, 2))
-           : (Gv == 1 ? XV_STEP_FN(1, 0) : Gv == 2 ? XV_STEP_FN(2, 0) : Gv == 3 ? XV_STEP_FN(3, 0)
-              : Gv == 4 ? XV_STEP_FN(4, 0) : XV_STEP_FN(5, 0));
-#undef XV_STEP_FN
-  }
-#define XV_STEP_FN(GV, BKV) reinterpret_cast<void*>(&anymdp_step_kernel<false, GV, false, true, BKV>)
-  void* fn = bk == 1 ? (Gv == 1 ? XV_STEP_FN(1, 1) : Gv == 2 ? XV_STEP_FN(2, 1) : XV_STEP_FN(3, 1))
-             : bk == 2 ? (Gv == 1 ? XV_STEP_FN(1, 2) : Gv == 2 ? XV_STEP_FN(2, 2) : Gv == 3 ? XV_STEP_FN(3, 2)
-                          : Gv == 4 ? XV_STEP_FN(4, 2) : XV_STEP_FN(5, 2))
-             : !fast ? XV_STEP_FN(0, 0)
-             : (Gv == 1 ? XV_STEP_FN(1, 0) : Gv == 2 ? XV_STEP_FN(2, 0) : Gv == 3 ? XV_STEP_FN(3, 0)
-                : Gv == 4 ? XV_STEP_FN(4, 0) : XV_STEP_FN(5, 0));
-#undef XV_STEP_FN
-  return fn;
+  // the hand-off (HAND) kernels exist for the fence and bucket searches only: nullptr for the binary search
+  return anymdp_select_variant(anymdp_variant_g(h, eff), anymdp_variant_bk(h, eff), [&](auto v) -> void* {
+    using V = decltype(v);
+    if constexpr (V::g != 0)
+      if (hand) return reinterpret_cast<void*>(&anymdp_step_kernel<false, V::g, false, true, V::bk, true>);
+    return hand ? nullptr : reinterpret_cast<void*>(&anymdp_step_kernel<false, V::g, false, true, V::bk>);
+  });
 }
+
+// the rings of a step_many call: slot j of each starts j * stride elements in
+struct AnyMDPRings {
+  size_t stride;
+  const int32_t* actions; int32_t* obs; float* reward; float* reward_gt; uint8_t* terminated; uint8_t* truncated; int32_t* final_obs;
+};
+// One step node of a graph: launch tick *d_tick + g, ring slot j.  The struct holds the kernel's arguments, which must live
+// until hipGraphAddKernelNode has taken them.
+struct AnyMDPStepNode {
+  AnyMDPArgs a;
+  AnyMDPStepIO io;
+  int T, md;
+  void* params[4];
+  void fill(hipKernelNodeParams* np, const xv_anymdp* h, void* fn, uint64_t* d_tick, int g, int j, const AnyMDPRings& R, int mode) {
+    a = h->a;
+    a.seed = h->eng->seed; a.gid_base = h->eng->env_id_base;
+    a.tick = (uint64_t)g; a.tick_dev = d_tick;
+    const size_t off = (size_t)j * R.stride;
+    io = AnyMDPStepIO{R.actions + off, nullptr, nullptr, nullptr, R.obs + off, R.reward + off, R.reward_gt + off, R.terminated + off,
+                      R.truncated + off, R.final_obs ? R.final_obs + off : nullptr, nullptr, nullptr, 0.0f};
+    T = 1; md = mode;
+    params[0] = &a; params[1] = &io; params[2] = &T; params[3] = &md;
+    np->func = fn; np->gridDim = dim3(xv_div_up(h->a.n_env, 256)); np->blockDim = dim3(256); np->kernelParams = params;
+  }
+};
 
 // the chain of `period` step nodes of handle `h` appended to `graph` behind `prev` (nullptr: a root); -> its last node
 static bool anymdp_add_chain(xv_anymdp* h, hipGraph_t graph, hipGraphNode_t* prev, uint64_t* d_tick, int eff, int period,
                              size_t stride, const int32_t* actions, int32_t* obs, float* reward, float* reward_gt,
-                             uint8_t* terminated, uint8_t* truncated, int32_t* final_obs, int mode, int j0 = 0, int dj = 1,
-                             bool hand = false, int reps = 1) {
-  const dim3 grid(xv_div_up(h->a.n_env, 256)), block(256);
-  void* fn = anymdp_graph_step_fn(h, eff, hand);
-  if (!fn) return false;
-  // `reps` ring cycles in one graph (overlapped paths): step g of the graph set goes to stream g % dj, uses ring slot
-  // g % period and tick base + g
-  for (int g = j0; g < reps * period; g += dj) {
-    const int j = g % period;
+                             uint8_t* terminated, uint8_t* truncated, int32_t* final_obs, int mode) {
+  void* fn = anymdp_graph_step_fn(h, eff);
+  const AnyMDPRings R{stride, actions, obs, reward, reward_gt, terminated, truncated, final_obs};
+  for (int j = 0; j < period; ++j) {
     hipKernelNodeParams np;
     memset(&np, 0, sizeof(np));
-    AnyMDPArgs a = h->a;
-    a.seed = h->eng->seed; a.gid_base = h->eng->env_id_base;
-    a.tick = (uint64_t)g; a.tick_dev = d_tick;
-    const size_t off = (size_t)j * stride;
-    AnyMDPStepIO io{actions + off, nullptr, nullptr, nullptr, obs + off, reward + off, reward_gt + off, terminated + off,
-                    truncated + off, final_obs ? final_obs + off : nullptr, nullptr, nullptr, 0.0f};
-    int T = 1, md = mode;
-    void* step_params[] = {&a, &io, &T, &md};
-    np.func = fn; np.gridDim = grid; np.blockDim = block; np.kernelParams = step_params;
+    AnyMDPStepNode sn;
+    sn.fill(&np, h, fn, d_tick, j, j, R, mode);
     hipGraphNode_t node;
     if (hipGraphAddKernelNode(&node, graph, *prev ? prev : nullptr, *prev ? 1 : 0, &np) != hipSuccess) return false;
     *prev = node;
@@ -2044,24 +2049,6 @@ static bool anymdp_add_tick_node(hipGraph_t graph, const hipGraphNode_t* deps, i
   np.kernelParams = tick_params;
   hipGraphNode_t node;
   return hipGraphAddKernelNode(&node, graph, deps, (size_t)n_deps, &np) == hipSuccess;
-}
-
-// head of cycle graph q of the overlapped paths: tick word q += period, then the cycle gate (every stream's graph: xv_pipe.h)
-static bool anymdp_add_head_node(xv_anymdp* h, hipGraph_t graph, hipGraphNode_t* prev, int q, int period, int unroll) {
-  hipKernelNodeParams np;
-  memset(&np, 0, sizeof(np));
-  uint64_t* t = h->d_ptick + q;
-  uint64_t dv = (uint64_t)period * (uint64_t)unroll;
-  uint32_t* seen = h->gate.d_seen + q;
-  const uint32_t* issued = h->gate.d_issued;
-  uint32_t* err = h->a.err;
-  void* params[] = {&t, &dv, &seen, &issued, &err};
-  np.func = reinterpret_cast<void*>(&anymdp_pipe_head_kernel); np.gridDim = dim3(1); np.blockDim = dim3(1);
-  np.kernelParams = params;
-  hipGraphNode_t node;
-  if (hipGraphAddKernelNode(&node, graph, nullptr, 0, &np) != hipSuccess) return false;
-  *prev = node;
-  return true;
 }
 
 static bool anymdp_ensure_graph(xv_anymdp* h, int period, size_t stride, const int32_t* actions, int32_t* obs, float* reward,
@@ -2174,22 +2161,15 @@ static int anymdp_many_plain(xv_anymdp* h, int k, int period, size_t stride, con
 // on long calls; profiles/r05_c_*, r05_d_burst_timeline.txt, r05_n_*).  Same launch ticks, same
 // results as the ordinary path (tests/test_gpu_chains.py).
 #define XV_ANYMDP_PIPE_GRAPH_MIN 64      // calls of at least this many steps are overlapped
-static bool anymdp_pipe_setup(xv_anymdp* h) {
-  if (h->side && h->side_for != h->eng->stream) {      // the engine moved to another stream: choose again
-    (void)hipStreamSynchronize(h->side);
-    anymdp_pipe_drop_graphs(h);
-    (void)hipStreamDestroy(h->side);
-    h->side = nullptr;
-  }
-  if (!h->side) {
-    // the side stream is chosen by measurement (xv_pipe.h): a ping-pong of chained launches over the two streams must cost
-    // about what the same chain costs on one stream — concurrent hardware queues, not two that take turns
-    h->side_for = h->eng->stream;
-    if (!xv_pipe_pick_side_stream(h->eng->stream, &h->side, nullptr, nullptr)) { h->side = nullptr; return false; }
-    if (!h->side_ev[0] && (hipEventCreateWithFlags(&h->side_ev[0], hipEventDisableTiming) != hipSuccess ||
-                           hipEventCreateWithFlags(&h->side_ev[1], hipEventDisableTiming) != hipSuccess))
-      return false;
-  }
+// the side streams of *D lanes (fewer where no third stream qualifies: *D = 2 then) and what is this handle's own: the graphs'
+// tick words, the gate, the snapshot for the replay
+static bool anymdp_pipe_setup(xv_anymdp* h, int* D) {
+  const XvPipeLanes L = anymdp_pipe_lanes(h, false);
+  if (xv_pipe_streams_stale(L)) anymdp_pipe_drop_graphs(h);      // the engine moved to another stream: choose again
+  const int got = xv_pipe_ensure_streams(L, *D);
+  if (got == 0) return false;
+  if (got < *D) (void)hipGetLastError();      // no third stream qualifies: two
+  *D = got;
   if (!h->d_ptick && hipMalloc(&h->d_ptick, XV_PIPE_DEPTH_MAX * sizeof(uint64_t)) != hipSuccess) return false;   // the graphs' tick words
   if (!h->gate.d_seen && !xv_pipe_gate_create(&h->gate)) return false;
   if (!h->d_snap && hipMalloc(&h->d_snap, (size_t)h->a.n_env * sizeof(uint2)) != hipSuccess) { h->d_snap = nullptr; return false; }
@@ -2201,131 +2181,44 @@ static bool anymdp_pipe_setup(xv_anymdp* h) {
 }
 // the replay kernel for this handle's layout and search (HAND kernels exist for the fence and bucket searches only)
 static bool anymdp_launch_replay(xv_anymdp* h, int eff, const AnyMDPStepIO& io, int period, int cycles, int mode, uint64_t t0) {
-  const int bk = eff == XV_ANYMDP_SEARCH_BUCKET ? h->a.bfmt : 0;
   AnyMDPArgs a = h->a;
   a.seed = h->eng->seed; a.gid_base = h->eng->env_id_base; a.tick = t0; a.tick_dev = nullptr;
   const dim3 grid(xv_div_up(h->a.n_env, 256)), block(256);
   uint32_t* h_fell = h->gate.d_issued + 1;
-#define XV_REPLAY(GV, BKV) \
-  hipLaunchKernelGGL((anymdp_replay_kernel<GV, BKV>), grid, block, 0, h->eng->stream, a, io, period, cycles, mode, \
-                     (const uint2*)h->d_snap, h->d_snap_w, h->a.err, h_fell)
-#define XV_REPLAY_G(BKV)                                                                 \
-  do {                                                                                   \
-    if (h->a.G == 1) XV_REPLAY(1, BKV); else if (h->a.G == 2) XV_REPLAY(2, BKV);          \
-    else if (h->a.G == 3) XV_REPLAY(3, BKV); else if (h->a.G == 4) XV_REPLAY(4, BKV);     \
-    else XV_REPLAY(5, BKV);                                                               \
-  } while (0)
-  if (bk == 1) {      // 7 cuts per line: G <= 3
-    if (h->a.G == 1) XV_REPLAY(1, 1); else if (h->a.G == 2) XV_REPLAY(2, 1); else XV_REPLAY(3, 1);
-  } else if (bk == 2) {
-    XV_REPLAY_G(2);
-  } else {
-    XV_REPLAY_G(0);
-  }
-#undef XV_REPLAY_G
-#undef XV_REPLAY
+  anymdp_select_variant(h->a.G, anymdp_variant_bk(h, eff), [&](auto v) {
+    using V = decltype(v);
+    if constexpr (V::g != 0)
+      hipLaunchKernelGGL((anymdp_replay_kernel<V::g, V::bk>), grid, block, 0, h->eng->stream, a, io, period, cycles, mode,
+                         (const uint2*)h->d_snap, h->d_snap_w, h->a.err, h_fell);
+  });
   return hipGetLastError() == hipSuccess;
 }
-// streams 2 .. depth - 1 (xv_pipe_depth() > 2): each accepted beside the engine's stream by the same timed trial
-static bool anymdp_pipe_setup_deep(xv_anymdp* h, int depth) {
-  XvPipeGate& G = h->gate;
-  if (G.side_n_for != h->eng->stream) {
-    for (int i = 0; i < 2; ++i)
-      if (G.side_n[i]) { (void)hipStreamSynchronize(G.side_n[i]); (void)hipStreamDestroy(G.side_n[i]); G.side_n[i] = nullptr; }
-    G.side_n_for = h->eng->stream;
-  }
-  for (int i = 0; i < depth - 2; ++i) {
-    // (beside the engine's stream AND beside the first side stream; a fourth stream is tried against those two only)
-    if (!G.side_n[i] && !xv_pipe_pick_side_stream(h->eng->stream, &G.side_n[i], nullptr, nullptr, h->side)) { G.side_n[i] = nullptr; return false; }
-    if (!G.ev_n[i] && hipEventCreateWithFlags(&G.ev_n[i], hipEventDisableTiming) != hipSuccess) return false;
-  }
-  return true;
-}
 
+// The graph set of the MDP steps on D lanes: HAND step kernels, each lane's tick word advanced by its head node.
 // -> cycles per graph the call uses (graphs built / reused), 0: this call is not overlapped, -1: failure
-static int anymdp_pipe_graphs(xv_anymdp* h, int D, int period, int cycles, size_t stride, const int32_t* actions, int32_t* obs,
-                              float* reward, float* reward_gt, uint8_t* terminated, uint8_t* truncated, int32_t* final_obs, int mode) {
+static int anymdp_pipe_graphs(xv_anymdp* h, int D, int period, int cycles, const AnyMDPRings& R, int mode) {
   const int eff = anymdp_effective_search(h);
-  const void* ptrs[7] = {actions, obs, reward, reward_gt, terminated, truncated, final_obs};
+  const void* ptrs[7] = {R.actions, R.obs, R.reward, R.reward_gt, R.terminated, R.truncated, R.final_obs};
   auto& K = h->pipe_key;
   const bool same = h->pgraph_exec[0] && h->pgraph_exec[1] && K.period == period && K.mode == mode && K.search == eff &&
-                    K.stride == stride && K.bucket == (const void*)h->a.bucket && K.seed == h->eng->seed &&
+                    K.stride == R.stride && K.bucket == (const void*)h->a.bucket && K.seed == h->eng->seed &&
                     K.gid_base == h->eng->env_id_base && memcmp(K.ptrs, ptrs, sizeof(ptrs)) == 0;
-  const bool same_d = same && h->gate.depth == D;
-  const int U = xv_pipe_pick_unroll(period, cycles, same_d ? h->gate.unroll[0] : 0, D);
-  if (U == 0) return 0;
-  if (same_d && U == h->gate.unroll[0]) return U;
-  (void)hipStreamSynchronize(h->side);
-  for (int i = 0; i < 2; ++i) if (h->gate.side_n[i]) (void)hipStreamSynchronize(h->gate.side_n[i]);
-  (void)hipStreamSynchronize(h->eng->stream);
-  anymdp_pipe_drop_graphs(h);
-  if (D > 2 && !anymdp_pipe_setup_deep(h, D)) return -1;
-  if (!xv_pipe_gate_sync(&h->gate)) return -1;      // (every stream of the handle has drained)
-  for (int q = 0; q < D; ++q) {
-    hipGraph_t* gr = q < 2 ? &h->pgraph[q] : &h->gate.graph_n[q - 2];
-    hipGraphExec_t* ge = q < 2 ? &h->pgraph_exec[q] : &h->gate.exec_n[q - 2];
-    if (hipGraphCreate(gr, 0) != hipSuccess) return -1;
-    hipGraphNode_t prev = nullptr;
-    if (!anymdp_add_head_node(h, *gr, &prev, q, period, U)) return -1;
-    if (!anymdp_add_chain(h, *gr, &prev, h->d_ptick + q, eff, period, stride, actions, obs, reward, reward_gt,
-                          terminated, truncated, final_obs, mode, q, D, true, U))
-      return -1;
-    if (hipGraphInstantiate(ge, *gr, nullptr, nullptr, 0) != hipSuccess) {
-      *ge = nullptr;
-      return -1;
-    }
-  }
+  const int have = (same && h->gate.depth == D) ? h->gate.unroll[0] : 0;
+  const int U = xv_pipe_pick_unroll(period, cycles, have, D);
+  if (U == 0 || U == have) return U;
+  anymdp_pipe_drop_graphs(h);      // (the token steps' set goes with it)
+  void* fn = anymdp_graph_step_fn(h, eff, true);
+  if (!fn) return -1;
+  AnyMDPStepNode sn;
+  if (!xv_pipe_build_set(anymdp_pipe_lanes(h, false, D), &h->gate, U, period, reinterpret_cast<void*>(&anymdp_pipe_head_kernel), h->d_ptick,
+                         h->a.err, [&](int g, int slot, int q, hipKernelNodeParams* np) { sn.fill(np, h, fn, h->d_ptick + q, g, slot, R, mode); }))
+    return -1;
   h->gate.depth = D;
-  K.period = period; K.mode = mode; K.search = eff; K.stride = stride; K.bucket = (const void*)h->a.bucket;
+  K.period = period; K.mode = mode; K.search = eff; K.stride = R.stride; K.bucket = (const void*)h->a.bucket;
   K.seed = h->eng->seed; K.gid_base = h->eng->env_id_base;
   memcpy(K.ptrs, ptrs, sizeof(ptrs));
   h->gate.unroll[0] = U;
   return U;
-}
-
-// the whole ring cycles of a call, overlapped; *issued = steps issued (0: the caller takes the ordinary path for all of it).
-// -> XV_OK, or an error when a cycle went out in part (the streams are joined either way)
-// what the replay of an overlapped call needs (ring slot 0 of the call's buffers)
-struct AnyMDPReplay {
-  AnyMDPStepIO io;      // MDP steps (xv_anymdp_step_many)
-  int ring_period, mode, eff;
-  bool tokens;          // token steps (xv_anymdp_step_tokens_many): `tio` instead of `io`
-  AnyMDPTokIO tio;
-};
-static int anymdp_pipe_launch(xv_anymdp* h, hipGraphExec_t* ex, int cycles, int period, int* issued, int depth = 2,
-                              const AnyMDPReplay* rp = nullptr);
-
-static int anymdp_pipe_run(xv_anymdp* h, int n_steps, int period, size_t stride, const int32_t* actions, int32_t* obs,
-                           float* reward, float* reward_gt, uint8_t* terminated, uint8_t* truncated, int32_t* final_obs,
-                           int mode, int* issued) {
-  *issued = 0;
-  const int cycles = n_steps / period;
-  static const int min_steps = getenv("XV_ANYMDP_PIPE_MIN_STEPS") ? atoi(getenv("XV_ANYMDP_PIPE_MIN_STEPS")) : XV_ANYMDP_PIPE_GRAPH_MIN;
-  if (cycles <= 0 || period % 2 != 0 || n_steps < min_steps) return XV_OK;
-  if (xv_pipe_backoff_step(&h->backoff, &h->gate)) return XV_OK;      // a recent call was replayed: one stream for a while
-  // two or three launches resident at once, or the one-stream path (xv_pipe.h)
-  int D = xv_pipe_choose_depth(anymdp_graph_step_fn(h, anymdp_effective_search(h), true), 256,
-                               (size_t)xv_div_up(h->a.n_env, 256), h->eng->device);
-  if (D > period) D = period;      // the steps in flight write distinct ring slots
-  if (D > 2 && xv_pipe_pick_unroll(period, cycles, 0, D) == 0) D = 2;      // too few ring cycles for a three-stream graph set
-  if (D < 2) return XV_OK;
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;      // not inside a stream capture: the set-up synchronises
-  if (hipStreamIsCapturing(h->eng->stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) { (void)hipGetLastError(); return XV_OK; }
-  const bool set_up = anymdp_pipe_setup(h);
-  if (set_up && D > 2 && !anymdp_pipe_setup_deep(h, D)) { (void)hipGetLastError(); D = 2; }      // no third stream qualifies: two
-  const int U = set_up ? anymdp_pipe_graphs(h, D, period, cycles, stride, actions, obs, reward, reward_gt, terminated,
-                                            truncated, final_obs, mode) : -1;
-  if (U < 0) {
-    (void)hipGetLastError();
-    h->pipe_failed = true;
-    return XV_OK;
-  }
-  if (U == 0) return XV_OK;      // too short for the graphs this handle holds: one stream
-  AnyMDPReplay rp;
-  memset(&rp, 0, sizeof(rp));
-  rp.io = AnyMDPStepIO{actions, nullptr, nullptr, nullptr, obs, reward, reward_gt, terminated, truncated, final_obs, nullptr, nullptr, 0.0f};
-  rp.ring_period = period; rp.mode = mode; rp.eff = anymdp_effective_search(h); rp.tokens = false;
-  return anymdp_pipe_launch(h, h->pgraph_exec, cycles / U, period * U, issued, h->gate.depth, &rp);
 }
 
 static __global__ __launch_bounds__(256) void anymdp_pipe_open_kernel(uint2* sr, int n, uint32_t tag, uint64_t* tick_words, int n_words,
@@ -2345,90 +2238,96 @@ static __global__ __launch_bounds__(256) void anymdp_pipe_open_kernel(uint2* sr,
   if (i == 0 && repairable) { const uint32_t e = *err; snap_w[0] = e; snap_w[1] = 0u; snap_w[2] = 0u; *err = e & ~(uint32_t)XV_DEVERR_HANDOFF; }
 }
 
-// `cycles` replays of the cycle graphs ex[0] (engine's stream) / ex[1] (side stream) / the deep ones: tags and tick words, fork,
-// launches, join
-static int anymdp_pipe_launch(xv_anymdp* h, hipGraphExec_t* ex, int cycles, int period, int* issued, int depth, const AnyMDPReplay* rp) {
+// The whole ring cycles of a call, overlapped — MDP and token steps alike; *issued = steps issued (0: the caller takes the
+// ordinary path for all of it).  fn: the HAND kernel whose launches must fit on the device together; graphs(D, ring_cycles):
+// the call's graph set on D lanes, built or reused (anymdp_pipe_graphs / anymdp_tok_pipe_graphs); io (MDP steps) or tio (token
+// steps, the other nullptr): ring slot 0 of the call's buffers, for the replay.  Tags and tick words, then fork, launches and
+// join (xv_pipe.h), then the replay kernel.
+// -> XV_OK, or an error when a cycle went out in part (the streams are joined either way)
+template <class Graphs>
+static int anymdp_pipe_call(xv_anymdp* h, int n_steps, int ring_period, int mode, int min_steps, const void* fn, const AnyMDPStepIO* io,
+                            const AnyMDPTokIO* tio, int* issued, Graphs&& graphs) {
+  *issued = 0;
+  const bool tokens = tio != nullptr;
+  // two or three launches resident at once, or the one-stream path (xv_pipe.h)
+  int D = xv_pipe_preflight(n_steps, ring_period, min_steps, &h->backoff, &h->gate, fn, 256, (size_t)xv_div_up(h->a.n_env, 256),
+                            h->eng->device, h->eng->stream);
+  if (D == 0) return XV_OK;
+  const int U = anymdp_pipe_setup(h, &D) ? graphs(D, n_steps / ring_period) : -1;
+  if (U < 0) {
+    (void)hipGetLastError();
+    h->pipe_failed = true;
+    return XV_OK;
+  }
+  if (U == 0) return XV_OK;      // too short for the graphs this handle holds: one stream
+  const int cycles = n_steps / ring_period / U, period = ring_period * U;      // replays of the graph set, steps in each
   hipStream_t st = h->eng->stream;
   const int test_bad_tag = getenv("XV_PIPE_TEST_BAD_TAG") ? atoi(getenv("XV_PIPE_TEST_BAD_TAG")) : 0;   // tests: env 0's tag is wrong
   const int test_fail = getenv("XV_PIPE_TEST_FAIL") ? atoi(getenv("XV_PIPE_TEST_FAIL")) : 0;            // tests: see anymdp_test_fail_kernel
   h->fell_seen = __atomic_load_n(h->gate.h_issued + 1, __ATOMIC_ACQUIRE);
-  const int deep = depth > 2 ? depth - 2 : 0;      // streams beyond the engine's and `side`
   const uint64_t t0 = h->eng->tick;
   // one launch opens the call: every record gets the tag of the first step (whatever ran since the last overlapped call
   // wrote the tag bits as 0), the graphs' tick words the base their head nodes advance by `period` first
   hipLaunchKernelGGL(anymdp_pipe_open_kernel, dim3(xv_div_up(h->a.n_env, 256)), dim3(256), 0, st, h->a.sr, h->a.n_env,
                      XV_ANYMDP_SR_TAG(t0), h->d_ptick, XV_PIPE_DEPTH_MAX, t0 - (uint64_t)period, h->d_snap, h->d_snap_w,
-                     h->a.err, (rp && test_bad_tag) ? 0 : -1, rp ? 1 : 0);
-  bool ok = hipGetLastError() == hipSuccess;
-  // fork: the side stream starts behind what the engine's stream holds now (the caller's actions, a reset, the tags above)
-  ok = ok && hipEventRecord(h->side_ev[0], st) == hipSuccess && hipStreamWaitEvent(h->side, h->side_ev[0], 0) == hipSuccess;
-  for (int i = 0; i < deep; ++i) ok = ok && hipStreamWaitEvent(h->gate.side_n[i], h->side_ev[0], 0) == hipSuccess;
-  if (!ok) {
+                     h->a.err, test_bad_tag ? 0 : -1, 1);
+  const XvPipeLanes L = anymdp_pipe_lanes(h, tokens, h->gate.depth);
+  h->ptick_valid = false;      // until the cycles have gone out
+  if (hipGetLastError() != hipSuccess || !xv_pipe_fork(L)) {      // (nothing is joined here: see xv_pipe_fork)
     (void)hipGetLastError();
-    h->pipe_failed = true; h->ptick_valid = false;
+    h->pipe_failed = true;
     return XV_OK;
   }
-  h->ptick_valid = false;      // until the cycles have gone out
-  int k = 0;
-  bool broken = false;
-  for (int c = 0; c < cycles; ++c) {
-    // both halves or neither: an even half without its odd half leaves the next even launch waiting (bounded, flagged)
-    // (the even half starts with the cycle gate: it runs once both halves are enqueued, however long the host takes)
-    if (hipGraphLaunch(ex[0], st) != hipSuccess) break;
-    xv_pipe_test_stall(c);
-    if (hipGraphLaunch(ex[1], h->side) != hipSuccess) { broken = true; xv_pipe_gate_release(&h->gate); break; }
-    for (int i = 0; i < deep && !broken; ++i) {
-      if (i == 0) xv_pipe_test_stall(c, 1);
-      if (hipGraphLaunch(h->gate.exec_n[i], h->gate.side_n[i]) != hipSuccess) broken = true;
-    }
-    if (broken) { xv_pipe_gate_release(&h->gate); break; }
-    xv_pipe_gate_release(&h->gate);
-    k += period;
-    h->eng->tick = t0 + (uint64_t)k;
-  }
-  if (k < cycles * period) { (void)hipGetLastError(); h->pipe_failed = true; }
-  bool joined = hipEventRecord(h->side_ev[1], h->side) == hipSuccess && hipStreamWaitEvent(st, h->side_ev[1], 0) == hipSuccess;
-  for (int i = 0; i < deep; ++i)
-    joined = hipEventRecord(h->gate.ev_n[i], h->gate.side_n[i]) == hipSuccess && hipStreamWaitEvent(st, h->gate.ev_n[i], 0) == hipSuccess && joined;
+  const XvPipeIssued r = xv_pipe_issue(L, &h->gate, cycles);
+  const int k = r.cycles * period;
+  h->eng->tick = t0 + (uint64_t)k;
+  if (r.cycles < cycles) { (void)hipGetLastError(); h->pipe_failed = true; }
   *issued = k;
-  if (broken || !joined) {
+  if (r.broken || !r.joined) {
     (void)hipGetLastError();
     h->pipe_failed = true;
     xv_set_error("xv_anymdp_step_many: an overlapped ring cycle could be issued only in part; the envs' states are undefined");
     return XV_ERR_HIP;
   }
-  if (rp && k > 0) {
+  if (k > 0) {
     // behind the join: should a hand-off of this call have expired, the call is replayed from its entry state on this
     // stream (anymdp_replay_kernel: a nearly empty launch otherwise) — an expiry costs time, never results
     if (test_fail) {
-      const size_t n_obs = (size_t)rp->ring_period * (size_t)h->a.n_env * (size_t)(rp->tokens ? h->d_obs : 1);
+      const size_t n_obs = (size_t)ring_period * (size_t)h->a.n_env * (size_t)(tokens ? h->d_obs : 1);
       hipLaunchKernelGGL(anymdp_test_fail_kernel, dim3(xv_div_up(h->a.n_env, 256)), dim3(256), 0, st, h->a.sr, h->a.n_env, h->a.err,
-                         rp->tokens ? rp->tio.obs : rp->io.obs, n_obs);
+                         tokens ? tio->obs : io->obs, n_obs);
     }
     bool replay_ok;
-    if (rp->tokens) {
+    if (tokens) {
       AnyMDPArgs a = h->a;
       a.seed = h->eng->seed; a.gid_base = h->eng->env_id_base; a.tick = t0; a.tick_dev = nullptr;
       AnyMDPTokArgs KA{h->obs_cdf, h->n_obs, h->d_obs, h->d_act, h->obs_bucket};
       const dim3 grid(xv_div_up(h->a.n_env, 256)), block(256);
       uint32_t* h_fell = h->gate.d_issued + 1;
-#define XV_TOK_REPLAY(FV, PV) \
-  hipLaunchKernelGGL((anymdp_tok_replay_kernel<FV, PV>), grid, block, 0, st, a, KA, rp->tio, rp->ring_period, k, rp->mode, \
-                     (const uint2*)h->d_snap, h->d_snap_w, h->a.err, h_fell)
-      if (h->a.bfmt == 1) { if (h->d_obs > 1) XV_TOK_REPLAY(1, true); else XV_TOK_REPLAY(1, false); }
-      else { if (h->d_obs > 1) XV_TOK_REPLAY(2, true); else XV_TOK_REPLAY(2, false); }
-#undef XV_TOK_REPLAY
+      anymdp_select_tok_variant(h, [&](auto v) {
+        using V = decltype(v);
+        hipLaunchKernelGGL((anymdp_tok_replay_kernel<V::fmt, V::pair>), grid, block, 0, st, a, KA, *tio, ring_period, k, mode,
+                           (const uint2*)h->d_snap, h->d_snap_w, h->a.err, h_fell);
+      });
       replay_ok = hipGetLastError() == hipSuccess;
     } else {
-      replay_ok = anymdp_launch_replay(h, rp->eff, rp->io, rp->ring_period, k / rp->ring_period, rp->mode, t0);
+      replay_ok = anymdp_launch_replay(h, anymdp_effective_search(h), *io, ring_period, k / ring_period, mode, t0);
     }
     if (!replay_ok) {
       (void)hipGetLastError();
       h->pipe_failed = true;      // (this call's hand-offs are flagged as before; the next calls take the one-stream path)
     }
+    h->ptick_value = h->eng->tick; h->ptick_valid = true; h->graph_used_last = true; h->pipe_used_last = true;
   }
-  if (k > 0) { h->ptick_value = h->eng->tick; h->ptick_valid = true; h->graph_used_last = true; h->pipe_used_last = true; }
   return XV_OK;
+}
+
+static int anymdp_pipe_run(xv_anymdp* h, int n_steps, int period, const AnyMDPRings& R, int mode, int* issued) {
+  static const int min_steps = getenv("XV_ANYMDP_PIPE_MIN_STEPS") ? atoi(getenv("XV_ANYMDP_PIPE_MIN_STEPS")) : XV_ANYMDP_PIPE_GRAPH_MIN;
+  const AnyMDPStepIO io{R.actions, nullptr, nullptr, nullptr, R.obs, R.reward, R.reward_gt, R.terminated, R.truncated, R.final_obs,
+                        nullptr, nullptr, 0.0f};      // (ring slot 0: for the replay)
+  return anymdp_pipe_call(h, n_steps, period, mode, min_steps, anymdp_graph_step_fn(h, anymdp_effective_search(h), true), &io, nullptr, issued,
+                          [&](int D, int cycles) { return anymdp_pipe_graphs(h, D, period, cycles, R, mode); });
 }
 
 // One handle per device may have the overlap on at a time, and never a view.  Two overlapped calls in flight at once can
@@ -2486,7 +2385,7 @@ extern "C" int xv_anymdp_step_many(xv_anymdp* h, int n_steps, int period, const 
       anymdp_effective_search(h) != XV_ANYMDP_SEARCH_BINARY) {
     XV_HIP(hipSetDevice(h->eng->device));
     h->graph_used_last = false;
-    const int rc = anymdp_pipe_run(h, n_steps, period, n, actions, obs, reward, reward_gt, terminated, truncated, final_obs,
+    const int rc = anymdp_pipe_run(h, n_steps, period, AnyMDPRings{n, actions, obs, reward, reward_gt, terminated, truncated, final_obs},
                                    autoreset_mode, &k);
     if (rc != XV_OK) return rc;
   }
@@ -2850,8 +2749,7 @@ extern "C" int xv_anymdp_build_buckets(xv_anymdp* h, int n_bucket) {
     // an instantiated step_many graph holds the old lines' address and count in its kernel arguments: drop it with them
     if (h->graph_exec) { (void)hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr; }
     if (h->graph) { (void)hipGraphDestroy(h->graph); h->graph = nullptr; }
-    if (h->side) XV_HIP(hipStreamSynchronize(h->side));
-    for (int i = 0; i < 2; ++i) if (h->gate.side_n[i]) XV_HIP(hipStreamSynchronize(h->gate.side_n[i]));
+    XV_HIP(xv_pipe_drain(anymdp_pipe_lanes(h, false)));
     anymdp_pipe_drop_graphs(h);
     (void)hipFree(h->bucket_rw);
     h->bucket_rw = nullptr; h->a.bucket = nullptr; h->a.NBK = 0; h->a.bfmt = 0;
@@ -2926,14 +2824,10 @@ static int anymdp_tok_launch_step(xv_anymdp* h, const AnyMDPTokIO& io, int mode)
   AnyMDPTokArgs K{h->obs_cdf, h->n_obs, h->d_obs, h->d_act, h->obs_bucket};
   const dim3 grid(xv_div_up(h->a.n_env, 256)), block(256);
   if (anymdp_tok_coop(h)) {   // bucket search: the cooperative kernel
-    const bool pair = K.d_obs > 1;
-    if (h->a.bfmt == 1) {
-      if (pair) hipLaunchKernelGGL((anymdp_tok_step_coop_kernel<INJECT, 1, true>), grid, block, 0, h->eng->stream, h->a, K, io, mode);
-      else hipLaunchKernelGGL((anymdp_tok_step_coop_kernel<INJECT, 1, false>), grid, block, 0, h->eng->stream, h->a, K, io, mode);
-    } else {
-      if (pair) hipLaunchKernelGGL((anymdp_tok_step_coop_kernel<INJECT, 2, true>), grid, block, 0, h->eng->stream, h->a, K, io, mode);
-      else hipLaunchKernelGGL((anymdp_tok_step_coop_kernel<INJECT, 2, false>), grid, block, 0, h->eng->stream, h->a, K, io, mode);
-    }
+    anymdp_select_tok_variant(h, [&](auto v) {
+      using V = decltype(v);
+      hipLaunchKernelGGL((anymdp_tok_step_coop_kernel<INJECT, V::fmt, V::pair>), grid, block, 0, h->eng->stream, h->a, K, io, mode);
+    });
   } else {
     hipLaunchKernelGGL(anymdp_tok_step_kernel<INJECT>, grid, block, 0, h->eng->stream, h->a, K, io, mode);
   }
@@ -2964,66 +2858,52 @@ extern "C" int xv_anymdp_step_tokens_info(xv_anymdp* h, const int32_t* action, i
   return anymdp_tok_launch_step<false>(h, io, autoreset_mode);
 }
 
-// n_steps token steps issued from C over ring buffers: step k reads actions slot k % period ([period][n_env][d_act]) and
-// writes slot k % period of the outputs (obs / final_obs [period][n_env][d_obs], the others [period][n_env]); equals
-// n_steps calls of xv_anymdp_step_tokens (a Python / ctypes loop costs more per call than the 10-20 us kernel)
 static void* anymdp_tok_hand_fn(const xv_anymdp* h) {      // the HAND instantiation of the cooperative token kernel for this handle
-  const bool pair = h->d_obs > 1;
-  return h->a.bfmt == 1 ? (pair ? reinterpret_cast<void*>(&anymdp_tok_step_coop_kernel<false, 1, true, true>)
-                                : reinterpret_cast<void*>(&anymdp_tok_step_coop_kernel<false, 1, false, true>))
-                        : (pair ? reinterpret_cast<void*>(&anymdp_tok_step_coop_kernel<false, 2, true, true>)
-                                : reinterpret_cast<void*>(&anymdp_tok_step_coop_kernel<false, 2, false, true>));
+  return anymdp_select_tok_variant(h, [](auto v) {
+    using V = decltype(v);
+    return reinterpret_cast<void*>(&anymdp_tok_step_coop_kernel<false, V::fmt, V::pair, true>);
+  });
 }
 
-// the two cycle graphs of the overlapped token step: HAND instantiations of the cooperative kernel, ring slots q, q + 2, ...
+// the rings of a step_tokens_many call: slot j of actions starts j * n_env * d_act elements in, of obs / final_obs
+// j * n_env * d_obs, of the others j * n_env
+struct AnyMDPTokRings {
+  const int32_t* action; int32_t* obs; float* reward; float* reward_gt; uint8_t* terminated; uint8_t* truncated; int32_t* final_obs;
+  AnyMDPTokIO slot(const xv_anymdp* h, int j) const {
+    const size_t o = (size_t)j * (size_t)h->a.n_env, da = (size_t)h->d_act, dob = (size_t)h->d_obs;
+    return AnyMDPTokIO{action + o * da, nullptr, nullptr, nullptr, nullptr, nullptr, obs + o * dob, reward + o, reward_gt + o,
+                       terminated + o, truncated + o, final_obs ? final_obs + o * dob : nullptr};
+  }
+};
+
+// the graph set of the overlapped token step on D lanes: HAND instantiations of the cooperative kernel
 // -> cycles per graph (built / reused), 0: this call is not overlapped, -1: failure
-static int anymdp_tok_pipe_graphs(xv_anymdp* h, int D, int period, int cycles, const int32_t* action, int32_t* obs, float* reward,
-                                  float* reward_gt, uint8_t* terminated, uint8_t* truncated, int32_t* final_obs, int mode) {
-  const void* ptrs[7] = {action, obs, reward, reward_gt, terminated, truncated, final_obs};
+static int anymdp_tok_pipe_graphs(xv_anymdp* h, int D, int period, int cycles, const AnyMDPTokRings& R, int mode) {
+  const void* ptrs[7] = {R.action, R.obs, R.reward, R.reward_gt, R.terminated, R.truncated, R.final_obs};
   auto& K = h->tpipe_key;
   const bool same = h->tgraph_exec[0] && h->tgraph_exec[1] && K.period == period && K.mode == mode && K.fmt == h->a.bfmt &&
                     K.d_obs == h->d_obs && K.d_act == h->d_act && K.bucket == (const void*)h->a.bucket &&
                     K.obs_bucket == (const void*)h->obs_bucket && K.seed == h->eng->seed && K.gid_base == h->eng->env_id_base &&
                     memcmp(K.ptrs, ptrs, sizeof(ptrs)) == 0;
-  const bool same_d = same && h->gate.depth == D;
-  const int U = xv_pipe_pick_unroll(period, cycles, same_d ? h->gate.unroll[1] : 0, D);
-  if (U == 0) return 0;
-  if (same_d && U == h->gate.unroll[1]) return U;
-  (void)hipStreamSynchronize(h->side);
-  for (int i = 0; i < 2; ++i) if (h->gate.side_n[i]) (void)hipStreamSynchronize(h->gate.side_n[i]);
-  (void)hipStreamSynchronize(h->eng->stream);
-  anymdp_pipe_drop_graphs(h);
-  if (D > 2 && !anymdp_pipe_setup_deep(h, D)) return -1;
-  if (!xv_pipe_gate_sync(&h->gate)) return -1;
+  const int have = (same && h->gate.depth == D) ? h->gate.unroll[1] : 0;
+  const int U = xv_pipe_pick_unroll(period, cycles, have, D);
+  if (U == 0 || U == have) return U;
+  anymdp_pipe_drop_graphs(h);      // (the MDP steps' set goes with it)
   void* fn = anymdp_tok_hand_fn(h);
-  const size_t n = (size_t)h->a.n_env, da = (size_t)h->d_act, dob = (size_t)h->d_obs;
-  const dim3 grid(xv_div_up(h->a.n_env, 256)), block(256);
-  for (int q = 0; q < D; ++q) {
-    hipGraph_t* gr = q < 2 ? &h->tgraph[q] : &h->gate.graph_n[q - 2];
-    hipGraphExec_t* ge = q < 2 ? &h->tgraph_exec[q] : &h->gate.exec_n[q - 2];
-    if (hipGraphCreate(gr, 0) != hipSuccess) return -1;
-    hipGraphNode_t prev = nullptr;
-    if (!anymdp_add_head_node(h, *gr, &prev, q, period, U)) return -1;
-    for (int g = q; g < U * period; g += D) {      // step g of the graph set: stream g % D, ring slot g % period, tick base + g
-      const int j = g % period;
-      AnyMDPArgs a = h->a;
-      a.seed = h->eng->seed; a.gid_base = h->eng->env_id_base;
-      a.tick = (uint64_t)g; a.tick_dev = h->d_ptick + q;
-      AnyMDPTokArgs KA{h->obs_cdf, h->n_obs, h->d_obs, h->d_act, h->obs_bucket};
-      const size_t o = (size_t)j * n;
-      AnyMDPTokIO io{action + o * da, nullptr, nullptr, nullptr, nullptr, nullptr, obs + o * dob, reward + o, reward_gt + o,
-                     terminated + o, truncated + o, final_obs ? final_obs + o * dob : nullptr};
-      int md = mode;
-      void* params[] = {&a, &KA, &io, &md};
-      hipKernelNodeParams np;
-      memset(&np, 0, sizeof(np));
-      np.func = fn; np.gridDim = grid; np.blockDim = block; np.kernelParams = params;
-      hipGraphNode_t node;
-      if (hipGraphAddKernelNode(&node, *gr, prev ? &prev : nullptr, prev ? 1 : 0, &np) != hipSuccess) return -1;
-      prev = node;
-    }
-    if (hipGraphInstantiate(ge, *gr, nullptr, nullptr, 0) != hipSuccess) { *ge = nullptr; return -1; }
-  }
+  AnyMDPArgs a;
+  AnyMDPTokArgs KA{h->obs_cdf, h->n_obs, h->d_obs, h->d_act, h->obs_bucket};
+  AnyMDPTokIO io;
+  int md = mode;
+  void* params[] = {&a, &KA, &io, &md};
+  if (!xv_pipe_build_set(anymdp_pipe_lanes(h, true, D), &h->gate, U, period, reinterpret_cast<void*>(&anymdp_pipe_head_kernel), h->d_ptick,
+                         h->a.err, [&](int g, int slot, int q, hipKernelNodeParams* np) {
+                           a = h->a;
+                           a.seed = h->eng->seed; a.gid_base = h->eng->env_id_base;
+                           a.tick = (uint64_t)g; a.tick_dev = h->d_ptick + q;
+                           io = R.slot(h, slot);
+                           np->func = fn; np->gridDim = dim3(xv_div_up(h->a.n_env, 256)); np->blockDim = dim3(256); np->kernelParams = params;
+                         }))
+    return -1;
   h->gate.depth = D;
   K.period = period; K.mode = mode; K.fmt = h->a.bfmt; K.d_obs = h->d_obs; K.d_act = h->d_act;
   K.bucket = (const void*)h->a.bucket; K.obs_bucket = (const void*)h->obs_bucket;
@@ -3044,44 +2924,19 @@ extern "C" int xv_anymdp_step_tokens_many(xv_anymdp* h, int n_steps, int period,
   XV_CHECK_ARG(h && h->obs_cdf && n_steps > 0 && period > 0);
   XV_CHECK_ARG(action && obs && reward && reward_gt && terminated && truncated);
   XV_CHECK_ARG(autoreset_mode >= 0 && autoreset_mode <= 2);
-  const size_t n = (size_t)h->a.n_env, da = (size_t)h->d_act, dob = (size_t)h->d_obs;
+  const AnyMDPTokRings R{action, obs, reward, reward_gt, terminated, truncated, final_obs};
   int k = 0;
   h->pipe_used_last = false;
-  const int cycles = n_steps / period;
-  if (h->overlap && !h->eng->dev_tick && !h->pipe_failed && anymdp_tok_coop(h) && cycles > 0 && period % 2 == 0 &&
-      n_steps >= XV_ANYMDP_PIPE_GRAPH_MIN && !xv_pipe_backoff_step(&h->backoff, &h->gate) && hipSetDevice(h->eng->device) == hipSuccess &&
-      xv_pipe_choose_depth(anymdp_tok_hand_fn(h), 256, (size_t)xv_div_up(h->a.n_env, 256), h->eng->device) >= 2) {
-    int D = xv_pipe_choose_depth(anymdp_tok_hand_fn(h), 256, (size_t)xv_div_up(h->a.n_env, 256), h->eng->device);
-    if (D > period) D = period;      // the steps in flight write distinct ring slots
-    if (D > 2 && xv_pipe_pick_unroll(period, cycles, 0, D) == 0) D = 2;
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    const bool capturing = hipStreamIsCapturing(h->eng->stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone;
-    if (!capturing) {
-      const bool set_up = anymdp_pipe_setup(h);
-      if (set_up && D > 2 && !anymdp_pipe_setup_deep(h, D)) { (void)hipGetLastError(); D = 2; }
-      const int U = set_up ? anymdp_tok_pipe_graphs(h, D, period, cycles, action, obs, reward, reward_gt, terminated,
-                                                    truncated, final_obs, autoreset_mode) : -1;
-      if (U > 0) {
-        AnyMDPReplay rp;
-        memset(&rp, 0, sizeof(rp));
-        rp.ring_period = period; rp.mode = autoreset_mode; rp.eff = 0; rp.tokens = true;
-        rp.tio = AnyMDPTokIO{action, nullptr, nullptr, nullptr, nullptr, nullptr, obs, reward, reward_gt, terminated, truncated, final_obs};
-        const int rc = anymdp_pipe_launch(h, h->tgraph_exec, cycles / U, period * U, &k, h->gate.depth, &rp);
-        if (rc != XV_OK) return rc;
-      } else if (U < 0) {
-        (void)hipGetLastError();
-        h->pipe_failed = true;
-      }
-    } else {
-      (void)hipGetLastError();
-    }
+  if (h->overlap && !h->eng->dev_tick && !h->pipe_failed && anymdp_tok_coop(h) && hipSetDevice(h->eng->device) == hipSuccess) {
+    const AnyMDPTokIO tio = R.slot(h, 0);
+    // (the minimum call length here is the constant: XV_ANYMDP_PIPE_MIN_STEPS moves it for the MDP steps only)
+    const int rc = anymdp_pipe_call(h, n_steps, period, autoreset_mode, XV_ANYMDP_PIPE_GRAPH_MIN, anymdp_tok_hand_fn(h), nullptr, &tio, &k,
+                                    [&](int D, int cycles) { return anymdp_tok_pipe_graphs(h, D, period, cycles, R, autoreset_mode); });
+    if (rc != XV_OK) return rc;
   }
   for (; k < n_steps; ++k) {
-    const size_t o = (size_t)(k % period) * n;
     anymdp_bind_rng(h, 1);
-    AnyMDPTokIO io{action + o * da, nullptr, nullptr, nullptr, nullptr, nullptr, obs + o * dob, reward + o, reward_gt + o,
-                   terminated + o, truncated + o, final_obs ? final_obs + o * dob : nullptr};
-    const int rc = anymdp_tok_launch_step<false>(h, io, autoreset_mode);
+    const int rc = anymdp_tok_launch_step<false>(h, R.slot(h, k % period), autoreset_mode);
     if (rc != XV_OK) return rc;
   }
   return XV_OK;

@@ -170,6 +170,23 @@ static int mixed_variant(const xv_anymdp* a, const xv_linds* l) {
   return bk * 2 + (l->a.NS == 32 ? 1 : 0);
 }
 
+// the ONE list of the fused kernels' instantiations (step, HAND step, replay) over mixed_variant's number: f gets the AnyMDP
+// packing (0 fence form, 1 the 7-cut bucket lines) and the LinDS state pad (16 | 32) as a type with compile-time members
+template <int ABK, int LNS> struct MixedVariant { static constexpr int abk = ABK, lns = LNS; };
+template <class F>
+static auto mixed_select_variant(int v, F&& f) {
+  return v == 0 ? f(MixedVariant<0, 16>{}) : v == 1 ? f(MixedVariant<0, 32>{}) : v == 2 ? f(MixedVariant<1, 16>{}) : f(MixedVariant<1, 32>{});
+}
+
+// the three families' kernel arguments over one slot of the caller's arrays (info: the steps / done outputs of xv_mixed_step)
+static void mixed_family_io(const xv_mixed_io& io, bool info, AnyMDPStepIO* aio, LinDSStepIO* lio, CartPoleIO* cio) {
+  *aio = AnyMDPStepIO{io.a_action, nullptr, nullptr, nullptr, io.a_obs, io.a_reward, io.a_reward_gt, io.a_terminated,
+                      io.a_truncated, io.a_final_obs, nullptr, nullptr, 0.0f, info ? io.a_steps : nullptr, info ? io.a_done : nullptr};
+  *lio = LinDSStepIO{io.l_action, nullptr, nullptr, io.l_obs, io.l_reward, io.l_terminated, io.l_truncated, io.l_cmd,
+                     io.l_error, io.l_final_obs, info ? io.l_steps : nullptr, info ? io.l_done : nullptr};
+  *cio = CartPoleIO{io.c_action, nullptr, io.c_obs, io.c_reward, io.c_terminated, io.c_truncated, io.c_final_obs, info ? io.c_done : nullptr};
+}
+
 extern "C" int xv_mixed_supported(xv_anymdp* a, xv_linds* l, xv_cartpole* c) {
   if (!a || !l || !c) return 0;
   if (a->eng->stream != l->eng->stream || a->eng->stream != c->eng->stream || a->eng->device != l->eng->device ||
@@ -227,23 +244,15 @@ extern "C" int xv_mixed_step(xv_anymdp* a, xv_linds* l, xv_cartpole* c, const xv
     l->a.tick = (uint64_t)0 - n_tot[1] + n_before[1];
     c->a.tick = (uint64_t)0 - n_tot[2] + n_before[2];
   }
-  AnyMDPStepIO aio{io->a_action, nullptr, nullptr, nullptr, io->a_obs, io->a_reward, io->a_reward_gt, io->a_terminated,
-                   io->a_truncated, io->a_final_obs, nullptr, nullptr, 0.0f, io->a_steps, io->a_done};
-  LinDSStepIO lio{io->l_action, nullptr, nullptr, io->l_obs, io->l_reward, io->l_terminated, io->l_truncated, io->l_cmd,
-                  io->l_error, io->l_final_obs, io->l_steps, io->l_done};
-  CartPoleIO cio{io->c_action, nullptr, io->c_obs, io->c_reward, io->c_terminated, io->c_truncated, io->c_final_obs, io->c_done};
+  AnyMDPStepIO aio; LinDSStepIO lio; CartPoleIO cio;
+  mixed_family_io(*io, true, &aio, &lio, &cio);
   const int nbA = xv_div_up(a->a.n_env, 256), nbL = xv_div_up(xv_div_up(l->a.n_slot, 16), 4), nbC = xv_div_up(c->a.n_env, 256);
   const dim3 grid(nbA + nbL + nbC), block(256);
   hipStream_t st = a->eng->stream;
-#define XV_MIXED_LAUNCH(AG, ABK, LNS) \
-  hipLaunchKernelGGL((mixed_step_kernel<AG, ABK, LNS, 16>), grid, block, 0, st, a->a, aio, nbA, l->a, lio, nbL, c->a, cio, autoreset_mode)
-  switch (v) {
-    case 0: XV_MIXED_LAUNCH(1, 0, 16); break;
-    case 1: XV_MIXED_LAUNCH(1, 0, 32); break;
-    case 2: XV_MIXED_LAUNCH(1, 1, 16); break;
-    default: XV_MIXED_LAUNCH(1, 1, 32); break;
-  }
-#undef XV_MIXED_LAUNCH
+  mixed_select_variant(v, [&](auto mv) {
+    using V = decltype(mv);
+    hipLaunchKernelGGL((mixed_step_kernel<1, V::abk, V::lns, 16>), grid, block, 0, st, a->a, aio, nbA, l->a, lio, nbL, c->a, cio, autoreset_mode);
+  });
   XV_LAUNCH_CHECK();
   return XV_OK;
 }
@@ -265,18 +274,18 @@ struct MixedPipeKey {
   int period, mode, variant, depth;
 };
 struct MixedPipe {
-  hipStream_t side;
-  hipStream_t side2;     // third stream (depth 3: steps k, k + 1, k + 2 in flight, xv_pipe.h)
-  hipEvent_t ev[2];
-  hipEvent_t ev2;
+  // the lanes (xv_pipe.h): side streams, fork / join events, one cycle graph per lane — as many as the shared routines
+  // handle; mixed_pipe_run says how many the batch uses
+  hipStream_t side[XV_PIPE_DEPTH_MAX - 1];
+  hipEvent_t fork, join[XV_PIPE_DEPTH_MAX - 1];
+  hipGraph_t graph[XV_PIPE_DEPTH_MAX];
+  hipGraphExec_t exec[XV_PIPE_DEPTH_MAX];
   uint64_t* d_tick;      // [family][stream], 4 words per family: the graphs' tick words
   uint32_t* d_hand;      // LinDS waves, then CartPole waves
   size_t hand_cap;
-  hipGraph_t graph[3];
-  hipGraphExec_t exec[3];
   MixedPipeKey key;
   bool key_valid, failed, used_last;
-  hipStream_t side_for;  // the engines' stream the side stream was chosen against
+  hipStream_t side_for;  // the engines' stream the side streams were chosen against
   XvPipeGate gate;       // the even half of a cycle starts once the host has enqueued both halves (xv_pipe.h)
   const xv_anymdp* used_by;
   // the states at the entry of the last overlapped call (restored by mixed_replay_kernel should a hand-off expire)
@@ -316,36 +325,24 @@ static __global__ void mixed_pipe_head_kernel(uint64_t* w, uint64_t dv, uint32_t
   if (seen) xv_pipe_gate_pass(seen, issued, err);
 }
 
-static void mixed_pipe_drop_graphs(MixedPipe& M) {
+static XvPipeLanes mixed_pipe_lanes(MixedPipe& M, hipStream_t st, int D = 0) {
+  XvPipeLanes L;
+  L.D = D; L.main = st; L.side_for = &M.side_for; L.fork = &M.fork;
+  for (int i = 0; i < XV_PIPE_DEPTH_MAX - 1; ++i) { L.side[i] = &M.side[i]; L.join[i] = &M.join[i]; }
+  for (int q = 0; q < XV_PIPE_DEPTH_MAX; ++q) { L.graph[q] = &M.graph[q]; L.exec[q] = &M.exec[q]; }
+  return L;
+}
+
+static void mixed_pipe_drop_graphs(MixedPipe& M, hipStream_t st) {      // (every lane drained first)
+  xv_pipe_drop_set(mixed_pipe_lanes(M, st));
   M.gate.unroll[0] = 0;
-  for (int q = 0; q < 3; ++q) {
-    if (M.exec[q]) (void)hipGraphExecDestroy(M.exec[q]);
-    if (M.graph[q]) (void)hipGraphDestroy(M.graph[q]);
-    M.exec[q] = nullptr; M.graph[q] = nullptr;
-  }
   M.key_valid = false;
 }
 
 static bool mixed_pipe_setup(MixedPipe& M, hipStream_t st, size_t n_hand, int depth) {
-  if (M.side && M.side_for != st) {      // measured against another engines' stream: choose again
-    (void)hipStreamSynchronize(M.side);
-    if (M.side2) (void)hipStreamSynchronize(M.side2);
-    mixed_pipe_drop_graphs(M);
-    (void)hipStreamDestroy(M.side);
-    if (M.side2) (void)hipStreamDestroy(M.side2);
-    M.side = nullptr; M.side2 = nullptr;
-  }
-  if (!M.side) {      // chosen by measurement (xv_pipe.h)
-    M.side_for = st;
-    if (!xv_pipe_pick_side_stream(st, &M.side, nullptr, nullptr)) { M.side = nullptr; return false; }
-    if (!M.ev[0] && (hipEventCreateWithFlags(&M.ev[0], hipEventDisableTiming) != hipSuccess ||
-                     hipEventCreateWithFlags(&M.ev[1], hipEventDisableTiming) != hipSuccess))
-      return false;
-  }
-  if (depth > 2 && !M.side2) {
-    if (!xv_pipe_pick_side_stream(st, &M.side2, nullptr, nullptr, M.side)) { M.side2 = nullptr; return false; }
-    if (!M.ev2 && hipEventCreateWithFlags(&M.ev2, hipEventDisableTiming) != hipSuccess) return false;
-  }
+  const XvPipeLanes L = mixed_pipe_lanes(M, st);
+  if (xv_pipe_streams_stale(L)) mixed_pipe_drop_graphs(M, st);      // measured against another engines' stream: choose again
+  if (xv_pipe_ensure_streams(L, depth) != depth) return false;      // chosen by measurement (xv_pipe.h)
   if (!M.d_tick && hipMalloc(&M.d_tick, 12 * sizeof(uint64_t)) != hipSuccess) return false;
   if (!M.gate.d_seen && !xv_pipe_gate_create(&M.gate)) return false;
   if (!M.d_snap_w) {
@@ -353,9 +350,7 @@ static bool mixed_pipe_setup(MixedPipe& M, hipStream_t st, size_t n_hand, int de
     if (hipMemsetAsync(M.d_snap_w, 0, 8 * sizeof(uint32_t), st) != hipSuccess) return false;
   }
   if (M.hand_cap < n_hand) {
-    (void)hipStreamSynchronize(M.side);
-    if (M.side2) (void)hipStreamSynchronize(M.side2);
-    (void)hipStreamSynchronize(st);
+    (void)xv_pipe_drain(L);
     if (M.d_hand) (void)hipFree(M.d_hand);
     M.d_hand = nullptr; M.hand_cap = 0; M.key_valid = false;
     if (hipMalloc(&M.d_hand, n_hand * sizeof(uint32_t)) != hipSuccess) return false;
@@ -378,20 +373,11 @@ static void mixed_io_slot(const xv_mixed_io* ring, size_t s, size_t na, size_t n
   *out = io;
 }
 
-template <int AG, int ABK, int LNS>
-static void mixed_launch_replay_v(dim3 grid, hipStream_t st, const AnyMDPArgs& A, const AnyMDPStepIO& aio, int nbA, const LinDSArgs& L,
-                                  const LinDSStepIO& lio, int nbL, const CartPoleArgs& C, const CartPoleIO& cio, int period, int cycles,
-                                  int mode, const MixedSnap& S) {
-  hipLaunchKernelGGL((mixed_replay_kernel<AG, ABK, LNS, 16>), grid, dim3(256), 0, st, A, aio, nbA, L, lio, nbL, C, cio, period, cycles, mode, S);
-}
-
 static void* mixed_hand_fn(int v) {
-  switch (v) {
-    case 0: return reinterpret_cast<void*>(&mixed_step_kernel<1, 0, 16, 16, true>);
-    case 1: return reinterpret_cast<void*>(&mixed_step_kernel<1, 0, 32, 16, true>);
-    case 2: return reinterpret_cast<void*>(&mixed_step_kernel<1, 1, 16, 16, true>);
-    default: return reinterpret_cast<void*>(&mixed_step_kernel<1, 1, 32, 16, true>);
-  }
+  return mixed_select_variant(v, [](auto mv) {
+    using V = decltype(mv);
+    return reinterpret_cast<void*>(&mixed_step_kernel<1, V::abk, V::lns, 16, true>);
+  });
 }
 
 // -> ring cycles per graph (built / reused), 0: this call is not overlapped, -1: failure
@@ -404,57 +390,31 @@ static int mixed_pipe_graphs(MixedPipe& M, xv_anymdp* a, xv_linds* l, xv_cartpol
   K.L.hand = M.d_hand; K.C.hand = M.d_hand + n_lw;
   memcpy(&K.ring, ring, sizeof(K.ring));
   K.period = period; K.mode = mode; K.variant = v; K.depth = D;
-  const bool same = M.key_valid && M.exec[0] && M.exec[1] && memcmp(&K, &M.key, sizeof(K)) == 0;
-  const int U = xv_pipe_pick_unroll(period, ring_cycles, same ? M.gate.unroll[0] : 0, D);
-  if (U == 0) return 0;
-  if (same && U == M.gate.unroll[0]) return U;
-  (void)hipStreamSynchronize(M.side);
-  if (M.side2) (void)hipStreamSynchronize(M.side2);
-  (void)hipStreamSynchronize(a->eng->stream);
-  mixed_pipe_drop_graphs(M);
-  if (!xv_pipe_gate_sync(&M.gate)) return -1;
+  const int have = (M.key_valid && M.exec[0] && M.exec[1] && memcmp(&K, &M.key, sizeof(K)) == 0) ? M.gate.unroll[0] : 0;
+  const int U = xv_pipe_pick_unroll(period, ring_cycles, have, D);
+  if (U == 0 || U == have) return U;
+  mixed_pipe_drop_graphs(M, a->eng->stream);
   const size_t na = (size_t)a->a.n_env, nl = (size_t)l->a.n_env, nc = (size_t)c->a.n_env;
   int nbA = xv_div_up(a->a.n_env, 256), nbL = xv_div_up(xv_div_up(l->a.n_slot, 16), 4), nbC = xv_div_up(c->a.n_env, 256);
   void* fn = mixed_hand_fn(v);
-  for (int q = 0; q < D; ++q) {
-    if (hipGraphCreate(&M.graph[q], 0) != hipSuccess) return -1;
-    hipGraphNode_t prev = nullptr;
-    {
-      uint64_t* w = M.d_tick + q;
-      uint64_t dv = (uint64_t)period * (uint64_t)U;
-      uint32_t* seen = M.gate.d_seen + q;      // every stream's graph starts with the cycle gate (xv_pipe.h)
-      const uint32_t* issued = M.gate.d_issued;
-      uint32_t* err = a->a.err;
-      void* hparams[5] = {&w, &dv, &seen, &issued, &err};
-      hipKernelNodeParams np;
-      memset(&np, 0, sizeof(np));
-      np.func = reinterpret_cast<void*>(&mixed_pipe_head_kernel); np.gridDim = dim3(1); np.blockDim = dim3(1); np.kernelParams = hparams;
-      if (hipGraphAddKernelNode(&prev, M.graph[q], nullptr, 0, &np) != hipSuccess) return -1;
-    }
-    for (int g = q; g < U * period; g += D) {      // step g of the graph set: stream g % D, ring slot g % period, tick base + g
-      const int s = g % period;
-      AnyMDPArgs A = K.A; LinDSArgs L = K.L; CartPoleArgs C = K.C;
-      const uint64_t tk = (uint64_t)g;
-      A.tick = tk; A.tick_dev = M.d_tick + q;
-      L.tick = tk; L.tick_dev = M.d_tick + 4 + q;
-      C.tick = tk; C.tick_dev = M.d_tick + 8 + q;
-      xv_mixed_io io;
-      mixed_io_slot(ring, (size_t)s, na, nl, nc, (size_t)l->a.NA, (size_t)l->a.NO, &io);
-      AnyMDPStepIO aio{io.a_action, nullptr, nullptr, nullptr, io.a_obs, io.a_reward, io.a_reward_gt, io.a_terminated,
-                       io.a_truncated, io.a_final_obs, nullptr, nullptr, 0.0f};
-      LinDSStepIO lio{io.l_action, nullptr, nullptr, io.l_obs, io.l_reward, io.l_terminated, io.l_truncated, io.l_cmd,
-                      io.l_error, io.l_final_obs};
-      CartPoleIO cio{io.c_action, nullptr, io.c_obs, io.c_reward, io.c_terminated, io.c_truncated, io.c_final_obs};
-      void* params[9] = {&A, &aio, &nbA, &L, &lio, &nbL, &C, &cio, &mode};
-      hipKernelNodeParams np;
-      memset(&np, 0, sizeof(np));
-      np.func = fn; np.gridDim = dim3(nbA + nbL + nbC); np.blockDim = dim3(256); np.kernelParams = params;
-      hipGraphNode_t node = nullptr;
-      if (hipGraphAddKernelNode(&node, M.graph[q], prev ? &prev : nullptr, prev ? 1 : 0, &np) != hipSuccess) return -1;
-      prev = node;
-    }
-    if (hipGraphInstantiate(&M.exec[q], M.graph[q], nullptr, nullptr, 0) != hipSuccess) { M.exec[q] = nullptr; return -1; }
-  }
+  // the kernel arguments of the step node being added (they live until the next one is filled)
+  AnyMDPArgs A; LinDSArgs L; CartPoleArgs C;
+  AnyMDPStepIO aio; LinDSStepIO lio; CartPoleIO cio;
+  void* params[9] = {&A, &aio, &nbA, &L, &lio, &nbL, &C, &cio, &mode};
+  // (the head kernel advances one tick word per family: M.d_tick + q, + 4 + q, + 8 + q; the error word is AnyMDP's)
+  if (!xv_pipe_build_set(mixed_pipe_lanes(M, a->eng->stream, D), &M.gate, U, period, reinterpret_cast<void*>(&mixed_pipe_head_kernel), M.d_tick,
+                         a->a.err, [&](int g, int slot, int q, hipKernelNodeParams* np) {
+                           A = K.A; L = K.L; C = K.C;
+                           const uint64_t tk = (uint64_t)g;
+                           A.tick = tk; A.tick_dev = M.d_tick + q;
+                           L.tick = tk; L.tick_dev = M.d_tick + 4 + q;
+                           C.tick = tk; C.tick_dev = M.d_tick + 8 + q;
+                           xv_mixed_io io;
+                           mixed_io_slot(ring, (size_t)slot, na, nl, nc, (size_t)l->a.NA, (size_t)l->a.NO, &io);
+                           mixed_family_io(io, false, &aio, &lio, &cio);
+                           np->func = fn; np->gridDim = dim3(nbA + nbL + nbC); np->blockDim = dim3(256); np->kernelParams = params;
+                         }))
+    return -1;
   M.key = K; M.key_valid = true;
   M.gate.unroll[0] = U;
   return U;
@@ -471,30 +431,27 @@ static int mixed_pipe_run(xv_anymdp* a, xv_linds* l, xv_cartpole* c, const xv_mi
   M.used_last = false; M.used_by = a;
   const int ring_cycles = n_steps / period;
   static const int min_steps = getenv("XV_MIXED_PIPE_MIN_STEPS") ? atoi(getenv("XV_MIXED_PIPE_MIN_STEPS")) : XV_MIXED_PIPE_MIN;
-  if (ring_cycles <= 0 || period % 2 != 0 || n_steps < min_steps) return XV_OK;
   if (M.failed && M.side_for == a->eng->stream) return XV_OK;      // tried beside this stream already
-  // a recent call with this handle was replayed: the ordinary loop for a while (the count lives in the AnyMDP handle — switching
-  // its overlap on again starts over — against this device's replay counter)
-  if (a->backoff_mixed.len == 0) xv_pipe_backoff_reset(&a->backoff_mixed, &M.gate);
-  if (xv_pipe_backoff_step(&a->backoff_mixed, &M.gate)) return XV_OK;
-  M.failed = false;
+  // the batch's own conditions, then the ones every overlapped path has (xv_pipe_preflight)
   if (a->eng == l->eng || a->eng == c->eng || l->eng == c->eng) return XV_OK;      // one tick per family and step
   if (a->eng->dev_tick || l->eng->dev_tick || c->eng->dev_tick) return XV_OK;
   if (a->eng->stream != l->eng->stream || a->eng->stream != c->eng->stream || l->eng->device != dev || c->eng->device != dev) return XV_OK;
   const int v = mixed_variant(a, l);
   if (v < 0) return XV_OK;
   XV_HIP(hipSetDevice(dev));
-  // two or three launches resident at once, or the ordinary loop (xv_pipe.h)
-  int D = xv_pipe_choose_depth(mixed_hand_fn(v), 256,
-                               (size_t)(xv_div_up(a->a.n_env, 256) + xv_div_up(xv_div_up(l->a.n_slot, 16), 4) + xv_div_up(c->a.n_env, 256)), dev);
-  if (D < 2) return XV_OK;
+  hipStream_t st = a->eng->stream;
+  // a recent call with this handle was replayed: the ordinary loop for a while (the count lives in the AnyMDP handle — switching
+  // its overlap on again starts over — against this device's replay counter)
+  if (a->backoff_mixed.len == 0) xv_pipe_backoff_reset(&a->backoff_mixed, &M.gate);
+  // two launches resident at once, or the ordinary loop (xv_pipe.h).  Capped at TWO lanes:
   // three launches in flight pay for the AnyMDP step (anymdp.hip) but not here: 4.26-4.36 us with two, 4.41 with three
   // (profiles/r05_y_*) — the LinDS chain, not the dispatch gap, bounds the fused step.  (The machinery takes D = 3: a ring
   // must then hold at least three slots, steps k and k + 2 would otherwise write one output slot at the same time.)
-  if (D > 2) D = 2;
-  hipStream_t st = a->eng->stream;
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) { (void)hipGetLastError(); return XV_OK; }
+  const int D = xv_pipe_preflight(n_steps, period, min_steps, &a->backoff_mixed, &M.gate, mixed_hand_fn(v), 256,
+                                  (size_t)(xv_div_up(a->a.n_env, 256) + xv_div_up(xv_div_up(l->a.n_slot, 16), 4) + xv_div_up(c->a.n_env, 256)),
+                                  dev, st, 2);
+  if (D == 0) return XV_OK;
+  M.failed = false;      // (a failure beside another stream: this call starts over)
   const int n_lw = xv_div_up(l->a.n_slot, 16), n_cw = xv_div_up(c->a.n_env, 64);
   anymdp_bind_rng(a, 0, false);
   linds_bind_rng(l, 0, false);
@@ -538,32 +495,19 @@ static int mixed_pipe_run(xv_anymdp* a, xv_linds* l, xv_cartpole* c, const xv_mi
   hipLaunchKernelGGL(mixed_pipe_open_kernel, dim3(xv_div_up(n_open, 256)), dim3(256), 0, st, a->a.sr, a->a.n_env, XV_ANYMDP_SR_TAG(ta),
                      M.d_hand, n_lw, (uint32_t)tl, M.d_hand + n_lw, n_cw, (uint32_t)tc, c->a.steps, c->a.need_reset, c->a.n_env,
                      M.d_tick, ta - (uint64_t)per_launch, tl - (uint64_t)per_launch, tc - (uint64_t)per_launch);   // the head nodes add it
-  bool ok = hipGetLastError() == hipSuccess && hipEventRecord(M.ev[0], st) == hipSuccess &&
-            hipStreamWaitEvent(M.side, M.ev[0], 0) == hipSuccess && (D < 3 || hipStreamWaitEvent(M.side2, M.ev[0], 0) == hipSuccess);
-  int k = 0;
-  bool broken = false;
-  if (ok) {
-    for (int cy = 0; cy < cycles; ++cy) {
-      // both halves or neither: an even half without its odd half leaves the next even launch waiting (bounded, flagged)
-      // (the even half starts with the cycle gate: it runs once both halves are enqueued, however long the host takes)
-      if (hipGraphLaunch(M.exec[0], st) != hipSuccess) break;
-      xv_pipe_test_stall(cy);
-      if (hipGraphLaunch(M.exec[1], M.side) != hipSuccess) { broken = true; xv_pipe_gate_release(&M.gate); break; }
-      if (D == 3) xv_pipe_test_stall(cy, 1);
-      if (D == 3 && hipGraphLaunch(M.exec[2], M.side2) != hipSuccess) { broken = true; xv_pipe_gate_release(&M.gate); break; }
-      xv_pipe_gate_release(&M.gate);
-      k += per_launch;
-    }
-  }
+  // fork, launches, join (xv_pipe.h).  (A fork that fails: no cycle, but this path still joins, and closes below — an AnyMDP
+  // handle's returns at once.)
+  const XvPipeLanes PL = mixed_pipe_lanes(M, st, D);
+  const bool ok = hipGetLastError() == hipSuccess && xv_pipe_fork(PL);
+  const XvPipeIssued r = xv_pipe_issue(PL, &M.gate, ok ? cycles : 0);
+  const int k = r.cycles * per_launch;
   a->eng->tick = ta + (uint64_t)k; l->eng->tick = tl + (uint64_t)k; c->eng->tick = tc + (uint64_t)k;
-  const bool joined = hipEventRecord(M.ev[1], M.side) == hipSuccess && hipStreamWaitEvent(st, M.ev[1], 0) == hipSuccess &&
-                      (D < 3 || (hipEventRecord(M.ev2, M.side2) == hipSuccess && hipStreamWaitEvent(st, M.ev2, 0) == hipSuccess));
   hipLaunchKernelGGL(mixed_pipe_close_kernel, dim3(xv_div_up(c->a.n_env, 256)), dim3(256), 0, st, c->a.steps, c->a.need_reset, c->a.n_env);
   bool closed = hipGetLastError() == hipSuccess;
-  if (closed && joined && !broken && k > 0) {
+  if (closed && r.joined && !r.broken && k > 0) {
     // should a hand-off of this call have expired: the call is replayed from its entry state on this stream (a nearly
     // empty launch otherwise) — an expiry costs time, never results
-    const size_t LA = (size_t)l->a.NA, LO = (size_t)l->a.NO;
+    const size_t LO = (size_t)l->a.NO;
     if (test_fail)
       hipLaunchKernelGGL(mixed_test_fail_kernel, dim3(256), dim3(256), 0, st, a->a.sr, a->a.n_env, l->a.x, snap_bytes[1] / sizeof(float),
                          c->a.state, c->a.n_env, l->a.err, ring->l_obs, (size_t)period * (size_t)l->a.n_env * LO, ring->a_obs,
@@ -572,12 +516,8 @@ static int mixed_pipe_run(xv_anymdp* a, xv_linds* l, xv_cartpole* c, const xv_mi
     A.seed = a->eng->seed; A.gid_base = a->eng->env_id_base; A.tick = ta; A.tick_dev = nullptr;
     L.seed = l->eng->seed; L.gid_base = l->eng->env_id_base; L.tick = tl; L.tick_dev = nullptr;
     C.seed = c->eng->seed; C.gid_base = c->eng->env_id_base; C.tick = tc; C.tick_dev = nullptr;
-    (void)LA;
-    AnyMDPStepIO aio{ring->a_action, nullptr, nullptr, nullptr, ring->a_obs, ring->a_reward, ring->a_reward_gt, ring->a_terminated,
-                     ring->a_truncated, ring->a_final_obs, nullptr, nullptr, 0.0f};
-    LinDSStepIO lio{ring->l_action, nullptr, nullptr, ring->l_obs, ring->l_reward, ring->l_terminated, ring->l_truncated, ring->l_cmd,
-                    ring->l_error, ring->l_final_obs};
-    CartPoleIO cio{ring->c_action, nullptr, ring->c_obs, ring->c_reward, ring->c_terminated, ring->c_truncated, ring->c_final_obs};
+    AnyMDPStepIO aio; LinDSStepIO lio; CartPoleIO cio;
+    mixed_family_io(*ring, false, &aio, &lio, &cio);      // (ring slot 0)
     MixedSnap S;
     S.a_sr = reinterpret_cast<const uint2*>(M.d_snap + snap_off[0]); S.l_x = reinterpret_cast<const float*>(M.d_snap + snap_off[1]);
     S.l_sn = reinterpret_cast<const int32_t*>(M.d_snap + snap_off[2]); S.c_state = reinterpret_cast<const double*>(M.d_snap + snap_off[3]);
@@ -585,17 +525,16 @@ static int mixed_pipe_run(xv_anymdp* a, xv_linds* l, xv_cartpole* c, const xv_mi
     S.w = M.d_snap_w; S.err[0] = a->a.err; S.err[1] = l->a.err; S.err[2] = c->a.err; S.h_fell = M.gate.d_issued + 1;
     const int nbA = xv_div_up(a->a.n_env, 256), nbL = xv_div_up(xv_div_up(l->a.n_slot, 16), 4), nbC = xv_div_up(c->a.n_env, 256);
     const dim3 grid(nbA + nbL + nbC);
-    switch (v) {
-      case 0: mixed_launch_replay_v<1, 0, 16>(grid, st, A, aio, nbA, L, lio, nbL, C, cio, period, k / period, mode, S); break;
-      case 1: mixed_launch_replay_v<1, 0, 32>(grid, st, A, aio, nbA, L, lio, nbL, C, cio, period, k / period, mode, S); break;
-      case 2: mixed_launch_replay_v<1, 1, 16>(grid, st, A, aio, nbA, L, lio, nbL, C, cio, period, k / period, mode, S); break;
-      default: mixed_launch_replay_v<1, 1, 32>(grid, st, A, aio, nbA, L, lio, nbL, C, cio, period, k / period, mode, S); break;
-    }
+    mixed_select_variant(v, [&](auto mv) {
+      using V = decltype(mv);
+      hipLaunchKernelGGL((mixed_replay_kernel<1, V::abk, V::lns, 16>), grid, dim3(256), 0, st, A, aio, nbA, L, lio, nbL, C, cio, period, k / period,
+                         mode, S);
+    });
     closed = hipGetLastError() == hipSuccess;
   }
   *issued = k;
   if (!ok || k < cycles * per_launch) { (void)hipGetLastError(); M.failed = true; }
-  if (broken || !joined || !closed) {
+  if (r.broken || !r.joined || !closed) {
     (void)hipGetLastError();
     M.failed = true;
     xv_set_error("xv_mixed_step_many: an overlapped ring cycle could be issued only in part; the envs' states are undefined");

@@ -13,6 +13,18 @@
 // engine's stream alone.  Candidates of several priorities are tried; the first whose ping-pong costs no more than
 // XV_PIPE_ACCEPT_RATIO x the one-stream chain (+ XV_PIPE_ACCEPT_SLACK_US) is kept.  If none qualifies the overlapped path
 // is not used on that handle (the ordinary one-stream path runs instead: same results).
+//
+// THE MECHANISM LIVES HERE, ONCE, for the AnyMDP MDP steps, the AnyMDP token steps (anymdp.hip) and the mixed batch
+// (mixed.hip) — second half of this file, "Lanes":
+//   xv_pipe_preflight       may this call be overlapped, and on how many lanes (call length, back-off, residency, capture)
+//   xv_pipe_ensure_streams  the side streams (chosen as above) and the fork / join events of 2 .. 4 lanes
+//   xv_pipe_drop_set        every lane drained, a graph set destroyed
+//   xv_pipe_build_set       one cycle graph per lane: gate head node, then the lane's steps (xv_pipe_lane_step) in a chain
+//   xv_pipe_fork / _issue   fork; the launch loop with the gate release ("both halves or neither") and the join
+// A caller keeps the state where it always did and hands it over as an XvPipeLanes view (pointers to its stream, event
+// and graph slots).  What a caller supplies beyond that is its own: the key that says when a graph set is stale, the
+// callable that fills the kernel-node parameters of step g on lane q, its head kernel with the tick words that kernel
+// advances, its open / close / replay kernels, its engines' ticks and its failure flags.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -20,6 +32,7 @@
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <thread>
 
 #include "xv_common.h"
@@ -152,19 +165,30 @@ static bool xv_pipe_pick_side_stream(hipStream_t main, hipStream_t* out, XvPipeC
 #define XV_PIPE_GATE_TIMEOUT 1000000000ull   // 10 s of the 100-MHz wall clock ...
 #define XV_PIPE_GATE_MIN_POLLS (1u << 20)     // ... and this many reads of the host's word (~2 us each): the wave's own waiting
 
+#define XV_PIPE_DEPTH_MAX 4      // lanes (= streams = steps in flight) at the most, see xv_pipe_depth()
+
+// Lanes 2 and 3 (depth 3 / 4: steps k .. k + 3 in flight) of an owner that has slots of its own for lanes 0 and 1 only.
+// Owned by the lanes routines below (xv_pipe_ensure_streams, xv_pipe_drop_set, xv_pipe_release_streams) through the
+// owner's XvPipeLanes view; no gate routine touches it.
+struct XvPipeDeepLanes {
+  hipStream_t side[XV_PIPE_DEPTH_MAX - 2];
+  hipEvent_t join[XV_PIPE_DEPTH_MAX - 2];
+  hipGraph_t graph[XV_PIPE_DEPTH_MAX - 2];
+  hipGraphExec_t exec[XV_PIPE_DEPTH_MAX - 2];
+};
+
 struct XvPipeGate {
   uint32_t* h_issued;   // pinned, mapped host words: [0] graph sets enqueued, [1] overlapped calls replayed after an expired hand-off
   uint32_t* d_issued;   // the device's view of them
   uint32_t* d_seen;     // [XV_PIPE_DEPTH_MAX] gates passed so far by the graphs of each stream (device memory)
   uint32_t issued;      // host mirror
-  int unroll[2];        // ring cycles per cycle graph of the graph pairs built on this gate (0: none built); see below
-  // streams 2 and 3 of the overlapped MDP step_many (depth 3 / 4: steps k .. k + 3 in flight), see xv_pipe_depth()
-  hipStream_t side_n[2];
-  hipStream_t side_n_for;   // the engine's stream they were chosen against
-  hipEvent_t ev_n[2];
-  hipGraph_t graph_n[2];
-  hipGraphExec_t exec_n[2];
-  int depth;            // streams the graphs of unroll[0] were built for (2 .. 4)
+  // the graph sets built on this gate: ring cycles per cycle graph (0: none built; xv_pipe_pick_unroll) of up to two kinds of
+  // set an owner keeps ([0] AnyMDP MDP steps / the mixed batch, [1] AnyMDP token steps), and the lanes they were built for
+  int unroll[2];
+  int depth;            // 2 .. XV_PIPE_DEPTH_MAX
+  // NOT part of the gate, it only travels with it: an AnyMDP handle embeds this struct and nothing else of this header, and
+  // has stream / event / graph fields for two lanes; its further lanes are kept here.  (mixed.hip keeps all lanes itself.)
+  XvPipeDeepLanes deep;
 };
 
 __device__ __forceinline__ void xv_pipe_gate_pass(uint32_t* seen, const uint32_t* issued, uint32_t* err) {
@@ -183,19 +207,18 @@ __device__ __forceinline__ void xv_pipe_gate_pass(uint32_t* seen, const uint32_t
 }
 
 static bool xv_pipe_gate_create(XvPipeGate* g) {
-  g->h_issued = nullptr; g->d_issued = nullptr; g->d_seen = nullptr; g->issued = 0; g->unroll[0] = g->unroll[1] = 0;
-  for (int i = 0; i < 2; ++i) { g->side_n[i] = nullptr; g->ev_n[i] = nullptr; g->graph_n[i] = nullptr; g->exec_n[i] = nullptr; }
-  g->side_n_for = nullptr; g->depth = 0;
+  // (`deep` is left alone: the owner zeroes the whole struct when it is made, and lanes may have been chosen by now)
+  g->h_issued = nullptr; g->d_issued = nullptr; g->d_seen = nullptr; g->issued = 0; g->unroll[0] = g->unroll[1] = 0; g->depth = 0;
   if (hipHostMalloc(reinterpret_cast<void**>(&g->h_issued), 64, hipHostMallocMapped) != hipSuccess) { g->h_issued = nullptr; return false; }
   for (int i = 0; i < 16; ++i) g->h_issued[i] = 0u;
   if (hipHostGetDevicePointer(reinterpret_cast<void**>(&g->d_issued), g->h_issued, 0) != hipSuccess) return false;
-  if (hipMalloc(&g->d_seen, 4 /* XV_PIPE_DEPTH_MAX */ * sizeof(uint32_t)) != hipSuccess) { g->d_seen = nullptr; return false; }
-  return hipMemset(g->d_seen, 0, 4 * sizeof(uint32_t)) == hipSuccess;
+  if (hipMalloc(&g->d_seen, XV_PIPE_DEPTH_MAX * sizeof(uint32_t)) != hipSuccess) { g->d_seen = nullptr; return false; }
+  return hipMemset(g->d_seen, 0, XV_PIPE_DEPTH_MAX * sizeof(uint32_t)) == hipSuccess;
 }
 // when a graph set is (re)built — every stream of the handle drained: all gate counters start from what the host has issued
 // (a stream that sat out some sets, e.g. the third one while two steps were in flight, would otherwise pass its next gates early)
 static bool xv_pipe_gate_sync(XvPipeGate* g) {
-  const uint32_t v[4] = {g->issued, g->issued, g->issued, g->issued};
+  const uint32_t v[XV_PIPE_DEPTH_MAX] = {g->issued, g->issued, g->issued, g->issued};
   return hipMemcpy(g->d_seen, v, sizeof(v), hipMemcpyHostToDevice) == hipSuccess;
 }
 static void xv_pipe_gate_destroy(XvPipeGate* g) {
@@ -312,7 +335,6 @@ static inline int xv_pipe_pick_unroll(int period, int cycles, int have, int dept
 // at 65,536 envs: 2a 3.64-3.85 -> **3.22-3.36 us**, 2b 3.21-3.25 -> **2.95-3.07**; four: 3.10-3.25 / 2.95-3.08, no better, and
 // four launches of 256 workgroups are all the device holds of this kernel (profiles/r05_y_*).  So: three where three
 // launches fit on the device together, else two, else none.  XV_PIPE_DEPTH = 2 .. 4 caps it (devtools A/B).
-#define XV_PIPE_DEPTH_MAX 4
 #define XV_PIPE_DEPTH_DEFAULT 3
 static inline int xv_pipe_depth() {
   static const int d = getenv("XV_PIPE_DEPTH") ? atoi(getenv("XV_PIPE_DEPTH")) : XV_PIPE_DEPTH_DEFAULT;
@@ -324,4 +346,185 @@ static int xv_pipe_choose_depth(const void* fn, int block_threads, size_t grid_b
   for (int d = xv_pipe_depth(); d >= 2; --d)
     if (xv_pipe_two_launches_fit(fn, block_threads, grid_blocks, device, d)) return d;
   return 0;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// Lanes.  An overlapped call runs on D = 2 .. XV_PIPE_DEPTH_MAX lanes: lane 0 is the engine's stream, lanes 1 .. D - 1 are
+// side streams; each lane replays one cycle graph per graph set.  XvPipeLanes is a VIEW of where an owner keeps all that
+// (AnyMDP: the handle's fields and gate.deep; the mixed batch: its per-device MixedPipe): filled on the stack, never kept.
+// Every slot pointer is set for all XV_PIPE_DEPTH_MAX lanes, whatever D: draining and dropping reach lanes a former,
+// deeper set used.
+struct XvPipeLanes {
+  int D;                                         // lanes of the graph set at hand (the routines that need it say so)
+  hipStream_t main;                              // lane 0
+  hipStream_t* side_for;                         // the engine's stream the side streams were chosen against
+  hipStream_t* side[XV_PIPE_DEPTH_MAX - 1];      // lanes 1 ..
+  hipEvent_t* fork;                              // recorded on lane 0, every side lane waits for it
+  hipEvent_t* join[XV_PIPE_DEPTH_MAX - 1];       // recorded on side lane q, lane 0 waits for it
+  hipGraph_t* graph[XV_PIPE_DEPTH_MAX];
+  hipGraphExec_t* exec[XV_PIPE_DEPTH_MAX];
+  hipStream_t stream(int q) const { return q == 0 ? main : *side[q - 1]; }
+};
+
+// Step i of lane q in a graph set of U ring cycles over D lanes -> g, the step's number in the set (-1: the lane has no
+// such step).  Lane q gets the steps g = q, q + D, ... < U * period; step g uses ring slot xv_pipe_step_slot(g, period) and
+// the launch tick "the lane's tick word + g".  With D <= period and D | U * period (xv_pipe_unroll_cost) every lane
+// gets U * period / D steps and any D consecutive steps — the ones in flight together — write D distinct ring slots.
+static inline int xv_pipe_lane_step(int q, int i, int D, int U, int period) {
+  const int g = q + i * D;
+  return g < U * period ? g : -1;
+}
+static inline int xv_pipe_step_slot(int g, int period) { return g % period; }
+
+// The side streams were chosen against another stream than the engine's present one: they will be chosen again
+// (xv_pipe_ensure_streams); the owner drops its graph sets first.
+static inline bool xv_pipe_streams_stale(const XvPipeLanes& L) { return *L.side[0] != nullptr && *L.side_for != L.main; }
+
+// every lane of the owner drained (the side lanes that exist, then the engine's stream) -> the first failure
+static hipError_t xv_pipe_drain(const XvPipeLanes& L) {
+  hipError_t rc = hipSuccess;
+  for (int q = XV_PIPE_DEPTH_MAX - 1; q >= 0; --q) {
+    if (q > 0 && !*L.side[q - 1]) continue;
+    const hipError_t e = hipStreamSynchronize(L.stream(q));
+    if (rc == hipSuccess) rc = e;
+  }
+  return rc;
+}
+
+// One graph set dropped: every lane drained, then the execs and graphs of all lanes destroyed.  (The owner forgets its key
+// and the gate's unroll / depth for the set.)
+static void xv_pipe_drop_set(const XvPipeLanes& L) {
+  (void)xv_pipe_drain(L);
+  for (int q = 0; q < XV_PIPE_DEPTH_MAX; ++q) {
+    if (*L.exec[q]) { (void)hipGraphExecDestroy(*L.exec[q]); *L.exec[q] = nullptr; }
+    if (*L.graph[q]) { (void)hipGraphDestroy(*L.graph[q]); *L.graph[q] = nullptr; }
+  }
+}
+
+static void xv_pipe_destroy_streams(const XvPipeLanes& L) {
+  for (int i = 0; i < XV_PIPE_DEPTH_MAX - 1; ++i)
+    if (*L.side[i]) { (void)hipStreamSynchronize(*L.side[i]); (void)hipStreamDestroy(*L.side[i]); *L.side[i] = nullptr; }
+}
+// the end of an owner: its side streams and events (graph sets dropped before)
+static void xv_pipe_release_streams(const XvPipeLanes& L) {
+  xv_pipe_destroy_streams(L);
+  if (*L.fork) { (void)hipEventDestroy(*L.fork); *L.fork = nullptr; }
+  for (int i = 0; i < XV_PIPE_DEPTH_MAX - 1; ++i)
+    if (*L.join[i]) { (void)hipEventDestroy(*L.join[i]); *L.join[i] = nullptr; }
+}
+
+// The side streams and events of lanes 1 .. depth - 1, made where they are missing.  Every stream is chosen by measurement
+// (xv_pipe_pick_side_stream): a ping-pong of chained launches over the two streams must cost about what the same chain costs
+// on one stream — concurrent hardware queues, not two that take turns; the third and the fourth are tried beside the
+// engine's stream AND beside the first side stream (a fourth is tried against those two only).  All are chosen again when
+// the engine has moved to another stream (xv_pipe_streams_stale: the owner has dropped its graph sets by then).
+// -> the lanes that can be used: `depth`; 2 when no third or fourth stream qualifies (the caller falls back to two lanes);
+// 0 when not even one side stream does, or an event of the first two lanes could not be made.
+static int xv_pipe_ensure_streams(const XvPipeLanes& L, int depth) {
+  if (xv_pipe_streams_stale(L)) xv_pipe_destroy_streams(L);
+  for (int q = 1; q < depth; ++q) {
+    hipStream_t* s = L.side[q - 1];
+    if (!*s) {
+      if (q == 1) *L.side_for = L.main;
+      if (!xv_pipe_pick_side_stream(L.main, s, nullptr, nullptr, q == 1 ? nullptr : *L.side[0])) { *s = nullptr; return q == 1 ? 0 : 2; }
+    }
+    if (q == 1 && !*L.fork && hipEventCreateWithFlags(L.fork, hipEventDisableTiming) != hipSuccess) return 0;
+    if (!*L.join[q - 1] && hipEventCreateWithFlags(L.join[q - 1], hipEventDisableTiming) != hipSuccess) return q == 1 ? 0 : 2;
+  }
+  return depth;
+}
+
+// May this call be overlapped, and on how many lanes?  -> 2 .. XV_PIPE_DEPTH_MAX, or 0: take the ordinary path.
+//   whole ring cycles of an even period, at least min_steps steps (shorter calls lose what the overlap gains: anymdp.hip);
+//   no back-off running (a recent call was replayed: one stream for a while);
+//   as many launches of `fn` resident at once as xv_pipe_choose_depth allows, at most depth_cap;
+//   D <= period: the steps in flight write distinct ring slots;
+//   too few ring cycles for a graph set of three or four lanes: two;
+//   not inside a stream capture: the set-up synchronises.
+static int xv_pipe_preflight(int n_steps, int period, int min_steps, XvPipeBackoff* backoff, const XvPipeGate* gate, const void* fn,
+                             int block_threads, size_t grid_blocks, int device, hipStream_t main, int depth_cap = XV_PIPE_DEPTH_MAX) {
+  const int cycles = n_steps / period;
+  if (cycles <= 0 || period % 2 != 0 || n_steps < min_steps) return 0;
+  if (xv_pipe_backoff_step(backoff, gate)) return 0;
+  int D = xv_pipe_choose_depth(fn, block_threads, grid_blocks, device);
+  if (D > depth_cap) D = depth_cap;
+  if (D > period) D = period;
+  if (D > 2 && xv_pipe_pick_unroll(period, cycles, 0, D) == 0) D = 2;
+  if (D < 2) return 0;
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(main, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) { (void)hipGetLastError(); return 0; }
+  return D;
+}
+
+// The cycle graphs of one set: per lane q < L.D a graph that starts with the head node — `head_fn(tick_words + q,
+// period * U, gate counter d_seen + q, the host's `issued` word, err)`: the lane's tick base for this replay, then the cycle
+// gate (EVERY lane's graph, see "The cycle gate") — followed by the lane's steps, one behind the other.  step(g, slot, q, &np)
+// fills the kernel-node parameters of step g (func, grid, block, kernelParams; the arguments must live until it is called
+// again).  Every lane has been drained and the old set dropped; the gate counters start from what the host has issued.
+template <class StepFn>
+static bool xv_pipe_build_set(const XvPipeLanes& L, XvPipeGate* gate, int U, int period, void* head_fn, uint64_t* tick_words,
+                              uint32_t* err, StepFn&& step) {
+  if (!xv_pipe_gate_sync(gate)) return false;      // (every stream of the owner has drained)
+  for (int q = 0; q < L.D; ++q) {
+    if (hipGraphCreate(L.graph[q], 0) != hipSuccess) return false;
+    hipGraphNode_t prev = nullptr;
+    {
+      uint64_t* t = tick_words + q;
+      uint64_t dv = (uint64_t)period * (uint64_t)U;
+      uint32_t* seen = gate->d_seen + q;
+      const uint32_t* issued = gate->d_issued;
+      void* params[] = {&t, &dv, &seen, &issued, &err};
+      hipKernelNodeParams np;
+      memset(&np, 0, sizeof(np));
+      np.func = head_fn; np.gridDim = dim3(1); np.blockDim = dim3(1); np.kernelParams = params;
+      if (hipGraphAddKernelNode(&prev, *L.graph[q], nullptr, 0, &np) != hipSuccess) return false;
+    }
+    for (int i = 0, g; (g = xv_pipe_lane_step(q, i, L.D, U, period)) >= 0; ++i) {
+      hipKernelNodeParams np;
+      memset(&np, 0, sizeof(np));
+      step(g, xv_pipe_step_slot(g, period), q, &np);
+      hipGraphNode_t node = nullptr;
+      if (hipGraphAddKernelNode(&node, *L.graph[q], &prev, 1, &np) != hipSuccess) return false;
+      prev = node;
+    }
+    if (hipGraphInstantiate(L.exec[q], *L.graph[q], nullptr, nullptr, 0) != hipSuccess) { *L.exec[q] = nullptr; return false; }
+  }
+  return true;
+}
+
+// An overlapped call on the L.D lanes of a graph set: xv_pipe_fork, then xv_pipe_issue (launches and join).
+//   fork: the side lanes start behind what the engine's stream holds now (the caller's actions, a reset, its open kernel).
+//     The two owners differ in what follows a fork that fails, and keep their ways: an AnyMDP handle returns at once; the
+//     mixed batch issues no cycle but joins all the same (xv_pipe_issue with cycles = 0) — its close kernel follows either way.
+//   per cycle: ALL LANES OR NONE.  A first launch that fails ends the loop, nothing of the cycle is out.  A later one that
+//     fails leaves graphs behind their gates, and the next launch on those lanes would wait (bounded, flagged) for steps that
+//     never come: the gate is released all the same and the call is `broken`.  Otherwise the gate is released once, after the
+//     last launch: no wave of a set becomes resident before the whole set is enqueued, however long the host takes between
+//     two launches (xv_pipe_test_stall holds it up there for the tests: before lane 1, and before lane 2).
+//   join: the engine's stream goes on behind every side lane.
+static bool xv_pipe_fork(const XvPipeLanes& L) {
+  bool ok = hipEventRecord(*L.fork, L.main) == hipSuccess;
+  for (int q = 1; q < L.D; ++q) ok = ok && hipStreamWaitEvent(L.stream(q), *L.fork, 0) == hipSuccess;
+  return ok;
+}
+struct XvPipeIssued {
+  int cycles;      // graph sets that went out whole
+  bool broken;     // a cycle went out in part: the envs' states are undefined
+  bool joined;
+};
+static XvPipeIssued xv_pipe_issue(const XvPipeLanes& L, XvPipeGate* gate, int cycles) {
+  XvPipeIssued r{0, false, true};
+  for (int c = 0; c < cycles; ++c) {
+    if (hipGraphLaunch(*L.exec[0], L.main) != hipSuccess) break;
+    for (int q = 1; q < L.D && !r.broken; ++q) {
+      if (q <= 2) xv_pipe_test_stall(c, q - 1);
+      if (hipGraphLaunch(*L.exec[q], L.stream(q)) != hipSuccess) r.broken = true;
+    }
+    xv_pipe_gate_release(gate);
+    if (r.broken) break;
+    r.cycles += 1;
+  }
+  for (int q = 1; q < L.D; ++q)
+    r.joined = hipEventRecord(*L.join[q - 1], L.stream(q)) == hipSuccess && hipStreamWaitEvent(L.main, *L.join[q - 1], 0) == hipSuccess && r.joined;
+  return r;
 }
