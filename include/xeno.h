@@ -983,6 +983,100 @@ int xv_metalm_get_state(xv_metalm* h, int32_t* query, int32_t* query_len, double
 int xv_metalm_set_state(xv_metalm* h, const int32_t* query, const int32_t* query_len, const double* cache,
                         const int32_t* steps);
 
+/* ------------------------------------------------------------------------------------------------
+ * AnyHVAC — reference: xenoverse/anyhvac/anyhvac_env.py HVACEnv :8-651 with control_type 'Temperature',
+ * no_switch_action=True and box actions, over the node classes of anyhvac_utils.py and utils/random_nn.py RandomFourier
+ * :346-368; tasks from anyhvac_sampler.py.  A handle holds n_env rooms; ONE launch steps them all, one workgroup per room,
+ * with the `iter_per_step` inner iterations (coolers, scatter, 5-point stencil) inside the kernel and the room's grid in
+ * LDS.  fp64 throughout except where the reference's own dtype is float32 (clipped action, set temperature, energy
+ * accumulator, cool_power, observations, the reward's target term).  New symbols only: no ABI bump.
+ *   set_task :65-154                -> xv_anyhvac_set_task (packed tables of n_task tasks, one task index per env)
+ *   reset :296-371                  -> xv_anyhvac_reset (grid = ambient + 2 N(0,1), Philox: (engine seed, env_id_base +
+ *                                      env, the call's tick, cell)), xv_anyhvac_reset_injected (the grid is given)
+ *   step :597-651 (update_states    -> xv_anyhvac_step / _step_injected / _rollout (T steps in one launch, bit-equal to T
+ *   :390-442, reward :444-527,         launches of one step).  XV_AUTORESET_SAME_STEP resets a finished env in the launch
+ *   _update_swith_action :574-587)     that finished it (obs is then the new episode's, final_* the finished one's);
+ *                                      XV_AUTORESET_DISABLED goes on stepping; NEXT_STEP is XV_ERR_UNSUPPORTED.
+ * Dimensions NW, NL (cells), C (coolers), S (sensors), H (heaters), KS, KH (Fourier terms of a sensor / heat curve) are the
+ * padded sizes of a batch of tasks; a task's own counts are in its table.  Limits (XV_ERR_UNSUPPORTED beyond): NW, NL <= 16,
+ * C <= 320, S, H <= 640, KS, KH <= 16.
+ * One task's table is XV_ANYHVAC_TASK_DOUBLES(NW, NL, C, S, H, KS, KH) float64 values, in this order (NC = NW * NL cells,
+ * cell (i, j) at i * NL + j; NWALL = (NW + 1) * (NL + 1) * 2 walls, wall (i, j, d) at (i * (NL + 1) + j) * 2 + d):
+ *   scalars[16]: n_width, n_length, coolers, sensors, heaters, cell_size, floor_height, floorceil_chtc, ambient_temp,
+ *                target_temperature, avg_total_heat, base heater's heat_base, period, n_terms, the default action
+ *                value (target - lower) / (upper - lower), the failure bound target + 6
+ *   base heater's order[KH], a[KH], b[KH]
+ *   convection_coeffs[NWALL], heat_capacity[NC]
+ *   sensors[S][8 + 3 KS]: the read's cells s0, s1, d0, d1 (clipped), weights k0, k1, drift period, n_terms, order[KS],
+ *                a[KS], b[KS]
+ *   heaters[H][4 + 3 KH]: base_factor, heat_base, period, n_terms, order[KH], a[KH], b[KH]
+ *   heat_diffuse[H][NC]
+ *   coolers[C][24]: s0, s1, d0, d1, k0, k1, nloc0, nloc1, power_eff_vent, eer_base, eer_decay_start, eer_zero_point,
+ *                eer_reverse, temp_diff_decay_ub, temp_diff_decay_lb, max_cooling_power, min_cooling_power, power_vent_min,
+ *                power_vent_ratio, base_bias, delay_seconds, 0, 0, 0
+ *   cooler_diffuse[C][NC], cooler_vent_diffuse[C][NWALL]
+ * A cooler's delay queue is a ring of XV_ANYHVAC_RING entries: the caller checks max(delay_seconds) / sec_per_iter + 2
+ * against it.  A NaN in net_heat or net_in (the reference raises ValueError): XV_DEVERR_NONFINITE, and the env's grid, time
+ * and counters are left as before the step (its delay queues are not).  An action outside [0, 1] is clipped. */
+#define XV_ANYHVAC_RING 256
+#define XV_ANYHVAC_NWALL(NW, NL) (((NW) + 1) * ((NL) + 1) * 2)
+#define XV_ANYHVAC_TASK_DOUBLES(NW, NL, C, S, H, KS, KH)                                                        \
+  (16 + 3 * (KH) + XV_ANYHVAC_NWALL(NW, NL) + (NW) * (NL) + (S) * (8 + 3 * (KS)) + (H) * (4 + 3 * (KH)) +      \
+   (H) * (NW) * (NL) + (C) * 24 + (C) * (NW) * (NL) + (C) * XV_ANYHVAC_NWALL(NW, NL))
+typedef struct xv_anyhvac xv_anyhvac;
+/* what a step reads and writes: device pointers, rows of n_env envs (xv_anyhvac_rollout: T such blocks one after the
+ * other per array).  final_* and the infos are nullable. */
+typedef struct xv_anyhvac_io {
+  const float* action;      /* [n_env][C], padded columns ignored */
+  float* sensor_readings;   /* [n_env][S] */
+  float* heat_readings;     /* [n_env][H] */
+  float* action_temp;       /* [n_env][C]: the set temperature, -1 for the resting cooler */
+  int32_t* timestep;        /* [n_env] */
+  double* reward;           /* [n_env] */
+  uint8_t* terminated;      /* [n_env] */
+  uint8_t* truncated;       /* [n_env] */
+  float* final_sensor_readings; /* the finished episode's last observation (same-step autoreset), zeros elsewhere */
+  float* final_heat_readings;
+  float* final_action_temp;
+  int32_t* final_timestep;
+  float* cool_power;        /* [n_env][C] */
+  double* heat_power;       /* [n_env][H] */
+  double* misc;             /* [n_env][8]: over_heat, over_tolerace, energy_cost, target_cost, time, rest index, warning
+                               count, episode step (before an autoreset) */
+} xv_anyhvac_io;
+/* an env's state, device pointers, every one nullable (skipped) */
+typedef struct xv_anyhvac_state {
+  double* grid;             /* [n_env][NW * NL] */
+  double* t;                /* [n_env] */
+  double* last_call;        /* [n_env]: time of the sensors' last call, NaN after a reset */
+  int32_t* episode_step;    /* [n_env] */
+  int32_t* warning_count;   /* [n_env] */
+  int32_t* rest_idx;        /* [n_env] */
+  double* rest_start;       /* [n_env][C] */
+  float* value;             /* [n_env][C]: the current action (the resting cooler's is the default value) */
+  double* filter;           /* [n_env][C]: the sensors' last outputs */
+  double* ring_t;           /* [n_env][XV_ANYHVAC_RING] */
+  double* ring_v;           /* [n_env][XV_ANYHVAC_RING][C] */
+  int32_t* head;            /* [n_env][C]: index of a queue's oldest entry, counted from the reset */
+  int32_t* tail;            /* [n_env]: entries pushed since the reset */
+} xv_anyhvac_state;
+int xv_anyhvac_create(xv_engine* e, int n_env, int NW, int NL, int C, int S, int H, int KS, int KH, int iter_per_step,
+                      double sec_per_iter, double set_lower_bound, double set_upper_bound, double max_t, int reward_mode,
+                      xv_anyhvac** out);   /* max_t = int(max_steps * iter_per_step * sec_per_iter): truncation at t >= max_t */
+int xv_anyhvac_destroy(xv_anyhvac* h);
+/* tables float64[n_task][XV_ANYHVAC_TASK_DOUBLES(...)], env_task int32[n_env]: device pointers, borrowed */
+int xv_anyhvac_set_task(xv_anyhvac* h, int n_task, const double* tables, const int32_t* env_task);
+/* mask uint8[n_env] or NULL (all); the observation arrays of io are written for the envs that were reset */
+int xv_anyhvac_reset(xv_anyhvac* h, const uint8_t* mask, const xv_anyhvac_io* io);
+/* grid float64[n_env][NW * NL] */
+int xv_anyhvac_reset_injected(xv_anyhvac* h, const uint8_t* mask, const double* grid, const xv_anyhvac_io* io);
+int xv_anyhvac_step(xv_anyhvac* h, const xv_anyhvac_io* io, int autoreset_mode);
+/* reset_grid float64[n_env][NW * NL]: the grid a same-step autoreset starts from (no tick is consumed) */
+int xv_anyhvac_step_injected(xv_anyhvac* h, const xv_anyhvac_io* io, const double* reset_grid, int autoreset_mode);
+int xv_anyhvac_rollout(xv_anyhvac* h, int T, const xv_anyhvac_io* io, int autoreset_mode);
+int xv_anyhvac_get_state(xv_anyhvac* h, const xv_anyhvac_state* out);
+int xv_anyhvac_set_state(xv_anyhvac* h, const xv_anyhvac_state* in);
+
 #ifdef __cplusplus
 }
 #endif

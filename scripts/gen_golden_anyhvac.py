@@ -1,0 +1,205 @@
+"""Golden fixtures of AnyHVAC: the REFERENCE's own sampler and env (xenoverse/anyhvac: HVACTaskSampler, HVACEnv) on the
+rooms listed in RUNS, and two tasks at the sampler's default constants.
+
+Build-container tooling, like scripts/gen_golden_metalm.py: the reference is imported read-only through
+oracle/_refimport.py; nothing under oracle/ is modified (the gymnasium stand-in there has no spaces.Dict and no
+spaces.MultiBinary, which HVACEnv.set_task asks for: both are added to the imported module in this process only).  The
+room-size constants are overridden on the imported sampler module.
+
+Per fixture: numpy.random.seed(seed); random.seed(seed); task = HVACTaskSampler(); env.set_task(task); env.reset(); then
+the run's actions.  The port (xenoverse_amd.anyhvac.HVACTaskSampler with the same constants and seeds) must return the
+flattened reference task array for array, bit for bit, and HVACHost runs alongside the recording from the recorded initial
+grid: every recorded quantity must be bit-equal at every step, or the script stops.  Two margins are taken along the run:
+the smallest |ambient - state[nloc]| any cooler saw at any inner iteration (the EER jump) and the smallest
+|sensor - failure_upperbound| at any step.  A seed that leaves the first below 1e-7 K or the second below 1e-4 K, or whose
+room misses the run's own condition, is passed over for the next one.
+
+Only data is written: tests/golden/anyhvac_<name>.npz (the flattened task under task_*, seeds, settings, the initial grid,
+per step the action, grid, t, observation, reward, flags, cool_power, heat_power, rest index and warning count, and the
+two margins).
+
+usage: python scripts/gen_golden_anyhvac.py
+"""
+import contextlib
+import io
+import os
+import random
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "oracle"))
+import _refimport  # noqa: E402
+
+from xenoverse_amd.anyhvac import host as H  # noqa: E402
+from xenoverse_amd.anyhvac import task_sampler as TS  # noqa: E402
+
+GOLD = os.path.join(ROOT, "tests", "golden")
+MIN_EER_MARGIN, MIN_FAIL_MARGIN = 1e-7, 1e-4
+quiet = lambda: contextlib.redirect_stdout(io.StringIO())  # noqa: E731
+
+
+def _reference():
+    _refimport.setup()
+    import gymnasium
+
+    class Dict(gymnasium.spaces.Space):
+        def __init__(self, spaces):
+            self.spaces = dict(spaces)
+
+    class MultiBinary(gymnasium.spaces.Space):
+        def __init__(self, n):
+            self.n = n
+    for cls in (Dict, MultiBinary):
+        if not hasattr(gymnasium.spaces, cls.__name__):
+            setattr(gymnasium.spaces, cls.__name__, cls)
+    from xenoverse.anyhvac import anyhvac_sampler
+    from xenoverse.anyhvac.anyhvac_env import HVACEnv
+    return anyhvac_sampler, HVACEnv
+
+
+def room(w, l, lo, hi):
+    return dict(ROOM_W_GRID_SIZE_LOW=w, ROOM_W_GRID_SIZE_HIGH=w + 1, ROOM_L_GRID_SIZE_LOW=l, ROOM_L_GRID_SIZE_HIGH=l + 1,
+                CELL_SIZE_LOW=lo, CELL_SIZE_HIGH=hi)
+
+
+def sample_both(S, seed, config):
+    """-> (reference task of objects, its flattening); the port must give the same arrays"""
+    saved = {k: getattr(S, k) for k in config}
+    for k, v in config.items():
+        setattr(S, k, v)
+    try:
+        np.random.seed(seed)
+        random.seed(seed)
+        with quiet():
+            ref = S.HVACTaskSampler()
+        state = np.random.get_state(), random.getstate()
+    finally:
+        for k, v in saved.items():
+            setattr(S, k, v)
+    flat = TS.task_from_reference(ref)
+    np.random.seed(seed)
+    random.seed(seed)
+    mine = TS.HVACTaskSampler(config=config)
+    assert set(mine) == set(flat)
+    for k in flat:
+        a, b = np.asarray(flat[k]), np.asarray(mine[k])
+        assert a.shape == b.shape and a.dtype == b.dtype and np.array_equal(a, b), "sampler port differs in %s" % k
+    np.random.set_state(state[0])
+    random.setstate(state[1])
+    return ref, flat
+
+
+def same(a, b, what, k):
+    a, b = np.asarray(a), np.asarray(b)
+    if a.dtype != b.dtype or a.shape != b.shape or a.tobytes() != b.tobytes():
+        raise SystemExit("HVACHost differs from the reference in %s at step %d" % (what, k))
+
+
+def record(HVACEnv, ref_task, flat, settings, generate_task, actions, until):
+    env = HVACEnv(**settings)
+    with quiet():
+        env.set_task(ref_task, generate_task=generate_task)
+        env.reset()
+    init = env.state.copy()
+    host = H.HVACHost(**settings)
+    host.set_task(flat, generate_task=generate_task)
+    assert host.avg_total_heat == env.avg_total_heat, "average total heat differs: %r %r" % (host.avg_total_heat,
+                                                                                             env.avg_total_heat)
+    host.reset(init)
+    rows = {}
+    fail_margin = np.inf
+    for k in range(10 ** 6):
+        a = actions(k, len(ref_task["coolers"]))
+        with quiet():
+            obs, r, term, trunc, info = env.step(a)
+        hobs, hr, hterm, htrunc, hinfo = host.step(a)
+        rec = dict(action=a, grid=env.state, t=np.float64(env.t), reward=np.float64(r), terminated=bool(term),
+                   truncated=bool(trunc), cool_power=info["cool_power"], heat_power=info["heat_power"],
+                   rest_idx=np.int32(env.current_rest_cooler_idx), warning_count=np.int32(env.warning_count),
+                   over_heat=np.int32(info["over_heat"]), over_tolerace=np.int32(info["over_tolerace"]),
+                   energy_cost=np.float64(info["energy_cost"]), target_cost=np.float64(info["target_cost"]),
+                   timestep=obs["timestep"][0], **{q: obs[q] for q in ("sensor_readings", "heat_readings", "action_temp")})
+        mine = dict(action=a, grid=host.state, t=np.float64(host.t), reward=np.float64(hr), terminated=bool(hterm),
+                    truncated=bool(htrunc), cool_power=hinfo["cool_power"], heat_power=hinfo["heat_power"],
+                    rest_idx=np.int32(host.rest_idx), warning_count=np.int32(host.warning_count),
+                    over_heat=np.int32(hinfo["over_heat"]), over_tolerace=np.int32(hinfo["over_tolerace"]),
+                    energy_cost=np.float64(hinfo["energy_cost"]), target_cost=np.float64(hinfo["target_cost"]),
+                    timestep=hobs["timestep"][0], **{q: hobs[q] for q in ("sensor_readings", "heat_readings", "action_temp")})
+        assert type(r) is type(hr) or (np.float64(r) == np.float64(hr)), (type(r), type(hr))
+        for q in rec:
+            same(rec[q], mine[q], q, k + 1)
+            rows.setdefault(q, []).append(np.array(rec[q]))
+        fail_margin = min(fail_margin, float(np.abs(obs["sensor_readings"].astype(np.float64)
+                                                    - env.failure_upperbound).min()))
+        if until(k + 1, term, trunc):
+            break
+    out = {q: np.array(v) for q, v in rows.items()}
+    out.update(init_grid=init, eer_margin=np.float64(host.eer_margin), fail_margin=np.float64(fail_margin),
+               avg_total_heat=np.float64(env.avg_total_heat), n_steps=np.int32(k + 1),
+               failure_upperbound=np.float64(env.failure_upperbound))
+    return out
+
+
+def uniform_actions(seed):
+    rng = np.random.RandomState(seed)
+    return lambda k, n: rng.uniform(0, 1, n).astype(np.float32)
+
+
+SLOW = dict(max_steps=20160, iter_per_step=200, sec_per_iter=0.15, reward_mode=0)
+# name -> (room constants, first seed, condition on the task, env settings, generate_task, actions(seed), stop rule)
+RUNS = {
+    "rot": (room(5, 6, 1.0, 1.5), 6, lambda t: 3 <= len(t["coolers"]) <= 6 and t["ambient_temp"] < t["target_temperature"] + 5,
+            SLOW, False, lambda s: (lambda k, n: np.full(n, 0.3 + 0.2 * np.sin(k), np.float32)), lambda k, te, tr: k >= 125),
+    "hot": (room(6, 5, 1.2, 1.6), 0, lambda t: t["ambient_temp"] > t["target_temperature"] + 7,
+            SLOW, True, lambda s: (lambda k, n: np.ones(n, np.float32)), lambda k, te, tr: te or k >= 60),
+    "trunc": (room(5, 7, 1.2, 1.6), 2, lambda t: True, dict(SLOW, max_steps=8), True,
+              lambda s: uniform_actions(1000 + s), lambda k, te, tr: tr or k >= 20),
+    "wide": (room(9, 11, 2.8, 3.0), 5, lambda t: len(t["coolers"]) > 64 and len(t["sensors"]) > 64, SLOW, True,
+             lambda s: uniform_actions(1000 + s), lambda k, te, tr: k >= 6),
+    "mode1": (room(5, 7, 1.2, 1.6), 2, lambda t: True, dict(SLOW, iter_per_step=50, sec_per_iter=0.2, reward_mode=1), True,
+              lambda s: uniform_actions(2000 + s), lambda k, te, tr: k >= 6),
+    "mode2": (room(5, 7, 1.2, 1.6), 2, lambda t: True, dict(SLOW, iter_per_step=50, sec_per_iter=0.2, reward_mode=2), True,
+              lambda s: uniform_actions(3000 + s), lambda k, te, tr: k >= 6),
+}
+
+
+def save(name, flat, extra):
+    d = {"task_" + k: np.asarray(v) for k, v in flat.items()}
+    d.update(extra)
+    path = os.path.join(GOLD, "anyhvac_%s.npz" % name)
+    np.savez_compressed(path, **d)
+    print("%-8s %7d bytes  %s" % (name, os.path.getsize(path),
+                                  {k: (float(v) if np.ndim(v) == 0 else np.shape(v)) for k, v in extra.items()
+                                   if k in ("eer_margin", "fail_margin", "n_steps", "seed", "rest_idx")}))
+
+
+def main():
+    S, HVACEnv = _reference()
+    for seed in (0, 1):
+        _, flat = sample_both(S, seed, {})
+        save("task_s%d" % seed, flat, dict(seed=np.int32(seed)))
+    for name, (config, seed0, cond, settings, gen, actions, until) in RUNS.items():
+        for seed in range(seed0, seed0 + 50):
+            try:
+                ref, flat = sample_both(S, seed, config)
+            except ValueError:      # the reference's one-cooler random.sample error
+                continue
+            if not cond(ref):
+                continue
+            out = record(HVACEnv, ref, flat, settings, gen, actions(seed), until)
+            if out["eer_margin"] >= MIN_EER_MARGIN and out["fail_margin"] >= MIN_FAIL_MARGIN:
+                break
+            print("%s: seed %d passed over (margins %g, %g)" % (name, seed, out["eer_margin"], out["fail_margin"]))
+        else:
+            raise SystemExit("no seed qualifies for %s" % name)
+        out.update(seed=np.int32(seed), generate_task=np.bool_(gen), config_keys=np.array(sorted(config)),
+                   config_values=np.array([config[k] for k in sorted(config)], np.float64),
+                   **{"set_" + k: np.asarray(v) for k, v in settings.items()})
+        save(name, flat, out)
+
+
+if __name__ == "__main__":
+    main()

@@ -1,0 +1,157 @@
+"""what the AnyHVAC tests share: the fixtures of scripts/gen_golden_anyhvac.py (tests/golden/anyhvac_*.npz) and the bounds a
+device run is held to against them.
+
+Device and host are written in the same order of operations (csrc/anyhvac.hip, xenoverse_amd/anyhvac/host.py) and the
+build forbids contraction, so they can differ only through
+  * exp (the sensors' low-pass filter), sin and cos (heat curves, sensor drift): the device library documents 1 ulp for
+    exp and 2 ulp for sin / cos in fp64, numpy's are within 1 ulp;
+  * the float32 means of the reward (numpy sums pairwise in float32; the device sums in fp64 and rounds once);
+  * the fp64 sum of the heater powers (numpy pairwise, the device a fixed tree).
+The bounds below follow from those alone; none is taken from a device run.
+"""
+import os
+
+import numpy as np
+
+from util import golden_files
+
+FILES = {os.path.basename(p)[len("anyhvac_"):-4]: p for p in golden_files("anyhvac_")}
+RUNS = ("rot", "hot", "trunc", "wide", "mode1", "mode2")
+TASKS_ONLY = ("task_s0", "task_s1")
+MIN_EER_MARGIN, MIN_FAIL_MARGIN = 1e-7, 1e-4
+EPS32 = 2.0 ** -24      # half a float32 ulp, relative
+INT_KEYS = ("ROOM_W_GRID_SIZE_LOW", "ROOM_W_GRID_SIZE_HIGH", "ROOM_L_GRID_SIZE_LOW", "ROOM_L_GRID_SIZE_HIGH")
+_cache = {}
+
+
+def load(name):
+    """-> (fixture dict, flat task dict, env settings, generate_task)"""
+    if name not in _cache:
+        g = dict(np.load(FILES[name], allow_pickle=False))
+        task = {k[5:]: (v if v.ndim else v[()]) for k, v in g.items() if k.startswith("task_")}
+        settings = gen = None
+        if name in RUNS:
+            settings = dict(max_steps=int(g["set_max_steps"]), iter_per_step=int(g["set_iter_per_step"]),
+                            sec_per_iter=float(g["set_sec_per_iter"]), reward_mode=int(g["set_reward_mode"]))
+            gen = bool(g["generate_task"])
+        _cache[name] = (g, task, settings, gen)
+    return _cache[name]
+
+
+def sampler_config(g):
+    return {str(k): (int(v) if str(k) in INT_KEYS else float(v)) for k, v in zip(g["config_keys"], g["config_values"])}
+
+
+def same_bits(a, b):
+    a, b = np.asarray(a), np.asarray(b)
+    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
+
+
+# ---- bounds of a device run against a recorded one ---------------------------------------------------------------------
+def grid_tol(g, k):
+    """one ulp of a temperature below 64 K-above-zero (2^-46 = 1.4e-14) per inner iteration so far, every one of the same
+    sign and none damped.  (The room damps them: random +-16-ulp perturbations of the host's exp / sin / cos, and a constant
+    bias of +1, -1 or +2 ulp on all three, each move its grid by at most 1.6e-13 K over any of the recorded runs.)"""
+    return (k + 1) * int(g["set_iter_per_step"]) * 2.0 ** -46
+
+
+HEAT_POWER_TOL = 1e-9      # W: 2-ulp sin / cos errors (4.4e-16) on up to 14 terms with coefficients up to 1e5: 6e-10
+
+
+def ulps32(a, b):
+    """|a - b| in float32 ulps of the larger magnitude"""
+    a, b = np.asarray(a, np.float32), np.asarray(b, np.float32)
+    sp = np.spacing(np.maximum(np.abs(a), np.abs(b)))
+    return np.abs(a.astype(np.float64) - b.astype(np.float64)) / sp
+
+
+def _mean_roundings(n):
+    """float32 roundings on the longest path of numpy's mean of n float32 numbers: its pairwise sum keeps 8 running sums
+    (n / 8 additions each), combines them in 3 levels, adds up to 7 left-over terms one by one, halves blocks above 128
+    terms recursively; then the division.  Each is at most half an ulp of a partial sum, and the terms here are not negative,
+    so of the total."""
+    return n / 8 + 3 + 7 + max(0, int(np.ceil(np.log2(max(n, 1) / 128)))) + 1
+
+
+def cost_tols(g, k, n_sensors, n_coolers):
+    """(target_cost, energy_cost, reward) bounds at step k: numpy's roundings of the float32 mean plus the ONE of the device,
+    which sums in fp64; the energy term's inputs may each sit a float32 rounding apart (2 more, see cool_power); the reward
+    adds 1.0 to the target term in float32 (a result below 4 in magnitude: an ulp is at most 2^-22)."""
+    tc, ec = abs(float(g["target_cost"][k])), abs(float(g["energy_cost"][k]))
+    t_tol = (_mean_roundings(n_sensors) + 1) * EPS32 * tc
+    e_tol = (_mean_roundings(n_coolers) + 3) * EPS32 * ec
+    return t_tol, e_tol, t_tol + e_tol + 2.0 ** -22
+
+
+def check_step(g, k, obs, reward, terminated, truncated, info, grid, label=""):
+    """a device step (numpy arrays of the room's true sizes) against step k of a recording: discrete outputs equal,
+    continuous ones within the bounds above"""
+    S, C = g["sensor_readings"].shape[1], g["action"].shape[1]
+    at = "%s step %d: " % (label, k + 1)
+    assert bool(terminated) == bool(g["terminated"][k]) and bool(truncated) == bool(g["truncated"][k]), at + "flags"
+    assert float(info["time"]) == float(g["t"][k]), at + "t"
+    assert int(obs["timestep"]) == int(g["timestep"][k]), at + "timestep"
+    assert int(info["rest_idx"]) == int(g["rest_idx"][k]), at + "rest index"
+    assert int(info["warning_count"]) == int(g["warning_count"][k]), at + "warning count"
+    assert int(info["over_heat"]) == int(g["over_heat"][k]) and int(info["over_tolerace"]) == int(g["over_tolerace"][k]), at
+    assert same_bits(np.asarray(obs["action_temp"], np.float32), g["action_temp"][k]), at + "action_temp"
+    d = float(np.abs(grid - g["grid"][k]).max())
+    assert d <= grid_tol(g, k), at + "grid off by %g K (bound %g)" % (d, grid_tol(g, k))
+    u = float(ulps32(obs["sensor_readings"], g["sensor_readings"][k]).max())
+    assert u <= 1.0, at + "sensor readings off by %g float32 ulp" % u
+    u = float(ulps32(obs["heat_readings"], g["heat_readings"][k]).max())
+    assert u <= 1.0, at + "heat readings off by %g float32 ulp" % u
+    d = float(np.abs(info["heat_power"] - g["heat_power"][k]).max())
+    assert d <= HEAT_POWER_TOL, at + "heat power off by %g W" % d
+    # the float32 energy accumulator takes 200 roundings; a device power 1e-13 off flips one of them once in ~1e6
+    u = float(ulps32(info["cool_power"], g["cool_power"][k]).max())
+    assert u <= 2.0, at + "cool power off by %g float32 ulp" % u
+    t_tol, e_tol, r_tol = cost_tols(g, k, S, C)
+    assert abs(float(info["target_cost"]) - float(g["target_cost"][k])) <= t_tol, at + "target cost"
+    assert abs(float(info["energy_cost"]) - float(g["energy_cost"][k])) <= e_tol, at + "energy cost"
+    if g["terminated"][k]:
+        assert float(reward) == float(g["reward"][k]) == -30.0, at + "failure reward"
+    else:
+        assert abs(float(reward) - float(g["reward"][k])) <= r_tol, at + "reward off by %g (bound %g)" % (
+            abs(float(reward) - float(g["reward"][k])), r_tol)
+
+
+# ---- device plumbing ------------------------------------------------------------------------------------------------
+def true_sizes(env, i, obs, reward, terminated, truncated, info, lead=()):
+    """env i of a batched result -> numpy arrays of its room's true sizes (lead: index of a rollout's step)"""
+    c = env.counts
+    nC, nS, nH = int(c["coolers"][i]), int(c["sensors"][i]), int(c["heaters"][i])
+    at = tuple(lead) + (i,)
+    o = dict(sensor_readings=obs["sensor_readings"][at][:nS].cpu().numpy(), heat_readings=obs["heat_readings"][at][:nH].cpu().numpy(),
+             action_temp=obs["action_temp"][at][:nC].cpu().numpy(), timestep=int(obs["timestep"][at]))
+    inf = {k: float(info[k][at]) for k in ("over_heat", "over_tolerace", "energy_cost", "target_cost", "time", "rest_idx",
+                                           "warning_count", "episode_step")}
+    inf["cool_power"] = info["cool_power"][at][:nC].cpu().numpy()
+    inf["heat_power"] = info["heat_power"][at][:nH].cpu().numpy()
+    return o, float(reward[at]), bool(terminated[at]), bool(truncated[at]), inf
+
+
+def grid_of(env, i):
+    NW, NL = env.dims[:2]
+    nw, nl = int(env.counts["n_width"][i]), int(env.counts["n_length"][i])
+    return env.get_state()["grid"][i].reshape(NW, NL)[:nw, :nl].cpu().numpy()
+
+
+def flat_result(o, r, te, tr, inf):
+    """every output of one env's step as one list of arrays (bit-equality of two runs)"""
+    return ([np.asarray(o[k]) for k in sorted(o)] + [np.float64(r), np.bool_(te), np.bool_(tr)]
+            + [np.asarray(inf[k]) for k in sorted(inf)])
+
+
+def pad_actions(env, per_env):
+    a = np.zeros((env.num_envs, env.dims[2]), np.float32)
+    for i, v in enumerate(per_env):
+        a[i, :len(v)] = v
+    return a
+
+
+def pad_grids(env, per_env):
+    g = np.zeros((env.num_envs,) + tuple(env.dims[:2]))
+    for i, v in enumerate(per_env):
+        g[i, :v.shape[0], :v.shape[1]] = v
+    return g

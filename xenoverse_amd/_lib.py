@@ -144,6 +144,16 @@ SIGNATURES = {
     "xv_metalm_step": [c_void_p] + [c_void_p] * 16,
     "xv_metalm_get_state": [c_void_p] * 5,
     "xv_metalm_set_state": [c_void_p] * 5,
+    "xv_anyhvac_create": [c_void_p] + [c_int] * 9 + [C.c_double] * 4 + [c_int, C.POINTER(c_void_p)],
+    "xv_anyhvac_destroy": [c_void_p],
+    "xv_anyhvac_set_task": [c_void_p, c_int, c_void_p, c_void_p],
+    "xv_anyhvac_reset": [c_void_p, c_void_p, c_void_p],                 # (handle, mask, xv_anyhvac_io*)
+    "xv_anyhvac_reset_injected": [c_void_p, c_void_p, c_void_p, c_void_p],
+    "xv_anyhvac_step": [c_void_p, c_void_p, c_int],
+    "xv_anyhvac_step_injected": [c_void_p, c_void_p, c_void_p, c_int],
+    "xv_anyhvac_rollout": [c_void_p, c_int, c_void_p, c_int],
+    "xv_anyhvac_get_state": [c_void_p, c_void_p],                       # (handle, xv_anyhvac_state*)
+    "xv_anyhvac_set_state": [c_void_p, c_void_p],
 }
 for _p in ("xv_cartpole", "xv_acrobot"):      # the control families share one set of entry points (csrc/xv_control.h)
     SIGNATURES.update({
@@ -174,6 +184,21 @@ class BucketCensus(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
+class AnyHVACIO(C.Structure):
+    """xv_anyhvac_io (include/xeno.h): device pointers of what a step reads and writes"""
+    FIELDS = ("action", "sensor_readings", "heat_readings", "action_temp", "timestep", "reward", "terminated", "truncated",
+              "final_sensor_readings", "final_heat_readings", "final_action_temp", "final_timestep", "cool_power",
+              "heat_power", "misc")
+    _fields_ = [(k, C.c_void_p) for k in FIELDS]
+
+
+class AnyHVACState(C.Structure):
+    """xv_anyhvac_state (include/xeno.h)"""
+    FIELDS = ("grid", "t", "last_call", "episode_step", "warning_count", "rest_idx", "rest_start", "value", "filter",
+              "ring_t", "ring_v", "head", "tail")
+    _fields_ = [(k, C.c_void_p) for k in FIELDS]
 
 
 class XenoError(RuntimeError):

@@ -1,0 +1,12 @@
+"""AnyHVAC: batched data-centre thermal environments (the reference's anyhvac family).
+
+    from xenoverse_amd.anyhvac import HVACEnv, HVACTaskSampler      # the reference's line with the package name changed
+
+HVACTaskSampler / task_from_reference: tasks as flat dicts (task_sampler.py); HVACHost: the fp64 numpy restatement, pinned
+bit for bit to recorded runs of the reference (host.py); HVACVecEnv / HVACEnv: the device envs (vec_env.py).
+"""
+from .config import DEFAULTS                                                      # noqa: F401
+from .host import HVACHost, average_total_heat, check_settings, heater_powers    # noqa: F401
+from .task_sampler import HVACTaskSampler, task_from_reference, wind_diffuser    # noqa: F401
+from .tables import build_tables                                                  # noqa: F401
+from .vec_env import HVACEnv, HVACVecEnv                                          # noqa: F401

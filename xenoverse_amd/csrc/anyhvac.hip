@@ -1,0 +1,632 @@
+// anyhvac.hip — AnyHVAC (include/xeno.h: xv_anyhvac_*): batched data-centre thermal rooms, one workgroup per room.
+//
+// Reference: anyhvac_env.py HVACEnv (control_type 'Temperature', no_switch_action=True, box actions); the bit-exact host
+// restatement the tests compare with is xenoverse_amd/anyhvac/host.py.  One step is `iters` inner iterations of
+//   A  per cooler (one lane each, strided past the block): bilinear read of the grid, push / pop of its delay ring, low-pass
+//      filter, proportional controller, EER, float32 energy accumulator -> -eer, power_cool, power_vent in LDS
+//   B  scatter: net_heat[cell] = static_heat[cell] + sum_c ((-eer_c) D_c[cell]) power_cool_c   (one lane per cell)
+//               net_chtc[wall] = chtc[wall] + sum_c (V_c[wall] power_vent_c) eff_vent_c        (lanes strided over walls)
+//      with the coolers in index order, which is the host's order of addition
+//   C  5-point stencil into the other grid buffer
+// with a workgroup barrier after each, the grid double-buffered in LDS, and the step's epilogue (time rounding,
+// observation, reward, counters, flags, same-step autoreset) in the same launch.  Every product and sum is written in the
+// host's order (the build has -ffp-contract=off), so device and host differ only by the last bits of exp, sin and cos and
+// by the order of the float32 means of the reward.  Sums over lanes are fixed-shape trees in LDS: an env's result does not
+// depend on the batch it runs in.
+#include <cmath>
+#include <new>
+
+#include "philox.h"
+#include "xv_common.h"
+
+#define HV_BLOCK 256
+#define HV_MAX_GRID 16
+#define HV_MAX_C 320
+#define HV_MAX_SH 640
+#define HV_MAX_K 16
+#define HV_MAX_WALL (17 * 17 * 2)
+#define HV_DRAW_GRID 7u      // Philox purpose of the reset grid (sub-index: the cell)
+#define HV_REST_SECONDS 3600.0
+#define HV_MAX_HEAT 20000.0
+
+struct HvArgs {
+  int NW, NL, C, S, H, KS, KH;      // padded sizes of the tables
+  const double* tables;
+  const int32_t* env_task;
+  int n_task, n_env, iters, reward_mode;
+  double dt, lb, ub, max_t;
+  // state
+  double *grid, *t, *last_call;
+  int32_t *episode_step, *warning_count, *rest_idx;
+  double* rest_start;
+  float* value;
+  double *filter, *ring_t, *ring_v;
+  int32_t *head, *tail;
+  uint32_t* err;
+  uint64_t seed, gid_base, tick;
+  const uint64_t* tick_dev;
+};
+
+struct xv_anyhvac {
+  xv_engine* eng;
+  HvArgs a;
+};
+
+struct HvTask {      // one task's table, taken apart (layout: include/xeno.h)
+  const double *sc, *base, *chtc, *hc, *sens, *heat, *hd, *cool, *cd, *cv;
+  int nw, nl, nC, nS, nH, NL, NC, NWALL, KS, KH, srow, hrow;
+};
+
+__device__ __forceinline__ HvTask hv_task(const HvArgs& P, int env) {
+  HvTask K;
+  const int NC = P.NW * P.NL, NWALL = XV_ANYHVAC_NWALL(P.NW, P.NL);
+  const size_t stride = (size_t)XV_ANYHVAC_TASK_DOUBLES(P.NW, P.NL, P.C, P.S, P.H, P.KS, P.KH);
+  int task = P.env_task[env];
+  task = task < 0 ? 0 : (task >= P.n_task ? P.n_task - 1 : task);
+  const double* p = P.tables + (size_t)task * stride;
+  K.NL = P.NL; K.NC = NC; K.NWALL = NWALL; K.KS = P.KS; K.KH = P.KH;
+  K.srow = 8 + 3 * P.KS; K.hrow = 4 + 3 * P.KH;
+  K.sc = p; p += 16;
+  K.base = p; p += 3 * P.KH;
+  K.chtc = p; p += NWALL;
+  K.hc = p; p += NC;
+  K.sens = p; p += (size_t)P.S * K.srow;
+  K.heat = p; p += (size_t)P.H * K.hrow;
+  K.hd = p; p += (size_t)P.H * NC;
+  K.cool = p; p += (size_t)P.C * 24;
+  K.cd = p; p += (size_t)P.C * NC;
+  K.cv = p;
+  // counts are clamped to the padded sizes: a table that lies cannot send an index out of its arrays
+  K.nw = min(max((int)K.sc[0], 1), P.NW); K.nl = min(max((int)K.sc[1], 1), P.NL);
+  K.nC = min(max((int)K.sc[2], 1), P.C); K.nS = min(max((int)K.sc[3], 1), P.S); K.nH = min(max((int)K.sc[4], 1), P.H);
+  return K;
+}
+
+__device__ __forceinline__ int hv_cell(const HvTask& K, double a, double b) {      // a clipped cell of a table row -> LDS index
+  const int i = min(max((int)a, 0), K.nw - 1), j = min(max((int)b, 0), K.nl - 1);
+  return i * K.NL + j;
+}
+
+// RandomFourier.__call__: y = 0; y += a sin(order x) + b cos(order x), term after term
+__device__ __forceinline__ double hv_series(const double* order, int K, int n, double x) {
+  const double *a = order + K, *b = order + 2 * K;
+  double y = 0.0;
+  n = min(n, K);
+  for (int j = 0; j < n; ++j) y = y + (a[j] * sin(order[j] * x) + b[j] * cos(order[j] * x));
+  return y;
+}
+
+__device__ __forceinline__ double hv_curve(double heat_base, double period, int n, const double* order, int K, double t) {
+  const double y = hv_series(order, K, n, t / period);
+  return fmin(heat_base + fmax(y, 0.0), HV_MAX_HEAT);
+}
+
+__device__ __forceinline__ double hv_heater(const HvTask& K, int h, double t) {
+  const double* r = K.heat + (size_t)h * K.hrow;
+  const double base = hv_curve(K.sc[11], K.sc[12], (int)K.sc[13], K.base, K.KH, t);
+  const double own = hv_curve(r[1], r[2], (int)r[3], r + 4, K.KH, t);
+  return r[0] * base + (1.0 - r[0]) * own;
+}
+
+// the bilinear read both node kinds make: r = {s0, s1, d0, d1, k0, k1, ...}
+__device__ __forceinline__ double hv_read(const HvTask& K, const double* g, const double* r) {
+  const int ss = hv_cell(K, r[0], r[1]), ds = hv_cell(K, r[2], r[1]), sd = hv_cell(K, r[0], r[3]), dd = hv_cell(K, r[2], r[3]);
+  const double k0 = r[4], k1 = r[5];
+  return g[ss] * (1.0 - k0) * (1.0 - k1) + g[ds] * k0 * (1.0 - k1) + g[sd] * (1.0 - k0) * k1 + g[dd] * k0 * k1;
+}
+
+// sum over the block, a fixed tree: the same value in every lane, the same bits in every batch
+__device__ __forceinline__ double hv_block_sum(double v, double* red) {
+  const int tid = threadIdx.x;
+  red[tid] = v;
+  __syncthreads();
+  for (int o = HV_BLOCK / 2; o > 0; o >>= 1) {
+    if (tid < o) red[tid] = red[tid] + red[tid + o];
+    __syncthreads();
+  }
+  const double s = red[0];
+  __syncthreads();
+  return s;
+}
+
+struct HvObsOut {
+  float *sensor, *heat, *atemp;
+  int32_t* timestep;
+};
+
+__device__ __forceinline__ HvObsOut hv_obs_rows(float* sensor, float* heat, float* atemp, int32_t* timestep, size_t row,
+                                                const HvArgs& P) {
+  HvObsOut o;
+  o.sensor = sensor ? sensor + row * P.S : nullptr;
+  o.heat = heat ? heat + row * P.H : nullptr;
+  o.atemp = atemp ? atemp + row * P.C : nullptr;
+  o.timestep = timestep ? timestep + row : nullptr;
+  return o;
+}
+
+// _get_obs: sensor readings, heater powers, set temperatures and the step index at time t; padded columns are zero.
+// loss / hot (nullable): this lane's share of sum max(sqrt(d), d), d = clip(reading - target, 0, 8) in float32, and of the
+// count of readings above the failure bound
+__device__ __forceinline__ void hv_obs(const HvArgs& P, const HvTask& K, const double* g, double t, int rest, const float* value,
+                                       const HvObsOut& o, double* loss, double* hot) {
+  const int tid = threadIdx.x;
+  const float target = (float)K.sc[9];
+  const double fub = K.sc[15];
+  double ls = 0.0, ht = 0.0;
+  for (int s = tid; s < P.S; s += HV_BLOCK) {
+    float v = 0.0f;
+    if (s < K.nS) {
+      const double* r = K.sens + (size_t)s * K.srow;
+      v = (float)(hv_read(K, g, r) + hv_series(r + 8, K.KS, (int)r[7], t / r[6]));
+      const float d = fminf(fmaxf(v - target, 0.0f), 8.0f);
+      ls += (double)fmaxf(sqrtf(d), d);
+      ht += ((double)v > fub) ? 1.0 : 0.0;
+    }
+    if (o.sensor) o.sensor[s] = v;
+  }
+  if (loss) *loss = ls;
+  if (hot) *hot = ht;
+  if (o.heat)
+    for (int h = tid; h < P.H; h += HV_BLOCK) o.heat[h] = h < K.nH ? (float)hv_heater(K, h, t) : 0.0f;
+  if (o.atemp)
+    for (int c = tid; c < P.C; c += HV_BLOCK) {
+      float a = 0.0f;
+      if (c < K.nC) a = c == rest ? -1.0f : value[c] * (float)(P.ub - P.lb) + (float)P.lb;
+      o.atemp[c] = a;
+    }
+  if (o.timestep && tid == 0) *o.timestep = (int32_t)(t / ((double)P.iters * P.dt));
+}
+
+struct HvEnv {      // what every lane carries of its env (uniform) and of its coolers (c = tid, tid + HV_BLOCK)
+  double t, last_call, rest_since;
+  int episode_step, warning_count, rest, tail;
+  double filt[2];
+  int head[2];
+};
+
+// HVACEnv.reset + Cooler.reset: grid into g (LDS), the rest into E and the env's global rows
+template <bool INJECT>
+__device__ __forceinline__ void hv_reset(const HvArgs& P, const HvTask& K, int env, uint64_t tick, const double* grid_in,
+                                         double* g, HvEnv& E) {
+  const int tid = threadIdx.x;
+  if (tid < K.NC) {
+    double v;
+    if (INJECT) {
+      v = grid_in[(size_t)env * K.NC + tid];
+    } else {
+      const xv_u32x4 w = xv_env_draw_sub(P.seed, P.gid_base + (uint64_t)env, tick, HV_DRAW_GRID, (uint32_t)tid);
+      v = K.sc[8] + 2.0 * (double)xv_normal1(w.x, w.y);
+    }
+    g[tid] = v;
+  }
+  E.t = 0.0; E.last_call = NAN; E.rest_since = 0.0;
+  E.episode_step = 0; E.warning_count = 0; E.rest = 0; E.tail = 0;
+  const float dflt = (float)K.sc[14];
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    const int c = tid + q * HV_BLOCK;
+    E.filt[q] = 0.0; E.head[q] = 0;
+    if (c < P.C) {
+      P.value[(size_t)env * P.C + c] = dflt;
+      P.rest_start[(size_t)env * P.C + c] = 0.0;
+    }
+  }
+  __syncthreads();
+}
+
+__device__ __forceinline__ void hv_load(const HvArgs& P, int env, double* g, HvEnv& E) {
+  const int tid = threadIdx.x, NC = P.NW * P.NL;
+  if (tid < NC) g[tid] = P.grid[(size_t)env * NC + tid];
+  E.t = P.t[env]; E.last_call = P.last_call[env];
+  E.episode_step = P.episode_step[env]; E.warning_count = P.warning_count[env];
+  E.rest = min(max(P.rest_idx[env], 0), P.C - 1); E.tail = P.tail[env];
+  E.rest_since = P.rest_start[(size_t)env * P.C + E.rest];
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    const int c = tid + q * HV_BLOCK;
+    E.filt[q] = c < P.C ? P.filter[(size_t)env * P.C + c] : 0.0;
+    E.head[q] = c < P.C ? P.head[(size_t)env * P.C + c] : 0;
+  }
+  __syncthreads();
+}
+
+__device__ __forceinline__ void hv_store(const HvArgs& P, int env, const double* g, const HvEnv& E) {
+  const int tid = threadIdx.x, NC = P.NW * P.NL;
+  if (tid < NC) P.grid[(size_t)env * NC + tid] = g[tid];
+  if (tid == 0) {
+    P.t[env] = E.t; P.last_call[env] = E.last_call;
+    P.episode_step[env] = E.episode_step; P.warning_count[env] = E.warning_count;
+    P.rest_idx[env] = E.rest; P.tail[env] = E.tail;
+    P.rest_start[(size_t)env * P.C + E.rest] = E.rest_since;
+  }
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    const int c = tid + q * HV_BLOCK;
+    if (c < P.C) {
+      P.filter[(size_t)env * P.C + c] = E.filt[q];
+      P.head[(size_t)env * P.C + c] = E.head[q];
+    }
+  }
+}
+
+template <bool INJECT>
+__global__ __launch_bounds__(HV_BLOCK) void xv_anyhvac_reset_kernel(HvArgs P, const uint8_t* mask, const double* grid_in,
+                                                                    xv_anyhvac_io io) {
+  __shared__ double s_grid[HV_MAX_GRID * HV_MAX_GRID];
+  const int env = blockIdx.x;
+  if (mask && !mask[env]) return;
+  const HvTask K = hv_task(P, env);
+  HvEnv E;
+  hv_reset<INJECT>(P, K, env, xv_launch_tick(P.tick, P.tick_dev), grid_in, s_grid, E);
+  hv_obs(P, K, s_grid, E.t, E.rest, P.value + (size_t)env * P.C,
+         hv_obs_rows(io.sensor_readings, io.heat_readings, io.action_temp, io.timestep, (size_t)env, P), nullptr, nullptr);
+  hv_store(P, env, s_grid, E);
+}
+
+template <bool INJECT>
+__global__ __launch_bounds__(HV_BLOCK) void xv_anyhvac_step_kernel(HvArgs P, xv_anyhvac_io io, const double* reset_grid,
+                                                                   int mode, int T) {
+  __shared__ double s_grid[2][HV_MAX_GRID * HV_MAX_GRID];
+  __shared__ double s_static[HV_MAX_GRID * HV_MAX_GRID];
+  __shared__ double s_chtc[HV_MAX_WALL];
+  __shared__ double s_ne[HV_MAX_C], s_pc[HV_MAX_C], s_pv[HV_MAX_C], s_ev[HV_MAX_C];
+  __shared__ float s_energy[HV_MAX_C];
+  __shared__ double s_heat[HV_MAX_SH];
+  __shared__ double s_red[HV_BLOCK];
+  __shared__ int s_bad;
+  const int env = blockIdx.x, tid = threadIdx.x;
+  const HvTask K = hv_task(P, env);
+  const int NL = K.NL, NC = K.NC;
+  const int ci = tid / NL, cj = tid - ci * NL;
+  const bool cell_on = tid < NC && ci < K.nw && cj < K.nl;
+  const double amb = K.sc[8], csa = K.sc[5] * K.sc[6], fcc_area = K.sc[7] * (K.sc[5] * K.sc[5]);
+  const double hc = cell_on ? K.hc[tid] : 1.0;
+  const size_t N = (size_t)P.n_env;
+  float* value = P.value + (size_t)env * P.C;
+  double* ring_t = P.ring_t + (size_t)env * XV_ANYHVAC_RING;
+  double* ring_v = P.ring_v + (size_t)env * XV_ANYHVAC_RING * P.C;
+  HvEnv E;
+  int cur = 0;
+  hv_load(P, env, s_grid[0], E);
+
+  for (int ts = 0; ts < T; ++ts) {
+    const size_t row = (size_t)ts * N + env;
+    const HvEnv E0 = E;      // what a NaN puts back, with the grid as the env's global row has it
+    if (tid == 0) s_bad = 0;
+    if (ts > 0 && tid < NC) P.grid[(size_t)env * NC + tid] = s_grid[cur][tid];
+    // -- _update_swith_action: the resting cooler hands over after MORE than an hour
+    if (E.t - E.rest_since > HV_REST_SECONDS) {
+      E.rest = E.rest + 1 > K.nC - 1 ? 0 : E.rest + 1;
+      E.rest_since = E.t;
+      if (tid == 0) P.rest_start[(size_t)env * P.C + E.rest] = E.t;
+    }
+    E.episode_step += 1;
+    // -- heater powers at the step's starting t, held for all iterations
+    for (int h = tid; h < P.H; h += HV_BLOCK) {
+      const double p = h < K.nH ? hv_heater(K, h, E.t) : 0.0;
+      s_heat[h] = p;
+      if (io.heat_power) io.heat_power[row * P.H + h] = p;
+    }
+    // -- this step's action: clipped float32, the resting cooler's replaced by the default value
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      const int c = tid + q * HV_BLOCK;
+      if (c < P.C) {
+        float v = io.action[row * P.C + c];
+        v = fminf(fmaxf(v, 0.0f), 1.0f);
+        if (!(v == v)) v = 0.0f;
+        if (c == E.rest) v = (float)K.sc[14];
+        value[c] = v;
+        s_energy[c] = 0.0f;
+        s_ev[c] = c < K.nC ? K.cool[(size_t)c * 24 + 8] : 0.0;
+      }
+    }
+    __syncthreads();
+    double heat_sum = 0.0;
+    for (int h = tid; h < K.nH; h += HV_BLOCK) heat_sum += s_heat[h];
+    heat_sum = hv_block_sum(heat_sum, s_red);      // current_heat_power (numpy sums pairwise: last bits may differ)
+    if (cell_on) {
+      double acc = 0.0;
+      for (int h = 0; h < K.nH; ++h) acc += K.hd[(size_t)h * NC + tid] * s_heat[h];
+      s_static[tid] = acc;
+    }
+    bool bad = false;
+
+    for (int it = 0; it < P.iters; ++it) {
+      const double* g = s_grid[cur];
+      const double call_dt = E.last_call == E.last_call ? E.t - E.last_call : 0.0;
+      // -- A: the coolers
+#pragma unroll
+      for (int q = 0; q < 2; ++q) {
+        const int c = tid + q * HV_BLOCK;
+        if (c < K.nC) {
+          const double* r = K.cool + (size_t)c * 24;
+          const double cur_in = hv_read(K, g, r) + r[19];
+          const int slot = E.tail & (XV_ANYHVAC_RING - 1);
+          ring_v[(size_t)slot * P.C + c] = cur_in;
+          if (c == 0) ring_t[slot] = E.t;
+          const double delay = r[20], cutoff = E.t - delay;
+          int head = E.head[q];
+          if (E.tail - head >= XV_ANYHVAC_RING) head = E.tail - (XV_ANYHVAC_RING - 1);      // (a ring the caller sized wrongly)
+          while (head < E.tail && ring_t[head & (XV_ANYHVAC_RING - 1)] < cutoff) ++head;
+          E.head[q] = head;
+          const double delayed = head < E.tail ? ring_v[(size_t)(head & (XV_ANYHVAC_RING - 1)) * P.C + c] : cur_in;
+          const double alpha = call_dt > 0.0 ? exp(-call_dt / (delay / 3.0)) : 1.0;
+          const double env_temp = alpha * E.filt[q] + (1.0 - alpha) * delayed;
+          E.filt[q] = env_temp;
+          double power_cool = 0.0, power_vent = 0.0;
+          bool plain = true;      // the reference's power is a Python float here: resting, or the ratio clamped
+          if (c != E.rest) {
+            const double set_temp = (double)(value[c] * (float)(P.ub - P.lb) + (float)P.lb);
+            const double temp_diff = env_temp - set_temp, ub = r[13], lb = r[14];
+            double power_all;
+            if (temp_diff > ub) power_all = (r[15] - r[16]) * 1.0 + r[16];
+            else if (temp_diff < lb) power_all = (r[15] - r[16]) * 0.0 + r[16];
+            else { power_all = (r[15] - r[16]) * ((temp_diff - lb) / (ub - lb)) + r[16]; plain = false; }
+            const double pr = r[18] * power_all;
+            const double m = r[17] > pr ? r[17] : pr;            // max(ratio * all, vent_min)
+            power_vent = power_all < m ? power_all : m;          // min(., all)
+            power_cool = power_all - power_vent;
+          }
+          const double diff_amb = amb - g[hv_cell(K, r[6], r[7])];
+          double eer;
+          if (diff_amb < 0.0) eer = r[12];
+          else if (diff_amb < r[10]) eer = r[9];
+          else if (diff_amb < r[11]) eer = r[9] * ((r[11] - diff_amb) / (r[11] - r[10]));
+          else eer = 0.0;
+          s_ne[c] = -eer; s_pc[c] = power_cool; s_pv[c] = power_vent;
+          // float32 array += power * dt under numpy's promotion: a Python-float product is rounded to float32 and added
+          // in float32, a numpy.float64 one is added in fp64 and the sum rounded (host.py)
+          const double step_energy = (power_cool + power_vent) * P.dt;
+          s_energy[c] = plain ? s_energy[c] + (float)step_energy : (float)((double)s_energy[c] + step_energy);
+        }
+      }
+      E.last_call = E.t;
+      E.tail += 1;
+      __syncthreads();
+      // -- B: scatter, coolers in index order
+      double nh = 0.0;
+      if (cell_on) {
+        nh = s_static[tid];
+        for (int c = 0; c < K.nC; ++c) nh += (s_ne[c] * K.cd[(size_t)c * NC + tid]) * s_pc[c];
+      }
+      for (int w = tid; w < K.NWALL; w += HV_BLOCK) {
+        double a = K.chtc[w];
+        for (int c = 0; c < K.nC; ++c) a += (K.cv[(size_t)c * K.NWALL + w] * s_pv[c]) * s_ev[c];
+        s_chtc[w] = a;
+      }
+      __syncthreads();
+      // -- C: the stencil, into the other buffer
+      if (cell_on) {
+        const double S = g[tid];
+        const double up = ci > 0 ? g[tid - NL] : amb, down = ci < K.nw - 1 ? g[tid + NL] : amb;
+        const double left = cj > 0 ? g[tid - 1] : amb, right = cj < K.nl - 1 ? g[tid + 1] : amb;
+        const int w = (ci * (NL + 1) + cj) * 2;
+        const double h0 = (-(S - up)) * s_chtc[w] * csa, h1 = (-(down - S)) * s_chtc[w + 2 * (NL + 1)] * csa;
+        const double v0 = (-(S - left)) * s_chtc[w + 1] * csa, v1 = (-(right - S)) * s_chtc[w + 3] * csa;
+        const double net_in = ((h0 - h1) + (v0 - v1)) + fcc_area * (amb - S);
+        bad = bad || nh != nh || net_in != net_in;
+        s_grid[cur ^ 1][tid] = S + (nh + net_in) / hc * P.dt;
+      }
+      cur ^= 1;
+      E.t += P.dt;
+      __syncthreads();
+    }
+    E.t = E.t >= 0.0 ? (double)(long long)(E.t + 0.5) : (double)(long long)(E.t - 0.5);
+    if (bad) atomicOr(&s_bad, 1);
+    __syncthreads();
+    const bool nonfinite = s_bad != 0;
+    if (nonfinite) {      // the reference raises: the grid, time and counters go back to the step's start
+      if (tid < NC) s_grid[cur][tid] = P.grid[(size_t)env * NC + tid];
+      E = E0;
+      if (tid == 0) atomicOr(P.err, XV_DEVERR_NONFINITE);
+      __syncthreads();
+    }
+    // -- observation, reward, flags
+    double loss, hot;
+    hv_obs(P, K, s_grid[cur], E.t, E.rest, value,
+           hv_obs_rows(io.sensor_readings, io.heat_readings, io.action_temp, io.timestep, row, P), &loss, &hot);
+    loss = hv_block_sum(loss, s_red);
+    hot = hv_block_sum(hot, s_red);
+    double psum = 0.0;
+    const float span = (float)(P.dt * (double)P.iters);
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      const int c = tid + q * HV_BLOCK;
+      if (c < P.C) {
+        const float p = c < K.nC ? s_energy[c] / span : 0.0f;
+        if (io.cool_power) io.cool_power[row * P.C + c] = p;
+        psum += (double)p;
+      }
+    }
+    psum = hv_block_sum(psum, s_red);
+    float target_cost = -0.5f * (float)(loss / (double)K.nS);
+    const float power = (float)(psum / (double)K.nC);
+    double energy_cost = -3.0 * (K.sc[10] / heat_sum) * (double)(power / 10000.0f);
+    if (P.reward_mode == 1) { energy_cost = energy_cost * 1.25; target_cost = target_cost * 0.75f; }
+    else if (P.reward_mode == 2) { energy_cost = energy_cost * 1.5; target_cost = target_cost * 0.5f; }
+    int overheat = 0, over_tol = 0;
+    double reward;
+    if (hot > 0.0 && E.episode_step > 5) {
+      overheat = 1;
+      E.warning_count = min(5 + 1, E.warning_count + 1);
+    } else {
+      E.warning_count = max(E.warning_count - 1, 0);
+    }
+    int term = 0;
+    if (E.warning_count > 5) { over_tol = 1; term = 1; reward = -30.0; }
+    else reward = (double)(1.0f + target_cost) + 0.0 + energy_cost + 0.0 + (overheat ? -10.0 : 0.0);
+    int trunc = E.t >= P.max_t ? 1 : 0;
+    if (nonfinite) { reward = NAN; term = 0; trunc = 0; E.warning_count = E0.warning_count; }
+    if (tid == 0) {
+      io.reward[row] = reward;
+      io.terminated[row] = (uint8_t)term;
+      io.truncated[row] = (uint8_t)trunc;
+      if (io.misc) {
+        double* m = io.misc + row * 8;
+        m[0] = overheat; m[1] = over_tol; m[2] = energy_cost; m[3] = (double)target_cost; m[4] = E.t; m[5] = E.rest;
+        m[6] = E.warning_count; m[7] = E.episode_step;
+      }
+    }
+    const bool redo = (term || trunc) && mode == XV_AUTORESET_SAME_STEP;
+    const HvObsOut fin = hv_obs_rows(io.final_sensor_readings, io.final_heat_readings, io.final_action_temp, io.final_timestep,
+                                     row, P);
+    if (redo) {
+      hv_obs(P, K, s_grid[cur], E.t, E.rest, value, fin, nullptr, nullptr);
+      __syncthreads();
+      hv_reset<INJECT>(P, K, env, xv_launch_tick(P.tick, P.tick_dev) + (uint64_t)ts, reset_grid, s_grid[cur], E);
+      hv_obs(P, K, s_grid[cur], E.t, E.rest, value,
+             hv_obs_rows(io.sensor_readings, io.heat_readings, io.action_temp, io.timestep, row, P), nullptr, nullptr);
+    } else {
+      if (fin.sensor) for (int s = tid; s < P.S; s += HV_BLOCK) fin.sensor[s] = 0.0f;
+      if (fin.heat) for (int h = tid; h < P.H; h += HV_BLOCK) fin.heat[h] = 0.0f;
+      if (fin.atemp) for (int c = tid; c < P.C; c += HV_BLOCK) fin.atemp[c] = 0.0f;
+      if (fin.timestep && tid == 0) *fin.timestep = 0;
+    }
+    __syncthreads();
+  }
+  hv_store(P, env, s_grid[cur], E);
+}
+
+#ifndef XV_KERNELS_ONLY
+// ---- host side of the C-ABI ---------------------------------------------------------------------------------------
+static void hv_bind_rng(xv_anyhvac* h, uint64_t ticks) {
+  h->a.seed = h->eng->seed;
+  h->a.gid_base = h->eng->env_id_base;
+  const XvTickBind b = xv_engine_bind_tick(h->eng, ticks);
+  h->a.tick = b.tick;
+  h->a.tick_dev = b.tick_dev;
+}
+
+extern "C" int xv_anyhvac_destroy(xv_anyhvac* h) {
+  if (!h) return XV_OK;
+  (void)hipSetDevice(h->eng->device);
+  (void)hipStreamSynchronize(h->eng->stream);
+  HvArgs& a = h->a;
+  void* ps[] = {a.grid, a.t, a.last_call, a.episode_step, a.warning_count, a.rest_idx, a.rest_start, a.value, a.filter,
+                a.ring_t, a.ring_v, a.head, a.tail};
+  for (void* q : ps) if (q) (void)hipFree(q);
+  delete h;
+  return XV_OK;
+}
+
+extern "C" int xv_anyhvac_create(xv_engine* e, int n_env, int NW, int NL, int C, int S, int H, int KS, int KH,
+                                 int iter_per_step, double sec_per_iter, double set_lower_bound, double set_upper_bound,
+                                 double max_t, int reward_mode, xv_anyhvac** out) {
+  XV_CHECK_ARG(out != nullptr);
+  *out = nullptr;
+  XV_CHECK_ARG(e && n_env > 0 && NW > 0 && NL > 0 && C > 0 && S > 0 && H > 0 && KS > 0 && KH > 0 && iter_per_step > 0);
+  XV_CHECK_ARG(sec_per_iter > 0.0 && set_upper_bound > set_lower_bound && reward_mode >= 0 && reward_mode <= 2);
+  if (NW > HV_MAX_GRID || NL > HV_MAX_GRID || C > HV_MAX_C || S > HV_MAX_SH || H > HV_MAX_SH || KS > HV_MAX_K || KH > HV_MAX_K) {
+    xv_set_error("xv_anyhvac_create: NW, NL <= %d, C <= %d, S, H <= %d, KS, KH <= %d (got %d x %d, C %d, S %d, H %d, KS %d, KH %d)",
+                 HV_MAX_GRID, HV_MAX_C, HV_MAX_SH, HV_MAX_K, NW, NL, C, S, H, KS, KH);
+    return XV_ERR_UNSUPPORTED;
+  }
+  XV_HIP(hipSetDevice(e->device));
+  xv_anyhvac* h = new (std::nothrow) xv_anyhvac();
+  if (!h) {
+    xv_set_error("xv_anyhvac_create: out of host memory");
+    return XV_ERR_NOMEM;
+  }
+  h->eng = e;
+  HvArgs& a = h->a;      // value-initialised: every pointer is null until it is set here
+  a.NW = NW; a.NL = NL; a.C = C; a.S = S; a.H = H; a.KS = KS; a.KH = KH;
+  a.n_env = n_env; a.iters = iter_per_step; a.reward_mode = reward_mode;
+  a.dt = sec_per_iter; a.lb = set_lower_bound; a.ub = set_upper_bound; a.max_t = max_t;
+  a.err = e->d_err;
+  const size_t n = (size_t)n_env, nc = (size_t)NW * NL, c = (size_t)C, ring = XV_ANYHVAC_RING;
+  struct { void** p; size_t bytes; int fill; } bufs[] = {
+      {(void**)&a.grid, n * nc * 8, 0}, {(void**)&a.t, n * 8, 0}, {(void**)&a.last_call, n * 8, 0xFF},
+      {(void**)&a.episode_step, n * 4, 0}, {(void**)&a.warning_count, n * 4, 0}, {(void**)&a.rest_idx, n * 4, 0},
+      {(void**)&a.rest_start, n * c * 8, 0}, {(void**)&a.value, n * c * 4, 0}, {(void**)&a.filter, n * c * 8, 0},
+      {(void**)&a.ring_t, n * ring * 8, 0}, {(void**)&a.ring_v, n * ring * c * 8, 0}, {(void**)&a.head, n * c * 4, 0},
+      {(void**)&a.tail, n * 4, 0}};
+  hipError_t r = hipSuccess;
+  for (auto& b : bufs) {
+    if (r == hipSuccess) r = hipMalloc(b.p, b.bytes);
+    if (r == hipSuccess) r = hipMemsetAsync(*b.p, b.fill, b.bytes, e->stream);      // (0xFF bytes: a NaN, "no last call")
+  }
+  if (r != hipSuccess) {
+    xv_set_error("xv_anyhvac_create: device allocation failed: %s", hipGetErrorString(r));
+    (void)xv_anyhvac_destroy(h);
+    return XV_ERR_HIP;
+  }
+  *out = h;
+  return XV_OK;
+}
+
+extern "C" int xv_anyhvac_set_task(xv_anyhvac* h, int n_task, const double* tables, const int32_t* env_task) {
+  XV_CHECK_ARG(h && n_task > 0 && tables && env_task);
+  h->a.n_task = n_task;
+  h->a.tables = tables;
+  h->a.env_task = env_task;
+  return XV_OK;
+}
+
+template <bool INJECT>
+static int hv_reset_call(xv_anyhvac* h, const uint8_t* mask, const double* grid, const xv_anyhvac_io* io) {
+  XV_CHECK_ARG(h && h->a.tables && (grid || !INJECT));
+  xv_anyhvac_io o = {};
+  if (io) o = *io;
+  hv_bind_rng(h, INJECT ? 0 : 1);
+  hipLaunchKernelGGL((xv_anyhvac_reset_kernel<INJECT>), dim3(h->a.n_env), dim3(HV_BLOCK), 0, h->eng->stream, h->a, mask, grid,
+                     o);
+  XV_LAUNCH_CHECK();
+  return XV_OK;
+}
+
+extern "C" int xv_anyhvac_reset(xv_anyhvac* h, const uint8_t* mask, const xv_anyhvac_io* io) {
+  return hv_reset_call<false>(h, mask, nullptr, io);
+}
+
+extern "C" int xv_anyhvac_reset_injected(xv_anyhvac* h, const uint8_t* mask, const double* grid, const xv_anyhvac_io* io) {
+  return hv_reset_call<true>(h, mask, grid, io);
+}
+
+template <bool INJECT>
+static int hv_step_call(xv_anyhvac* h, const xv_anyhvac_io* io, const double* reset_grid, int mode, int T) {
+  XV_CHECK_ARG(h && h->a.tables && io && io->action && io->reward && io->terminated && io->truncated && T > 0);
+  XV_CHECK_ARG(reset_grid || !INJECT);
+  if (mode != XV_AUTORESET_DISABLED && mode != XV_AUTORESET_SAME_STEP) {
+    xv_set_error("xv_anyhvac: autoreset mode %d is not built (disabled and same_step are)", mode);
+    return XV_ERR_UNSUPPORTED;
+  }
+  hv_bind_rng(h, INJECT ? 0 : (uint64_t)T);
+  hipLaunchKernelGGL((xv_anyhvac_step_kernel<INJECT>), dim3(h->a.n_env), dim3(HV_BLOCK), 0, h->eng->stream, h->a, *io,
+                     reset_grid, mode, T);
+  XV_LAUNCH_CHECK();
+  return XV_OK;
+}
+
+extern "C" int xv_anyhvac_step(xv_anyhvac* h, const xv_anyhvac_io* io, int autoreset_mode) {
+  return hv_step_call<false>(h, io, nullptr, autoreset_mode, 1);
+}
+
+extern "C" int xv_anyhvac_step_injected(xv_anyhvac* h, const xv_anyhvac_io* io, const double* reset_grid, int autoreset_mode) {
+  return hv_step_call<true>(h, io, reset_grid, autoreset_mode, 1);
+}
+
+extern "C" int xv_anyhvac_rollout(xv_anyhvac* h, int T, const xv_anyhvac_io* io, int autoreset_mode) {
+  return hv_step_call<false>(h, io, nullptr, autoreset_mode, T);
+}
+
+template <bool SET>
+static int hv_state_copy(xv_anyhvac* h, const xv_anyhvac_state* s) {
+  XV_CHECK_ARG(h && s);
+  const HvArgs& a = h->a;
+  const size_t n = (size_t)a.n_env, nc = (size_t)a.NW * a.NL, c = (size_t)a.C, ring = XV_ANYHVAC_RING;
+  struct { void* user; void* own; size_t bytes; } rows[] = {
+      {s->grid, a.grid, n * nc * 8}, {s->t, a.t, n * 8}, {s->last_call, a.last_call, n * 8},
+      {s->episode_step, a.episode_step, n * 4}, {s->warning_count, a.warning_count, n * 4}, {s->rest_idx, a.rest_idx, n * 4},
+      {s->rest_start, a.rest_start, n * c * 8}, {s->value, a.value, n * c * 4}, {s->filter, a.filter, n * c * 8},
+      {s->ring_t, a.ring_t, n * ring * 8}, {s->ring_v, a.ring_v, n * ring * c * 8}, {s->head, a.head, n * c * 4},
+      {s->tail, a.tail, n * 4}};
+  for (auto& r : rows)
+    if (r.user)
+      XV_HIP(hipMemcpyAsync(SET ? r.own : r.user, SET ? r.user : r.own, r.bytes, hipMemcpyDeviceToDevice, h->eng->stream));
+  return XV_OK;
+}
+
+extern "C" int xv_anyhvac_get_state(xv_anyhvac* h, const xv_anyhvac_state* out) { return hv_state_copy<false>(h, out); }
+extern "C" int xv_anyhvac_set_state(xv_anyhvac* h, const xv_anyhvac_state* in) { return hv_state_copy<true>(h, in); }
+#endif  // XV_KERNELS_ONLY
