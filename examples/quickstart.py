@@ -110,3 +110,18 @@ torch.cuda.synchronize()
 o_all = env.step(torch.zeros(env.num_envs, dtype=torch.int32, device=env.device))      # the whole env again: fresh draws
 print("sub-batches:", len(subs), "x", subs[0].num_envs, "envs; observation of sub 2:", tuple(o[0].shape), "| whole env:", tuple(o_all[0].shape))
 env.close()
+
+# 10. AnyHVAC: the reference's PID teacher (HVACSolverGTPID) inside the launch, 8 controller-driven steps of 64 rooms at once
+import random  # noqa: E402
+
+import numpy as np  # noqa: E402
+
+from xenoverse_amd.anyhvac import HVACTaskSampler, HVACVecEnv  # noqa: E402
+np.random.seed(0), random.seed(0)                 # the sampler draws from both global streams, as the reference's does
+hvac = HVACVecEnv(64, seed=2)
+hvac.set_task([HVACTaskSampler()], generate_task=True)
+hvac.reset()
+hvac.set_pid("gt")
+obs, reward, terminated, truncated, info = hvac.rollout_teacher(8)
+print("AnyHVAC teacher rollout: actions", tuple(info["action"].shape), "mean reward %.3f" % reward.mean().item())
+hvac.close()

@@ -1077,6 +1077,36 @@ int xv_anyhvac_rollout(xv_anyhvac* h, int T, const xv_anyhvac_io* io, int autore
 int xv_anyhvac_get_state(xv_anyhvac* h, const xv_anyhvac_state* out);
 int xv_anyhvac_set_state(xv_anyhvac* h, const xv_anyhvac_state* in);
 
+/* The PID teachers — reference: xenoverse/anyhvac/anyhvac_solver.py HVACSolverGTPID / HVACSolverLOCPID .policy (the two
+ * differ in the weight matrix only; HVACSolverGridSearchPID is a batch of envs with per-env gains).  Per env:
+ *   diff = target - readings (float32); acc_diff += diff (fp64); d_e = -(kp diff - kd (diff - last_diff) / delta_t +
+ *   ki acc_diff), delta_t = iter_per_step * sec_per_iter / 60; x = d_e @ weights; flat = [x > -0.05, clip(x, 0, 1)]
+ *   (float32); the env's action is 1 - clip(x, 0, 1).
+ * With Python-float gains the reference's first two products are float32 expressions, with numpy.float64 gains
+ * (XV_ANYHVAC_PID_FLOAT64) all three are fp64.  The sum over sensors runs in index order (numpy's matmul leaves its order
+ * open: last bits of x may differ).  New symbols only: no ABI bump. */
+#define XV_ANYHVAC_PID_FLOAT64 1
+#define XV_ANYHVAC_PID_STATS 8
+/* weights float64[n_task][S][C] (padded rows and columns zero), gains float64[n_env][3] (kp, ki, kd): device pointers,
+ * borrowed.  Allocates the controller's state per env — acc_diff double[S], last_obs float[S], a fresh flag — and resets it. */
+int xv_anyhvac_set_pid(xv_anyhvac* h, const double* weights, const double* gains, int kind_flags);
+/* one controller call per env, no step: readings float32[n_env][S], or NULL for the env's current observation (recomputed
+ * from its grid and t by the step epilogue's own function).  action_out float32[n_env][C] = 1 - value (padded columns 0);
+ * flat_out float32[n_env][2 C] (switch columns, then value columns) or NULL.  The controller's state advances. */
+int xv_anyhvac_pid_action(xv_anyhvac* h, const float* readings, float* action_out, float* flat_out);
+/* T steps in one launch with the controller in front of every step (io->action is not read); bit-equal to T rounds of
+ * xv_anyhvac_pid_action + xv_anyhvac_step.  A same-step autoreset also resets that env's controller.  action_out
+ * float32[T][n_env][C].  stats float64[n_env][8] or NULL is ADDED to (maximum: max'ed), over the T steps' resulting
+ * observations and the real sensors, e = reading - target in float32: sum |e|, max |e|, sum e^2, count(|e| <= 1),
+ * count(|e| <= 2), count(reading > target + 2), sum of rewards, sample count. */
+int xv_anyhvac_rollout_pid(xv_anyhvac* h, int T, const xv_anyhvac_io* io, float* action_out, double* stats,
+                           int autoreset_mode);
+/* acc_diff float64[n_env][S], last_obs float32[n_env][S], fresh int32[n_env]: device pointers, every one nullable */
+int xv_anyhvac_pid_get_state(xv_anyhvac* h, double* acc_diff, float* last_obs, int32_t* fresh);
+int xv_anyhvac_pid_set_state(xv_anyhvac* h, const double* acc_diff, const float* last_obs, const int32_t* fresh);
+/* acc_diff = 0, last_obs = 0, fresh = 1 for the envs of mask uint8[n_env] (NULL: all): a new solver's state */
+int xv_anyhvac_pid_reset(xv_anyhvac* h, const uint8_t* mask);
+
 #ifdef __cplusplus
 }
 #endif

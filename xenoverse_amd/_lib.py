@@ -154,6 +154,12 @@ SIGNATURES = {
     "xv_anyhvac_rollout": [c_void_p, c_int, c_void_p, c_int],
     "xv_anyhvac_get_state": [c_void_p, c_void_p],                       # (handle, xv_anyhvac_state*)
     "xv_anyhvac_set_state": [c_void_p, c_void_p],
+    "xv_anyhvac_set_pid": [c_void_p, c_void_p, c_void_p, c_int],            # (handle, weights, gains, kind_flags)
+    "xv_anyhvac_pid_action": [c_void_p, c_void_p, c_void_p, c_void_p],
+    "xv_anyhvac_rollout_pid": [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int],
+    "xv_anyhvac_pid_get_state": [c_void_p, c_void_p, c_void_p, c_void_p],
+    "xv_anyhvac_pid_set_state": [c_void_p, c_void_p, c_void_p, c_void_p],
+    "xv_anyhvac_pid_reset": [c_void_p, c_void_p],
 }
 for _p in ("xv_cartpole", "xv_acrobot"):      # the control families share one set of entry points (csrc/xv_control.h)
     SIGNATURES.update({

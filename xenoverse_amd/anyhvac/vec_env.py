@@ -7,7 +7,13 @@ action_temp[N, C] (float32), timestep[N] (int32) — with `counts` (per env: coo
 beside them; padded columns are zero and padded action columns are ignored.  Rewards are float64.  Same-step autoreset (the
 engine's default) hands out the new episode's first observation and the finished one's last under info["final_obs"];
 autoreset_mode="disabled" goes on stepping as the reference's env would; "next_step" is not built.
+
+The PID teachers (pid.py restates the reference's solvers on the host): set_pid() puts a controller with per-env gains on
+the device, pid_action() makes one controller call, rollout_teacher(T) runs T controller-driven steps in ONE launch.
+HVACSolverGTPID / HVACSolverLOCPID / HVACSolverGridSearchPID are the reference-shaped classes over the one-room HVACEnv;
+the grid search evaluates its candidates as the envs of one batch.
 """
+import itertools
 import ctypes as C
 
 import numpy as np
@@ -19,6 +25,7 @@ from ..spaces import Box
 from ..vector import VectorEnv
 from .config import RING_CAPACITY
 from .host import check_ring, check_settings
+from .pid import DEFAULT_GAINS, GAINS, first_strict_minimum, pid_weights, search_score
 from .tables import build_tables
 
 OBS_KEYS = ("sensor_readings", "heat_readings", "action_temp", "timestep")
@@ -48,6 +55,7 @@ class HVACVecEnv(VectorEnv):
                             action_temp=bool(include_last_action_in_observation),
                             timestep=bool(include_timestep_in_observation))
         self._h = None
+        self._pid = None
         self.need_reset = True
 
     # -- tasks ----------------------------------------------------------------------------------------------------
@@ -90,6 +98,7 @@ class HVACVecEnv(VectorEnv):
         self.default_action_value = np.array([(float(tasks[i]["target_temperature"]) - self.lower_bound)
                                               / (self.upper_bound - self.lower_bound) for i in env_task])
         self._targets = np.array([float(tasks[i]["target_temperature"]) for i in env_task])
+        self._tasks, self._generate_task = list(tasks), bool(generate_task)
         self.task_set = True
         self.need_reset = True
 
@@ -167,6 +176,8 @@ class HVACVecEnv(VectorEnv):
         io = self._io(b)
         _lib.check(self.lib.xv_anyhvac_reset(self._h, _lib.ptr(mask), C.byref(io)))
         self.need_reset = False
+        if self._pid is not None:
+            self.pid_reset(mask)
         return self._obs(b), {}
 
     def reset_injected(self, state, mask=None):
@@ -178,6 +189,8 @@ class HVACVecEnv(VectorEnv):
         io = self._io(b)
         _lib.check(self.lib.xv_anyhvac_reset_injected(self._h, _lib.ptr(m), _lib.ptr(g), C.byref(io)))
         self.need_reset = False
+        if self._pid is not None:
+            self.pid_reset(m)
         return self._obs(b)
 
     def _require_reset(self):
@@ -190,6 +203,7 @@ class HVACVecEnv(VectorEnv):
         b = self._buffers((), self.autoreset_mode == "same_step")
         io = self._io(b, a)
         _lib.check(self.lib.xv_anyhvac_step(self._h, C.byref(io), AUTORESET[self.autoreset_mode]))
+        self._pid_follow(b)
         return self._result(b)
 
     def step_injected(self, actions, reset_state):
@@ -198,6 +212,7 @@ class HVACVecEnv(VectorEnv):
         b = self._buffers((), self.autoreset_mode == "same_step")
         io = self._io(b, a)
         _lib.check(self.lib.xv_anyhvac_step_injected(self._h, C.byref(io), _lib.ptr(g), AUTORESET[self.autoreset_mode]))
+        self._pid_follow(b)
         return self._result(b)
 
     def rollout(self, actions):
@@ -209,7 +224,128 @@ class HVACVecEnv(VectorEnv):
         b = self._buffers((T,), self.autoreset_mode == "same_step")
         io = self._io(b, a)
         _lib.check(self.lib.xv_anyhvac_rollout(self._h, T, C.byref(io), AUTORESET[self.autoreset_mode]))
+        self._pid_follow(b)
         return self._result(b)
+
+    # -- the PID teacher -------------------------------------------------------------------------------------------
+    def set_pid(self, kind="gt", kp=DEFAULT_GAINS["kp"], ki=DEFAULT_GAINS["ki"], kd=DEFAULT_GAINS["kd"], gains="python",
+                weights=None):
+        """put the reference's PID controller on the device.  kind: 'gt' (HVACSolverGTPID's weights) or 'loc'
+        (HVACSolverLOCPID's); weights: one float64 [S_task, C_task] matrix per task instead.  kp, ki, kd: scalars or [N]
+        arrays, one triple per env.  gains: 'python' (the arithmetic of Python-float gains, the solvers' defaults) or
+        'float64' (of numpy.float64 gains, the grid search's).  The controllers start as new solvers do."""
+        self._require_task()
+        if gains not in GAINS:
+            raise ValueError("gains must be one of %s" % (GAINS,))
+        Cc, S = self.dims[2], self.dims[3]
+        if weights is None:
+            weights = [pid_weights(t, kind) for t in self._tasks]
+        elif isinstance(weights, np.ndarray) and weights.ndim == 2:
+            weights = [weights]
+        if len(weights) != len(self._tasks):
+            raise ValueError("weights: one [sensors, coolers] matrix per task")
+        w = np.zeros((len(self._tasks), S, Cc))
+        for i, (m, t) in enumerate(zip(weights, self._tasks)):
+            m = np.asarray(m, np.float64)
+            if m.shape != (len(t["sensor_loc"]), len(t["cooler_loc"])):
+                raise ValueError("weights of task %d must have shape %s" % (i, (len(t["sensor_loc"]), len(t["cooler_loc"]))))
+            w[i, :m.shape[0], :m.shape[1]] = m
+        g = np.stack([np.broadcast_to(np.asarray(v, np.float64), (self.num_envs,)) for v in (kp, ki, kd)], axis=1)
+        pid = dict(weights=torch.from_numpy(w).to(self.device), gains=torch.from_numpy(np.ascontiguousarray(g)).to(self.device))
+        _lib.check(self.lib.xv_anyhvac_set_pid(self._h, _lib.ptr(pid["weights"]), _lib.ptr(pid["gains"]),
+                                               1 if gains == "float64" else 0))
+        self.engine.sync()
+        self._pid = pid      # (the handle borrows both tensors)
+
+    def _require_pid(self):
+        self._require_task()
+        if self._pid is None:
+            raise Exception("Must \"set_pid\" before asking the teacher")
+
+    def pid_action(self, sensor_readings=None, return_flat=False):
+        """one controller call per env, no step -> the env's action float32 [N, C] (1 - value; padded columns 0).
+        sensor_readings: float32 [N, S], default the envs' current observation.  return_flat: also the reference's flat
+        action as float32 [N, 2, C] (switch row, value row).  The controllers' state advances."""
+        self._require_pid()
+        Cc, S = self.dims[2], self.dims[3]
+        r = None
+        if sensor_readings is not None:
+            r = self._dev(sensor_readings, torch.float32)
+            if r.shape != (self.num_envs, S):
+                raise ValueError("sensor_readings must have shape %s" % ((self.num_envs, S),))
+        else:
+            self._require_reset()
+        act = torch.zeros((self.num_envs, Cc), dtype=torch.float32, device=self.device)
+        flat = torch.zeros((self.num_envs, 2, Cc), dtype=torch.float32, device=self.device) if return_flat else None
+        _lib.check(self.lib.xv_anyhvac_pid_action(self._h, _lib.ptr(r), _lib.ptr(act), _lib.ptr(flat)))
+        if r is not None:
+            self.engine.sync()      # (r may be a temporary)
+        return (self._out(act), self._out(flat)) if return_flat else self._out(act)
+
+    def rollout_teacher(self, T, return_stats=False, stats=None):
+        """T controller-driven steps in ONE launch -> rollout()'s tuple with info["action"] float32 [T, N, C] (what the
+        teacher did); bit-equal to T rounds of pid_action() + step().  return_stats: info["pid_stats"] float64 [N, 8] over
+        the T steps' resulting readings of the real sensors, e = reading - target in float32: sum |e|, max |e|, sum e^2,
+        count(|e| <= 1), count(|e| <= 2), count(reading > target + 2), sum of rewards, sample count.  stats: a tensor
+        of an earlier call to go on accumulating into."""
+        self._require_pid()
+        self._require_reset()
+        T = int(T)
+        b = self._buffers((T,), self.autoreset_mode == "same_step")
+        io = self._io(b)
+        act = torch.zeros((T, self.num_envs, self.dims[2]), dtype=torch.float32, device=self.device)
+        if stats is None and return_stats:
+            stats = torch.zeros((self.num_envs, 8), dtype=torch.float64, device=self.device)
+        if stats is not None and (stats.shape != (self.num_envs, 8) or stats.dtype != torch.float64
+                                  or stats.device != self.device or not stats.is_contiguous()):
+            raise ValueError("stats must be a contiguous float64 [num_envs, 8] tensor on the env's device")
+        _lib.check(self.lib.xv_anyhvac_rollout_pid(self._h, T, C.byref(io), _lib.ptr(act), _lib.ptr(stats),
+                                                   AUTORESET[self.autoreset_mode]))
+        out = self._result(b)
+        out[4]["action"] = self._out(act)
+        if stats is not None:
+            out[4]["pid_stats"] = self._out(stats)
+        return out
+
+    def pid_reset(self, mask=None):
+        """acc_diff = 0, last observation = 0 for the envs of mask (default all): a new solver's state"""
+        self._require_pid()
+        m = None if mask is None else self._dev(mask, torch.uint8)
+        _lib.check(self.lib.xv_anyhvac_pid_reset(self._h, _lib.ptr(m)))
+        self._pid["mask"] = m      # (kept alive until the next call's replaces it)
+
+    def _pid_follow(self, b):
+        """after step() / rollout() under same-step autoreset: an env that was reset gets a fresh controller, as inside
+        rollout_teacher()"""
+        if self._pid is not None and self.autoreset_mode == "same_step":
+            done = b["terminated"] | b["truncated"]
+            self.pid_reset(done if done.dim() == 1 else done.amax(0))
+
+    def _pid_state_shapes(self):
+        n, S = self.num_envs, self.dims[3]
+        return dict(acc_diff=((n, S), torch.float64), last_obs=((n, S), torch.float32), fresh=((n,), torch.int32))
+
+    def get_pid_state(self):
+        """-> dict of device tensors: acc_diff float64 [N, S], last_obs float32 [N, S], fresh int32 [N] (1 from a reset
+        to the first controller call)"""
+        self._require_pid()
+        out = {k: torch.empty(shape, dtype=dt, device=self.device) for k, (shape, dt) in self._pid_state_shapes().items()}
+        _lib.check(self.lib.xv_anyhvac_pid_get_state(self._h, *[_lib.ptr(out[k]) for k in ("acc_diff", "last_obs", "fresh")]))
+        self.engine.sync()
+        return out
+
+    def set_pid_state(self, **state):
+        """any subset of get_pid_state()'s entries"""
+        self._require_pid()
+        shapes, ts = self._pid_state_shapes(), {}
+        for k, v in state.items():
+            if k not in shapes:
+                raise ValueError("unknown PID state entry %r" % (k,))
+            ts[k] = self._dev(v, shapes[k][1])
+            if tuple(ts[k].shape) != shapes[k][0]:
+                raise ValueError("PID state entry %s must have shape %s" % (k, shapes[k][0]))
+        _lib.check(self.lib.xv_anyhvac_pid_set_state(self._h, *[_lib.ptr(ts.get(k)) for k in ("acc_diff", "last_obs", "fresh")]))
+        self.engine.sync()
 
     # -- state ----------------------------------------------------------------------------------------------------
     def _state_shapes(self):
@@ -269,6 +405,7 @@ class HVACVecEnv(VectorEnv):
         if self._h is not None:
             self.lib.xv_anyhvac_destroy(self._h)
             self._h = None
+        self._pid = None
 
 
 class HVACEnv(object):
@@ -336,3 +473,137 @@ class HVACEnv(object):
 
     def close(self):
         self.vec.close()
+
+
+class HVACSolverGTPID(object):
+    """the reference's HVACSolverGTPID over the one-room HVACEnv (set_task and reset first): .policy(observation) -> the flat
+    float32 [2C] action (switch columns, value columns), computed on the device; the env's action is 1 - policy(obs)[C:].
+    kp, ki, kd and corr_sensor_cooler are attributes as there; gains that are numpy.float64 scalars take the float64
+    arithmetic numpy gives the reference with them."""
+    kind = "gt"
+
+    def __init__(self, env):
+        if not getattr(env, "task_set", False):
+            raise Exception("Must call \"set_task\" first")
+        self.env = env
+        vec = env.vec
+        task = vec._tasks[0]
+        self.target_temperature = float(task["target_temperature"])
+        self.sec_per_step = vec.iter_per_step * vec.sec_per_iter
+        self.lower_bound, self.upper_bound = vec.lower_bound, vec.upper_bound
+        self.delta_t = self.sec_per_step / 60
+        self.kp, self.ki, self.kd = DEFAULT_GAINS["kp"], DEFAULT_GAINS["ki"], DEFAULT_GAINS["kd"]
+        self.corr_sensor_cooler = pid_weights(task, self.kind)
+        self.n_sensors, self.n_coolers = self.corr_sensor_cooler.shape
+        self._on_device = None
+        self._push(keep_state=False)
+
+    def _gains_mode(self):
+        kinds = {isinstance(g, np.floating) for g in (self.kp, self.ki, self.kd)}
+        if len(kinds) != 1:
+            raise ValueError("kp, ki and kd must be all Python floats or all numpy.float64 scalars")
+        return "float64" if kinds.pop() else "python"
+
+    def _push(self, keep_state=True):
+        """the gains and weights as the attributes have them now -> the device (the controller's state is kept)"""
+        want = (float(self.kp), float(self.ki), float(self.kd), self._gains_mode(), self.corr_sensor_cooler.tobytes())
+        if want == self._on_device and self.env.vec._pid is not None:
+            return
+        vec = self.env.vec
+        state = vec.get_pid_state() if keep_state and vec._pid is not None else None
+        vec.set_pid(kp=self.kp, ki=self.ki, kd=self.kd, gains=want[3], weights=[self.corr_sensor_cooler])
+        if state is not None:
+            vec.set_pid_state(**state)
+        self._on_device = want
+
+    def reset(self):
+        self._push()
+        self.env.vec.pid_reset()
+
+    def policy(self, observation):
+        obs = np.array(observation)[:self.n_sensors]
+        if obs.dtype != np.float32 or obs.shape != (self.n_sensors,):
+            raise ValueError("the observation must be the env's float32 sensor readings")
+        self._push()
+        _, flat = self.env.vec.pid_action(obs[None], return_flat=True)
+        return flat[0, :, :self.n_coolers].reshape(-1).cpu().numpy()
+
+
+class HVACSolverLOCPID(HVACSolverGTPID):
+    """HVACSolverGTPID with the inverse-distance weight matrix"""
+    kind = "loc"
+
+
+class HVACSolverGridSearchPID(HVACSolverGTPID):
+    """the reference's HVACSolverGridSearchPID: .search() evaluates every (kp, ki, kd) of the three linspaces for max_steps
+    controller-driven steps and returns the candidate with the lowest score.  Here the candidates are the envs of ONE batch
+    (a private HVACVecEnv), each with its own gains, all with the env's task and the SAME initial grid (the reference
+    draws a new one per candidate)."""
+    MAX_T = 64      # steps per launch
+
+    def __init__(self, env, kp_range=(1e-3, 5e-2, 10), ki_range=(1e-2, 1e-1, 10), kd_range=(1e-3, 2e-2, 10)):
+        super().__init__(env)
+        self.kp_values, self.ki_values, self.kd_values = (np.linspace(r[0], r[1], r[2]) for r in (kp_range, ki_range, kd_range))
+        self.kp_range, self.ki_range, self.kd_range = kp_range, ki_range, kd_range
+        self.search_results, self.best_params = [], None
+        self.search_rollouts, self.search_stats = [], np.zeros((0, 8))
+
+    @staticmethod
+    def metrics_from_stats(st, max_steps):
+        """a pid_stats row -> the reference's metrics (std from the two sums)"""
+        n = st[7]
+        mean = st[0] / n
+        return {"mean_error": mean, "max_error": st[1], "std_error": float(np.sqrt(max(st[2] / n - mean * mean, 0.0))),
+                "error_within_2C": st[4] / n * 100, "error_within_1C": st[3] / n * 100, "mean_reward": st[6] / max_steps,
+                "mean_overshoot": st[5] / max_steps}
+
+    def search(self, max_steps=1000, apply_best=True, chunk=None, init_grid=None, keep_rollouts=False):
+        """-> best_params (the reference's dict).  chunk: candidates per batch (default all at once); init_grid [nw, nl]:
+        the grid every candidate starts from; without it the caller's env IS RESET (as the reference's search resets it)
+        and its new grid taken; keep_rollouts: rollout_teacher()'s tuples, per chunk a list of calls, stay in
+        self.search_rollouts.  search_stats: the candidates' pid_stats rows, float64 [n, 8]."""
+        vec0 = self.env.vec
+        task = vec0._tasks[0]
+        nw, nl = int(task["n_width"]), int(task["n_length"])
+        if init_grid is None:
+            vec0.reset()
+            init_grid = vec0.get_state()["grid"][0].reshape(vec0.dims[0], vec0.dims[1])[:nw, :nl].cpu().numpy()
+        init_grid = np.asarray(init_grid, np.float64).reshape(nw, nl)
+        cands = list(itertools.product(self.kp_values, self.ki_values, self.kd_values))
+        chunk = len(cands) if chunk is None else max(1, int(chunk))
+        self.search_results, self.search_rollouts, rows = [], [], []
+        for lo in range(0, len(cands), chunk):
+            part = np.array(cands[lo:lo + chunk])
+            vec = HVACVecEnv(len(part), max_steps=vec0.max_steps, iter_per_step=vec0.iter_per_step,
+                             sec_per_iter=vec0.sec_per_iter, set_lower_bound=vec0.lower_bound,
+                             set_upper_bound=vec0.upper_bound, reward_mode=vec0.reward_mode, device=str(self.env.vec.device),
+                             autoreset_mode="disabled")
+            vec.set_task([task], generate_task=vec0._generate_task)
+            vec.reset_injected(np.repeat(init_grid[None], len(part), axis=0))
+            vec.set_pid(kp=part[:, 0], ki=part[:, 1], kd=part[:, 2], gains="float64", weights=[self.corr_sensor_cooler])
+            stats, calls = None, []
+            for t0 in range(0, max_steps, self.MAX_T):
+                out = vec.rollout_teacher(min(self.MAX_T, max_steps - t0), stats=stats, return_stats=True)
+                stats = out[4]["pid_stats"]
+                if keep_rollouts:
+                    calls.append(out)
+            rows.append(stats.cpu().numpy())
+            self.search_rollouts.append(calls)
+            vec.close()
+        self.search_stats = np.concatenate(rows)
+        for (kp, ki, kd), st in zip(cands, self.search_stats):
+            m = dict(kp=kp, ki=ki, kd=kd, **self.metrics_from_stats(st, max_steps))
+            m["score"] = search_score(m)
+            self.search_results.append(m)
+        self.best_params = first_strict_minimum(self.search_results)
+        if apply_best and self.best_params:
+            self.apply_params(self.best_params["kp"], self.best_params["ki"], self.best_params["kd"])
+        return self.best_params
+
+    def apply_params(self, kp=None, ki=None, kd=None):
+        if kp is not None:
+            self.kp = kp
+        if ki is not None:
+            self.ki = ki
+        if kd is not None:
+            self.kd = kd

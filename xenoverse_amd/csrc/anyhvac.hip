@@ -13,6 +13,12 @@
 // host's order (the build has -ffp-contract=off), so device and host differ only by the last bits of exp, sin and cos and
 // by the order of the float32 means of the reward.  Sums over lanes are fixed-shape trees in LDS: an env's result does not
 // depend on the batch it runs in.
+//
+// The PID teacher (anyhvac_solver.py HVACSolverGTPID / LOCPID .policy; host restatement xenoverse_amd/anyhvac/pid.py) is
+// hv_pid: lanes strided over the sensors form the float32 diff, advance the fp64 acc_diff and leave d_e in LDS; after one
+// barrier lanes strided over the coolers sum d_e[s] corr[s][c] over the task's sensors in index order (a row of the
+// row-major weights is read coalesced across c), clip, round to float32 and write 1 - value.  It is called by a kernel of
+// its own (xv_anyhvac_pid_action) and, as the PID instantiation of the step kernel, in front of every step of a rollout.
 #include <cmath>
 #include <new>
 
@@ -50,11 +56,17 @@ struct HvArgs {
 struct xv_anyhvac {
   xv_engine* eng;
   HvArgs a;
+  // the PID teacher's arguments (xv_anyhvac_set_pid): weights, gains, arithmetic flag; the state it owns
+  const double *pid_weights, *pid_gains;
+  int pid_f64;
+  double* pid_acc;
+  float* pid_last_obs;
+  int32_t* pid_fresh;
 };
 
 struct HvTask {      // one task's table, taken apart (layout: include/xeno.h)
   const double *sc, *base, *chtc, *hc, *sens, *heat, *hd, *cool, *cd, *cv;
-  int nw, nl, nC, nS, nH, NL, NC, NWALL, KS, KH, srow, hrow;
+  int nw, nl, nC, nS, nH, NL, NC, NWALL, KS, KH, srow, hrow, task;
 };
 
 __device__ __forceinline__ HvTask hv_task(const HvArgs& P, int env) {
@@ -64,6 +76,7 @@ __device__ __forceinline__ HvTask hv_task(const HvArgs& P, int env) {
   int task = P.env_task[env];
   task = task < 0 ? 0 : (task >= P.n_task ? P.n_task - 1 : task);
   const double* p = P.tables + (size_t)task * stride;
+  K.task = task;
   K.NL = P.NL; K.NC = NC; K.NWALL = NWALL; K.KS = P.KS; K.KH = P.KH;
   K.srow = 8 + 3 * P.KS; K.hrow = 4 + 3 * P.KH;
   K.sc = p; p += 16;
@@ -146,9 +159,9 @@ __device__ __forceinline__ HvObsOut hv_obs_rows(float* sensor, float* heat, floa
 
 // _get_obs: sensor readings, heater powers, set temperatures and the step index at time t; padded columns are zero.
 // loss / hot (nullable): this lane's share of sum max(sqrt(d), d), d = clip(reading - target, 0, 8) in float32, and of the
-// count of readings above the failure bound
+// count of readings above the failure bound; keep (nullable): the readings once more, [P.S] in LDS, entry s by lane s % HV_BLOCK
 __device__ __forceinline__ void hv_obs(const HvArgs& P, const HvTask& K, const double* g, double t, int rest, const float* value,
-                                       const HvObsOut& o, double* loss, double* hot) {
+                                       const HvObsOut& o, double* loss, double* hot, float* keep = nullptr) {
   const int tid = threadIdx.x;
   const float target = (float)K.sc[9];
   const double fub = K.sc[15];
@@ -163,6 +176,7 @@ __device__ __forceinline__ void hv_obs(const HvArgs& P, const HvTask& K, const d
       ht += ((double)v > fub) ? 1.0 : 0.0;
     }
     if (o.sensor) o.sensor[s] = v;
+    if (keep) keep[s] = v;
   }
   if (loss) *loss = ls;
   if (hot) *hot = ht;
@@ -263,9 +277,117 @@ __global__ __launch_bounds__(HV_BLOCK) void xv_anyhvac_reset_kernel(HvArgs P, co
   hv_store(P, env, s_grid, E);
 }
 
-template <bool INJECT>
+
+// ---- the PID teacher ---------------------------------------------------------------------------------------------------
+struct HvPid {
+  const double* weights;      // [n_task][S][C] corr_sensor_cooler, padded rows and columns zero
+  const double* gains;        // [n_env][3]: kp, ki, kd
+  double* acc;                // [n_env][S] acc_diff
+  float* last_obs;            // [n_env][S] last_observation
+  int32_t* fresh;             // [n_env]: 1 from a reset to the first controller call
+  int f64;                    // the gains are numpy.float64 scalars (all three products in fp64), not Python floats
+  float* action_out;          // [T][n_env][C]
+  float* flat_out;            // [n_env][2 C] or null (xv_anyhvac_pid_action)
+  double* stats;              // [n_env][XV_ANYHVAC_PID_STATS] or null (xv_anyhvac_rollout_pid)
+};
+
+// One controller call of env.  obs[P.S]: the readings (entry s is read by lane s % HV_BLOCK only); act[P.C]: the env's
+// action 1 - value, padded columns 0; flat (nullable): the reference's [switch[P.C], value[P.C]].  acc_diff and
+// last_obs advance.  Every lane of the block calls it: there is one barrier inside.
+//   diff = target - obs, last_diff = target - last_obs, dd = diff - last_diff              float32
+//   d_e = -(kp diff - kd dd / delta_t + ki acc_diff): the first two products float32 under Python-float gains (numpy
+//   rounds the gain and delta_t to float32), fp64 under numpy.float64 gains; ki acc_diff fp64 always
+__device__ __forceinline__ void hv_pid(const HvArgs& P, const HvTask& K, const HvPid& D, int env, const float* obs, double* s_de,
+                                       float* act, float* flat) {
+  const int tid = threadIdx.x;
+  const double* gn = D.gains + (size_t)env * 3;
+  const double kp = gn[0], ki = gn[1], kd = gn[2];
+  const double delta_t = (double)P.iters * P.dt / 60.0;
+  const float target = (float)K.sc[9];
+  double* acc = D.acc + (size_t)env * P.S;
+  float* last = D.last_obs + (size_t)env * P.S;
+  for (int s = tid; s < P.S; s += HV_BLOCK) {
+    double de = 0.0;
+    if (s < K.nS) {
+      const float o = obs[s];
+      const float diff = target - o, last_diff = target - last[s];
+      const double a = acc[s] + (double)diff;
+      acc[s] = a;
+      last[s] = o;
+      const float dd = diff - last_diff;
+      double pd;
+      if (D.f64) pd = kp * (double)diff - kd * (double)dd / delta_t;
+      else pd = (double)((float)kp * diff - (float)kd * dd / (float)delta_t);
+      de = -(pd + ki * a);
+    }
+    s_de[s] = de;
+  }
+  if (tid == 0) D.fresh[env] = 0;
+  __syncthreads();
+  const double* W = D.weights + (size_t)K.task * P.S * P.C;
+  for (int c = tid; c < P.C; c += HV_BLOCK) {
+    float a = 0.0f, sw = 0.0f, v = 0.0f;
+    if (c < K.nC) {
+      double x = 0.0;
+      for (int s = 0; s < K.nS; ++s) x += s_de[s] * W[(size_t)s * P.C + c];
+      sw = x > -0.05 ? 1.0f : 0.0f;
+      v = x == x ? (float)fmin(fmax(x, 0.0), 1.0) : (float)x;
+      a = 1.0f - v;
+    }
+    act[c] = a;
+    if (flat) { flat[c] = sw; flat[P.C + c] = v; }
+  }
+}
+
+__device__ __forceinline__ void hv_pid_clear(const HvArgs& P, const HvPid& D, int env) {
+  for (int s = threadIdx.x; s < P.S; s += HV_BLOCK) {
+    D.acc[(size_t)env * P.S + s] = 0.0;
+    D.last_obs[(size_t)env * P.S + s] = 0.0f;
+  }
+  if (threadIdx.x == 0) D.fresh[env] = 1;
+}
+
+__device__ __forceinline__ double hv_block_max(double v, double* red) {
+  const int tid = threadIdx.x;
+  red[tid] = v;
+  __syncthreads();
+  for (int o = HV_BLOCK / 2; o > 0; o >>= 1) {
+    if (tid < o) red[tid] = fmax(red[tid], red[tid + o]);
+    __syncthreads();
+  }
+  const double s = red[0];
+  __syncthreads();
+  return s;
+}
+
+__global__ __launch_bounds__(HV_BLOCK) void xv_anyhvac_pid_reset_kernel(HvArgs P, HvPid D, const uint8_t* mask) {
+  const int env = blockIdx.x;
+  if (mask && !mask[env]) return;
+  hv_pid_clear(P, D, env);
+}
+
+// one controller call per env without a step: the readings given, or the env's current observation (hv_obs of its grid
+// and t: the function and inputs of the step's epilogue, so the same bits)
+__global__ __launch_bounds__(HV_BLOCK) void xv_anyhvac_pid_kernel(HvArgs P, HvPid D, const float* readings) {
+  __shared__ double s_grid[HV_MAX_GRID * HV_MAX_GRID];
+  __shared__ double s_de[HV_MAX_SH];
+  __shared__ float s_obs[HV_MAX_SH];
+  const int env = blockIdx.x, tid = threadIdx.x;
+  const HvTask K = hv_task(P, env);
+  if (readings) {
+    for (int s = tid; s < P.S; s += HV_BLOCK) s_obs[s] = readings[(size_t)env * P.S + s];
+  } else {
+    if (tid < K.NC) s_grid[tid] = P.grid[(size_t)env * K.NC + tid];
+    __syncthreads();
+    hv_obs(P, K, s_grid, P.t[env], 0, nullptr, hv_obs_rows(nullptr, nullptr, nullptr, nullptr, 0, P), nullptr, nullptr, s_obs);
+  }
+  hv_pid(P, K, D, env, s_obs, s_de, D.action_out + (size_t)env * P.C, D.flat_out ? D.flat_out + (size_t)env * 2 * P.C : nullptr);
+}
+
+// PID: the teacher's controller call in front of every step (the action is D.action_out's row, not io.action's)
+template <bool INJECT, bool PID>
 __global__ __launch_bounds__(HV_BLOCK) void xv_anyhvac_step_kernel(HvArgs P, xv_anyhvac_io io, const double* reset_grid,
-                                                                   int mode, int T) {
+                                                                   int mode, int T, HvPid D) {
   __shared__ double s_grid[2][HV_MAX_GRID * HV_MAX_GRID];
   __shared__ double s_static[HV_MAX_GRID * HV_MAX_GRID];
   __shared__ double s_chtc[HV_MAX_WALL];
@@ -274,6 +396,8 @@ __global__ __launch_bounds__(HV_BLOCK) void xv_anyhvac_step_kernel(HvArgs P, xv_
   __shared__ double s_heat[HV_MAX_SH];
   __shared__ double s_red[HV_BLOCK];
   __shared__ int s_bad;
+  __shared__ double s_de[PID ? HV_MAX_SH : 1];
+  __shared__ float s_obs[PID ? HV_MAX_SH : 1];      // the readings the next controller call takes
   const int env = blockIdx.x, tid = threadIdx.x;
   const HvTask K = hv_task(P, env);
   const int NL = K.NL, NC = K.NC;
@@ -288,6 +412,10 @@ __global__ __launch_bounds__(HV_BLOCK) void xv_anyhvac_step_kernel(HvArgs P, xv_
   HvEnv E;
   int cur = 0;
   hv_load(P, env, s_grid[0], E);
+  const float* act_in = PID ? D.action_out : io.action;
+  double st_abs = 0.0, st_max = 0.0, st_sq = 0.0, st_c1 = 0.0, st_c2 = 0.0, st_over = 0.0, st_rew = 0.0, st_n = 0.0;
+  if (PID)
+    hv_obs(P, K, s_grid[0], E.t, E.rest, value, hv_obs_rows(nullptr, nullptr, nullptr, nullptr, 0, P), nullptr, nullptr, s_obs);
 
   for (int ts = 0; ts < T; ++ts) {
     const size_t row = (size_t)ts * N + env;
@@ -307,12 +435,14 @@ __global__ __launch_bounds__(HV_BLOCK) void xv_anyhvac_step_kernel(HvArgs P, xv_
       s_heat[h] = p;
       if (io.heat_power) io.heat_power[row * P.H + h] = p;
     }
+    // -- the teacher: readings -> PID -> this step's action row (column c is written by the lane that reads it below)
+    if (PID) hv_pid(P, K, D, env, s_obs, s_de, D.action_out + row * P.C, nullptr);
     // -- this step's action: clipped float32, the resting cooler's replaced by the default value
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
       const int c = tid + q * HV_BLOCK;
       if (c < P.C) {
-        float v = io.action[row * P.C + c];
+        float v = act_in[row * P.C + c];
         v = fminf(fmaxf(v, 0.0f), 1.0f);
         if (!(v == v)) v = 0.0f;
         if (c == E.rest) v = (float)K.sc[14];
@@ -425,7 +555,17 @@ __global__ __launch_bounds__(HV_BLOCK) void xv_anyhvac_step_kernel(HvArgs P, xv_
     // -- observation, reward, flags
     double loss, hot;
     hv_obs(P, K, s_grid[cur], E.t, E.rest, value,
-           hv_obs_rows(io.sensor_readings, io.heat_readings, io.action_temp, io.timestep, row, P), &loss, &hot);
+           hv_obs_rows(io.sensor_readings, io.heat_readings, io.action_temp, io.timestep, row, P), &loss, &hot,
+           PID ? s_obs : nullptr);
+    if (PID && D.stats) {      // e = reading - target in float32, over the real sensors (this lane's entries of s_obs)
+      const float target = (float)K.sc[9], over = (float)(K.sc[9] + 2.0);
+      for (int s = tid; s < K.nS; s += HV_BLOCK) {
+        const double ae = (double)fabsf(s_obs[s] - target);
+        st_abs += ae; st_max = fmax(st_max, ae); st_sq += ae * ae;
+        st_c1 += ae <= 1.0 ? 1.0 : 0.0; st_c2 += ae <= 2.0 ? 1.0 : 0.0;
+        st_over += s_obs[s] > over ? 1.0 : 0.0; st_n += 1.0;
+      }
+    }
     loss = hv_block_sum(loss, s_red);
     hot = hv_block_sum(hot, s_red);
     double psum = 0.0;
@@ -458,6 +598,7 @@ __global__ __launch_bounds__(HV_BLOCK) void xv_anyhvac_step_kernel(HvArgs P, xv_
     else reward = (double)(1.0f + target_cost) + 0.0 + energy_cost + 0.0 + (overheat ? -10.0 : 0.0);
     int trunc = E.t >= P.max_t ? 1 : 0;
     if (nonfinite) { reward = NAN; term = 0; trunc = 0; E.warning_count = E0.warning_count; }
+    if (PID) st_rew += reward;
     if (tid == 0) {
       io.reward[row] = reward;
       io.terminated[row] = (uint8_t)term;
@@ -476,7 +617,9 @@ __global__ __launch_bounds__(HV_BLOCK) void xv_anyhvac_step_kernel(HvArgs P, xv_
       __syncthreads();
       hv_reset<INJECT>(P, K, env, xv_launch_tick(P.tick, P.tick_dev) + (uint64_t)ts, reset_grid, s_grid[cur], E);
       hv_obs(P, K, s_grid[cur], E.t, E.rest, value,
-             hv_obs_rows(io.sensor_readings, io.heat_readings, io.action_temp, io.timestep, row, P), nullptr, nullptr);
+             hv_obs_rows(io.sensor_readings, io.heat_readings, io.action_temp, io.timestep, row, P), nullptr, nullptr,
+             PID ? s_obs : nullptr);
+      if (PID) hv_pid_clear(P, D, env);      // the new episode starts with a fresh controller
     } else {
       if (fin.sensor) for (int s = tid; s < P.S; s += HV_BLOCK) fin.sensor[s] = 0.0f;
       if (fin.heat) for (int h = tid; h < P.H; h += HV_BLOCK) fin.heat[h] = 0.0f;
@@ -486,6 +629,18 @@ __global__ __launch_bounds__(HV_BLOCK) void xv_anyhvac_step_kernel(HvArgs P, xv_
     __syncthreads();
   }
   hv_store(P, env, s_grid[cur], E);
+  if (PID && D.stats) {      // lane partials over the T steps, then one fixed tree each: the same bits in any batch
+    double* st = D.stats + (size_t)env * XV_ANYHVAC_PID_STATS;
+    const double sums[6] = {st_abs, st_sq, st_c1, st_c2, st_over, st_n};
+    double red[6];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) red[i] = hv_block_sum(sums[i], s_red);
+    const double mx = hv_block_max(st_max, s_red);
+    if (tid == 0) {
+      st[0] += red[0]; st[1] = fmax(st[1], mx); st[2] += red[1]; st[3] += red[2]; st[4] += red[3]; st[5] += red[4];
+      st[6] += st_rew; st[7] += red[5];
+    }
+  }
 }
 
 #ifndef XV_KERNELS_ONLY
@@ -504,7 +659,7 @@ extern "C" int xv_anyhvac_destroy(xv_anyhvac* h) {
   (void)hipStreamSynchronize(h->eng->stream);
   HvArgs& a = h->a;
   void* ps[] = {a.grid, a.t, a.last_call, a.episode_step, a.warning_count, a.rest_idx, a.rest_start, a.value, a.filter,
-                a.ring_t, a.ring_v, a.head, a.tail};
+                a.ring_t, a.ring_v, a.head, a.tail, h->pid_acc, h->pid_last_obs, h->pid_fresh};
   for (void* q : ps) if (q) (void)hipFree(q);
   delete h;
   return XV_OK;
@@ -592,8 +747,8 @@ static int hv_step_call(xv_anyhvac* h, const xv_anyhvac_io* io, const double* re
     return XV_ERR_UNSUPPORTED;
   }
   hv_bind_rng(h, INJECT ? 0 : (uint64_t)T);
-  hipLaunchKernelGGL((xv_anyhvac_step_kernel<INJECT>), dim3(h->a.n_env), dim3(HV_BLOCK), 0, h->eng->stream, h->a, *io,
-                     reset_grid, mode, T);
+  hipLaunchKernelGGL((xv_anyhvac_step_kernel<INJECT, false>), dim3(h->a.n_env), dim3(HV_BLOCK), 0, h->eng->stream, h->a, *io,
+                     reset_grid, mode, T, HvPid{});
   XV_LAUNCH_CHECK();
   return XV_OK;
 }
@@ -629,4 +784,84 @@ static int hv_state_copy(xv_anyhvac* h, const xv_anyhvac_state* s) {
 
 extern "C" int xv_anyhvac_get_state(xv_anyhvac* h, const xv_anyhvac_state* out) { return hv_state_copy<false>(h, out); }
 extern "C" int xv_anyhvac_set_state(xv_anyhvac* h, const xv_anyhvac_state* in) { return hv_state_copy<true>(h, in); }
+
+// ---- the PID teacher ---------------------------------------------------------------------------------------------------
+static HvPid hv_pid_args(const xv_anyhvac* h, float* action_out, float* flat_out, double* stats) {
+  HvPid D = {};
+  D.weights = h->pid_weights; D.gains = h->pid_gains; D.f64 = h->pid_f64;
+  D.acc = h->pid_acc; D.last_obs = h->pid_last_obs; D.fresh = h->pid_fresh;
+  D.action_out = action_out; D.flat_out = flat_out; D.stats = stats;
+  return D;
+}
+
+extern "C" int xv_anyhvac_pid_reset(xv_anyhvac* h, const uint8_t* mask) {
+  XV_CHECK_ARG(h && h->pid_acc);
+  hipLaunchKernelGGL(xv_anyhvac_pid_reset_kernel, dim3(h->a.n_env), dim3(HV_BLOCK), 0, h->eng->stream, h->a,
+                     hv_pid_args(h, nullptr, nullptr, nullptr), mask);
+  XV_LAUNCH_CHECK();
+  return XV_OK;
+}
+
+extern "C" int xv_anyhvac_set_pid(xv_anyhvac* h, const double* weights, const double* gains, int kind_flags) {
+  XV_CHECK_ARG(h && h->a.tables && weights && gains && (kind_flags & ~XV_ANYHVAC_PID_FLOAT64) == 0);
+  XV_HIP(hipSetDevice(h->eng->device));
+  if (!h->pid_acc) {
+    const size_t n = (size_t)h->a.n_env, s = (size_t)h->a.S;
+    hipError_t r = hipMalloc((void**)&h->pid_acc, n * s * 8);
+    if (r == hipSuccess) r = hipMalloc((void**)&h->pid_last_obs, n * s * 4);
+    if (r == hipSuccess) r = hipMalloc((void**)&h->pid_fresh, n * 4);
+    if (r != hipSuccess) {
+      xv_set_error("xv_anyhvac_set_pid: device allocation failed: %s", hipGetErrorString(r));
+      void* ps[] = {h->pid_acc, h->pid_last_obs, h->pid_fresh};
+      for (void* q : ps) if (q) (void)hipFree(q);
+      h->pid_acc = nullptr; h->pid_last_obs = nullptr; h->pid_fresh = nullptr;
+      return XV_ERR_HIP;
+    }
+  }
+  h->pid_weights = weights;
+  h->pid_gains = gains;
+  h->pid_f64 = (kind_flags & XV_ANYHVAC_PID_FLOAT64) ? 1 : 0;
+  return xv_anyhvac_pid_reset(h, nullptr);
+}
+
+extern "C" int xv_anyhvac_pid_action(xv_anyhvac* h, const float* readings, float* action_out, float* flat_out) {
+  XV_CHECK_ARG(h && h->a.tables && h->pid_acc && action_out);
+  hipLaunchKernelGGL(xv_anyhvac_pid_kernel, dim3(h->a.n_env), dim3(HV_BLOCK), 0, h->eng->stream, h->a,
+                     hv_pid_args(h, action_out, flat_out, nullptr), readings);
+  XV_LAUNCH_CHECK();
+  return XV_OK;
+}
+
+extern "C" int xv_anyhvac_rollout_pid(xv_anyhvac* h, int T, const xv_anyhvac_io* io, float* action_out, double* stats,
+                                      int autoreset_mode) {
+  XV_CHECK_ARG(h && h->a.tables && h->pid_acc && io && io->reward && io->terminated && io->truncated && action_out && T > 0);
+  if (autoreset_mode != XV_AUTORESET_DISABLED && autoreset_mode != XV_AUTORESET_SAME_STEP) {
+    xv_set_error("xv_anyhvac: autoreset mode %d is not built (disabled and same_step are)", autoreset_mode);
+    return XV_ERR_UNSUPPORTED;
+  }
+  hv_bind_rng(h, (uint64_t)T);
+  hipLaunchKernelGGL((xv_anyhvac_step_kernel<false, true>), dim3(h->a.n_env), dim3(HV_BLOCK), 0, h->eng->stream, h->a, *io,
+                     (const double*)nullptr, autoreset_mode, T, hv_pid_args(h, action_out, nullptr, stats));
+  XV_LAUNCH_CHECK();
+  return XV_OK;
+}
+
+template <bool SET>
+static int hv_pid_state_copy(xv_anyhvac* h, double* acc_diff, float* last_obs, int32_t* fresh) {
+  XV_CHECK_ARG(h && h->pid_acc);
+  const size_t n = (size_t)h->a.n_env, s = (size_t)h->a.S;
+  struct { void* user; void* own; size_t bytes; } rows[] = {
+      {acc_diff, h->pid_acc, n * s * 8}, {last_obs, h->pid_last_obs, n * s * 4}, {fresh, h->pid_fresh, n * 4}};
+  for (auto& r : rows)
+    if (r.user)
+      XV_HIP(hipMemcpyAsync(SET ? r.own : r.user, SET ? r.user : r.own, r.bytes, hipMemcpyDeviceToDevice, h->eng->stream));
+  return XV_OK;
+}
+
+extern "C" int xv_anyhvac_pid_get_state(xv_anyhvac* h, double* acc_diff, float* last_obs, int32_t* fresh) {
+  return hv_pid_state_copy<false>(h, acc_diff, last_obs, fresh);
+}
+extern "C" int xv_anyhvac_pid_set_state(xv_anyhvac* h, const double* acc_diff, const float* last_obs, const int32_t* fresh) {
+  return hv_pid_state_copy<true>(h, const_cast<double*>(acc_diff), const_cast<float*>(last_obs), const_cast<int32_t*>(fresh));
+}
 #endif  // XV_KERNELS_ONLY
