@@ -982,6 +982,24 @@ int xv_metalm_step(xv_metalm* h, const int32_t* answer, const int32_t* answer_le
 int xv_metalm_get_state(xv_metalm* h, int32_t* query, int32_t* query_len, double* cache, int32_t* steps);
 int xv_metalm_set_state(xv_metalm* h, const int32_t* query, const int32_t* query_len, const double* cache,
                         const int32_t* steps);
+/* The training streams of xenoverse/metalang/generator_v3.py:48-173 (generate_data_v3_single_task_qa / _qar / _qara), ONE
+ * launch: every env's workgroup runs rounds of policy + step from the handle's state (query, cached hidden state, steps)
+ * until its own data cursor reaches L or max_rounds rounds are done, splices query, answer, label and reward token into
+ * data and label [n_env][L] (tokens at or past L are dropped; what max_rounds leaves unfilled is 0), and leaves the state of
+ * its last sub-step.  K = max_rounds x (2 for QARA, else 1) sub-steps (one policy + step pair each).  t_choices: device
+ * float64 [n_choice], unused for QA (which answers at T = 1e-3).  t_index: device int32 [n_env][K] indices into t_choices,
+ * or NULL: min(floor(u n_choice), n_choice - 1) with a Philox u.  u_*: device float64 [n_env][K][max_len + 1] injected
+ * uniforms per pass, or NULL (Philox).  marks: 11 HOST ints, the tokens s q a r1 r2 r3 r4 r5 r> r= r<.  filled [n_env]: the
+ * data cursor, at most L; rounds [n_env]: rounds begun.  reward float64 and t_index_out int32 [n_env][K], nullable, are
+ * written for the sub-steps that ran (QA forms no reward and draws no temperature: neither buffer is written).  The call consumes 2 K ticks:
+ * sub-step k draws what policy() would at tick + 2 k and what step() would at tick + 2 k + 1. */
+#define XV_METALM_QA 0
+#define XV_METALM_QAR 1
+#define XV_METALM_QARA 2
+int xv_metalm_stream(xv_metalm* h, int datatype, int L, int max_rounds, const double* t_choices, int n_choice,
+                     const int32_t* t_index, const double* u_policy, const double* u_greedy, const double* u_low,
+                     const double* u_query, const int32_t* marks, int32_t* data, int32_t* label, int32_t* filled,
+                     int32_t* rounds, double* reward, int32_t* t_index_out);
 
 /* ------------------------------------------------------------------------------------------------
  * AnyHVAC — reference: xenoverse/anyhvac/anyhvac_env.py HVACEnv :8-651 with control_type 'Temperature',

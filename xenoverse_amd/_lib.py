@@ -144,6 +144,7 @@ SIGNATURES = {
     "xv_metalm_step": [c_void_p] + [c_void_p] * 16,
     "xv_metalm_get_state": [c_void_p] * 5,
     "xv_metalm_set_state": [c_void_p] * 5,
+    "xv_metalm_stream": [c_void_p, c_int, c_int, c_int, c_void_p, c_int] + [c_void_p] * 12,
     "xv_anyhvac_create": [c_void_p] + [c_int] * 9 + [C.c_double] * 4 + [c_int, C.POINTER(c_void_p)],
     "xv_anyhvac_destroy": [c_void_p],
     "xv_anyhvac_set_task": [c_void_p, c_int, c_void_p, c_void_p],

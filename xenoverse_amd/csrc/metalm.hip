@@ -204,6 +204,8 @@ __device__ __forceinline__ double lm_tanh(double x, const double* tt) {      // 
   return __longlong_as_double(__double_as_longlong(r) | (bits & (long long)0x8000000000000000ull));
 }
 
+#include "metalm_pass.h"
+
 template <bool TL>
 __global__ __launch_bounds__(256) void metalm_kernel(LMArgs P, LMCall C) {
   extern __shared__ double lm_tab[];
@@ -213,24 +215,12 @@ __global__ __launch_bounds__(256) void metalm_kernel(LMArgs P, LMCall C) {
   for (int i = threadIdx.x; i < 18 * 16; i += blockDim.x) lm_tt[i] = __longlong_as_double((long long)lm_tanh_tab[i]);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int env = blockIdx.x;
-  const int V = P.V, E = P.E, H = P.H, max_len = P.max_len;
-  const int NC = (V + 63) >> 6;
+  const int H = P.H, max_len = P.max_len;
   const int kind = C.mode == LM_MODE_STEP ? (wave == 0 ? LM_LABEL : wave == 1 ? LM_GREEDY : wave == 2 ? LM_LOW : LM_QUERY)
                                           : (C.mode == LM_MODE_RESET ? LM_QUERY : LM_POLICY);
   uint32_t err = 0u;
-  int task = P.env_task[env];
-  if ((unsigned)task >= (unsigned)P.n_task) { err |= XV_DEVERR_ACTION_RANGE; task = 0; }
-  const double* emb = P.emb + (size_t)task * V * E;
-  const double* w_h = P.w_h + (size_t)task * (H + E) * H;
-  const double* b_h = P.b_h + (size_t)task * H;
-  const double* w_d = P.w_d + (size_t)task * H * V;
-  const double* b_d = P.b_d + (size_t)task * V;
-  if (TL) {
-    const int n0 = V * E, n1 = n0 + (H + E) * H, n2 = n1 + H, n3 = n2 + H * V, n4 = n3 + V;
-    for (int i = threadIdx.x; i < n4; i += blockDim.x)
-      lm_tab[i] = i < n0 ? emb[i] : i < n1 ? w_h[i - n0] : i < n2 ? b_h[i - n1] : i < n3 ? w_d[i - n2] : b_d[i - n3];
-    emb = lm_tab; w_h = lm_tab + n0; b_h = lm_tab + n1; w_d = lm_tab + n2; b_d = lm_tab + n3;
-  }
+  const double *emb, *w_h, *b_h, *w_d, *b_d;
+  lm_tables<TL>(P, env, lm_tab, err, emb, w_h, b_h, w_d, b_d);
   double* hs = lm_hs[wave];
   // every pass but the query starts from the cached state; the query wave overwrites that state only at its end, behind
   // this barrier
@@ -252,208 +242,17 @@ __global__ __launch_bounds__(256) void metalm_kernel(LMArgs P, LMCall C) {
   const double temp1 = kind == LM_POLICY ? temp0 : 1.0;
   if (kind == LM_POLICY && !(temp0 > 0.0 && temp0 <= 1.0e300)) err |= XV_DEVERR_NONFINITE;
 
-  bool col[LM_NC], fun[LM_NC];
-  double bd[LM_NC], echo[LM_NC];
-#pragma unroll
-  for (int c = 0; c < LM_NC; ++c) {
-    const int v = lane + 64 * c;
-    col[c] = v < V;
-    fun[c] = (P.fmask[c] >> lane) & 1ull;
-    bd[c] = col[c] ? b_d[v] : 0.0;
-    echo[c] = 0.0;
-  }
-  double bh[2];
-#pragma unroll
-  for (int r = 0; r < 2; ++r) bh[r] = lane + 64 * r < H ? b_h[lane + 64 * r] : 0.0;
-
-  // the last (H + E) mod 4 terms of a hidden row's dot product are the BLAS matvec's tail, added in its own order (with
-  // H not a multiple of 4 that matvec sums its last H mod 4 rows in yet another order, which is not followed)
-  const int m3 = (H & 3) ? 0 : (E & 3);
-  double stop_bias = -1.0e+6, ppl_sum = 0.0;
-  int tok_in = 0, n_out = 0, n_step = 0;
-  bool done = skip;
-  for (int tb = 0; !done; tb += 64) {
-    // ---- this block's 64 positions: the uniform (or, teacher-forced, the given token) of position tb + lane ----
-    const int pos = tb + lane;
-    double u_l = 0.0;
-    int a_l = P.stop;
-    if (kind == LM_LABEL) {
-      if (pos < n_ans) {
-        a_l = C.ans[(size_t)env * max_len + pos];
-        if ((unsigned)a_l >= (unsigned)V) { err |= XV_DEVERR_ACTION_RANGE; a_l = P.stop; }
-      }
-    } else if (pos <= max_len) {
-      if (u_in) {
-        u_l = u_in[(size_t)env * (max_len + 1) + pos];
-      } else {
-        const xv_u32x4 w = xv_env_draw_sub(P.seed, gid, tick, XV_DRAW_METALM, ((uint32_t)kind << 16) | ((uint32_t)pos >> 1));
-        u_l = (pos & 1) ? xv_u53(w.z, w.w) : xv_u53(w.x, w.y);
-      }
-    }
-    int my_tok = 0;
-    for (int k = 0; k < 64 && !done; ++k) {
-      // ---- the hidden state: rows lane and lane + 64 ----
-      const double* er = emb + tok_in * E;
-      double hn[2];
-#pragma unroll
-      for (int r = 0; r < 2; ++r) {
-        const int row = lane + 64 * r;
-        hn[r] = 0.0;
-        if (64 * r < H) {      // wave-uniform
-          const double* wr = w_h + (row < H ? row : 0);
-          double a4[4] = {0.0, 0.0, 0.0, 0.0};
-          int q = 0;
-          for (; q + 3 < H; q += 4) {
-            a4[0] = fma(wr[(q + 0) * H], hs[q + 0], a4[0]);
-            a4[1] = fma(wr[(q + 1) * H], hs[q + 1], a4[1]);
-            a4[2] = fma(wr[(q + 2) * H], hs[q + 2], a4[2]);
-            a4[3] = fma(wr[(q + 3) * H], hs[q + 3], a4[3]);
-          }
-          for (; q < H; ++q) a4[q & 3] = fma(wr[q * H], hs[q], a4[q & 3]);
-          const double* we = wr + (size_t)H * H;
-          for (q = 0; q < E - m3; ++q) a4[(H + q) & 3] = fma(we[q * H], er[q], a4[(H + q) & 3]);
-          double a = (a4[0] + a4[2]) + (a4[1] + a4[3]);      // the order of the BLAS matvec behind the host's `@`
-          if (m3) {                                           // and of its tail
-            const double* wt = we + (E - m3) * H;
-            const double* et = er + (E - m3);
-            if (m3 == 1) {
-              a = fma(wt[0], et[0], a);
-            } else {
-              double t = fma(wt[0], et[0], wt[H] * et[1]);
-              if (m3 == 3) t = fma(wt[2 * H], et[2], t);
-              a += t;
-            }
-          }
-          a += bh[r];
-          hn[r] = lm_tanh(a, lm_tt);
-        }
-      }
-      lm_wave_sync();
-#pragma unroll
-      for (int r = 0; r < 2; ++r)
-        if (lane + 64 * r < H) hs[lane + 64 * r] = hn[r];
-      lm_wave_sync();
-      // ---- logits of columns lane + 64 c ----
-      double l[LM_NC];
-#pragma unroll
-      for (int c = 0; c < LM_NC; ++c) {
-        l[c] = 0.0;
-        if (c < NC) {          // wave-uniform
-          const int v = lane + 64 * c;
-          const double* wc = w_d + (col[c] ? v : 0);
-          double a4[4] = {0.0, 0.0, 0.0, 0.0};
-          int q = 0;
-          for (; q + 3 < H; q += 4) {
-            a4[0] = fma(wc[(q + 0) * V], hs[q + 0], a4[0]);
-            a4[1] = fma(wc[(q + 1) * V], hs[q + 1], a4[1]);
-            a4[2] = fma(wc[(q + 2) * V], hs[q + 2], a4[2]);
-            a4[3] = fma(wc[(q + 3) * V], hs[q + 3], a4[3]);
-          }
-          for (; q < H; ++q) a4[q & 3] = fma(wc[q * V], hs[q], a4[q & 3]);
-          double a = (a4[0] + a4[2]) + (a4[1] + a4[3]);
-          a += bd[c];
-          a += echo[c];
-          if (v == P.stop) a += stop_bias;
-          if (fun[c]) a = -1.0e+6;
-          l[c] = a;
-          if (v == tok_in) echo[c] -= 0.05;
-        }
-      }
-      stop_bias = stop_bias < 0.0 ? 0.02 : stop_bias + 0.02;
-      // ---- the decoder's weights e, their sum ----
-      const double T = n_step == 0 ? temp0 : temp1;
-      double e[LM_NC], part = 0.0;
-      if (kind == LM_LOW || kind == LM_LABEL) {
-#pragma unroll
-        for (int c = 0; c < LM_NC; ++c) {
-          double x = l[c];
-          if (kind == LM_LOW && lane + 64 * c >= 1 && x < -1.0e+5) x = 0.0;
-          e[c] = (c < NC && col[c]) ? exp(x) : 0.0;
-          part += e[c];
-        }
-      } else {
-        double m = -1.0e+300;
-#pragma unroll
-        for (int c = 0; c < LM_NC; ++c)
-          if (c < NC && col[c]) m = fmax(m, l[c]);
-        m = lm_wave_max(m);
-#pragma unroll
-        for (int c = 0; c < LM_NC; ++c) {
-          e[c] = (c < NC && col[c]) ? exp((l[c] - m) / T) : 0.0;
-          part += e[c];
-        }
-      }
-      const double S = lm_lane(lm_wave_scan(part), 63);
-      if (!(S > 0.0) || !(S <= 1.0e300)) err |= XV_DEVERR_NONFINITE;
-      double p[LM_NC];
-#pragma unroll
-      for (int c = 0; c < LM_NC; ++c) p[c] = e[c] / S;
-      // ---- the token ----
-      int sym = 0;
-      if (kind != LM_LABEL) {
-        const double u = lm_lane(u_l, k);
-        double s[LM_NC], run = 0.0;
-#pragma unroll
-        for (int c = 0; c < LM_NC; ++c) {
-          s[c] = run;
-          if (c < NC) {
-            s[c] = lm_wave_scan(p[c]) + run;
-            run = lm_lane(s[c], 63);
-          }
-        }
-        sym = -1;
-#pragma unroll
-        for (int c = 0; c < LM_NC; ++c) {
-          if (c < NC) {
-            const unsigned long long hit = __ballot(col[c] && s[c] / run > u);
-            if (sym < 0 && hit) sym = 64 * c + (__ffsll((long long)hit) - 1);
-          }
-        }
-        if (sym < 0) sym = V - 1;      // searchsorted past the end: never with u < 1
-      }
-      if (kind == LM_LABEL || (kind == LM_GREEDY && sym != 0)) {
-        double bv = -1.0;
-        int bi = 0x7fffffff;
-#pragma unroll
-        for (int c = 0; c < LM_NC; ++c)
-          if (c < NC && col[c] && p[c] > bv) { bv = p[c]; bi = lane + 64 * c; }
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) {
-          const double ov = __shfl_xor(bv, m, 64);
-          const int oi = __shfl_xor(bi, m, 64);
-          if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-        }
-        sym = bi;
-      }
-      sym = __builtin_amdgcn_readfirstlane(sym);      // every lane holds the same value: say so
-      // the token whose probability is reported: the given one (label) or the chosen one
-      const int given = kind == LM_LABEL ? __builtin_amdgcn_readlane(a_l, k) : sym;
-      double pg = p[0];
-#pragma unroll
-      for (int c = 1; c < LM_NC; ++c)
-        if ((given >> 6) == c) pg = p[c];
-      pg = lm_lane(pg, given & 63);
-      ppl_sum += -log(fmax(pg, 1.0e-10));
-      ++n_step;
-      if (kind == LM_LABEL) {
-        if (lane == k) my_tok = sym;
-        ++n_out;
-        tok_in = given;
-        done = n_step > n_ans;
-      } else if (sym == P.stop) {
-        done = true;
-      } else if (n_out >= max_len) {
-        err |= XV_DEVERR_LENGTH;      // the step after max_len tokens did not draw the stop token: the pass is cut
-        done = true;
-      } else {
-        if (lane == k) my_tok = sym;
-        ++n_out;
-        tok_in = sym;
-      }
-    }
-    int32_t* dst = kind == LM_QUERY ? P.query + (size_t)env * max_len : out ? out + (size_t)env * stride : nullptr;
-    if (dst && pos < n_out) dst[pos] = my_tok;
-  }
+  LMPass A;
+  A.kind = kind; A.skip = skip; A.n_ans = n_ans;
+  A.ans = C.ans ? C.ans + (size_t)env * max_len : nullptr;
+  A.u = u_in ? u_in + (size_t)env * (max_len + 1) : nullptr;
+  A.gid = gid; A.tick = tick; A.temp0 = temp0; A.temp1 = temp1;
+  A.dst = kind == LM_QUERY ? P.query + (size_t)env * max_len : out ? out + (size_t)env * stride : nullptr;
+  A.dst2 = nullptr; A.at = A.at2 = A.cap = 0; A.fuse = false;
+  lm_pass<false>(P, emb, w_h, b_h, w_d, b_d, hs, lm_tt, lane, A, err);
+  const int n_step = A.n_step;
+  const double ppl_sum = A.ppl_sum;
+  int n_out = A.n_out;
 
   if (kind == LM_QUERY) {
     int32_t* q = P.query + (size_t)env * max_len;
@@ -490,6 +289,201 @@ __global__ __launch_bounds__(256) void metalm_kernel(LMArgs P, LMCall C) {
     }
   } else if (C.mode == LM_MODE_RESET && lane == 0) {
     P.steps[env] = 0;
+  }
+  if (err) atomicOr(P.err, err);
+}
+
+// ---- the training streams (xenoverse/metalang/generator_v3.py:48-173; host restatement: metalang/stream_host.py) ----------
+// ONE WORKGROUP PER ENV runs round after round from the handle's state until its own data cursor reaches L (or max_rounds):
+// no launch boundary, so no env waits for the batch's longest pass.  A sub-step is what policy() + step() do: wave 0 runs
+// the policy pass with the label pass over its own answer fused into the token step (lm_pass), waves 1 and 2 the greedy and
+// rnd passes, wave 3 the next query unless the sub-step is cached (QARA's first); they meet at ONE barrier, behind which
+// every thread forms the reward from the four means.  What a sub-step leaves for that barrier (means, lengths, the query's
+// hidden state) is kept twice, by the parity of the sub-step, so a wave that runs ahead never overwrites what a slower
+// one has yet to read.  Tokens go straight to their place in the stream: the position of every piece of a round is known
+// once the lengths before it are (the query's before the round, answer 1's before QARA's second sub-step).  Tokens at or
+// past L are not stored.  Sub-step k draws its policy pass (and its temperature: pass kind 5, position 0) at tick + 2 k
+// and the other passes at tick + 2 k + 1: the ticks the same policy() / step() calls would bind.
+enum { LM_QA = XV_METALM_QA, LM_QAR = XV_METALM_QAR, LM_QARA = XV_METALM_QARA, LM_TEMP = 5 };
+enum { LM_S = 0, LM_Q = 1, LM_A = 2, LM_R1 = 3, LM_RGT = 8, LM_REQ = 9, LM_RLT = 10 };
+
+struct LMStream {
+  int datatype, L, max_rounds, K, n_choice;
+  const double* t_choices;   // [n_choice]
+  const int32_t* t_index;    // [N][K] or nullptr (drawn)
+  const double* u[4];        // policy, greedy, low, query: [N][K][max_len + 1] or nullptr (Philox)
+  int32_t marks[11];         // s q a r1..r5 r> r= r<
+  int32_t* data;             // [N][L]
+  int32_t* label;            // [N][L]
+  int32_t* filled;           // [N]
+  int32_t* rounds;           // [N]
+  double* reward;            // [N][K]; nullable
+  int32_t* t_index_out;      // [N][K]; nullable
+};
+
+template <bool TL>
+__global__ __launch_bounds__(256) void metalm_stream_kernel(LMArgs P, LMStream S) {
+  extern __shared__ double lm_tab[];
+  __shared__ double lm_hs[4][LM_H_MAX];
+  __shared__ double lm_cache[2][LM_H_MAX];
+  __shared__ double lm_mean[2][4];
+  __shared__ int lm_len[2][4];
+  __shared__ double lm_tt[18 * 16];
+  for (int i = threadIdx.x; i < 18 * 16; i += blockDim.x) lm_tt[i] = __longlong_as_double((long long)lm_tanh_tab[i]);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int env = blockIdx.x;
+  const int H = P.H, max_len = P.max_len, L = S.L, K = S.K;
+  const int kind = wave == 0 ? LM_POLICY : wave == 1 ? LM_GREEDY : wave == 2 ? LM_LOW : LM_QUERY;
+  uint32_t err = 0u;
+  const double *emb, *w_h, *b_h, *w_d, *b_d;
+  lm_tables<TL>(P, env, lm_tab, err, emb, w_h, b_h, w_d, b_d);
+  for (int j = threadIdx.x; j < H; j += blockDim.x) lm_cache[0][j] = P.cache[(size_t)env * H + j];
+  __syncthreads();
+
+  double* hs = lm_hs[wave];
+  int32_t* data = S.data + (size_t)env * L;
+  int32_t* label = S.label + (size_t)env * L;
+  int32_t* query = P.query + (size_t)env * max_len;
+  const uint64_t tick0 = xv_launch_tick(P.tick, P.tick_dev);
+  const uint64_t gid = P.gid_base + (uint64_t)env;
+  const int per = S.datatype == LM_QARA ? 2 : 1;
+  const bool rewarded = S.datatype != LM_QA;
+  int nq = P.query_len[env];
+  if (nq < 0 || nq > max_len) { err |= XV_DEVERR_ACTION_RANGE; nq = nq < 0 ? 0 : max_len; }
+  int cur = 0, d0 = 0, l0 = 0, k = 0, round = 0;
+  int ad1 = 0, al1 = 0, n1 = 0;      // QARA: where answer 1 and its label went, and its length
+  double r1 = 0.0;
+  while (d0 < L && round < S.max_rounds) {
+    for (int sub = 0; sub < per; ++sub, ++k) {
+      const bool cached = per == 2 && sub == 0;
+      const int par = k & 1;
+      // data: q obs s a ACT ...;  label: obs s a LABEL ...;  QARA's second answer follows  s r a  behind the first
+      const int ad = sub == 0 ? d0 + nq + 3 : ad1 + n1 + 3;
+      const int al = sub == 0 ? l0 + nq + 2 : al1 + n1 + 4;
+      int ti = -1;
+      double temp = 1.0e-3;      // QA
+      if (rewarded && kind == LM_POLICY) {      // the policy wave alone needs it (and its first thread reports it)
+        if (S.t_index) {
+          ti = S.t_index[(size_t)env * K + k];
+          if ((unsigned)ti >= (unsigned)S.n_choice) { err |= XV_DEVERR_ACTION_RANGE; ti = 0; }
+        } else {
+          const xv_u32x4 w = xv_env_draw_sub(P.seed, gid, tick0 + 2 * (uint64_t)k, XV_DRAW_METALM, (uint32_t)LM_TEMP << 16);
+          ti = (int)(xv_u53(w.x, w.y) * (double)S.n_choice);
+          ti = ti < S.n_choice - 1 ? ti : S.n_choice - 1;
+        }
+        temp = S.t_choices[ti];
+      }
+      if (kind == LM_POLICY && !(temp > 0.0 && temp <= 1.0e300)) err |= XV_DEVERR_NONFINITE;
+      if (threadIdx.x == 0 && rewarded && S.t_index_out) S.t_index_out[(size_t)env * K + k] = ti;
+
+      for (int j = lane; j < H; j += 64) hs[j] = kind == LM_QUERY ? 0.0 : lm_cache[cur][j];
+      lm_wave_sync();
+      if (kind == LM_QUERY && sub == 0) {      // the head of the round, by the wave that will overwrite the query
+        for (int i = lane; i < nq; i += 64) {
+          const int t = query[i];
+          if (d0 + 1 + i < L) data[d0 + 1 + i] = t;
+          if (l0 + i < L) label[l0 + i] = t;
+        }
+        if (lane == 0) {
+          if (d0 < L) data[d0] = S.marks[LM_Q];
+          if (d0 + nq + 1 < L) data[d0 + nq + 1] = S.marks[LM_S];
+          if (d0 + nq + 2 < L) data[d0 + nq + 2] = S.marks[LM_A];
+          if (l0 + nq < L) label[l0 + nq] = S.marks[LM_S];
+          if (l0 + nq + 1 < L) label[l0 + nq + 1] = S.marks[LM_A];
+        }
+      }
+      LMPass A;
+      A.kind = kind;
+      A.skip = kind == LM_QUERY ? cached : kind != LM_POLICY && !rewarded;
+      A.n_ans = 0; A.ans = nullptr;
+      const double* u_in = S.u[wave];
+      A.u = u_in ? u_in + ((size_t)env * K + k) * (max_len + 1) : nullptr;
+      A.gid = gid;
+      A.tick = tick0 + 2 * (uint64_t)k + (kind == LM_POLICY ? 0 : 1);
+      A.temp0 = kind == LM_QUERY ? 10.0 : kind == LM_POLICY ? temp : 1.0;
+      A.temp1 = kind == LM_POLICY ? temp : 1.0;
+      A.dst = kind == LM_POLICY ? data : kind == LM_QUERY ? query : nullptr;
+      A.at = kind == LM_POLICY ? ad : 0;
+      A.dst2 = kind == LM_POLICY ? label : nullptr;
+      A.at2 = al;
+      A.cap = kind == LM_POLICY ? L : max_len;
+      A.fuse = rewarded && kind == LM_POLICY;
+      lm_pass<true>(P, emb, w_h, b_h, w_d, b_d, hs, lm_tt, lane, A, err);
+      if (kind == LM_QUERY && !cached) {
+        for (int i = A.n_out + lane; i < max_len; i += 64) query[i] = 0;
+        for (int j = lane; j < H; j += 64) lm_cache[cur ^ 1][j] = hs[j];
+      }
+      if (lane == 0) {
+        const double sum = kind == LM_POLICY ? A.ppl_sum2 : A.ppl_sum;      // wave 0 reports the label pass
+        lm_mean[par][wave] = A.n_step ? sum / (double)A.n_step : 0.0;
+        lm_len[par][wave] = A.n_out;
+      }
+      __syncthreads();
+      const int na = lm_len[par][0];
+      double r = 0.0;
+      if (rewarded) {
+        const double ppl = lm_mean[par][0], ppl_min = lm_mean[par][1], ppl_max = lm_mean[par][2];
+        r = (ppl_max - ppl_min) / fmax(ppl - ppl_min + 0.1, 1.0e-3) - 2.0;      // metalangv3.py:32
+        if (threadIdx.x == 0 && S.reward) S.reward[(size_t)env * K + k] = r;
+      }
+      if (cached) {      // QARA's first sub-step: the reward token waits for the second
+        ad1 = ad; al1 = al; n1 = na; r1 = r;
+        continue;
+      }
+      int dn, ln;      // the cursors behind this round
+      if (S.datatype == LM_QARA) {
+        const double deta = r1 - r;      // generator_v3.py:97-104, in its order
+        const int rt = deta > 0.20 ? S.marks[LM_RGT] : deta < 0.5 ? S.marks[LM_RLT] : S.marks[LM_REQ];
+        dn = ad + na + 1;
+        ln = al + na + 3;
+        if (threadIdx.x == 0) {
+          if (ad1 + n1 < L) data[ad1 + n1] = S.marks[LM_S];
+          if (ad1 + n1 + 1 < L) data[ad1 + n1 + 1] = rt;
+          if (ad1 + n1 + 2 < L) data[ad1 + n1 + 2] = S.marks[LM_A];
+          if (ad + na < L) data[ad + na] = S.marks[LM_S];
+          if (al1 + n1 + 1 < L) label[al1 + n1 + 1] = S.marks[LM_S];
+          if (al1 + n1 + 2 < L) label[al1 + n1 + 2] = rt;
+          if (al1 + n1 + 3 < L) label[al1 + n1 + 3] = S.marks[LM_A];
+          if (al + na + 1 < L) label[al + na + 1] = S.marks[LM_S];
+          if (al + na + 2 < L) label[al + na + 2] = S.marks[LM_Q];
+        }
+      } else if (S.datatype == LM_QAR) {
+        const int rt = S.marks[LM_R1 + (r < 0.0 ? 0 : r < 0.5 ? 1 : r < 1.0 ? 2 : r < 2.0 ? 3 : 4)];      // :52-62
+        dn = ad + na + 2;
+        ln = al + na + 4;
+        if (threadIdx.x == 0) {
+          if (ad + na < L) data[ad + na] = S.marks[LM_S];
+          if (ad + na + 1 < L) data[ad + na + 1] = rt;
+          if (al + na + 1 < L) label[al + na + 1] = S.marks[LM_S];
+          if (al + na + 2 < L) label[al + na + 2] = rt;
+          if (al + na + 3 < L) label[al + na + 3] = S.marks[LM_Q];
+        }
+      } else {
+        dn = ad + na + 1;
+        ln = al + na + 2;
+        if (threadIdx.x == 0) {
+          if (ad + na < L) data[ad + na] = S.marks[LM_S];
+          if (al + na < L) label[al + na] = S.marks[LM_S];
+          if (al + na + 1 < L) label[al + na + 1] = S.marks[LM_Q];
+        }
+      }
+      d0 = dn;
+      l0 = ln < L ? ln : L;      // the label stream runs ahead of the data stream: keep its cursor in range
+      nq = lm_len[par][3];
+      cur ^= 1;
+    }
+    ++round;
+  }
+  // what max_rounds left unfilled is 0; the state the last sub-step left goes back to the handle
+  const int df = d0 < L ? d0 : L;
+  for (int i = df + (int)threadIdx.x; i < L; i += blockDim.x) data[i] = 0;
+  for (int i = l0 + (int)threadIdx.x; i < L; i += blockDim.x) label[i] = 0;
+  for (int j = threadIdx.x; j < H; j += blockDim.x) P.cache[(size_t)env * H + j] = lm_cache[cur][j];
+  if (threadIdx.x == 0) {
+    P.query_len[env] = nq;
+    P.steps[env] += k;
+    S.filled[env] = df;
+    S.rounds[env] = round;
   }
   if (err) atomicOr(P.err, err);
 }
@@ -646,6 +640,46 @@ extern "C" int xv_metalm_step(xv_metalm* h, const int32_t* answer, const int32_t
   c.out_tok[3] = query; c.out_len[3] = query_len; c.out_stride[3] = h->a.max_len;
   c.reward = reward; c.ppl = ppl; c.steps_out = steps;
   return lm_launch(h, __func__, c);
+}
+
+extern "C" int xv_metalm_stream(xv_metalm* h, int datatype, int L, int max_rounds, const double* t_choices, int n_choice,
+                                const int32_t* t_index, const double* u_policy, const double* u_greedy, const double* u_low,
+                                const double* u_query, const int32_t* marks, int32_t* data, int32_t* label, int32_t* filled,
+                                int32_t* rounds, double* reward, int32_t* t_index_out) {
+  XV_CHECK_ARG(h != nullptr && marks != nullptr && data != nullptr && label != nullptr && filled != nullptr &&
+               rounds != nullptr);
+  XV_CHECK_ARG(datatype == XV_METALM_QA || datatype == XV_METALM_QAR || datatype == XV_METALM_QARA);
+  XV_CHECK_ARG(L >= 1 && L <= 0x3fffffff && max_rounds >= 1 && max_rounds <= 0x1fffffff);      // cursors and 2 K stay ints
+  XV_CHECK_ARG(datatype == XV_METALM_QA || (t_choices != nullptr && n_choice >= 1));
+  if (!h->task_set) {
+    xv_set_error("%s: no task set (xv_metalm_set_task)", __func__);
+    return XV_ERR_INVALID;
+  }
+  LMStream s = LMStream();
+  for (int i = 0; i < 11; ++i) {
+    XV_CHECK_ARG(marks[i] >= 0 && marks[i] < h->a.V);
+    s.marks[i] = marks[i];
+  }
+  s.datatype = datatype; s.L = L; s.max_rounds = max_rounds;
+  s.K = max_rounds * (datatype == XV_METALM_QARA ? 2 : 1);
+  s.n_choice = n_choice; s.t_choices = t_choices; s.t_index = t_index;
+  s.u[0] = u_policy; s.u[1] = u_greedy; s.u[2] = u_low; s.u[3] = u_query;
+  s.data = data; s.label = label; s.filled = filled; s.rounds = rounds; s.reward = reward; s.t_index_out = t_index_out;
+  xv_engine* e = h->eng;
+  XV_HIP(hipSetDevice(e->device));
+  LMArgs a = h->a;
+  const XvTickBind tb = xv_engine_bind_tick(e, 2 * (uint64_t)s.K);      // policy and step of every sub-step, used or not
+  a.tick = tb.tick;
+  a.tick_dev = tb.tick_dev;
+  a.seed = e->seed;
+  a.gid_base = e->env_id_base;
+  const dim3 grid((unsigned)a.N), block(256);
+  if (a.tab_n)
+    hipLaunchKernelGGL(metalm_stream_kernel<true>, grid, block, sizeof(double) * (size_t)a.tab_n, e->stream, a, s);
+  else
+    hipLaunchKernelGGL(metalm_stream_kernel<false>, grid, block, 0, e->stream, a, s);
+  XV_LAUNCH_CHECK();
+  return XV_OK;
 }
 
 static int lm_state_copy(xv_metalm* h, bool get, int32_t* query, int32_t* query_len, double* cache, int32_t* steps) {

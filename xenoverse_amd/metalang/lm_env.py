@@ -173,6 +173,73 @@ class MetaLMV3VecEnv(object):
                     low_len=low_len, steps=steps)
         return (query, query_len), reward, terminated, steps >= self.max_steps, info
 
+    # ---- the training streams ---------------------------------------------------------------------------------------
+    def stream(self, datatype, L, T_choices=None, t_index=None, max_rounds=None, draws=None):
+        """The reference's generate_data_v3_single_task_qa / _qar / _qara (generator_v3.py:48-173) for every env, in ONE
+        launch, from the env's current state (after reset(), or wherever the last call left it): rounds of policy + step
+        spliced into -> data, label int32 [num_envs, L], info.  datatype: "QA", "QAR" or "QARA"; the layouts and the
+        reference behaviours kept are in metalang/stream_host.py.  An env stops when its data row is full or after
+        max_rounds rounds (default ceil(L / the shortest round): always enough; fewer leave zeros behind info["filled"]).
+
+        K = max_rounds x (2 for QARA, else 1) sub-steps (one policy + step pair each).  T_choices float64 [n]
+        (default numpy.logspace(-1, 4, 20)); t_index int[num_envs, K]: the temperature of every sub-step as an index
+        into T_choices (default: drawn from Philox).  draws: dict of float64 [num_envs, K, max_len + 1] for u_policy,
+        u_greedy, u_low, u_query.  The call advances the tick by 2 K: sub-step k draws what policy() would at tick + 2 k
+        and what step() would at tick + 2 k + 1, however many sub-steps an env needs.
+
+        info: filled, rounds int32 [num_envs]; reward float64 and t_index int32 [num_envs, K] of the sub-steps that ran
+        (0 and -1 elsewhere, and for QA, which forms no reward and answers at T = 1e-3)."""
+        import torch
+        from .stream_host import DATATYPES, SHORTEST_ROUND, default_T_choices, marks_of
+        self._live()
+        if datatype not in DATATYPES:
+            raise ValueError("datatype must be one of QAR, QA, QARA")
+        if int(L) != L or int(L) < 1:
+            raise ValueError("L must be an integer of at least 1")
+        L = int(L)
+        if max_rounds is None:
+            max_rounds = -(-L // SHORTEST_ROUND[datatype])
+        if int(max_rounds) != max_rounds or int(max_rounds) < 1:
+            raise ValueError("max_rounds must be an integer of at least 1")
+        max_rounds = int(max_rounds)
+        K = max_rounds * (2 if datatype == "QARA" else 1)
+        choices = torch.as_tensor(default_T_choices() if T_choices is None else np.asarray(T_choices, np.float64),
+                                  dtype=torch.float64).to(self.device).contiguous()
+        if choices.dim() != 1 or choices.numel() < 1 or not bool(((choices > 0) & torch.isfinite(choices)).all()):
+            raise ValueError("T_choices must be a non-empty 1-D array of positive finite temperatures")
+        n_choice = int(choices.numel())
+        ti = None
+        if t_index is not None:
+            if torch.is_tensor(t_index) and t_index.is_floating_point() or (
+                    not torch.is_tensor(t_index) and np.asarray(t_index).dtype.kind not in "iu"):
+                raise ValueError("t_index must be an integer array")
+            ti = torch.as_tensor(t_index).to(self.device, torch.int32).contiguous()
+            if tuple(ti.shape) != (self.num_envs, K):
+                raise ValueError("t_index must have shape %s, got %s" % ((self.num_envs, K), tuple(ti.shape)))
+            if datatype != "QA" and (int(ti.min()) < 0 or int(ti.max()) >= n_choice):
+                raise ValueError("t_index must hold indices into the %d T_choices" % n_choice)
+        us = []
+        for key in ("u_policy", "u_greedy", "u_low", "u_query"):
+            u = None
+            if draws is not None and draws.get(key) is not None:
+                u = torch.as_tensor(draws[key], dtype=torch.float64).to(self.device).contiguous()
+                if tuple(u.shape) != (self.num_envs, K, self.max_len + 1):
+                    raise ValueError("draws[%r] must have shape %s, got %s" % (key, (self.num_envs, K, self.max_len + 1),
+                                                                               tuple(u.shape)))
+            us.append(u)
+        marks = (C.c_int32 * 11)(*marks_of())
+        data = torch.empty((self.num_envs, L), dtype=torch.int32, device=self.device)
+        label = torch.empty((self.num_envs, L), dtype=torch.int32, device=self.device)
+        filled = torch.empty(self.num_envs, dtype=torch.int32, device=self.device)
+        rounds = torch.empty(self.num_envs, dtype=torch.int32, device=self.device)
+        reward = torch.zeros((self.num_envs, K), dtype=torch.float64, device=self.device)
+        t_used = torch.full((self.num_envs, K), -1, dtype=torch.int32, device=self.device)
+        code = DATATYPES.index(datatype)      # XV_METALM_QA, _QAR, _QARA
+        _lib.check(self.lib.xv_metalm_stream(self._h, code, L, max_rounds, _lib.ptr(choices), n_choice, _lib.ptr(ti),
+                                             *(_lib.ptr(u) for u in us), marks, _lib.ptr(data), _lib.ptr(label),
+                                             _lib.ptr(filled), _lib.ptr(rounds), _lib.ptr(reward), _lib.ptr(t_used)))
+        return data, label, dict(filled=filled, rounds=rounds, reward=reward, t_index=t_used)
+
     # ---- state ------------------------------------------------------------------------------------------------------
     def get_state(self):
         """what a later set_state needs to go on as if nothing had happened: the queries, the cached hidden states, the
