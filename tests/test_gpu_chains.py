@@ -152,6 +152,45 @@ def test_k_chains_with_plain_launches(how):
     _same(ref, got)
 
 
+def test_chain_graph_is_rebuilt_on_other_rings_and_reused_on_the_same_ones():
+    """how = graph: the parent's K-branch graph names the rings it was built on.  Call A on ring 1, B on fresh rings (the graph
+    is rebuilt), C on ring 1 again (rebuilt once more), D on ring 1 (reused) — every ring after every call, the env records
+    and the tick equal one chain's, and the calls of whole cycles replay a graph (state 1)"""
+    tab = oracle.anymdp_synth(seed=12, task_index_base=0, n_task=16, S=64, A=8, s0_max=4)
+    n, P = 1024, 8
+    acts_np = np.random.RandomState(5).randint(0, 8, (P, n)).astype(np.int32)
+
+    def run(chains, how):
+        env = AnyMDPVecEnv(n, seed=77, autoreset_mode="same_step", bucket_lines="off")
+        env.set_task(_dev_tables(tab))
+        env.set_search("fence")
+        env.set_step_many_graph(True)
+        env.reset()
+        acts = torch.as_tensor(acts_np, device=env.device)
+        rec, rings, states = [], [], []
+        for n_steps, ring in ((3 * P + 5, None), (2 * P, None), (2 * P, 0), (P, 0)):
+            r = env.step_many(n_steps, acts, out=None if ring is None else rings[ring], chains=chains, how=how)
+            if ring is None:
+                rings.append(r)
+            else:
+                assert r is rings[ring]
+            torch.cuda.synchronize()
+            states.append(int(env.lib.xv_anymdp_step_many_graph_state(env._h)))
+            for q in rings:      # every ring after every call
+                rec.append({k: _np(v).copy() for k, v in q.items()})
+        s, st, nr = env.get_state()
+        rec.append({"state": _np(s), "steps": _np(st), "need_reset": _np(nr), "tick": np.asarray(env.engine.tick)})
+        assert env.check_errors() == 0
+        env.close()
+        return rec, states
+
+    ref, _ = run(1, "streams")
+    got, states = run(4, "graph")
+    _same(ref, got)
+    assert states[2] == 1 and states[3] == 1, states
+    assert ref[0]["terminated"].sum() > 0 and not np.array_equal(ref[1]["obs"], ref[2]["obs"])      # episodes end; B wrote rings of its own
+
+
 @pytest.mark.parametrize("search", ["bucket", "fence"])
 @pytest.mark.parametrize("how,chains", [("streams", 2), ("streams", 4), ("streams", 8), ("graph", 4)])
 def test_k_chains_equal_one_chain_at_65536_envs(search, how, chains):
@@ -328,6 +367,47 @@ def test_overlapped_token_steps_equal_plain_launches(kind):
         env.close()
     _same(res[0], res[1])
     assert res[0][0]["obs"].std() > 0 and (res[0][0]["terminated"].sum() + res[0][0]["truncated"].sum() + res[0][1]["reward"].std()) > 0
+
+
+@pytest.mark.parametrize("kind", ["pomdp", "mtpomdp"])
+def test_overlapped_token_graphs_are_reused_on_the_same_rings(kind):
+    """xv_anymdp_step_tokens_many with the overlap on: call 2 names the actions and rings of call 1 (the cycle graphs are
+    reused), call 3 other ones (rebuilt), call 4 the first ones again — every ring after every call, the env records and the
+    tick equal the plain launches', and every call is overlapped (state 1)"""
+    from util import golden_files, load_anymdp_tok_golden
+    tasks = [load_anymdp_tok_golden(p)[1] for p in golden_files("anymdptok_") if ("mtpomdp" in p) == (kind == "mtpomdp")]
+    n, P = 1536, 8
+    env_task = (np.arange(n) % len(tasks)).astype(np.int32)
+    res = []
+    for overlap in (False, True):
+        env = AnyMDPVecEnv(n, seed=13, autoreset_mode="same_step")
+        env.set_task(tasks, env_task_index=env_task)
+        env.set_search("bucket", n_bucket=16)
+        assert env.token_kernel == "cooperative"
+        env.set_step_many_overlap(overlap)
+        env.reset()
+        d_act = env._tok[1]
+        rng = np.random.RandomState(3)
+        acts = [torch.as_tensor(rng.randint(0, int(env.na), (P, n, d_act)).astype(np.int32), device=env.device) for _ in range(2)]
+        rec, rings = [], []
+        for n_steps, a, ring in ((72, 0, None), (64, 0, 0), (80, 1, None), (64, 0, 0)):
+            out = env.step_tokens_many(n_steps, acts[a], out=None if ring is None else rings[ring])
+            if ring is None:
+                rings.append(out)
+            else:
+                assert out is rings[ring]
+            torch.cuda.synchronize()
+            for q in rings:      # every ring after every call
+                rec.append({k: _np(v).copy() for k, v in q.items()})
+            if overlap:
+                assert env.step_many_overlap_state == 1
+        s, st, nr = env.get_state()
+        rec.append({"state": _np(s), "steps": _np(st), "nr": _np(nr), "tick": np.asarray(env.engine.tick)})
+        assert env.check_errors() == 0
+        res.append(rec)
+        env.close()
+    _same(res[0], res[1])
+    assert res[0][0]["obs"].std() > 0 and not np.array_equal(res[0][2]["obs"], res[0][3]["obs"])
 
 
 def test_one_overlapped_handle_per_device_and_never_a_view():
