@@ -934,6 +934,48 @@ int xv_metalang_generate(xv_metalang* h, int L, const double* u, int32_t* tokens
 int xv_metalang_log_prob(xv_metalang* h, int L, const int32_t* tokens, double* logp);
 
 /* ------------------------------------------------------------------------------------------------
+ * MetaLangV1 — reference: xenoverse/metalang/metalangv1.py (add_noise :39-50, data_generator :57-74), tasks from
+ * metalang/task_sampler.py TaskSamplerV1 :52-73: the pattern-recovery (denoising) generator.  A handle holds n_seq sequences,
+ * each under its own task; one launch generates them all.  A sequence is a stream of positions q = 0 .. L: segment k is
+ * pattern p_k followed by one separator (token 0), segments are drawn while their start is < L + 1 (:63); features[q] =
+ * the stream's token corrupted, q < L; labels[q - 1] = the clean token, q >= 1 (:74).  Corruption of a non-separator
+ * position (:43-49): noise_value where u_noise < error_ratio, 0 instead where additionally u_mask < mask_ratio; both
+ * comparisons strict, in fp64.  Integer work and two comparisons: the device equals the reference bit for bit.  New symbols
+ * only: no ABI bump.
+ *   set_task :52-55   -> xv_metalang1_set_task: ragged tables in CSR form.  task_pattern_start int32[n_task + 1]: task t owns
+ *                        patterns [task_pattern_start[t], task_pattern_start[t + 1]) of pattern_start int32[n_pattern_total
+ *                        + 1]; pattern p is pattern_tokens[pattern_start[p] .. pattern_start[p + 1]) (int32[n_token_total]);
+ *                        n_vocab int32[n_task], error_ratio float64[n_task], seq_task int32[n_seq].  Device pointers,
+ *                        borrowed until the next set_task / destroy.
+ *   data_generator    -> xv_metalang1_generate: features, labels int32[n_seq][L]; kinds uint8[n_seq][L], nullable: per
+ *   :57-74               feature position 0 clean, 1 replaced (also where the replacement equals the original), 2 masked,
+ *                        3 separator; n_segments int32[n_seq], nullable: the segments drawn.  The call advances the tick by one.
+ * Draws.  Injected (all four arrays or none): pattern_index int32[n_seq][n_slot] by segment, noise_value int32[n_seq][L + 1],
+ * u_noise, u_mask float64[n_seq][L + 1] by stream position; entries at separator positions are ignored.  Otherwise Philox
+ * through the counter layout of csrc/philox.h xv_env_draw_sub — counter = {id lo, id hi, tick lo, purpose | tick hi << 8},
+ * key = {seed lo, seed hi ^ (0x80000000 | sub)}, id = env_id_base + sequence — with
+ *   purpose 10, sub = k >> 2, word k & 3 = w: pattern index of segment k = (uint64(w) * n_patterns) >> 32
+ *   purpose 11, sub = q >> 2, word q & 3 = w: noise_value of position q = (uint64(w) * n_vocab) >> 32
+ *   purpose 12, sub = q >> 1, words 0,1 (q even) or 2,3 (q odd) = a, b: u_noise = ((a >> 5) * 2^26 + (b >> 6)) / 2^53
+ *   purpose 13, sub = q >> 1, likewise: u_mask
+ * A draw does not depend on the launch geometry or on how sequences are split over handles.  An integer in [0, n) from one
+ * 32-bit word: a value's probability is off by at most n / 2^32 relative (2.3e-5 at n = 100,000; one half at n = 2^31).
+ * Limits (XV_ERR_UNSUPPORTED beyond, the text names the limit): 1 <= L <= 16,777,216 (2^24: stream positions and segment
+ * starts are int32 sums of 64 lengths at a time).  Pattern lengths >= 1, n_patterns >= 1, n_vocab up to 2^31 - 1 and any
+ * number of segments are supported; the tables' sizes are int32.  No read leaves a table: an injected pattern index outside
+ * [0, n_patterns), a noise value outside [0, n_vocab), a task index or a table entry out of range is clamped, a sequence that
+ * needs more than n_slot injected slots repeats pattern 0 — each sets XV_DEVERR_ACTION_RANGE. */
+typedef struct xv_metalang1 xv_metalang1;
+int xv_metalang1_create(xv_engine* e, int n_seq, xv_metalang1** out);
+int xv_metalang1_destroy(xv_metalang1* h);
+int xv_metalang1_set_task(xv_metalang1* h, int n_task, int n_pattern_total, int n_token_total,
+                          const int32_t* task_pattern_start, const int32_t* pattern_start, const int32_t* pattern_tokens,
+                          const int32_t* n_vocab, const double* error_ratio, const int32_t* seq_task);
+int xv_metalang1_generate(xv_metalang1* h, int L, double mask_ratio, const int32_t* pattern_index, int n_slot,
+                          const int32_t* noise_value, const double* u_noise, const double* u_mask, int32_t* features,
+                          int32_t* labels, uint8_t* kinds, int32_t* n_segments);
+
+/* ------------------------------------------------------------------------------------------------
  * MetaLMV3 — reference: xenoverse/metalang/metalangv3.py (MetaLMV3Env :4-42) over xenoverse/utils/random_nn.py RandomLM
  * :218-344 and its decoders softmax_sampling :193-198, rnd_sampling :200-206, high_sampling :208-216; tasks from
  * metalang/task_sampler.py TaskSamplerV3 :86-98.  A handle holds n_env envs; an env is one task index, the current query

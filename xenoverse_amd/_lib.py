@@ -136,6 +136,10 @@ SIGNATURES = {
     "xv_metalang_set_task": [c_void_p, c_int] + [c_void_p] * 8,
     "xv_metalang_generate": [c_void_p, c_int, c_void_p, c_void_p, c_void_p],
     "xv_metalang_log_prob": [c_void_p, c_int, c_void_p, c_void_p],
+    "xv_metalang1_create": [c_void_p, c_int, C.POINTER(c_void_p)],
+    "xv_metalang1_destroy": [c_void_p],
+    "xv_metalang1_set_task": [c_void_p, c_int, c_int, c_int] + [c_void_p] * 6,
+    "xv_metalang1_generate": [c_void_p, c_int, C.c_double, c_void_p, c_int] + [c_void_p] * 7,
     "xv_metalm_create": [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, C.POINTER(c_void_p)],
     "xv_metalm_destroy": [c_void_p],
     "xv_metalm_set_task": [c_void_p, c_int] + [c_void_p] * 6,

@@ -1,8 +1,9 @@
-"""MetaLangV2 tasks: the reference's TaskSamplerV2 (xenoverse/metalang/task_sampler.py:22-50), bit for bit.
+"""MetaLang tasks: the reference's TaskSamplerV2 and TaskSamplerV1 (xenoverse/metalang/task_sampler.py:22-50, :52-73), bit for
+bit.
 
 The reference seeds numpy's process-global legacy generator and draws, in this order, the n-gram choice (only when n_gram is
-a list) and five normal arrays.  Here the same stream comes from a private RandomState(seed): equal numbers, and the
-caller's global generator is left alone."""
+a list) and five normal arrays (V2), or per pattern a Poisson length and its int32 tokens (V1).  Here the same stream comes
+from a private RandomState(seed): equal numbers, and the caller's global generator is left alone."""
 import os
 
 import numpy as np
@@ -32,6 +33,20 @@ def TaskSamplerV2(seed=None, n_emb=16, n_hidden=64, n_vocab=256, n_gram=3, _lamb
         "n_vocab": n_vocab,
         "n_gram": n_gram,
     }
+
+
+def TaskSamplerV1(seed=None, n_vocab=64, n_patterns=10, n_gram=64, error_ratio=0.1):
+    """n_patterns patterns of max(3, Poisson(n_gram)) tokens in [0, n_vocab) (token 0, the separator's id, included)"""
+    if seed is None:
+        seed = int.from_bytes(os.urandom(4), "little")
+    rs = np.random.RandomState(seed)
+    if isinstance(n_gram, list):
+        n_gram = rs.choice(n_gram)
+    patterns = []
+    for _ in range(n_patterns):
+        l_r = max(3, rs.poisson(n_gram))
+        patterns.append(rs.randint(0, n_vocab, size=(l_r), dtype="int32"))
+    return {"patterns": patterns, "n_vocab": n_vocab, "n_patterns": n_patterns, "error_ratio": error_ratio, "n_gram": n_gram}
 
 
 def check_limit(name, value):
