@@ -666,6 +666,74 @@ int xv_linds_mpc_solve(xv_linds_mpc* m, const float* x, const float* ref, float*
 int xv_linds_rollout_mpc(xv_linds_mpc* m, int T, float* action, float* obs, float* reward, uint8_t* terminated,
                          uint8_t* truncated, float* cmd, float* error, float* final_obs, int32_t* status, int32_t* iters);
 
+/* LinDS task sampler on the device (additions within ABI 12; csrc/linds_sampler.hip) — reference:
+ * xenoverse/linds/task_sampler.py sample_variants_ :12-58, LinearDSSampler :60-132 (start-state rejection loop :107-132),
+ * LinearDSSamplerRandomDim :134-154, RandomFourier utils/random_nn.py:346-368.  One launch over candidates
+ * [cand_base, cand_base + n_cand), one workgroup per candidate: the head (matrices, scales, trim, reward scalars,
+ * target_valid, target_type), then start attempts a = 0, 1, ... (born_loc, initial states, noise_drift, command) in chunks;
+ * the LOWEST passing attempt below max_draws wins, else the candidate is `exhausted`.  Accepted candidates are discretised
+ * (zero-order hold, below) and written into the table slots xv_linds_create consumes.
+ *
+ * Randomness: Philox4x32-10, key = seed, counter = {candidate lo, candidate hi, stream, draw}; stream 0 is the head, stream
+ * 1 + a is start attempt a.  One call gives two uniforms (words 0,1 and words 2,3, 53 bits each as numpy's random_sample) or
+ * one fp64 Box-Muller pair (r = sqrt(-2 log(1 - u_first)), angle 2 pi u_second; members cos, sin).  Element n of a block of
+ * normals is member n & 1 of call base + (n >> 1); element q of a block of uniforms is half q & 1 of call base + (q >> 1).
+ * Exponentials are -log(1 - u) * scale, integers floor(u * n).
+ *   head draws:    0 (ns, na) and 1.first (no) with random dims; 1.second max_steps; 2 (A scale, X scale); 3 (trim, width);
+ *                  4 (action_cost uniform, exponential); 5 (reward_base, terminate_punish); 6 (punish gate {0,1,1},
+ *                  reward_factor); 7 (target_valid's eps, target_type); blocks 0x1000 AB row-major [ns][ns + na] normals,
+ *                  0x2000 X normals, 0x3000 C row-major [no][ns] normals, 0x10000 + 16 r target_valid uniforms of redraw r.
+ *   attempt draws: 0 (born_loc exponential, noise_drift); 1 (static gate {0,1} | Fourier n_items, delay); 2 + k integer part
+ *                  and 8 + k normal part of Fourier order k = 1..5; block 16 static command normals; 64 + 64 k normals and
+ *                  64 + 64 k + 32 exponentials of Fourier term k's [no][2] coefficients; block 1024 + 16 i initial state i.
+ * A candidate is a pure function of (seed, the dims arguments, candidate index): independent of n_cand, cand_base splits,
+ * chunk size and launch geometry.  Departures from the reference, all documented in DESIGN.md: no rank test on B and C
+ * (untrimmed Gaussian matrices), an attempt with born_loc > NI fails, `exhausted` instead of an unbounded loop.
+ *
+ * random_dim = 0: (ns, na, no) are the task's dims.  random_dim != 0: they are LinearDSSamplerRandomDim's maxima
+ * (max_state_dim, max_action_dim, max_observation_dim); the pads must cover every dim it can draw.
+ * Pads: ns <= NS <= 32, na <= NA <= 16, no <= NO <= 32, 1 <= NI <= 64; 1 <= max_draws <= 2^30.
+ * `tables`: [n_cand]-leading slots of xv_linds_tables (WRITTEN here, for accepted candidates only; the caller zero-fills
+ * them: padding is not touched) — layout, padding and rounding of linds.tables.build_tables; nullable.  `dense`: fp64
+ * values, nullable (needs `tables`); the head arrays A, B, C, X, Y are written for every candidate.
+ * status int32[n_cand]: 0 accepted, 1 exhausted, 2 discretisation failed (non-finite or scale cap; tables zero). */
+typedef struct xv_linds_dense {
+  double* A;          /* [n_cand][NS][NS] */
+  double* B;          /* [n_cand][NS][NA] */
+  double* C;          /* [n_cand][NO][NS] */
+  double* X;          /* [n_cand][NS] */
+  double* Y;          /* [n_cand][NO] */
+  double* init;       /* [n_cand][NI][NS] */
+  double* phi;        /* [n_cand][NS][NS] */
+  double* gam;        /* [n_cand][NS][NA] */
+  double* four_order; /* [n_cand][KMAX] */
+  double* four_coef;  /* [n_cand][KMAX][NO][2] */
+  double* cmd0;       /* [n_cand][NO] */
+} xv_linds_dense;
+typedef struct xv_linds_cand_info {
+  int32_t status, attempt;          /* attempt: the accepted attempt index, -1 when exhausted */
+  int32_t ns, na, no;
+  int32_t a_scale, x_scale;         /* indices into {.01,.02,.05,.1,.2} and {0,.05,.1} */
+  int32_t trim, width;              /* 0 banded, 1 triangular, 2 none */
+  int32_t max_steps, n_init, n_terms, delay;
+  int32_t type;                     /* 1 dynamic_target, 0 static_target */
+  int32_t valid_rounds, zoh_s;      /* draws of target_valid; halvings of the discretisation */
+  int8_t target_valid[32];
+  double action_cost, reward_base, terminate_punish, reward_factor, noise_drift, eps;
+} xv_linds_cand_info;
+int xv_linds_sample_tasks(xv_engine* e, uint64_t seed, int64_t cand_base, int n_cand, int random_dim, int ns, int na, int no,
+                          int NS, int NA, int NO, int NI, double dt, int64_t max_draws, const xv_linds_tables* tables,
+                          const xv_linds_dense* dense, xv_linds_cand_info* info, int32_t* status);
+/* Zero-order hold alone, for tasks from anywhere: A double[n_task][NS][NS], B double[n_task][NS][NA], X double[n_task][NS]
+ * (zero-padded beyond ns[t]) -> phiT float[n_task][NS][NS], gamT float[n_task][NA][NS], xt float[n_task][NS] as in
+ * xv_linds_tables; phi double[n_task][NS][NS] / gam double[n_task][NS][NA] nullable.  One workgroup per task, matrices in
+ * LDS, fp64: with M = A h, h = dt / 2^s the smallest halving with |M|_inf <= 0.25, S(h) = sum_{k<18} A^k h^{k+1} / (k+1)!
+ * by Horner, Phi = I + A S, Gamma = S B, and s doublings S <- S + Phi S, Phi <- Phi Phi.  Every sum runs in a fixed order.
+ * status int32[n_task]: 0 ok, 1 non-finite input or result, 2 s above the cap of 40; a failed task's tables are zero. */
+int xv_linds_build_zoh(xv_engine* e, int n_task, const int32_t* ns, int NS, int NA, const double* A, const double* B,
+                       const double* X, double dt, float* phiT, float* gamT, float* xt, double* phi, double* gam,
+                       int32_t* status);
+
 /* ------------------------------------------------------------------------------------------------
  * CartPole — reference: xenoverse/metacontrol/random_cartpole.py (set_task :46-50, step :52-61, reset
  * :63-75).  The physics is gymnasium's CartPoleEnv.step (third-party dependency, `gymnasium>=1.0.0` in the

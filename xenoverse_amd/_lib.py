@@ -115,6 +115,8 @@ SIGNATURES = {
     "xv_linds_mpc_action": [c_void_p] * 5,
     "xv_linds_mpc_solve": [c_void_p] + [c_void_p] * 5,
     "xv_linds_rollout_mpc": [c_void_p, c_int] + [c_void_p] * 10,
+    "xv_linds_sample_tasks": [c_void_p, c_u64, c_i64] + [c_int] * 9 + [C.c_double, c_i64] + [c_void_p] * 4,
+    "xv_linds_build_zoh": [c_void_p, c_int, c_void_p, c_int, c_int] + [c_void_p] * 3 + [C.c_double] + [c_void_p] * 6,
     "xv_maze_create": [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, C.c_double, C.c_double,
                        c_void_p, c_void_p, C.POINTER(c_void_p)],
     "xv_maze_destroy": [c_void_p],
