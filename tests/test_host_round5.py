@@ -1,5 +1,6 @@
 """Host-side pieces added in round 5 (no GPU): output slabs, the device table builder's eligibility rule, the rendezvous
 store selection of the RCCL communicator, the mixed workload's fabricated records."""
+import ctypes as C
 import os
 import sys
 
@@ -7,7 +8,7 @@ import numpy as np
 import torch
 
 from xenoverse_amd.anymdp.tables import device_buildable
-from xenoverse_amd.vector import OutputSlabs
+from xenoverse_amd.vector import OutputSlabs, StepOutputs
 
 
 def test_output_slabs_hand_out_disjoint_tensors_with_matching_pointers():
@@ -76,6 +77,102 @@ def test_output_slabs_are_recycled_only_when_nobody_can_reach_them():
     for _ in range(64):
         sl.next()
     assert sl.made == made                       # once the holders are gone their slabs serve again: nothing new is allocated
+
+
+_FIELDS = [("obs", torch.float32, (4,)), ("fobs", torch.float32, (4,)), ("final", torch.int32, (), -1), ("reward", torch.float32, ()),
+           ("term", torch.uint8, ()), ("done", torch.uint8, ())]
+_ORDER = ("obs", "reward", "term", "fobs", "final", "done")
+
+
+def _step_outputs(**kw):
+    return StepOutputs(_FIELDS, 5, "cpu", _ORDER, as_bool=("term", "done"), zero_on_refill=("fobs",),
+                       derived={"obs_u": ("obs", lambda t: t[:, :3]), "first": ("fobs", lambda t: t[:, 0])}, **kw)
+
+
+def _check_set(s):
+    """pointers by name, in the C call's order, and views: all of one set agree"""
+    names = [f[0] for f in _FIELDS]
+    for k in names:
+        assert s.ptr[k] == s.t[k].data_ptr(), k
+    assert s.ints == tuple(s.ptr[k] for k in _ORDER)
+    assert tuple(p.value for p in s.args) == s.ints
+    assert s.t["term"].dtype == torch.bool and s.t["done"].dtype == torch.bool and s.t["reward"].dtype == torch.float32
+    assert s.t["obs"].shape == (5, 4) and s.t["obs_u"].shape == (5, 3) and s.t["first"].shape == (5,)
+    s.t["obs"].fill_(3.0); s.t["fobs"].fill_(4.0)
+    assert s.t["obs_u"].data_ptr() == s.ptr["obs"] and float(s.t["obs_u"][4, 2]) == 3.0      # derived views alias their field
+    assert s.t["first"].data_ptr() == s.ptr["fobs"] and float(s.t["first"][4]) == 4.0
+    raw = torch.frombuffer((C.c_uint8 * 5).from_address(s.ptr["term"]), dtype=torch.uint8)
+    s.t["term"].fill_(True)
+    assert raw.tolist() == [1] * 5                                                           # a bool view aliases its bytes
+
+
+def test_persistent_output_sets_alternate_hold_and_start_filled():
+    so = _step_outputs(copy=False, n_sets=2)
+    assert so.persistent
+    a, b = so.next(), so.next()
+    assert a is not b
+    for s in (a, b):                                  # a fresh set: zeros, and the fill value where one is declared
+        assert int(s.t["final"].min()) == -1 == int(s.t["final"].max())
+        assert float(s.t["obs"].abs().max()) == 0.0 and float(s.t["fobs"].abs().max()) == 0.0 and not bool(s.t["done"].any())
+        _check_set(s)
+    seq = [so.next() for _ in range(6)]
+    assert [x is a for x in seq] == [True, False] * 3 and all(x is a or x is b for x in seq)
+    for k in [f[0] for f in _FIELDS]:                  # every field's memory repeats with period 2
+        p = [x.t[k].data_ptr() for x in seq]
+        assert p[0] != p[1] and p == p[:2] * 3, k
+    so.hold(True)
+    held = [so.next() for _ in range(5)]
+    assert all(x is held[0] for x in held) and held[0] is a          # the set that was next stays
+    so.hold(False)
+    seq = [so.next() for _ in range(4)]
+    assert seq[0] is a and seq[1] is b and seq[2] is a and seq[3] is b
+    a.t["fobs"].fill_(7.0)                            # copy=False: a zero_on_refill field keeps what the caller (a step) left there
+    assert [so.next() is a for _ in range(3)] == [True, False, True] and float(a.t["fobs"].min()) == 7.0
+
+
+def test_one_persistent_output_set_is_the_same_objects_every_time():
+    so = _step_outputs(copy=False)
+    s = so.next()
+    t = dict(s.t)
+    _check_set(s)
+    for _ in range(5):
+        s2 = so.next()
+        assert s2 is s and all(s2.t[k] is v for k, v in t.items())
+    so.hold(True)
+    assert so.next() is s
+    so.hold(False)
+    assert so.next() is s
+
+
+def test_to_numpy_output_set_zeroes_partly_written_fields_before_every_step():
+    so = _step_outputs(copy=True, to_numpy=True, n_sets=2)      # to_numpy: one set whatever copy and n_sets say
+    assert so.persistent
+    s = so.next()
+    _check_set(s)
+    for k in range(4):
+        s2 = so.next()
+        assert s2 is s
+        assert float(s.t["fobs"].abs().max()) == 0.0 and float(s.t["first"].abs().max()) == 0.0
+        assert float(s.t["obs"].min()) == 3.0                        # (only the declared fields are cleared)
+        s.t["fobs"].fill_(k + 1.0)                                   # what a step would leave behind
+
+
+def test_copy_true_output_sets_come_from_slabs():
+    so = _step_outputs(copy=True, K=4)
+    assert not so.persistent
+    seen, kept = set(), []
+    for step in range(11):                            # three slabs
+        s = so.next()
+        assert float(s.t["fobs"].abs().max()) == 0.0                 # zeroed once per slab, before any of its sets is handed out
+        _check_set(s)
+        assert s.ptr["obs"] not in seen
+        seen.add(s.ptr["obs"])
+        s.t["obs"].fill_(step)
+        kept.append(s.t["obs"])
+    so.hold(True)                                     # nothing to pin: every step still gets memory of its own
+    assert so.next().ptr["obs"] not in seen
+    for step, t in enumerate(kept):
+        assert float(t[4, 3]) == step
 
 
 def test_device_buildable_rule():

@@ -271,6 +271,25 @@ def fn_address(name):
     return C.cast(getattr(load(), name), C.c_void_p).value
 
 
+_step_fns = {}      # name -> (_xvfast.icall or None, address, ctypes function)
+
+
+def step_call(name, h, action, outputs, mode):
+    """THE hot call of every family: `name`(h, action, *outputs' pointers in the C call's order, mode) — through the
+    trampoline when it is built, through ctypes otherwise.  outputs: a vector.OutputSet."""
+    e = _step_fns.get(name)
+    if e is None:
+        f = fast()
+        e = _step_fns[name] = (f.icall if f is not None else None, fn_address(name), getattr(load(), name))
+    icall, address, fn = e
+    if icall is not None:
+        rc = icall(address, h.value, action.data_ptr(), *outputs.ints, mode)
+    else:
+        rc = fn(h, C.c_void_p(action.data_ptr()), *outputs.args, mode)
+    if rc:
+        check(rc)
+
+
 def check(rc):
     if rc != 0:
         msg = load().xv_last_error()

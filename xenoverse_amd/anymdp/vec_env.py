@@ -13,7 +13,7 @@ import torch
 from .. import _lib
 from ..engine import AUTORESET
 from ..spaces import Discrete, MultiDiscrete
-from ..vector import OutputSlabs, VectorEnv
+from ..vector import StepOutputs, VectorEnv
 from .tables import build_obs_tables, build_tables, build_tables_device, device_buildable
 
 _TABLE_KEYS = ("rows", "state_map", "term_mask", "s0_cdf", "s0_ids", "max_steps")
@@ -35,8 +35,8 @@ class AnyMDPVecEnv(VectorEnv):
         overridden by each task's own `max_steps` at set_task (anymdp_env.py:23-34).
 
         copy (as gymnasium's SyncVectorEnv(copy=...)): True returns fresh tensors from every step().  False returns
-        views of two engine-owned output sets used alternately — what step() returned stays valid until the step
-        after the next one — and takes the per-step host cost from ~50 us (clones, bool conversions) to a launch, a
+        views of engine-owned output sets (MDP tasks: two, used alternately — what step() returned stays valid until the
+        step after the next one; vector.StepOutputs) — and takes the per-step host cost from ~50 us (clones, bool conversions) to a launch, a
         16-KB copy and one fused op (`scripts/bench_python_step.py`).
 
         bucket_lines: "auto" (default) — at set_task the engine takes the census of 16 bucket lines per row and builds them
@@ -50,8 +50,6 @@ class AnyMDPVecEnv(VectorEnv):
         self.copy = bool(copy)
         self.bucket_lines = bucket_lines
         self.device_tables = bool(device_tables)      # set_task forms the row records of raw task dicts on the device
-        self._ring = None
-        self._tok_cache = None
         self._set_spaces(Discrete(1), Discrete(1))   # placeholders until set_task, as in the reference
         self._h = None
         self._many_cache = None
@@ -170,8 +168,15 @@ class AnyMDPVecEnv(VectorEnv):
                     if ex.code != _lib.XV_ERR_UNSUPPORTED:
                         raise
 
+    _STEP_ORDER = ("obs", "reward", "reward_gt", "term", "trunc", "final_obs", "steps", "done")      # xv_anymdp_step*_info
+
+    def _fields(self, tail):
+        i32, f32, u8 = torch.int32, torch.float32, torch.uint8
+        return [("obs", i32, tail), ("final_obs", i32, tail, -1), ("steps", i32, ()), ("reward", f32, ()), ("reward_gt", f32, ()),
+                ("term", u8, ()), ("trunc", u8, ()), ("done", u8, ())]
+
     def _make_buffers(self):
-        """spaces for the task type and the output buffers step() / reset() write (set_task, and a view made by split())"""
+        """spaces for the task type and the buffers reset() writes (set_task, and a view made by split())"""
         n, d, S, A = self.num_envs, self.device, self.S, self.A
         if self._tok is not None:
             d_obs, d_act = self._tok
@@ -180,34 +185,18 @@ class AnyMDPVecEnv(VectorEnv):
             else:
                 self._set_spaces(Discrete(self.no), Discrete(A))
             self._tobs = torch.zeros((n, d_obs), dtype=torch.int32, device=d)
-            self._tfobs = torch.full((n, d_obs), -1, dtype=torch.int32, device=d)
-        self._tok_cache = None          # (copy=False token steps cache pointers and views of the buffers made here)
-        self._slabs = None              # copy=True: output sets of 64 steps per allocation (made at the first step)
-        self._obs = torch.zeros(n, dtype=torch.int32, device=d)
-        self._reward = torch.zeros(n, dtype=torch.float32, device=d)
-        self._reward_gt = torch.zeros(n, dtype=torch.float32, device=d)
-        self._term = torch.zeros(n, dtype=torch.uint8, device=d)
-        self._trunc = torch.zeros(n, dtype=torch.uint8, device=d)
-        self._final_obs = torch.full((n,), -1, dtype=torch.int32, device=d)
-        self._steps = torch.zeros(n, dtype=torch.int32, device=d)
-        self._done = torch.zeros(n, dtype=torch.uint8, device=d)
+        self._plain_buffers(self._fields(()))
+        self._outputs = None      # made at the first step
         self._tgt = torch.zeros((n, S), dtype=torch.float64, device=d) if self.with_transition_gt else None
-        self._ring = None
-        if (not self.copy) and (not self.to_numpy) and self._tok is None and not self.with_transition_gt:
-            self._ring, self._ring_pos = [], 0
-            for _ in range(2):
-                b = dict(obs=torch.zeros(n, dtype=torch.int32, device=d), reward=torch.zeros(n, dtype=torch.float32, device=d),
-                         reward_gt=torch.zeros(n, dtype=torch.float32, device=d),
-                         term=torch.zeros(n, dtype=torch.uint8, device=d), trunc=torch.zeros(n, dtype=torch.uint8, device=d),
-                         final_obs=torch.full((n,), -1, dtype=torch.int32, device=d),
-                         steps=torch.zeros(n, dtype=torch.int32, device=d), done=torch.zeros(n, dtype=torch.uint8, device=d))
-                b["term_b"], b["trunc_b"], b["done_b"] = (b[k].view(torch.bool) for k in ("term", "trunc", "done"))
-                b["args"] = tuple(C.c_void_p(b[k].data_ptr()) for k in
-                                  ("obs", "reward", "reward_gt", "term", "trunc", "final_obs"))
-                b["steps_p"] = C.c_void_p(b["steps"].data_ptr())
-                b["done_p"] = C.c_void_p(b["done"].data_ptr())
-                b["ints"] = tuple(x.value for x in b["args"]) + (b["steps"].data_ptr(), b["done"].data_ptr())
-                self._ring.append(b)
+
+    def _make_outputs(self):
+        """the output sets step() writes: the kernels write every field of every env (final_obs: -1 where the env goes on).  MDP
+        steps alternate between two persistent sets under copy=False, token steps write one"""
+        first = (lambda t: t[:, 0]) if self.task_type == "POMDP" else (lambda t: t)      # a POMDP observation is its one token
+        self._step_fn = "xv_anymdp_step_info" if self._tok is None else "xv_anymdp_step_tokens_info"
+        return self._make_step_outputs(self._fields(() if self._tok is None else (self._tok[0],)), self._STEP_ORDER,
+                                       n_sets=2 if self._tok is None else 1, as_bool=("term", "trunc", "done"),
+                                       derived={"obs_u": ("obs", first), "final_obs_u": ("final_obs", first)})
 
     SEARCH = {"auto": 0, "binary": 1, "fence": 3, "bucket": 4}
     _SEARCH_NAME = {1: "binary", 3: "fence", 4: "bucket"}
@@ -273,13 +262,14 @@ class AnyMDPVecEnv(VectorEnv):
         mask = None
         if options is not None and options.get("reset_mask") is not None:
             mask = self._dev(options["reset_mask"], torch.uint8)
-        self._detach("_obs")
+        self._adopt_latest(**{"_obs" if self._tok is None else "_tobs": "obs"})
         if self._tok is not None:
             self._detach("_tobs")      # a masked reset writes part of it: never into the tensor the last step handed out
             _lib.check(self.lib.xv_anymdp_reset_tokens(self._h, _lib.ptr(mask), _lib.ptr(self._tobs)))
             self.need_reset = False
             self._sync_views()
             return self._tok_obs(self._tobs), {"steps": self._out(self._get_steps())}
+        self._detach("_obs")
         _lib.check(self.lib.xv_anymdp_reset(self._h, _lib.ptr(mask), _lib.ptr(self._obs)))
         self.need_reset = False
         self._sync_views()
@@ -307,37 +297,12 @@ class AnyMDPVecEnv(VectorEnv):
             raise AssertionError(f"Action {tuple(a.shape)} is out of range")   # anymdp_env.py:117
         return a.contiguous()
 
-    def _tok_make_cache(self):
-        pomdp = self.task_type == "POMDP"
-        return dict(key=(self._tobs.data_ptr(), self._tfobs.data_ptr()),
-                    args=tuple(C.c_void_p(t.data_ptr()) for t in (self._tobs, self._reward, self._reward_gt, self._term,
-                                                                  self._trunc, self._tfobs, self._steps, self._done)),
-                    obs=self._tobs[:, 0] if pomdp else self._tobs, fobs=self._tfobs[:, 0] if pomdp else self._tfobs,
-                    term_b=self._term.view(torch.bool), trunc_b=self._trunc.view(torch.bool),
-                    done_b=self._done.view(torch.bool))
-
-    def _tok_fresh(self):
-        """before a token step: the step kernels write observation, rewards, flags and final_obs (-1 where the env goes on) of
-        EVERY env, so fresh buffers are swapped in and handed out without copies (the previous call's tensors are never
-        written again)"""
-        self._renew("_tobs", "_reward", "_reward_gt", "_term", "_trunc", "_tfobs")
-
-    def _tok_ret(self, from_launch=False):
-        """from_launch: the step wrote `_steps` and `_done` itself (xv_anymdp_step_tokens_info)"""
-        infos = {"steps": self._of(self._steps) if from_launch else self._out(self._get_steps()),
-                 "reward_gt": self._of(self._reward_gt)}
-        if self.autoreset_mode == "same_step":
-            infos["final_obs"] = self._of(self._tfobs[:, 0] if self.task_type == "POMDP" else self._tfobs)
-            infos["_final_obs"] = self._obf(self._done) if from_launch else \
-                self._out((self._term | self._trunc).view(torch.bool))
-        obs = self._tobs[:, 0] if self.task_type == "POMDP" else self._tobs
-        return (self._of(obs), self._of(self._reward), self._obf(self._term), self._obf(self._trunc), infos)
-
     def reset_tokens_injected(self, u_reset, u_obs_reset, mask=None):
         self._require_task()
         ur = self._dev(u_reset, torch.float64)
         uo = self._dev(u_obs_reset, torch.float64)
         m = None if mask is None else self._dev(mask, torch.uint8)
+        self._adopt_latest(_tobs="obs")
         self._detach("_tobs")
         _lib.check(self.lib.xv_anymdp_reset_tokens_injected(self._h, _lib.ptr(m), _lib.ptr(ur), _lib.ptr(uo),
                                                             _lib.ptr(self._tobs)))
@@ -350,18 +315,17 @@ class AnyMDPVecEnv(VectorEnv):
         a = self._tok_action(actions)
         args = [self._dev(u, torch.float64), self._dev(z, torch.float32), self._dev(u_obs, torch.float64),
                 self._dev(u_reset, torch.float64), self._dev(u_obs_reset, torch.float64)]
-        self._tok_fresh()
-        _lib.check(self.lib.xv_anymdp_step_tokens_injected(
-            self._h, _lib.ptr(a), *[_lib.ptr(x) for x in args], _lib.ptr(self._tobs), _lib.ptr(self._reward),
-            _lib.ptr(self._reward_gt), _lib.ptr(self._term), _lib.ptr(self._trunc), _lib.ptr(self._tfobs),
-            AUTORESET[self.autoreset_mode]))
-        return self._tok_ret()
+        s = (self._outputs or self._make_outputs()).next()
+        _lib.check(self.lib.xv_anymdp_step_tokens_injected(self._h, _lib.ptr(a), *[_lib.ptr(x) for x in args], *s.args[:6],
+                                                           AUTORESET[self.autoreset_mode]))
+        return self._finish(self._steps_and_done(s), a)
 
     def reset_injected(self, u, mask=None):
         """Parity hook: the initial-state uniform is supplied per env (fp64 in [0,1))."""
         self._require_task()
         u = self._dev(u, torch.float64)
         m = None if mask is None else self._dev(mask, torch.uint8)
+        self._adopt_latest(_obs="obs")
         self._detach("_obs")
         _lib.check(self.lib.xv_anymdp_reset_injected(self._h, _lib.ptr(m), _lib.ptr(u), _lib.ptr(self._obs)))
         self.need_reset = False
@@ -391,113 +355,38 @@ class AnyMDPVecEnv(VectorEnv):
         if floor > eng.tick:
             eng.tick = floor
 
-    def _infos(self, actions):
-        infos = {"steps": self._out(self._get_steps()), "reward_gt": self._of(self._reward_gt)}
-        if self.autoreset_mode == "same_step":
-            infos["final_obs"] = self._of(self._final_obs)
-            infos["_final_obs"] = self._out((self._term | self._trunc).view(torch.bool))
-        if self.with_transition_gt:
+    def _steps_and_done(self, s):
+        """after a launch that writes the first six outputs only (the *_injected hooks): `steps` and the done mask"""
+        _lib.check(self.lib.xv_anymdp_get_state(self._h, None, s.ptr["steps"], None))
+        torch.bitwise_or(s.t["term"], s.t["trunc"], out=s.t["done"])
+        return s
+
+    def _finish(self, s, actions):
+        """the output set a step launch has written -> step()'s return value"""
+        t = s.t
+        infos = {"steps": t["steps"], "reward_gt": t["reward_gt"]}
+        if self._auto == 2:      # same_step
+            infos["final_obs"] = t["final_obs_u"]
+            infos["_final_obs"] = t["done"]
+        if self.with_transition_gt:      # a launch of its own, after the common path
             _lib.check(self.lib.xv_anymdp_transition_gt(self._h, _lib.ptr(actions), _lib.ptr(self._tgt)))
-            infos["transition_gt"] = self._out(self._tgt.clone())
-        return infos
+            infos["transition_gt"] = self._tgt.clone()
+        if self.to_numpy:
+            return self._numpy(t["obs_u"], t["reward"], t["term"], t["trunc"], infos)
+        return t["obs_u"], t["reward"], t["term"], t["trunc"], infos
 
     def step(self, actions):
         self._check_step()
-        if self._tok is not None:
+        if self._tok is None:
+            a = self._dev(actions, torch.int32)
+            if a.shape != (self.num_envs,):
+                raise AssertionError(f"Action {tuple(a.shape)} is out of range")
+        else:
             a = self._tok_action(actions)
-            if not self.copy and not self.to_numpy:     # persistent outputs: pointers and views are made once
-                c = self._tok_cache
-                if c is None or c["key"] != (self._tobs.data_ptr(), self._tfobs.data_ptr()):
-                    c = self._tok_cache = self._tok_make_cache()
-                _lib.check(self.lib.xv_anymdp_step_tokens_info(self._h, C.c_void_p(a.data_ptr()), *c["args"],
-                                                               AUTORESET[self.autoreset_mode]))
-                infos = {"steps": self._steps, "reward_gt": self._reward_gt}
-                if self.autoreset_mode == "same_step":
-                    infos["final_obs"] = c["fobs"]
-                    infos["_final_obs"] = c["done_b"]
-                return c["obs"], self._reward, c["term_b"], c["trunc_b"], infos
-            self._tok_fresh()
-            self._renew("_steps", "_done")
-            # ONE launch: the token step writes info["steps"] and the terminated | truncated mask itself
-            _lib.check(self.lib.xv_anymdp_step_tokens_info(
-                self._h, _lib.ptr(a), _lib.ptr(self._tobs), _lib.ptr(self._reward), _lib.ptr(self._reward_gt),
-                _lib.ptr(self._term), _lib.ptr(self._trunc), _lib.ptr(self._tfobs), _lib.ptr(self._steps), _lib.ptr(self._done),
-                AUTORESET[self.autoreset_mode]))
-            return self._tok_ret(from_launch=True)
-        a = self._dev(actions, torch.int32)
-        if a.shape != (self.num_envs,):
-            raise AssertionError(f"Action {tuple(a.shape)} is out of range")
-        if self._ring is not None:      # copy=False: outputs are views of the output set this step writes
-            b = self._ring[self._ring_pos]
-            if not self._holding:           # a captured loop (capture.py) writes one output set: its policy reads it back
-                self._ring_pos ^= 1
-            lib, mode = self.lib, AUTORESET[self.autoreset_mode]
-            # ONE launch: the step kernel writes info["steps"] and the terminated | truncated mask itself (xv_anymdp_step_info)
-            f = _lib.fast()
-            if f is not None:
-                rc = f.icall(self._fn_step_info(), self._h.value, a.data_ptr(), *b["ints"], mode)
-                if rc:
-                    _lib.check(rc)
-            else:
-                _lib.check(lib.xv_anymdp_step_info(self._h, C.c_void_p(a.data_ptr()), *b["args"], b["steps_p"], b["done_p"], mode))
-            infos = {"steps": b["steps"], "reward_gt": b["reward_gt"]}
-            if mode == 2:
-                infos["final_obs"] = b["final_obs"]
-                infos["_final_obs"] = b["done_b"]
-            return b["obs"], b["reward"], b["term_b"], b["trunc_b"], infos
-        if self.copy and not self.to_numpy and not self.with_transition_gt:
-            # copy=True without copies and without allocations: the step writes every output for every env into the next set of
-            # a slab made for 64 steps at once (vector.OutputSlabs); what earlier steps handed out is never written again
-            t, p, pi = self._slab_next3()
-            mode = AUTORESET[self.autoreset_mode]
-            f = _lib.fast()
-            if f is not None:      # the CPython trampoline (csrc/xvfast.c): the same call without ctypes' marshalling
-                rc = f.icall(self._fn_step_info(), self._h.value, a.data_ptr(), *pi, mode)
-                if rc:
-                    _lib.check(rc)
-            else:
-                _lib.check(self.lib.xv_anymdp_step_info(self._h, C.c_void_p(a.data_ptr()), *p, mode))
-            self._obs = t["obs"]      # (reset() and the accessors read the latest observation from here)
-            infos = {"steps": t["steps"], "reward_gt": t["reward_gt"]}
-            if mode == 2:
-                infos["final_obs"] = t["final_obs"]
-                infos["_final_obs"] = t["done"]
-            return t["obs"], t["reward"], t["term"], t["trunc"], infos
-        # copy=True without copies: the step writes every output for every env, so fresh buffers are swapped in
-        self._renew("_obs", "_reward", "_reward_gt", "_term", "_trunc", "_final_obs", "_steps", "_done")
-        _lib.check(self.lib.xv_anymdp_step_info(
-            self._h, _lib.ptr(a), _lib.ptr(self._obs), _lib.ptr(self._reward), _lib.ptr(self._reward_gt),
-            _lib.ptr(self._term), _lib.ptr(self._trunc), _lib.ptr(self._final_obs), _lib.ptr(self._steps), _lib.ptr(self._done),
-            AUTORESET[self.autoreset_mode]))
-        infos = {"steps": self._of(self._steps), "reward_gt": self._of(self._reward_gt)}
-        if self.autoreset_mode == "same_step":
-            infos["final_obs"] = self._of(self._final_obs)
-            infos["_final_obs"] = self._obf(self._done)
-        if self.with_transition_gt:
-            _lib.check(self.lib.xv_anymdp_transition_gt(self._h, _lib.ptr(a), _lib.ptr(self._tgt)))
-            infos["transition_gt"] = self._out(self._tgt.clone())
-        return (self._of(self._obs), self._of(self._reward), self._obf(self._term), self._obf(self._trunc), infos)
-
-    _FN_STEP_INFO = [None]
-
-    def _fn_step_info(self):
-        if self._FN_STEP_INFO[0] is None:
-            self._FN_STEP_INFO[0] = _lib.fn_address("xv_anymdp_step_info")
-        return self._FN_STEP_INFO[0]
-
-    def _slab_next(self):
-        return self._slab_next3()[:2]
-
-    def _slab_next3(self):
-        """copy=True: the next output set of a 64-step slab (vector.OutputSlabs) -> (dict of tensors, pointers in the order
-        obs, reward, reward_gt, term, trunc, final_obs, steps, done — as ctypes objects and as ints)"""
-        if self._slabs is None:
-            i32, f32, u8 = torch.int32, torch.float32, torch.uint8
-            self._slabs = OutputSlabs([("obs", i32, ()), ("final_obs", i32, ()), ("steps", i32, ()), ("reward", f32, ()),
-                                       ("reward_gt", f32, ()), ("term", u8, ()), ("trunc", u8, ()), ("done", u8, ())],
-                                      self.num_envs, self.device, K=64, as_bool=("term", "trunc", "done"),
-                                      order=("obs", "reward", "reward_gt", "term", "trunc", "final_obs", "steps", "done"))
-        return self._slabs.next3()
+        s = (self._outputs or self._make_outputs()).next()
+        # ONE launch: the step kernel writes info["steps"] and the terminated | truncated mask itself
+        _lib.step_call(self._step_fn, self._h, a, s, self._auto)
+        return self._finish(s, a)
 
     def step_injected(self, actions, u, z, u_reset):
         """Parity hook (C-ABI xv_anymdp_step_injected): random inputs supplied per env."""
@@ -506,13 +395,10 @@ class AnyMDPVecEnv(VectorEnv):
         u = self._dev(u, torch.float64)
         z = self._dev(z, torch.float32)
         ur = self._dev(u_reset, torch.float64)
-        self._renew("_obs", "_reward", "_reward_gt", "_term", "_trunc", "_final_obs")
-        _lib.check(self.lib.xv_anymdp_step_injected(
-            self._h, _lib.ptr(a), _lib.ptr(u), _lib.ptr(z), _lib.ptr(ur), _lib.ptr(self._obs),
-            _lib.ptr(self._reward), _lib.ptr(self._reward_gt), _lib.ptr(self._term), _lib.ptr(self._trunc),
-            _lib.ptr(self._final_obs), AUTORESET[self.autoreset_mode]))
-        return (self._of(self._obs), self._of(self._reward), self._obf(self._term), self._obf(self._trunc),
-                self._infos(a))
+        s = (self._outputs or self._make_outputs()).next()
+        _lib.check(self.lib.xv_anymdp_step_injected(self._h, _lib.ptr(a), _lib.ptr(u), _lib.ptr(z), _lib.ptr(ur), *s.args[:6],
+                                                    AUTORESET[self.autoreset_mode]))
+        return self._finish(self._steps_and_done(s), a)
 
     def rollout(self, actions, out=None):
         """Fused open-loop rollout: actions int32[T, N] -> dict of [T, N] device tensors, one launch.
@@ -783,9 +669,9 @@ class AnyMDPVecEnv(VectorEnv):
 
     # ---- accessors (anymdp_env.py:134-165) ----------------------------------------------------------
     def _get_steps(self):
-        self._renew("_steps")
-        _lib.check(self.lib.xv_anymdp_get_state(self._h, None, _lib.ptr(self._steps), None))
-        return self._steps if (self.copy and not self.to_numpy) else self._steps.clone()
+        st = torch.empty(self.num_envs, dtype=torch.int32, device=self.device)
+        _lib.check(self.lib.xv_anymdp_get_state(self._h, None, _lib.ptr(st), None))
+        return st
 
     @property
     def inner_state(self):

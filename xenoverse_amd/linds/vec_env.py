@@ -13,7 +13,7 @@ import torch
 from .. import _lib
 from ..engine import AUTORESET
 from ..spaces import Box
-from ..vector import OutputSlabs, VectorEnv
+from ..vector import VectorEnv
 from .tables import build_tables
 
 _F32 = ("phiT", "gamT", "cT", "xt", "y0", "valid", "cmd0", "four_coef", "scal", "init")
@@ -122,18 +122,17 @@ class LinDSVecEnv(VectorEnv):
         self._h = h
         self._tab = dev
         self.n_task = n_task
-        n = self.num_envs
-        self._step_cache = None      # (copy=False steps cache pointers and views of the buffers made here)
-        self._slabs = None           # copy=True: output sets of 64 steps per allocation (vector.OutputSlabs), made at the first step
-        self._obs = torch.zeros((n, self.NO), dtype=torch.float32, device=d)
-        self._cmd = torch.zeros((n, self.NO), dtype=torch.float32, device=d)
-        self._fobs = torch.zeros((n, self.NO), dtype=torch.float32, device=d)
-        self._reward = torch.zeros(n, dtype=torch.float32, device=d)
-        self._error = torch.zeros(n, dtype=torch.float32, device=d)
-        self._term = torch.zeros(n, dtype=torch.uint8, device=d)
-        self._trunc = torch.zeros(n, dtype=torch.uint8, device=d)
-        self._steps = torch.zeros(n, dtype=torch.int32, device=d)
-        self._done = torch.zeros(n, dtype=torch.uint8, device=d)
+        f32, u8, i32, NO, uo = torch.float32, torch.uint8, torch.int32, self.NO, self.user_dims[1]
+        cut = (lambda t: t[:, :uo]) if uo != NO else (lambda t: t)      # the user's columns of a padded row
+        fields = [("obs", f32, (NO,)), ("cmd", f32, (NO,)), ("fobs", f32, (NO,)), ("reward", f32, ()), ("error", f32, ()),
+                  ("steps", i32, ()), ("term", u8, ()), ("trunc", u8, ()), ("done", u8, ())]
+        self._plain_buffers(fields)
+        # a step writes final_obs rows of FINISHED envs only (64 B per env-step that ~93 % of the envs do not need): copy=True /
+        # to_numpy hand out zero rows elsewhere (zero_on_refill); with copy=False the rows of unfinished envs keep whatever an
+        # earlier episode end left there — read them under info["_final_obs"]
+        self._make_step_outputs(fields, ("obs", "reward", "term", "trunc", "cmd", "error", "fobs", "steps", "done"),
+                                as_bool=("term", "trunc", "done"), zero_on_refill=("fobs",),
+                                derived={"obs_u": ("obs", cut), "cmd_u": ("cmd", cut), "fobs_u": ("fobs", cut)})
         self._path_name = "auto"
         self._command_type = np.where(tab["ints"][:, 3] > 0, "dynamic_target", "static_target") \
             if not torch.is_tensor(tab["ints"]) else None
@@ -169,18 +168,12 @@ class LinDSVecEnv(VectorEnv):
         return a.contiguous()
 
     def _steps_now(self):
-        self._renew("_steps")      # the launch writes every entry: a fresh buffer, handed out as it is (no copy)
-        _lib.check(self.lib.xv_linds_get_state(self._h, None, _lib.ptr(self._steps), None))
-        return self._steps if (self.copy and not self.to_numpy) else self._steps.clone()
+        st = torch.empty(self.num_envs, dtype=torch.int32, device=self.device)
+        _lib.check(self.lib.xv_linds_get_state(self._h, None, _lib.ptr(st), None))
+        return st
 
-    def _infos(self, with_final, fresh=False):
-        o = self._of if fresh else self._o      # fresh: the buffers were renewed before the launch (step paths)
-        infos = {"steps": self._out(self._steps_now()), "command": o(self._user_obs(self._cmd)),
-                 "error": o(self._error)}
-        if with_final and self.autoreset_mode == "same_step":
-            infos["final_obs"] = o(self._user_obs(self._fobs))
-            infos["_final_obs"] = self._out((self._term | self._trunc).view(torch.bool))
-        return infos
+    def _reset_infos(self):
+        return {"steps": self._out(self._steps_now()), "command": self._o(self._user_obs(self._cmd)), "error": self._o(self._error)}
 
     # -- API ----------------------------------------------------------------------------------------
     def reset(self, *, seed=None, options=None):
@@ -190,11 +183,12 @@ class LinDSVecEnv(VectorEnv):
         mask = None
         if options is not None and options.get("reset_mask") is not None:
             mask = self._dev(options["reset_mask"], torch.uint8)
+        self._adopt_latest(_obs="obs", _cmd="cmd", _error="error")
         self._detach("_obs", "_cmd", "_error")
         _lib.check(self.lib.xv_linds_reset(self._h, _lib.ptr(mask), _lib.ptr(self._obs), _lib.ptr(self._cmd),
                                            _lib.ptr(self._error)))
         self.need_reset = False
-        infos = self._infos(False)
+        infos = self._reset_infos()
         if self._command_type is not None:
             infos["command_type"] = self._command_type[self._tab["env_task"].cpu().numpy()]
         return self._o(self._user_obs(self._obs)), infos
@@ -203,130 +197,49 @@ class LinDSVecEnv(VectorEnv):
         self._require_task()
         idx = self._dev(init_index, torch.int32)
         m = None if mask is None else self._dev(mask, torch.uint8)
+        self._adopt_latest(_obs="obs", _cmd="cmd", _error="error")
         self._detach("_obs", "_cmd", "_error")
         _lib.check(self.lib.xv_linds_reset_injected(self._h, _lib.ptr(m), _lib.ptr(idx), _lib.ptr(self._obs),
                                                     _lib.ptr(self._cmd), _lib.ptr(self._error)))
         self.need_reset = False
-        return self._o(self._user_obs(self._obs)), self._infos(False)
+        return self._o(self._user_obs(self._obs)), self._reset_infos()
 
     def _check_step(self):
         if (not self.task_set) or self.need_reset:
             raise Exception("Must \"set_task\" and \"reset\" before doing any actions")   # linds_env.py:134-135
 
-    _STEP_OUTPUTS = ("_obs", "_reward", "_term", "_trunc", "_cmd", "_error")   # all fully written by a step
+    def _steps_and_done(self, s):
+        """after a launch that writes the first seven outputs only (the scalar test kernel, step_injected): `steps` and the done
+        mask by a launch / an op of their own — left out, with their infos, when lean_infos asks for no extra launches"""
+        if not self.lean_infos:
+            _lib.check(self.lib.xv_linds_get_state(self._h, None, s.ptr["steps"], None))
+            torch.bitwise_or(s.t["term"], s.t["trunc"], out=s.t["done"])
+        return self._finish(s, not self.lean_infos)
 
-    def _make_step_cache(self):
-        return dict(key=(self._obs.data_ptr(), self._fobs.data_ptr(), self._done.data_ptr()),
-                    args=tuple(C.c_void_p(t.data_ptr()) for t in (self._obs, self._reward, self._term, self._trunc, self._cmd,
-                                                                  self._error, self._fobs, self._steps, self._done)),
-                    ints=tuple(t.data_ptr() for t in (self._obs, self._reward, self._term, self._trunc, self._cmd,
-                                                      self._error, self._fobs, self._steps, self._done)),
-                    obs=self._user_obs(self._obs), cmd=self._user_obs(self._cmd), fobs=self._user_obs(self._fobs),
-                    term_b=self._term.view(torch.bool), trunc_b=self._trunc.view(torch.bool),
-                    done_b=self._done.view(torch.bool))
-
-    def _fresh_final_obs(self):
-        """the step writes final_obs rows of FINISHED envs only (64 B per env-step that ~93 % of the envs do not need):
-        copy=True / to_numpy hand out zero rows elsewhere, as before; with copy=False the rows of unfinished envs keep
-        whatever an earlier episode end left there — read them under info["_final_obs"]"""
-        if self.copy and not self.to_numpy:
-            self._fobs = torch.zeros_like(self._fobs)
-        elif self.to_numpy:
-            self._fobs.zero_()
-
-    def _ret(self):
-        if self.lean_infos:      # captured loops: nothing that needs a launch of its own (no `steps`, no `_final_obs` mask)
-            infos = {"command": self._of(self._user_obs(self._cmd)), "error": self._of(self._error)}
-            if self.autoreset_mode == "same_step":
-                infos["final_obs"] = self._of(self._user_obs(self._fobs))
-        else:
-            infos = self._infos(True, fresh=True)
-        return (self._of(self._user_obs(self._obs)), self._of(self._reward),
-                self._obf(self._term), self._obf(self._trunc), infos)
+    def _finish(self, s, full=True):
+        """the output set a step launch has written -> step()'s return value"""
+        t = s.t
+        infos = {"command": t["cmd_u"], "error": t["error"]}
+        if full:
+            infos["steps"] = t["steps"]
+        if self._auto == 2:      # same_step
+            infos["final_obs"] = t["fobs_u"]
+            if full:
+                infos["_final_obs"] = t["done"]
+        if self.to_numpy:
+            return self._numpy(t["obs_u"], t["reward"], t["term"], t["trunc"], infos)
+        return t["obs_u"], t["reward"], t["term"], t["trunc"], infos
 
     def step(self, actions):
         self._check_step()
         a = self._action(actions)
-        slab = self.copy and not self.to_numpy and self._path_name != "scalar"
-        if not slab:
-            self._renew(*self._STEP_OUTPUTS)
-            self._fresh_final_obs()
-        if self._path_name == "scalar":      # the test kernel: steps and the done mask by a launch / an op of their own
-            _lib.check(self.lib.xv_linds_step(self._h, _lib.ptr(a), _lib.ptr(self._obs), _lib.ptr(self._reward),
-                                              _lib.ptr(self._term), _lib.ptr(self._trunc), _lib.ptr(self._cmd),
-                                              _lib.ptr(self._error), _lib.ptr(self._fobs),
-                                              AUTORESET[self.autoreset_mode]))
-            return self._ret()
-        if not self.copy and not self.to_numpy:      # persistent outputs: pointers and views are made once
-            c = self._step_cache
-            if c is None or c["key"] != (self._obs.data_ptr(), self._fobs.data_ptr(), self._done.data_ptr()):
-                c = self._step_cache = self._make_step_cache()
-            f = _lib.fast()
-            if f is not None:
-                rc = f.icall(self._fn_step_info(), self._h.value, a.data_ptr(), *c["ints"], AUTORESET[self.autoreset_mode])
-                if rc:
-                    _lib.check(rc)
-            else:
-                _lib.check(self.lib.xv_linds_step_info(self._h, C.c_void_p(a.data_ptr()), *c["args"], AUTORESET[self.autoreset_mode]))
-            infos = {"steps": self._steps, "command": c["cmd"], "error": self._error}
-            if self.autoreset_mode == "same_step":
-                infos["final_obs"] = c["fobs"]
-                infos["_final_obs"] = c["done_b"]
-            return c["obs"], self._reward, c["term_b"], c["trunc_b"], infos
-        if slab:
-            # copy=True without copies, allocations or new tensor objects: the step writes every output of every env into the next
-            # set of a slab made for 64 steps (vector.OutputSlabs; recycled once nobody can reach it); final_obs — written for
-            # finished envs only — is zero-filled once per slab, so unfinished envs read zero rows as before
-            t, p, pi = self._slab_next3()
-            f = _lib.fast()
-            if f is not None:      # the CPython trampoline (csrc/xvfast.c): the same call without ctypes' marshalling
-                rc = f.icall(self._fn_step_info(), self._h.value, a.data_ptr(), *pi, AUTORESET[self.autoreset_mode])
-                if rc:
-                    _lib.check(rc)
-            else:
-                _lib.check(self.lib.xv_linds_step_info(self._h, C.c_void_p(a.data_ptr()), *p, AUTORESET[self.autoreset_mode]))
-            self._obs, self._cmd, self._error = t["obs"], t["cmd"], t["error"]      # (reset() and the accessors read these)
-            infos = {"steps": t["steps"], "command": t["cmd_u"], "error": t["error"]}
-            if self.autoreset_mode == "same_step":
-                infos["final_obs"] = t["fobs_u"]
-                infos["_final_obs"] = t["done"]
-            return t["obs_u"], t["reward"], t["term"], t["trunc"], infos
-        # ONE launch: the step kernel writes info["steps"] and the terminated | truncated mask itself (xv_linds_step_info)
-        self._renew("_steps", "_done")
-        _lib.check(self.lib.xv_linds_step_info(self._h, _lib.ptr(a), _lib.ptr(self._obs), _lib.ptr(self._reward),
-                                               _lib.ptr(self._term), _lib.ptr(self._trunc), _lib.ptr(self._cmd),
-                                               _lib.ptr(self._error), _lib.ptr(self._fobs), _lib.ptr(self._steps),
-                                               _lib.ptr(self._done), AUTORESET[self.autoreset_mode]))
-        infos = {"steps": self._of(self._steps), "command": self._of(self._user_obs(self._cmd)), "error": self._of(self._error)}
-        if self.autoreset_mode == "same_step":
-            infos["final_obs"] = self._of(self._user_obs(self._fobs))
-            infos["_final_obs"] = self._obf(self._done)
-        return (self._of(self._user_obs(self._obs)), self._of(self._reward), self._obf(self._term), self._obf(self._trunc), infos)
-
-    _FN_STEP_INFO = [None]
-
-    def _fn_step_info(self):
-        if self._FN_STEP_INFO[0] is None:
-            self._FN_STEP_INFO[0] = _lib.fn_address("xv_linds_step_info")
-        return self._FN_STEP_INFO[0]
-
-    def _slab_next(self):
-        return self._slab_next3()[:2]
-
-    def _slab_next3(self):
-        """copy=True: the next output set of a 64-step slab -> (dict of tensors incl. the user's columns obs_u / cmd_u / fobs_u,
-        pointers in the order obs, reward, term, trunc, cmd, error, fobs, steps, done — as ctypes objects and as ints)"""
-        if self._slabs is None:
-            f32, u8, i32, NO = torch.float32, torch.uint8, torch.int32, self.NO
-            uo = self.user_dims[1]
-            cut = (lambda t: t[:, :uo]) if uo != NO else (lambda t: t)
-            self._slabs = OutputSlabs([("obs", f32, (NO,)), ("cmd", f32, (NO,)), ("fobs", f32, (NO,)), ("reward", f32, ()),
-                                       ("error", f32, ()), ("steps", i32, ()), ("term", u8, ()), ("trunc", u8, ()), ("done", u8, ())],
-                                      self.num_envs, self.device, K=64, as_bool=("term", "trunc", "done"),
-                                      order=("obs", "reward", "term", "trunc", "cmd", "error", "fobs", "steps", "done"),
-                                      derived={"obs_u": ("obs", cut), "cmd_u": ("cmd", cut), "fobs_u": ("fobs", cut)},
-                                      zero_on_refill=("fobs",))
-        return self._slabs.next3()
+        s = self._outputs.next()
+        if self._path_name == "scalar":      # the test kernel
+            _lib.check(self.lib.xv_linds_step(self._h, _lib.ptr(a), *s.args[:7], AUTORESET[self.autoreset_mode]))
+            return self._steps_and_done(s)
+        # ONE launch: the step kernel writes info["steps"] and the terminated | truncated mask itself
+        _lib.step_call("xv_linds_step_info", self._h, a, s, self._auto)
+        return self._finish(s)
 
     def step_injected(self, actions, z, init_index):
         """Parity hook: z float[NS, N] standard normals (process noise), init_index int[N] (used on reset)."""
@@ -338,13 +251,10 @@ class LinDSVecEnv(VectorEnv):
             p[:z.shape[0]] = z
             z = p
         idx = self._dev(init_index, torch.int32)
-        self._renew(*self._STEP_OUTPUTS)
-        self._fresh_final_obs()
-        _lib.check(self.lib.xv_linds_step_injected(
-            self._h, _lib.ptr(a), _lib.ptr(z.contiguous()), _lib.ptr(idx), _lib.ptr(self._obs),
-            _lib.ptr(self._reward), _lib.ptr(self._term), _lib.ptr(self._trunc), _lib.ptr(self._cmd),
-            _lib.ptr(self._error), _lib.ptr(self._fobs), AUTORESET[self.autoreset_mode]))
-        return self._ret()
+        s = self._outputs.next()
+        _lib.check(self.lib.xv_linds_step_injected(self._h, _lib.ptr(a), _lib.ptr(z.contiguous()), _lib.ptr(idx), *s.args[:7],
+                                                   AUTORESET[self.autoreset_mode]))
+        return self._steps_and_done(s)
 
     def step_many(self, n_steps, actions, out=None):
         """n_steps vector steps issued from C (xv_linds_step_many): actions float32[P, N, na] is a ring of P action sets,

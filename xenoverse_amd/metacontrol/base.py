@@ -11,7 +11,7 @@ from .. import _lib
 from ..engine import AUTORESET
 from ..vector import VectorEnv
 
-_CALLS = ("create", "destroy", "reset", "reset_injected", "step_info", "rollout", "step_injected", "get_state", "set_state")
+_CALLS = ("create", "destroy", "reset", "reset_injected", "rollout", "step_injected", "get_state", "set_state")
 
 
 def _versatile(setting, default_range, default_value, rng):
@@ -69,14 +69,11 @@ class ControlVecEnv(VectorEnv):
                                   _lib.ptr(self._tab["params"]), _lib.ptr(self._tab["scale"]), *self._create_extras(),
                                   _lib.ptr(self._tab["env_task"]), C.byref(h)))
         self._h = h
-        n, w = self.num_envs, self.OBS_DIM
-        self._obs = torch.zeros((n, w), dtype=torch.float32, device=d)
-        self._fobs = torch.zeros((n, w), dtype=torch.float32, device=d)
-        self._reward = torch.zeros(n, dtype=torch.float32, device=d)
-        self._term = torch.zeros(n, dtype=torch.uint8, device=d)
-        self._trunc = torch.zeros(n, dtype=torch.uint8, device=d)
-        self._done = torch.zeros(n, dtype=torch.uint8, device=d)       # terminated | truncated, written by the step launch
-        self._step_cache = None      # (copy=False steps cache pointers and views of these buffers)
+        f32, u8, w = torch.float32, torch.uint8, self.OBS_DIM
+        fields = [("obs", f32, (w,)), ("fobs", f32, (w,)), ("reward", f32, ()), ("term", u8, ()), ("trunc", u8, ()), ("done", u8, ())]
+        self._plain_buffers(fields)
+        self._make_step_outputs(fields, ("obs", "reward", "term", "trunc", "fobs", "done"), as_bool=("term", "trunc", "done"))
+        self._step_fn = self.PREFIX + "_step_info"
         self.task_set = True
         self.need_reset = True
 
@@ -87,6 +84,7 @@ class ControlVecEnv(VectorEnv):
         mask = None
         if options is not None and options.get("reset_mask") is not None:
             mask = self._dev(options["reset_mask"], torch.uint8)
+        self._adopt_latest(_obs="obs")
         self._detach("_obs")
         _lib.check(self._c_reset(self._h, _lib.ptr(mask), _lib.ptr(self._obs)))
         self.need_reset = False
@@ -96,21 +94,23 @@ class ControlVecEnv(VectorEnv):
         self._require_task()
         u = self._dev(u, torch.float64)
         m = None if mask is None else self._dev(mask, torch.uint8)
+        self._adopt_latest(_obs="obs")
         self._detach("_obs")
         _lib.check(self._c_reset_injected(self._h, _lib.ptr(m), _lib.ptr(u), _lib.ptr(self._obs)))
         self.need_reset = False
         return self._o(self._obs)
 
-    def _ret(self, from_launch=False):
-        """from_launch: the step wrote `_done` itself (xv_*_step_info)"""
+    def _finish(self, s):
+        """the output set a step launch has written (all of it, for every env) -> step()'s return value"""
+        t = s.t
         infos = {}
-        if self.autoreset_mode == "same_step":
-            infos["final_obs"] = self._of(self._fobs)
-            if not self.lean_infos:       # flags are 0 / 1 bytes: a view, no conversion
-                infos["_final_obs"] = self._obf(self._done) if from_launch else \
-                    self._out((self._term | self._trunc).view(torch.bool))
-        return (self._of(self._obs), self._of(self._reward), self._obf(self._term),
-                self._obf(self._trunc), infos)
+        if self._auto == 2:      # same_step
+            infos["final_obs"] = t["fobs"]
+            if not self.lean_infos:
+                infos["_final_obs"] = t["done"]
+        if self.to_numpy:
+            return self._numpy(t["obs"], t["reward"], t["term"], t["trunc"], infos)
+        return t["obs"], t["reward"], t["term"], t["trunc"], infos
 
     def _require_reset(self):
         if (not self.task_set) or self.need_reset:
@@ -120,26 +120,9 @@ class ControlVecEnv(VectorEnv):
         self._require_reset()
         a = self._dev(actions, torch.int32)
         assert a.shape == (self.num_envs,)
-        if not self.copy and not self.to_numpy:      # persistent outputs: pointers and views are made once
-            c = self._step_cache
-            if c is None or c["key"] != (self._obs.data_ptr(), self._fobs.data_ptr(), self._done.data_ptr()):
-                c = self._step_cache = dict(
-                    key=(self._obs.data_ptr(), self._fobs.data_ptr(), self._done.data_ptr()),
-                    args=tuple(C.c_void_p(t.data_ptr()) for t in (self._obs, self._reward, self._term, self._trunc, self._fobs,
-                                                                  self._done)),
-                    term_b=self._term.view(torch.bool), trunc_b=self._trunc.view(torch.bool), done_b=self._done.view(torch.bool))
-            _lib.check(self._c_step_info(self._h, C.c_void_p(a.data_ptr()), *c["args"], AUTORESET[self.autoreset_mode]))
-            infos = {}
-            if self.autoreset_mode == "same_step":
-                infos["final_obs"] = self._fobs
-                if not self.lean_infos:
-                    infos["_final_obs"] = c["done_b"]
-            return self._obs, self._reward, c["term_b"], c["trunc_b"], infos
-        self._renew("_obs", "_reward", "_term", "_trunc", "_fobs", "_done")      # all fully written by the step
-        _lib.check(self._c_step_info(self._h, _lib.ptr(a), _lib.ptr(self._obs), _lib.ptr(self._reward),
-                                     _lib.ptr(self._term), _lib.ptr(self._trunc), _lib.ptr(self._fobs), _lib.ptr(self._done),
-                                     AUTORESET[self.autoreset_mode]))      # one launch: the done mask comes from the step kernel
-        return self._ret(from_launch=True)
+        s = self._outputs.next()
+        _lib.step_call(self._step_fn, self._h, a, s, self._auto)      # one launch: the done mask comes from the step kernel
+        return self._finish(s)
 
     def rollout(self, actions, out=None):
         """Fused open-loop roll-out: actions int32[T, N] -> dict of [T, N(, OBS_DIM)] device tensors from one launch with
@@ -162,11 +145,11 @@ class ControlVecEnv(VectorEnv):
     def step_injected(self, actions, u_reset):
         a = self._dev(actions, torch.int32)
         u = self._dev(u_reset, torch.float64)
-        self._renew("_obs", "_reward", "_term", "_trunc", "_fobs")
-        _lib.check(self._c_step_injected(self._h, _lib.ptr(a), _lib.ptr(u), _lib.ptr(self._obs), _lib.ptr(self._reward),
-                                         _lib.ptr(self._term), _lib.ptr(self._trunc), _lib.ptr(self._fobs),
-                                         AUTORESET[self.autoreset_mode]))
-        return self._ret()
+        s = self._outputs.next()
+        _lib.check(self._c_step_injected(self._h, _lib.ptr(a), _lib.ptr(u), *s.args[:5], AUTORESET[self.autoreset_mode]))
+        if not self.lean_infos:      # the done mask by an op of its own
+            torch.bitwise_or(s.t["term"], s.t["trunc"], out=s.t["done"])
+        return self._finish(s)
 
     def get_state(self):
         n, d = self.num_envs, self.device

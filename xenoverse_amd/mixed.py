@@ -30,6 +30,19 @@ class _MixedIO(C.Structure):   # xv_mixed_io (include/xeno.h)
         "a_steps", "a_done", "l_steps", "l_done", "c_done")]      # ABI 12: steps / done masks from the fused launch (nullable)
 
 
+def _io_outputs(prefix, **fields):
+    return tuple((prefix + k, v) for k, v in fields.items())
+
+
+# xv_mixed_io field -> the field of the family's output set (AnyMDPVecEnv, LinDSVecEnv, ControlVecEnv: set_task) it points at
+_IO_OUTPUTS = (
+    _io_outputs("a_", obs="obs", reward="reward", reward_gt="reward_gt", terminated="term", truncated="trunc",
+                final_obs="final_obs", steps="steps", done="done"),
+    _io_outputs("l_", obs="obs", reward="reward", terminated="term", truncated="trunc", cmd="cmd", error="error",
+                final_obs="fobs", steps="steps", done="done"),
+    _io_outputs("c_", obs="obs", reward="reward", terminated="term", truncated="trunc", final_obs="fobs", done="done"))
+
+
 class MixedBatch(object):
     def __init__(self, device="cuda:0", seed=0, streams="shared"):
         assert streams in ("shared", "separate")
@@ -39,7 +52,7 @@ class MixedBatch(object):
         self.envs = {}
         self.streams = {}
         self._trio = None          # (_fused_trio result, cached until add())
-        self._fast = None          # copy=False: the marshalled xv_mixed_io structs and the returned views of step_fused
+        self._fast = {}            # step_fused: three persistent output sets -> [xv_mixed_io filled for them, its byref, the sets, the return value]
 
     def add(self, name, env_cls, num_envs, env_id_base=0, **kwargs):
         """Create `env_cls(num_envs, engine=<engine on a private stream>, **kwargs)` under `name`."""
@@ -49,7 +62,7 @@ class MixedBatch(object):
         env._own_engine = True   # closed with the env
         self.envs[name] = env
         self.streams[name] = st
-        self._trio = self._fast = None
+        self._trio, self._fast = None, {}
         return env
 
     def _on(self, name):
@@ -114,107 +127,47 @@ class MixedBatch(object):
         """One launch for the whole mixed batch (xv_mixed_step).  actions: dict name -> batched action, as for step().
         -> dict name -> (obs, reward, terminated, truncated, infos), bit for bit what step() returns.  Handles without a
         fused instantiation (AnyMDP on the per-lane search or S > 112, LinDS on the scalar path or other pads) are stepped
-        by step() — three launches, same results."""
+        by step() — three launches, same results.
+
+        Each env hands out its next output set, the fused kernel writes all three (info["steps"] and the done masks included,
+        ABI 12), and each env turns its set into what its own step() returns."""
         pick, mode = self._fused_trio()
         (na, ea), (nl, el), (nc, ec) = pick["a"], pick["l"], pick["c"]
         if ea._tok is not None:
             raise ValueError("step_fused serves MDP tasks")
-        ea._check_step(); el._check_step()
-        if (not ec.task_set) or ec.need_reset:
-            raise Exception("Must \"set_task\" and \"reset\" before doing any actions")
-        if not ea.lib.xv_mixed_supported(ea._h, el._h, ec._h):      # asked BEFORE any output buffer is renewed
+        ea._check_step(); el._check_step(); ec._require_reset()
+        if not ea.lib.xv_mixed_supported(ea._h, el._h, ec._h):      # asked BEFORE any output set is taken
             return self.step(actions)
         aa = ea._dev(actions[na], torch.int32)
         al = el._action(actions[nl])
         ac = ec._dev(actions[nc], torch.int32)
         if aa.shape != (ea.num_envs,) or ac.shape != (ec.num_envs,):
             raise AssertionError("action batch shapes do not match the env counts")
-        if ea._ring is not None and not (el.copy or el.to_numpy or ec.copy or ec.to_numpy):
-            return self._step_fused_persistent(na, ea, nl, el, nc, ec, aa, al, ac, mode)
-        if all(e.copy and not e.to_numpy for e in (ea, el, ec)) and not ea.with_transition_gt and el._path_name != "scalar":
-            # copy=True: AnyMDP and LinDS outputs come from their 64-step slabs (no allocation, no new tensor objects: vector.
-            # OutputSlabs), CartPole's five from fresh buffers; ONE launch writes everything incl. steps and the done masks
-            ta, pa = ea._slab_next()
-            tl, pl = el._slab_next()
-            ec._renew("_obs", "_reward", "_term", "_trunc", "_fobs", "_done")
-            P = _lib.ptr
-            io = _MixedIO(P(aa), pa[0], pa[1], pa[2], pa[3], pa[4], pa[5],
-                          P(al), pl[0], pl[1], pl[2], pl[3], pl[4], pl[5], pl[6],
-                          P(ac), P(ec._obs), P(ec._reward), P(ec._term), P(ec._trunc), P(ec._fobs),
-                          pa[6], pa[7], pl[7], pl[8], P(ec._done))
-            _lib.check(ea.lib.xv_mixed_step(ea._h, el._h, ec._h, C.byref(io), AUTORESET[mode]))
-            ea._obs = ta["obs"]
-            el._obs, el._cmd, el._error = tl["obs"], tl["cmd"], tl["error"]
-            ia = {"steps": ta["steps"], "reward_gt": ta["reward_gt"]}
-            il = {"steps": tl["steps"], "command": tl["cmd_u"], "error": tl["error"]}
-            if mode == "same_step":
-                ia["final_obs"], ia["_final_obs"] = ta["final_obs"], ta["done"]
-                il["final_obs"], il["_final_obs"] = tl["fobs_u"], tl["done"]
-            return {na: (ta["obs"], ta["reward"], ta["term"], ta["trunc"], ia),
-                    nl: (tl["obs_u"], tl["reward"], tl["term"], tl["trunc"], il), nc: ec._ret(from_launch=True)}
-        ring = None
-        if ea._ring is not None:      # copy=False: the AnyMDP family writes one of its two engine-owned output sets
-            ring = ea._ring[ea._ring_pos]
-            if not ea._holding:
-                ea._ring_pos ^= 1
-            a_out = [ring[k] for k in ("obs", "reward", "reward_gt", "term", "trunc", "final_obs")]
-        else:
-            ea._renew("_obs", "_reward", "_reward_gt", "_term", "_trunc", "_final_obs")
-            a_out = [ea._obs, ea._reward, ea._reward_gt, ea._term, ea._trunc, ea._final_obs]
-        el._renew(*el._STEP_OUTPUTS); el._fresh_final_obs()
-        ec._renew("_obs", "_reward", "_term", "_trunc", "_fobs")
-        io = _MixedIO(*[_lib.ptr(t) for t in (
-            [aa] + a_out + [al, el._obs, el._reward, el._term, el._trunc, el._cmd, el._error, el._fobs,
-                            ac, ec._obs, ec._reward, ec._term, ec._trunc, ec._fobs])])
-        _lib.check(ea.lib.xv_mixed_step(ea._h, el._h, ec._h, C.byref(io), AUTORESET[mode]))
-        if ring is not None:
-            infos = {"reward_gt": ring["reward_gt"]}
-            if mode == "same_step":
-                infos["final_obs"] = ring["final_obs"]
-            if not ea.lean_infos:
-                _lib.check(ea.lib.xv_anymdp_get_state(ea._h, None, ring["steps_p"], None))
-                infos["steps"] = ring["steps"]
-                if mode == "same_step":
-                    torch.bitwise_or(ring["term"], ring["trunc"], out=ring["done"])
-                    infos["_final_obs"] = ring["done_b"]
-            ra = (ring["obs"], ring["reward"], ring["term_b"], ring["trunc_b"], infos)
-        else:
-            ra = (ea._of(ea._obs), ea._of(ea._reward), ea._obf(ea._term), ea._obf(ea._trunc), ea._infos(aa))
-        return {na: ra, nl: el._ret(), nc: ec._ret()}
-
-    def _step_fused_persistent(self, na, ea, nl, el, nc, ec, aa, al, ac, mode):
-        """copy=False on all three families: every output lives in engine-owned buffers (AnyMDP: two sets used alternately), so
-        the xv_mixed_io structs, their pointers and the views handed out are made once; a step sets three action pointers and
-        makes ONE launch — the fused kernel writes info["steps"] and the done masks itself (ABI 12)"""
-        key = (tuple(b["obs"].data_ptr() for b in ea._ring), el._obs.data_ptr(), el._fobs.data_ptr(), el._steps.data_ptr(),
-               ec._obs.data_ptr(), ec._fobs.data_ptr(), ec._done.data_ptr(), mode)
-        f = self._fast
-        if f is None or f["key"] != key:
-            P = _lib.ptr
-            sets = []
-            lc = el._make_step_cache()
-            for b in ea._ring:
-                io = _MixedIO(None, P(b["obs"]), P(b["reward"]), P(b["reward_gt"]), P(b["term"]), P(b["trunc"]), P(b["final_obs"]),
-                              None, P(el._obs), P(el._reward), P(el._term), P(el._trunc), P(el._cmd), P(el._error), P(el._fobs),
-                              None, P(ec._obs), P(ec._reward), P(ec._term), P(ec._trunc), P(ec._fobs),
-                              P(b["steps"]), P(b["done"]), P(el._steps), P(el._done), P(ec._done))
-                ia = {"reward_gt": b["reward_gt"], "steps": b["steps"]}
-                il = {"steps": el._steps, "command": lc["cmd"], "error": el._error}
-                ic = {}
-                if mode == "same_step":
-                    ia["final_obs"], ia["_final_obs"] = b["final_obs"], b["done_b"]
-                    il["final_obs"], il["_final_obs"] = lc["fobs"], lc["done_b"]
-                    ic["final_obs"], ic["_final_obs"] = ec._fobs, ec._done.view(torch.bool)
-                sets.append((io, C.byref(io), {na: (b["obs"], b["reward"], b["term_b"], b["trunc_b"], ia),
-                                               nl: (lc["obs"], el._reward, lc["term_b"], lc["trunc_b"], il),
-                                               nc: (ec._obs, ec._reward, ec._term.view(torch.bool), ec._trunc.view(torch.bool), ic)}))
-            f = self._fast = {"key": key, "sets": sets, "mode": AUTORESET[mode]}
-        pos = ea._ring_pos
-        if not ea._holding:
-            ea._ring_pos ^= 1
-        io, ref, out = f["sets"][pos]
+        oa, ol, oc = ea._outputs or ea._make_outputs(), el._outputs, ec._outputs
+        sets = (oa.next(), ol.next(), oc.next())
+        # persistent sets (copy=False, to_numpy): the struct filled for a combination of sets is kept with them — and so is what
+        # the envs return for it, where that is the same objects every time (no conversion, no launch of its own)
+        key = None
+        if oa.persistent and ol.persistent and oc.persistent:
+            key = (id(sets[0]), id(sets[1]), id(sets[2]), ea.lean_infos, el.lean_infos, ec.lean_infos)
+        hit = self._fast.get(key)
+        if hit is None:
+            io = _MixedIO()
+            for s, names in zip(sets, _IO_OUTPUTS):
+                for field, name in names:
+                    setattr(io, field, s.ptr[name])
+            hit = [io, C.byref(io), sets, None]
+            if key is not None:
+                if len(self._fast) >= 8:      # (sets of tasks long replaced: an env makes new ones at every set_task)
+                    self._fast.clear()
+                self._fast[key] = hit
+        io, ref, _, out = hit
         io.a_action, io.l_action, io.c_action = aa.data_ptr(), al.data_ptr(), ac.data_ptr()
-        _lib.check(ea.lib.xv_mixed_step(ea._h, el._h, ec._h, ref, f["mode"]))
+        _lib.check(ea.lib.xv_mixed_step(ea._h, el._h, ec._h, ref, AUTORESET[mode]))
+        if out is None:
+            out = {na: ea._finish(sets[0], aa), nl: el._finish(sets[1]), nc: ec._finish(sets[2])}
+            if key is not None and not (ea.to_numpy or el.to_numpy or ec.to_numpy or ea.with_transition_gt):
+                hit[3] = out
         return out
 
     def capture(self, policy_fn, obs, unroll=1, warmup=1, lean=True):

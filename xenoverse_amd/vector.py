@@ -16,6 +16,17 @@ except Exception:      # not installed: the same surface on a plain class
     _GymVectorEnv = object
 
 
+class OutputSet(object):
+    """What one step writes: `t` name -> tensor (bool views and derived views included), the device pointers in the order the
+    C call takes them as ctypes objects (`args`) and as ints (`ints`, for _xvfast.icall), and `ptr` name -> int."""
+    __slots__ = ("t", "args", "ints", "ptr", "after")
+
+    def __init__(self, t, ptr, order):
+        self.t, self.ptr = t, {k: p.value for k, p in ptr.items()}
+        self.args = tuple(ptr[k] for k in order)
+        self.ints = tuple(self.ptr[k] for k in order)
+
+
 class OutputSlabs(object):
     """Fresh output tensors for every step() at the cost of none: the outputs of K consecutive steps are carved out of ONE
     allocation per dtype (K x fields x N), the per-step tensors and their device pointers are made when the slab is, and a
@@ -50,11 +61,12 @@ class OutputSlabs(object):
         self.order = list(order) if order is not None else [f[0] for f in self.fields]
         self.keep = max(1, int(keep))
         self._sets, self._pos = [], 0
-        self._ring = []          # cached slabs, oldest first; the last one is the slab in use
+        self.last = None         # the set handed out last (it counts as a holder of its slab)
+        self._cached = []          # cached slabs, oldest first; the last one is the slab in use
         self.made = 0            # slabs allocated so far (tests, diagnostics)
         self.recycled = 0        # slabs handed out again
 
-    def _make(self):
+    def _make(self, alloc=torch.empty):
         import ctypes as C
         by = {}
         for name, dt, tail in self.fields:
@@ -66,7 +78,7 @@ class OutputSlabs(object):
             # [field][step][n * tail]: two unbind() calls hand out every per-step tensor (slicing K x fields views one by one
             # in Python cost more than the allocations it was meant to save)
             width = max(self.n * math.prod(t) for _, t in fl)
-            slab = torch.empty((len(fl), self.K, width), dtype=dt, device=self.device)
+            slab = alloc((len(fl), self.K, width), dtype=dt, device=self.device)
             storages.append(slab.untyped_storage())
             base, esz = slab.data_ptr(), slab.element_size()
             fields = (slab.view(torch.bool) if dt == torch.uint8 else slab).unbind(0)
@@ -87,11 +99,10 @@ class OutputSlabs(object):
         for name, (field, fn) in self.derived.items():
             for k in range(self.K):
                 per_step[k][name] = fn(per_step[k][field])
-        rec = {"zero": zero_blocks,
-               "sets": [(per_step[k], tuple(ptrs[k][name] for name in self.order), tuple(ptrs[k][name].value for name in self.order))
-                        for k in range(self.K)],
-               "flat": [t for d in per_step for t in d.values()] + per_step, "tensors": [t for d in per_step for t in d.values()],
-               "storages": storages}      # (`flat` counts the per-step dicts too: next() hands them out)
+        sets = [OutputSet(per_step[k], ptrs[k], self.order) for k in range(self.K)]
+        rec = {"zero": zero_blocks, "sets": sets,
+               "flat": [t for d in per_step for t in d.values()] + per_step + sets, "tensors": [t for d in per_step for t in d.values()],
+               "storages": storages}      # (`flat` counts the per-step dicts and sets too: next() / next_set() hand them out)
         self.made += 1
         return rec
 
@@ -105,35 +116,96 @@ class OutputSlabs(object):
         # the oldest cached slab nobody outside can reach, else a new one.  (The slab just used up is the newest: the
         # caller usually still holds its last outputs, so it is looked at last.)
         pick = None
-        for i, rec in enumerate(self._ring):
+        for i, rec in enumerate(self._cached):
             if self._counts(rec) == rec["idle"]:
-                pick = self._ring.pop(i)
+                pick = self._cached.pop(i)
                 self.recycled += 1
                 break
         if pick is None:
             pick = self._make()
             pick["idle"] = None
-        self._ring.append(pick)
+        self._cached.append(pick)
         for blk in pick["zero"]:
             blk.zero_()
         if pick["idle"] is None:      # (taken with every temporary of _make gone: the slab is referenced exactly as when it idles)
             pick["idle"] = self._counts(pick)
-        while len(self._ring) > self.keep:
-            self._ring.pop(0)
+        while len(self._cached) > self.keep:
+            self._cached.pop(0)
         self._sets = pick["sets"]
         self._pos = 0
 
     def next(self):
         """-> (dict name -> tensor, tuple of ctypes pointers in `order`) of a set no earlier step has written — or one whose
         earlier contents nobody can reach any more"""
-        return self.next3()[:2]
+        s = self.next_set()
+        return s.t, s.args
 
-    def next3(self):
-        """next() plus the same pointers as plain ints (for _xvfast.icall)"""
+    def next_set(self):
+        """the same set as an OutputSet (pointers also as ints and by name)"""
         if self._pos >= len(self._sets):
             self._refill()
-        s = self._sets[self._pos]
+        s = self.last = self._sets[self._pos]
         self._pos += 1
+        return s
+
+
+class StepOutputs(object):
+    """Where a family's step() writes, and who owns that memory afterwards — decided here and nowhere else.  An env builds one
+    per set_task from its field list and takes `next()` before every step launch: an OutputSet.
+
+      copy=True                 sets of recycled 64-step slabs (OutputSlabs): nothing handed out is ever written again while
+                                anybody can see it;
+      copy=False                `n_sets` persistent sets used round robin — what a step returned is valid until the step
+                                `n_sets` calls later; `hold(True)` pins the current set (captured loops: the policy reads the
+                                observation where the step writes it), `hold(False)` resumes; `zero_on_refill` fields are
+                                NOT zeroed again (rows a step leaves alone keep what an earlier step wrote);
+      to_numpy=True             one persistent set, `zero_on_refill` fields zeroed before every step; the env converts on the
+                                way out.
+
+    fields: [(name, torch dtype, trailing shape[, fill])] — `fill` is what a persistent set holds before its first step
+    (default 0); order / as_bool / derived / zero_on_refill: as OutputSlabs."""
+
+    def __init__(self, fields, n, device, order, copy=True, to_numpy=False, n_sets=1, as_bool=(), derived=None,
+                 zero_on_refill=(), K=64):
+        self.persistent = bool(to_numpy) or not copy
+        plain = [f[:3] for f in fields]
+        if not self.persistent:
+            self._slabs = OutputSlabs(plain, n, device, K=K, as_bool=as_bool, order=order, derived=derived,
+                                      zero_on_refill=zero_on_refill)
+            self.next = self._slabs.next_set      # (slabs are made at the first step: 64 steps of outputs are not small)
+            return
+        rec = OutputSlabs(plain, n, device, K=1 if to_numpy else n_sets, as_bool=as_bool, order=order, derived=derived,
+                          zero_on_refill=zero_on_refill)._make(alloc=torch.zeros)      # never refilled, never checked for holders
+        sets = rec["sets"]
+        for s, after in zip(sets, sets[1:] + sets[:1]):      # a ring: `after` is the set of the following step
+            s.after = after
+            for f in fields:
+                if len(f) > 3 and f[3]:
+                    s.t[f[0]].fill_(f[3])
+        self._cur, self.last, self._held = sets[0], None, False
+        if to_numpy:
+            self._zero, self.next = rec["zero"], self._next_zeroed
+
+    def hold(self, on):
+        """True: next() keeps returning the set it would return now; False: sets alternate again"""
+        self._held = bool(on)
+
+    def next(self):
+        s = self.last = self._cur
+        if not self._held:
+            self._cur = s.after
+        return s
+
+    def _next_zeroed(self):
+        for blk in self._zero:
+            blk.zero_()
+        self.last = self._cur
+        return self._cur
+
+    def take_last(self):
+        """the set next() returned last — the latest outputs — once: None when nothing was stepped since the last call"""
+        own = self if self.persistent else self._slabs
+        s, own.last = own.last, None
         return s
 
 
@@ -152,6 +224,7 @@ class VectorEnv(_GymVectorEnv):
         self.device = self.engine.device
         self.lib = self.engine.lib
         self.autoreset_mode = autoreset_mode
+        self._auto = AUTORESET[autoreset_mode]      # as the C-ABI takes it (XV_AUTORESET_*)
         self.metadata = dict(type(self).metadata, autoreset_mode=autoreset_mode)
         self.to_numpy = bool(to_numpy)
         # copy (as gymnasium's SyncVectorEnv(copy=...)): True returns fresh tensors from every call; False returns
@@ -159,6 +232,7 @@ class VectorEnv(_GymVectorEnv):
         self.copy = bool(copy)
         # lean_infos: step() returns only the infos that cost no extra launch (captured loops: xenoverse_amd/capture.py)
         self.lean_infos = False
+        self._outputs = None      # StepOutputs of the families that step through output sets (_make_step_outputs)
         self._holding = False
         self.closed = False
         self.task_set = False
@@ -209,6 +283,31 @@ class VectorEnv(_GymVectorEnv):
                 if t is not None:
                     setattr(self, name, t.clone())
 
+    def _plain_buffers(self, fields):
+        """one engine-owned buffer per field as `self._<name>`: what reset() writes (_adopt_latest rebinds those to the latest
+        step's outputs), and fixed memory for callers that time bare kernels (scripts/bench_families.py)"""
+        for f in fields:
+            setattr(self, "_" + f[0], torch.full((self.num_envs,) + tuple(f[2]), f[3] if len(f) > 3 else 0, dtype=f[1],
+                                                 device=self.device))
+
+    def _adopt_latest(self, **names):
+        """before reset() writes its buffers: when steps were made since the last reset, `self.<attr>` becomes field `name` of
+        the latest step's output set — a masked reset then keeps the other envs' last observation"""
+        s = self._outputs.take_last() if self._outputs is not None else None
+        if s is not None:
+            for attr, name in names.items():
+                setattr(self, attr, s.t[name])
+
+    def _make_step_outputs(self, fields, order, **kw):
+        """-> this env's StepOutputs for `fields` (set_task, or the first step after it)"""
+        self._outputs = StepOutputs(fields, self.num_envs, self.device, order, copy=self.copy, to_numpy=self.to_numpy, **kw)
+        self._outputs.hold(self._holding)
+        return self._outputs
+
+    def _numpy(self, obs, reward, term, trunc, infos):
+        """to_numpy: what a step hands out is converted here, on the way out"""
+        return (self._out(obs), self._out(reward), self._out(term), self._out(trunc), {k: self._out(v) for k, v in infos.items()})
+
     def _of(self, t):
         """an output buffer that was renewed before the launch (or copy=False): handed out as it is"""
         return self._out(t)
@@ -229,6 +328,8 @@ class VectorEnv(_GymVectorEnv):
         """while a captured loop exists: pins whatever the family alternates between step() calls (output sets) and,
         when asked, leaves out the infos that need a launch of their own"""
         self._holding = bool(on)
+        if self._outputs is not None:
+            self._outputs.hold(on)
         self.lean_infos = self._lean_wanted if on else self._lean_saved
 
     AUTO_UNROLL = 8      # one hipGraphLaunch costs the host about what it replaces; 8 iterations per launch: 15 -> 7.3 us per step
