@@ -124,4 +124,13 @@ hvac.reset()
 hvac.set_pid("gt")
 obs, reward, terminated, truncated, info = hvac.rollout_teacher(8)
 print("AnyHVAC teacher rollout: actions", tuple(info["action"].shape), "mean reward %.3f" % reward.mean().item())
+task = hvac._tasks[0]
+hvac.close()
+# the action space the reference's RL trainer uses: 13 temperature steps per cooler, mapped inside the step kernel
+hvac = HVACVecEnv(64, seed=2, reward_mode=1, action_mode="diff", discretize_rl_action_space=True)
+hvac.set_task([task], generate_task=True)
+hvac.reset()
+bins = torch.randint(0, 13, (8, 64, hvac.dims[2]), dtype=torch.int32, device=hvac.device)
+obs, reward, terminated, truncated, info = hvac.rollout(bins)
+print("AnyHVAC difference actions: sensors above target at the last step", info["step_stat"]["hot_0"][-1, :4].tolist())
 hvac.close()

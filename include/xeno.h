@@ -1235,6 +1235,50 @@ int xv_anyhvac_pid_set_state(xv_anyhvac* h, const double* acc_diff, const float*
 /* acc_diff = 0, last_obs = 0, fresh = 1 for the envs of mask uint8[n_env] (NULL: all): a new solver's state */
 int xv_anyhvac_pid_reset(xv_anyhvac* h, const uint8_t* mask);
 
+/* The RL action spaces — reference: anyhvac_env.py HVACEnvDiscreteAction :782-827 and HVACEnvDiffAction :829-1276 (flat
+ * branches, no_switch_action=True); host restatement xenoverse_amd/anyhvac/actions.py.  The mapping runs inside the step
+ * kernel, per step, from the value the env applied at the step before (the resting cooler's column: the default value):
+ *   DISCRETE  temp = float32 v (ub - lb) + lb; value = clip((rint(temp / 0.1 [float32]) * 0.1 - lb) / (ub - lb), 0, 1)
+ *   DIFF      bin = the int32 index, or clip(rint(float32 v * 12), 0, 12); delta = -3 + 0.5 bin;
+ *             temp = float32 last (ub - lb) + lb + delta [fp64]; under TOO_COLD_LIMIT temp = max(temp, target - 3);
+ *             value = clip((rint(temp / 0.1) * 0.1 - lb) / (ub - lb), 0, 1)
+ * rounded to float32; bit-equal to the reference.  Under XV_ANYHVAC_ACT_COST each (env, cooler) keeps its last <= 10 bins
+ * (one uint64: 4 bits per entry holding bin + 1, the newest lowest, 0 = empty) and the step's reward — the failure reward
+ * too — gets action_cost = -mean_c(0.5 cost_table[bin_c] + 0.5 * 0.6 * reversals_c) added in fp64, reversals_c the
+ * adjacent pairs of opposite nonzero sign in the window, the mean summed in index order (numpy: pairwise).  A bin outside
+ * 0...12 or a NaN input: XV_DEVERR_ACTION_RANGE; that cooler's value keeps its bits, its delta is 0 and bin 6 (no step)
+ * enters its window.  reset, reset_injected and a same-step autoreset empty the env's windows.  A step that ends in
+ * XV_DEVERR_NONFINITE puts grid, time and counters back but, as value[] in every mode, leaves the windows advanced by that
+ * step's bins.  New symbols only: no ABI bump. */
+#define XV_ANYHVAC_ACT_BOX 0
+#define XV_ANYHVAC_ACT_DISCRETE 1
+#define XV_ANYHVAC_ACT_DIFF 2
+#define XV_ANYHVAC_ACT_COST 1             /* flags of XV_ANYHVAC_ACT_DIFF */
+#define XV_ANYHVAC_ACT_TOO_COLD_LIMIT 2
+#define XV_ANYHVAC_ACT_BINS 13
+#define XV_ANYHVAC_STAT_COUNTS 8
+/* what a mapped step reads and writes beside xv_anyhvac_io: device pointers, rows as there, every one nullable */
+typedef struct xv_anyhvac_act_io {
+  const int32_t* action_index;  /* [n_env][C] bins (DIFF only); NULL: io->action's float32 row is mapped */
+  float* applied_value;         /* [n_env][C] the value the env applied (last_action["value"]); padded columns 0 */
+  double* delta;                /* [n_env][C] the temperature step taken, K (DISCRETE: 0); padded columns 0 */
+  double* action_cost;          /* [n_env] what was added to the reward (0 without XV_ANYHVAC_ACT_COST) */
+  int32_t* stat_counts;         /* [n_env][8] readings with reading - target > 0, 2, 4, 6 and < 0, -2, -4, -6 (float32) */
+} xv_anyhvac_act_io;
+/* cost_table: XV_ANYHVAC_ACT_BINS float64 on the HOST (copied), needed under XV_ANYHVAC_ACT_COST.  The first call with a
+ * mapped mode allocates the windows; they are emptied then and whenever the mode changes, and kept when only the flags do.
+ * Under a mapped mode xv_anyhvac_step / _step_injected / _rollout / _rollout_pid return XV_ERR_INVALID, under
+ * XV_ANYHVAC_ACT_BOX the mapped calls do. */
+int xv_anyhvac_set_action_mode(xv_anyhvac* h, int mode, int flags, const double* cost_table);
+int xv_anyhvac_step_mapped(xv_anyhvac* h, const xv_anyhvac_io* io, const xv_anyhvac_act_io* act, int autoreset_mode);
+int xv_anyhvac_step_mapped_injected(xv_anyhvac* h, const xv_anyhvac_io* io, const xv_anyhvac_act_io* act,
+                                    const double* reset_grid, int autoreset_mode);
+/* T steps in one launch, bit-equal to T calls of xv_anyhvac_step_mapped; every array of io and act has a leading T */
+int xv_anyhvac_rollout_mapped(xv_anyhvac* h, int T, const xv_anyhvac_io* io, const xv_anyhvac_act_io* act, int autoreset_mode);
+/* window uint64[n_env][C]: device pointer */
+int xv_anyhvac_act_get_state(xv_anyhvac* h, uint64_t* window);
+int xv_anyhvac_act_set_state(xv_anyhvac* h, const uint64_t* window);
+
 #ifdef __cplusplus
 }
 #endif

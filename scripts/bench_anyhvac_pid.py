@@ -6,10 +6,14 @@
 (ii) HVACSolverGridSearchPID.search: 10 x 10 x 10 gain triples, 64 steps, on the `rot` room (6 coolers, 6 sensors) — one
      batch of 1,000 envs; the time includes building the private env and its tables.
 
+(iii) with --action-mode discrete | diff: rollout(actions) of shape (i) under that action mode (the difference mode with
+     integer bins and the action cost on) against the box-mode rollout of the same room, batch and T, alternating.
+
 Clock: a host clock around calls that end in a device synchronise.  Every timed shape is run once before it is timed;
 each figure is the median of `--repeats` alternated samples, all samples are kept in the output.
 
-usage: python scripts/bench_anyhvac_pid.py [--envs 1024] [--T 16] [--repeats 5] [--out profiles/anyhvac_pid_bench.json]
+usage: python scripts/bench_anyhvac_pid.py [--envs 1024] [--T 16] [--repeats 5] [--action-mode box]
+                                           [--out profiles/anyhvac_pid_bench.json]
 """
 import argparse
 import json
@@ -69,6 +73,40 @@ def controller_cost(room, n, T, repeats, iter_per_step, sec_per_iter):
                 teacher_env_steps_per_s=n * T / a, samples_teacher_s=teacher, samples_rollout_s=replay, device_errors=errors)
 
 
+def action_mode_cost(room, n, T, repeats, iter_per_step, sec_per_iter, mode):
+    task, grid = load_room(room)
+    grids = np.repeat(grid[None], n, axis=0)
+    C = len(task["cooler_loc"])
+    rng = np.random.RandomState(0)
+    opts = dict(action_mode=mode)
+    if mode == "diff":
+        opts.update(discretize_rl_action_space=True, add_action_cost=True)
+        mapped_actions = torch.from_numpy(rng.randint(0, 13, (T, n, C)).astype(np.int32)).cuda()
+    else:
+        mapped_actions = torch.from_numpy(rng.uniform(0, 1, (T, n, C)).astype(np.float32)).cuda()
+    box_actions = torch.from_numpy(rng.uniform(0, 1, (T, n, C)).astype(np.float32)).cuda()
+    envs = []
+    for o in ({}, opts):
+        env = HVACVecEnv(n, iter_per_step=iter_per_step, sec_per_iter=sec_per_iter, autoreset_mode="disabled", **o)
+        env.set_task([task], generate_task=True)
+        envs.append(env)
+    box, mapped = envs
+    samples = {"box": [], mode: []}
+    for i in range(repeats + 1):      # (the first round warms both shapes up)
+        for key, env, acts in (("box", box, box_actions), (mode, mapped, mapped_actions)):
+            env.reset_injected(grids)
+            t = timed(lambda: env.rollout(acts), env)
+            if i:
+                samples[key].append(t)
+    errors = box.check_errors() | mapped.check_errors()
+    box.close()
+    mapped.close()
+    a, b = statistics.median(samples["box"]), statistics.median(samples[mode])
+    return dict(room=room, coolers=C, sensors=len(task["sensor_loc"]), envs=n, T=T, iter_per_step=iter_per_step,
+                sec_per_iter=sec_per_iter, action_mode=mode, box_rollout_s=a, mapped_rollout_s=b, mapped_over_box=b / a,
+                samples_box_s=samples["box"], samples_mapped_s=samples[mode], device_errors=errors)
+
+
 def search_time(repeats, max_steps=64, points=10):
     task, grid = load_room("gt_rot")
     env = HVACEnv()
@@ -92,6 +130,7 @@ def main():
     ap.add_argument("--envs", type=int, default=1024)
     ap.add_argument("--T", type=int, default=16)
     ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--action-mode", default="box", choices=("box", "discrete", "diff"))
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "anyhvac_pid_bench.json"))
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -100,10 +139,14 @@ def main():
                controller_cost=[controller_cost("gt_rot", a.envs, a.T, a.repeats, 200, 0.15),
                                 controller_cost("gt_wide", max(a.envs // 4, 1), max(a.T // 4, 1), a.repeats, 200, 0.15)],
                search=search_time(a.repeats))
+    if a.action_mode != "box":
+        out["action_mode_cost"] = [action_mode_cost("gt_rot", a.envs, a.T, a.repeats, 200, 0.15, a.action_mode),
+                                   action_mode_cost("gt_wide", max(a.envs // 4, 1), max(a.T // 4, 1), a.repeats, 200, 0.15,
+                                                    a.action_mode)]
     with open(a.out, "w") as f:
         json.dump(out, f, indent=1)
         f.write("\n")
-    print(json.dumps({k: out[k] for k in ("controller_cost", "search")}))
+    print(json.dumps({k: out[k] for k in ("controller_cost", "search", "action_mode_cost") if k in out}))
 
 
 if __name__ == "__main__":

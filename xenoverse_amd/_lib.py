@@ -167,6 +167,12 @@ SIGNATURES = {
     "xv_anyhvac_pid_get_state": [c_void_p, c_void_p, c_void_p, c_void_p],
     "xv_anyhvac_pid_set_state": [c_void_p, c_void_p, c_void_p, c_void_p],
     "xv_anyhvac_pid_reset": [c_void_p, c_void_p],
+    "xv_anyhvac_set_action_mode": [c_void_p, c_int, c_int, c_void_p],       # (handle, mode, flags, host cost table)
+    "xv_anyhvac_step_mapped": [c_void_p, c_void_p, c_void_p, c_int],        # (handle, xv_anyhvac_io*, xv_anyhvac_act_io*, mode)
+    "xv_anyhvac_step_mapped_injected": [c_void_p, c_void_p, c_void_p, c_void_p, c_int],
+    "xv_anyhvac_rollout_mapped": [c_void_p, c_int, c_void_p, c_void_p, c_int],
+    "xv_anyhvac_act_get_state": [c_void_p, c_void_p],
+    "xv_anyhvac_act_set_state": [c_void_p, c_void_p],
 }
 for _p in ("xv_cartpole", "xv_acrobot"):      # the control families share one set of entry points (csrc/xv_control.h)
     SIGNATURES.update({
@@ -211,6 +217,12 @@ class AnyHVACState(C.Structure):
     """xv_anyhvac_state (include/xeno.h)"""
     FIELDS = ("grid", "t", "last_call", "episode_step", "warning_count", "rest_idx", "rest_start", "value", "filter",
               "ring_t", "ring_v", "head", "tail")
+    _fields_ = [(k, C.c_void_p) for k in FIELDS]
+
+
+class AnyHVACActIO(C.Structure):
+    """xv_anyhvac_act_io (include/xeno.h)"""
+    FIELDS = ("action_index", "applied_value", "delta", "action_cost", "stat_counts")
     _fields_ = [(k, C.c_void_p) for k in FIELDS]
 
 

@@ -5,12 +5,15 @@
 HVACTaskSampler / task_from_reference: tasks as flat dicts (task_sampler.py); HVACHost: the fp64 numpy restatement, pinned
 bit for bit to recorded runs of the reference (host.py); HVACVecEnv / HVACEnv: the device envs (vec_env.py);
 PIDHost / pid_weights / pid_search_host: the reference's PID teachers restated on the host (pid.py);
-HVACSolverGTPID / HVACSolverLOCPID / HVACSolverGridSearchPID: the teachers on the device (vec_env.py).
+HVACSolverGTPID / HVACSolverLOCPID / HVACSolverGridSearchPID: the teachers on the device (vec_env.py);
+DiscreteActionHost / DiffActionHost: the reference's RL action spaces restated on the host (actions.py);
+HVACEnvDiscreteAction / HVACEnvDiffAction: the same on the device, HVACVecEnv(action_mode=...) batched (vec_env.py).
 """
+from .actions import ActionMapHost, DiffActionHost, DiscreteActionHost            # noqa: F401
 from .config import DEFAULTS                                                      # noqa: F401
 from .host import HVACHost, average_total_heat, check_settings, heater_powers    # noqa: F401
 from .pid import PIDHost, pid_search_host, pid_weights                            # noqa: F401
 from .task_sampler import HVACTaskSampler, task_from_reference, wind_diffuser    # noqa: F401
 from .tables import build_tables                                                  # noqa: F401
-from .vec_env import (HVACEnv, HVACSolverGridSearchPID, HVACSolverGTPID, HVACSolverLOCPID,   # noqa: F401
+from .vec_env import (HVACEnv, HVACEnvDiffAction, HVACEnvDiscreteAction, HVACSolverGridSearchPID, HVACSolverGTPID, HVACSolverLOCPID,   # noqa: F401
                       HVACVecEnv)

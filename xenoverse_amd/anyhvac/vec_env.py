@@ -12,6 +12,12 @@ The PID teachers (pid.py restates the reference's solvers on the host): set_pid(
 the device, pid_action() makes one controller call, rollout_teacher(T) runs T controller-driven steps in ONE launch.
 HVACSolverGTPID / HVACSolverLOCPID / HVACSolverGridSearchPID are the reference-shaped classes over the one-room HVACEnv;
 the grid search evaluates its candidates as the envs of one batch.
+
+The RL action spaces (actions.py restates the reference's classes on the host): HVACVecEnv(action_mode="discrete" | "diff")
+maps every step's raw actions inside the step kernel — float32 [N, C], or under action_mode="diff" with
+discretize_rl_action_space=True an integer tensor of bins 0...12 — and adds info["applied_value"], info["delta"],
+info["action_cost"] (with add_action_cost) and info["step_stat"].  HVACEnvDiscreteAction / HVACEnvDiffAction are the
+reference-shaped one-room classes.
 """
 import itertools
 import ctypes as C
@@ -21,8 +27,9 @@ import torch
 
 from .. import _lib
 from ..engine import AUTORESET
-from ..spaces import Box
+from ..spaces import Box, MultiDiscrete
 from ..vector import VectorEnv
+from .actions import ACTION_MODES, COST_TABLE, N_BINS, STAT_KEYS, RunningStat
 from .config import RING_CAPACITY
 from .host import check_ring, check_settings
 from .pid import DEFAULT_GAINS, GAINS, first_strict_minimum, pid_weights, search_score
@@ -39,8 +46,13 @@ class HVACVecEnv(VectorEnv):
     def __init__(self, num_envs, max_steps=20160, iter_per_step=200, sec_per_iter=0.15, set_lower_bound=16,
                  set_upper_bound=32, reward_mode=0, include_heat_in_observation=True,
                  include_last_action_in_observation=True, include_timestep_in_observation=True, device="cuda:0", seed=0,
-                 env_id_base=0, autoreset_mode="same_step", to_numpy=False, engine=None, **excluded):
+                 env_id_base=0, autoreset_mode="same_step", to_numpy=False, engine=None, action_mode="box",
+                 discretize_rl_action_space=False, add_action_cost=False, too_cold_limit=True, **excluded):
         check_settings(**excluded)
+        if action_mode not in ACTION_MODES:
+            raise ValueError("action_mode must be one of %s" % (ACTION_MODES,))
+        if action_mode != "diff" and (discretize_rl_action_space or add_action_cost):
+            raise ValueError("discretize_rl_action_space and add_action_cost belong to action_mode='diff'")
         if reward_mode not in (0, 1, 2):
             raise ValueError("reward_mode must be 0, 1 or 2")
         if autoreset_mode == "next_step":
@@ -54,6 +66,9 @@ class HVACVecEnv(VectorEnv):
         self.include = dict(heat_readings=bool(include_heat_in_observation),
                             action_temp=bool(include_last_action_in_observation),
                             timestep=bool(include_timestep_in_observation))
+        self.action_mode = action_mode
+        self.discretize_rl_action_space, self.add_action_cost = bool(discretize_rl_action_space), bool(add_action_cost)
+        self.too_cold_limit = bool(too_cold_limit)
         self._h = None
         self._pid = None
         self.need_reset = True
@@ -91,7 +106,11 @@ class HVACVecEnv(VectorEnv):
                                               float(max_t), self.reward_mode, C.byref(h)))
         self._h = h
         _lib.check(self.lib.xv_anyhvac_set_task(h, n_task, _lib.ptr(self._tab["table"]), _lib.ptr(self._tab["env_task"])))
-        self._set_spaces(None, Box(0.0, 1.0, shape=(Cc,), dtype=np.float32))
+        self._push_action_mode()
+        if self.action_mode == "diff" and self.discretize_rl_action_space:
+            self._set_spaces(None, MultiDiscrete([N_BINS] * Cc))
+        else:
+            self._set_spaces(None, Box(0.0, 1.0, shape=(Cc,), dtype=np.float32))
         self.single_observation_spaces = dict(
             sensor_readings=Box(10, 50, shape=(S,), dtype=np.float32), heat_readings=Box(0.0, 50000.0, shape=(H,)),
             action_temp=Box(-1, 33, shape=(Cc,)), timestep=Box(0, 30000, shape=(1,), dtype=np.int32))
@@ -101,6 +120,24 @@ class HVACVecEnv(VectorEnv):
         self._tasks, self._generate_task = list(tasks), bool(generate_task)
         self.task_set = True
         self.need_reset = True
+
+    def _push_action_mode(self):
+        if self.action_mode == "box":
+            return
+        flags = 0
+        if self.action_mode == "diff":
+            flags = (1 if self.add_action_cost else 0) | (2 if self.too_cold_limit else 0)
+        table = np.ascontiguousarray(COST_TABLE, np.float64)
+        _lib.check(self.lib.xv_anyhvac_set_action_mode(self._h, ACTION_MODES.index(self.action_mode), flags,
+                                                       table.ctypes.data_as(C.c_void_p)))
+
+    def set_too_cold_limit(self, too_cold_limit):
+        """the reference's setter: from the next step on; the action windows are kept"""
+        if self.action_mode != "diff":
+            raise ValueError("too_cold_limit belongs to action_mode='diff'")
+        self.too_cold_limit = bool(too_cold_limit)
+        if self._h is not None:
+            self._push_action_mode()      # (the mode stays: only the flags change)
 
     def _set_spaces(self, single_obs, single_act):
         self.single_observation_space = self.observation_space = single_obs
@@ -118,6 +155,9 @@ class HVACVecEnv(VectorEnv):
                  action_temp=z((Cc,), torch.float32), timestep=z((), torch.int32), reward=z((), torch.float64),
                  terminated=z((), torch.uint8), truncated=z((), torch.uint8), cool_power=z((Cc,), torch.float32),
                  heat_power=z((H,), torch.float64), misc=z((8,), torch.float64))
+        if self.action_mode != "box":
+            b.update(applied_value=z((Cc,), torch.float32), delta=z((Cc,), torch.float64), action_cost=z((), torch.float64),
+                     stat_counts=z((len(STAT_KEYS),), torch.int32))
         if final:
             for k, dt in zip(OBS_KEYS, (torch.float32, torch.float32, torch.float32, torch.int32)):
                 b["final_" + k] = z(b[k].shape[len(shape):], dt)
@@ -142,6 +182,14 @@ class HVACVecEnv(VectorEnv):
         misc = b["misc"]
         info = {k: self._out(misc[..., i]) for i, k in enumerate(MISC)}
         info["cool_power"], info["heat_power"] = self._out(b["cool_power"]), self._out(b["heat_power"])
+        if self.action_mode != "box":
+            info["applied_value"], info["delta"] = self._out(b["applied_value"]), self._out(b["delta"])
+            if self.add_action_cost:
+                info["action_cost"] = self._out(b["action_cost"])
+            stat = {k: self._out(b["stat_counts"][..., i]) for i, k in enumerate(STAT_KEYS)}
+            stat.update(fail=self._out(b["terminated"].to(torch.int32)), reward=self._out(b["reward"]),
+                        cooler_power=self._out(torch.round(b["cool_power"].sum(-1), decimals=4)))
+            info["step_stat"] = stat
         if self.autoreset_mode == "same_step":
             info["final_obs"] = self._obs(b, "final_")
             info["_final_obs"] = self._out((b["terminated"] | b["truncated"]).bool())
@@ -163,6 +211,58 @@ class HVACVecEnv(VectorEnv):
         if a.shape != tuple(lead) + (self.num_envs, self.dims[2]):
             raise ValueError("actions must have shape %s" % (tuple(lead) + (self.num_envs, self.dims[2]),))
         return a
+
+    def _mapped(self, actions, T=None, reset_state=None):
+        """one launch of a mapped mode: step (T None), step_injected (reset_state given) or rollout (T steps)"""
+        lead = () if T is None else (T,)
+        shape = tuple(lead) + (self.num_envs, self.dims[2])
+        integer = (actions.dtype in (torch.int32, torch.int64)) if torch.is_tensor(actions) else \
+            np.issubdtype(np.asarray(actions).dtype, np.integer)
+        a = idx = None
+        if integer:
+            if not (self.action_mode == "diff" and self.discretize_rl_action_space):
+                raise ValueError("integer actions need action_mode='diff' with discretize_rl_action_space=True")
+            idx = self._dev(actions, torch.int32)
+        else:
+            a = self._dev(actions, torch.float32)
+        if (idx if integer else a).shape != shape:
+            raise ValueError("actions must have shape %s" % (shape,))
+        b = self._buffers(lead, self.autoreset_mode == "same_step")
+        io = self._io(b, a)
+        act = _lib.AnyHVACActIO()
+        act.action_index = _lib.ptr(idx)
+        for k in _lib.AnyHVACActIO.FIELDS[1:]:
+            setattr(act, k, b[k].data_ptr())
+        mode = AUTORESET[self.autoreset_mode]
+        if T is not None:
+            _lib.check(self.lib.xv_anyhvac_rollout_mapped(self._h, T, C.byref(io), C.byref(act), mode))
+        elif reset_state is not None:
+            g = self._pad_grid(reset_state)
+            _lib.check(self.lib.xv_anyhvac_step_mapped_injected(self._h, C.byref(io), C.byref(act), _lib.ptr(g), mode))
+        else:
+            _lib.check(self.lib.xv_anyhvac_step_mapped(self._h, C.byref(io), C.byref(act), mode))
+        return self._result(b)
+
+    def get_act_state(self):
+        """-> dict(window int64 [N, C]): per cooler the last <= 10 bins of the action cost's window, 4 bits per entry holding
+        bin + 1, the newest lowest, 0 = empty"""
+        self._require_task()
+        if self.action_mode == "box":
+            raise ValueError("action_mode='box' keeps no action state")
+        w = torch.empty((self.num_envs, self.dims[2]), dtype=torch.int64, device=self.device)
+        _lib.check(self.lib.xv_anyhvac_act_get_state(self._h, _lib.ptr(w)))
+        self.engine.sync()
+        return dict(window=w)
+
+    def set_act_state(self, window):
+        self._require_task()
+        if self.action_mode == "box":
+            raise ValueError("action_mode='box' keeps no action state")
+        w = self._dev(window, torch.int64)
+        if tuple(w.shape) != (self.num_envs, self.dims[2]):
+            raise ValueError("window must have shape %s" % ((self.num_envs, self.dims[2]),))
+        _lib.check(self.lib.xv_anyhvac_act_set_state(self._h, _lib.ptr(w)))
+        self.engine.sync()
 
     # -- episode --------------------------------------------------------------------------------------------------
     def reset(self, *, seed=None, options=None):
@@ -199,6 +299,8 @@ class HVACVecEnv(VectorEnv):
 
     def step(self, actions):
         self._require_reset()
+        if self.action_mode != "box":
+            return self._mapped(actions)
         a = self._actions(actions)
         b = self._buffers((), self.autoreset_mode == "same_step")
         io = self._io(b, a)
@@ -208,6 +310,8 @@ class HVACVecEnv(VectorEnv):
 
     def step_injected(self, actions, reset_state):
         self._require_reset()
+        if self.action_mode != "box":
+            return self._mapped(actions, reset_state=reset_state)
         a, g = self._actions(actions), self._pad_grid(reset_state)
         b = self._buffers((), self.autoreset_mode == "same_step")
         io = self._io(b, a)
@@ -220,6 +324,8 @@ class HVACVecEnv(VectorEnv):
         launch; bit-equal to T calls of step()"""
         self._require_reset()
         T = int(torch.as_tensor(actions).shape[0]) if not torch.is_tensor(actions) else int(actions.shape[0])
+        if self.action_mode != "box":
+            return self._mapped(actions, T=T)
         a = self._actions(actions, (T,))
         b = self._buffers((T,), self.autoreset_mode == "same_step")
         io = self._io(b, a)
@@ -234,6 +340,8 @@ class HVACVecEnv(VectorEnv):
         (HVACSolverLOCPID's); weights: one float64 [S_task, C_task] matrix per task instead.  kp, ki, kd: scalars or [N]
         arrays, one triple per env.  gains: 'python' (the arithmetic of Python-float gains, the solvers' defaults) or
         'float64' (of numpy.float64 gains, the grid search's).  The controllers start as new solvers do."""
+        if self.action_mode != "box":
+            raise ValueError("the PID teachers put out box actions: set_pid needs action_mode='box'")
         self._require_task()
         if gains not in GAINS:
             raise ValueError("gains must be one of %s" % (GAINS,))
@@ -288,6 +396,8 @@ class HVACVecEnv(VectorEnv):
         the T steps' resulting readings of the real sensors, e = reading - target in float32: sum |e|, max |e|, sum e^2,
         count(|e| <= 1), count(|e| <= 2), count(reading > target + 2), sum of rewards, sample count.  stats: a tensor
         of an earlier call to go on accumulating into."""
+        if self.action_mode != "box":
+            raise ValueError("the PID teachers put out box actions: rollout_teacher needs action_mode='box'")
         self._require_pid()
         self._require_reset()
         T = int(T)
@@ -412,12 +522,13 @@ class HVACEnv(object):
     """one room with the reference's surface: HVACEnv(**keywords); set_task(task, generate_task=False); reset() ->
     (obs, info); step(action[C]) -> (obs, reward, terminated, truncated, info), numpy arrays of the room's true sizes.
     The episode is not reset behind the caller's back (autoreset_mode='disabled')."""
+    ACTION_MODE = "box"
 
     def __init__(self, max_steps=20160, iter_per_step=200, sec_per_iter=0.15, set_lower_bound=16, set_upper_bound=32,
                  verbose=False, action_space_format='box', include_heat_in_observation=True,
                  include_switch_in_observation=False, include_last_action_in_observation=True,
                  include_timestep_in_observation=True, no_switch_action=True, reward_mode=0, device="cuda:0", seed=0):
-        self.vec = HVACVecEnv(1, max_steps=max_steps, iter_per_step=iter_per_step, sec_per_iter=sec_per_iter,
+        self.vec = HVACVecEnv(1, action_mode=self.ACTION_MODE, max_steps=max_steps, iter_per_step=iter_per_step, sec_per_iter=sec_per_iter,
                               set_lower_bound=set_lower_bound, set_upper_bound=set_upper_bound, reward_mode=reward_mode,
                               include_heat_in_observation=include_heat_in_observation,
                               include_last_action_in_observation=include_last_action_in_observation,
@@ -453,10 +564,13 @@ class HVACEnv(object):
         return self._np(obs), {"time": 0.0}
 
     def step(self, action):
-        a = np.zeros((1, self.vec.dims[2]), np.float32)
         n = int(self.vec.counts["coolers"][0])
-        a[0, :n] = np.asarray(action, np.float32).reshape(-1)[:n]
+        action = np.asarray(action)
+        integer = self.ACTION_MODE == "diff" and self.vec.discretize_rl_action_space and np.issubdtype(action.dtype, np.integer)
+        a = np.zeros((1, self.vec.dims[2]), np.int32 if integer else np.float32)
+        a[0, :n] = action.reshape(-1)[:n]
         obs, r, term, trunc, info = self.vec.step(a)
+        self._last = info
         c = self.vec.counts
         out = {k: float(info[k][0]) for k in ("energy_cost", "target_cost", "time")}
         out.update(over_heat=int(info["over_heat"][0]), over_tolerace=int(info["over_tolerace"][0]),
@@ -473,6 +587,58 @@ class HVACEnv(object):
 
     def close(self):
         self.vec.close()
+
+
+class _StatEnv(HVACEnv):
+    """HVACEnv + stat(): info["step_stat"] with the reference's keys and its running averages as attributes"""
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        self.stats = RunningStat()
+
+    def _finish(self, out):
+        obs, reward, terminated, truncated, info = out
+        raw = self._last
+        n = int(self.vec.counts["coolers"][0])
+        info["last_control"] = {"value": raw["applied_value"][0, :n].cpu().numpy()}
+        if self.vec.add_action_cost:
+            info["action_cost"] = float(raw["action_cost"][0])
+        cnt = [int(raw["step_stat"][k][0]) for k in STAT_KEYS]
+        info["step_stat"] = self.stats.update(int(raw["episode_step"][0]), int(self.vec.counts["sensors"][0]), cnt[:4], cnt[4:],
+                                              info["cool_power"], terminated, reward)
+        return obs, reward, terminated, truncated, info
+
+
+for _k in ("avg_reward", "avg_cooler_power_per_step", "over_heat_percentage", "over_cool_percentage", "fail_percentage"):
+    setattr(_StatEnv, _k, property(lambda self, k=_k: getattr(self.stats, k)))
+
+
+class HVACEnvDiscreteAction(_StatEnv):
+    """the reference's HVACEnvDiscreteAction: absolute actions rounded to 0.1 K on the device, info["step_stat"]"""
+    ACTION_MODE = "discrete"
+
+    def step(self, action):
+        return self._finish(super().step(action))
+
+
+class HVACEnvDiffAction(_StatEnv):
+    """the reference's HVACEnvDiffAction: each action is one of 13 temperature steps on the cooler's previous set-point"""
+    ACTION_MODE = "diff"
+
+    def set_too_cold_limit(self, too_cold_limit):
+        self.vec.set_too_cold_limit(too_cold_limit)
+
+    def set_task(self, task, discretize_rl_action_space=False, add_action_cost=False, too_cold_limit=True,
+                 generate_task=False):
+        vec = self.vec      # (the options go to the device with the handle set_task builds)
+        vec.discretize_rl_action_space, vec.add_action_cost = bool(discretize_rl_action_space), bool(add_action_cost)
+        vec.too_cold_limit = bool(too_cold_limit)
+        super().set_task(task, generate_task=generate_task)
+
+    def step(self, action, call_diff_action=True):
+        if not call_diff_action:
+            raise ValueError("call_diff_action=False is not supported by xenoverse_amd.anyhvac (the mapping runs on the device)")
+        return self._finish(super().step(action))
 
 
 class HVACSolverGTPID(object):

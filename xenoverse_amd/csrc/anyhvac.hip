@@ -19,6 +19,13 @@
 // barrier lanes strided over the coolers sum d_e[s] corr[s][c] over the task's sensors in index order (a row of the
 // row-major weights is read coalesced across c), clip, round to float32 and write 1 - value.  It is called by a kernel of
 // its own (xv_anyhvac_pid_action) and, as the PID instantiation of the step kernel, in front of every step of a rollout.
+//
+// The RL action spaces (anyhvac_env.py HVACEnvDiscreteAction / HVACEnvDiffAction; host restatement
+// xenoverse_amd/anyhvac/actions.py) are the step kernel's action mode AM: in the two mapped modes the lane that owns a
+// cooler turns the raw input — a float32, or an int32 bin under the difference mode — into this step's value from the
+// value the env applied at the step before, in the host's operations and order; the action cost keeps each cooler's last
+// ten bins in one 64-bit word; the eight stat() counts are taken on the float32 readings of the observation.  All of it sits
+// outside the iteration loop and uses the LDS the box kernel has (s_ne before the loop, s_red after it).
 #include <cmath>
 #include <new>
 
@@ -34,6 +41,7 @@
 #define HV_DRAW_GRID 7u      // Philox purpose of the reset grid (sub-index: the cell)
 #define HV_REST_SECONDS 3600.0
 #define HV_MAX_HEAT 20000.0
+#define HV_WINDOW_MASK ((1ull << 40) - 1)      // ten 4-bit entries: bin + 1, 0 = empty; the newest in the low bits
 
 struct HvArgs {
   int NW, NL, C, S, H, KS, KH;      // padded sizes of the tables
@@ -53,9 +61,22 @@ struct HvArgs {
   const uint64_t* tick_dev;
 };
 
+struct HvAct {      // the mapped action modes' arguments (xv_anyhvac_set_action_mode, xv_anyhvac_act_io)
+  const int32_t* index;            // [T][n_env][C] bins, or null: io.action's floats are mapped
+  float* applied;                  // [T][n_env][C] or null
+  double *delta, *cost;            // [T][n_env][C], [T][n_env] or null
+  int32_t* counts;                 // [T][n_env][XV_ANYHVAC_STAT_COUNTS] or null
+  unsigned long long* window;      // [n_env][C]
+  const double* table;             // [XV_ANYHVAC_ACT_BINS] the cost's non-zero-step term per bin
+  int flags;
+};
+
 struct xv_anyhvac {
   xv_engine* eng;
   HvArgs a;
+  int act_mode, act_flags;
+  unsigned long long* act_window;
+  double* act_table;
   // the PID teacher's arguments (xv_anyhvac_set_pid): weights, gains, arithmetic flag; the state it owns
   const double *pid_weights, *pid_gains;
   int pid_f64;
@@ -158,10 +179,12 @@ __device__ __forceinline__ HvObsOut hv_obs_rows(float* sensor, float* heat, floa
 }
 
 // _get_obs: sensor readings, heater powers, set temperatures and the step index at time t; padded columns are zero.
+// cnt (nullable): eight counters this lane's readings are added to, stat()'s thresholds.
 // loss / hot (nullable): this lane's share of sum max(sqrt(d), d), d = clip(reading - target, 0, 8) in float32, and of the
 // count of readings above the failure bound; keep (nullable): the readings once more, [P.S] in LDS, entry s by lane s % HV_BLOCK
 __device__ __forceinline__ void hv_obs(const HvArgs& P, const HvTask& K, const double* g, double t, int rest, const float* value,
-                                       const HvObsOut& o, double* loss, double* hot, float* keep = nullptr) {
+                                       const HvObsOut& o, double* loss, double* hot, float* keep = nullptr,
+                                       int* cnt = nullptr) {
   const int tid = threadIdx.x;
   const float target = (float)K.sc[9];
   const double fub = K.sc[15];
@@ -174,6 +197,11 @@ __device__ __forceinline__ void hv_obs(const HvArgs& P, const HvTask& K, const d
       const float d = fminf(fmaxf(v - target, 0.0f), 8.0f);
       ls += (double)fmaxf(sqrtf(d), d);
       ht += ((double)v > fub) ? 1.0 : 0.0;
+      if (cnt) {      // stat(): reading - target in float32 against 0, +-2, +-4, +-6 (this lane's share)
+        const float e = v - target;
+        cnt[0] += e > 0.0f; cnt[1] += e > 2.0f; cnt[2] += e > 4.0f; cnt[3] += e > 6.0f;
+        cnt[4] += e < 0.0f; cnt[5] += e < -2.0f; cnt[6] += e < -4.0f; cnt[7] += e < -6.0f;
+      }
     }
     if (o.sensor) o.sensor[s] = v;
     if (keep) keep[s] = v;
@@ -261,6 +289,12 @@ __device__ __forceinline__ void hv_store(const HvArgs& P, int env, const double*
       P.head[(size_t)env * P.C + c] = E.head[q];
     }
   }
+}
+
+__global__ __launch_bounds__(HV_BLOCK) void xv_anyhvac_act_reset_kernel(unsigned long long* window, int C, const uint8_t* mask) {
+  const int env = blockIdx.x;
+  if (mask && !mask[env]) return;
+  for (int c = threadIdx.x; c < C; c += HV_BLOCK) window[(size_t)env * C + c] = 0ull;
 }
 
 template <bool INJECT>
@@ -384,10 +418,54 @@ __global__ __launch_bounds__(HV_BLOCK) void xv_anyhvac_pid_kernel(HvArgs P, HvPi
   hv_pid(P, K, D, env, s_obs, s_de, D.action_out + (size_t)env * P.C, D.flat_out ? D.flat_out + (size_t)env * 2 * P.C : nullptr);
 }
 
+// one mapped action of cooler c: the raw input and the value applied at the step before -> this step's value before the
+// base step's clip (fp64), the bin taken (idx; 6 = no change) and whether the input was in range.  The host's operations
+// in the host's order (actions.py): float32 v (ub - lb) + lb; under DIFF an fp64 add of the bin's step, the target - 3
+// floor, / 0.1 in fp64; under DISCRETE / 0.1 in float32; round half to even, * 0.1 in fp64, back to a value.
+template <int AM>
+__device__ __forceinline__ double hv_map_action(const HvArgs& P, const HvTask& K, const HvAct& A, size_t at, const float* act_in,
+                                                float last, int& idx, bool& ok) {
+  const float span = (float)(P.ub - P.lb), lo = (float)P.lb;
+  double temp;
+  idx = (XV_ANYHVAC_ACT_BINS - 1) / 2;
+  if (AM == XV_ANYHVAC_ACT_DIFF) {
+    if (A.index) {
+      const int i = A.index[at];
+      ok = i >= 0 && i < XV_ANYHVAC_ACT_BINS;
+      if (ok) idx = i;
+    } else {
+      const float raw = act_in[at];
+      ok = raw == raw;
+      if (ok) idx = (int)fminf(fmaxf(rintf(raw * (float)(XV_ANYHVAC_ACT_BINS - 1)), 0.0f), (float)(XV_ANYHVAC_ACT_BINS - 1));
+    }
+    temp = (double)(last * span + lo) + (-3.0 + 0.5 * (double)idx);
+    const double floor_temp = K.sc[9] - 3.0;
+    if ((A.flags & XV_ANYHVAC_ACT_TOO_COLD_LIMIT) && temp < floor_temp) temp = floor_temp;
+    temp = rint(temp / 0.1) * 0.1;
+  } else {
+    const float raw = act_in[at];
+    ok = raw == raw;
+    temp = (double)rintf((raw * span + lo) / 0.1f) * 0.1;
+  }
+  return (temp - P.lb) / (P.ub - P.lb);
+}
+
+// adjacent nonzero sign reversals among a window's entries (bin + 1 per 4 bits; 7 is the zero step)
+__device__ __forceinline__ int hv_reversals(unsigned long long w) {
+  int n = 0;
+#pragma unroll
+  for (int j = 0; j < 9; ++j) {
+    const int a = (int)((w >> (4 * j)) & 15u), b = (int)((w >> (4 * j + 4)) & 15u);
+    n += (a != 0 && b != 0 && ((a > 7 && b < 7) || (a < 7 && b > 7))) ? 1 : 0;
+  }
+  return n;
+}
+
 // PID: the teacher's controller call in front of every step (the action is D.action_out's row, not io.action's)
-template <bool INJECT, bool PID>
+// AM: XV_ANYHVAC_ACT_BOX (the action row is the value), _DISCRETE, _DIFF (the row is mapped, hv_map_action)
+template <bool INJECT, bool PID, int AM>
 __global__ __launch_bounds__(HV_BLOCK) void xv_anyhvac_step_kernel(HvArgs P, xv_anyhvac_io io, const double* reset_grid,
-                                                                   int mode, int T, HvPid D) {
+                                                                   int mode, int T, HvPid D, HvAct A) {
   __shared__ double s_grid[2][HV_MAX_GRID * HV_MAX_GRID];
   __shared__ double s_static[HV_MAX_GRID * HV_MAX_GRID];
   __shared__ double s_chtc[HV_MAX_WALL];
@@ -438,20 +516,49 @@ __global__ __launch_bounds__(HV_BLOCK) void xv_anyhvac_step_kernel(HvArgs P, xv_
     // -- the teacher: readings -> PID -> this step's action row (column c is written by the lane that reads it below)
     if (PID) hv_pid(P, K, D, env, s_obs, s_de, D.action_out + row * P.C, nullptr);
     // -- this step's action: clipped float32, the resting cooler's replaced by the default value
+    const bool cost_on = AM == XV_ANYHVAC_ACT_DIFF && (A.flags & XV_ANYHVAC_ACT_COST) != 0;
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
       const int c = tid + q * HV_BLOCK;
       if (c < P.C) {
-        float v = act_in[row * P.C + c];
-        v = fminf(fmaxf(v, 0.0f), 1.0f);
-        if (!(v == v)) v = 0.0f;
+        float v;
+        if (AM == XV_ANYHVAC_ACT_BOX) {
+          v = act_in[row * P.C + c];
+          v = fminf(fmaxf(v, 0.0f), 1.0f);
+          if (!(v == v)) v = 0.0f;
+        } else {      // padded columns keep their value and put out zeros
+          v = value[c];
+          double dl = 0.0;
+          if (c < K.nC) {
+            int idx;
+            bool ok;
+            const double x = hv_map_action<AM>(P, K, A, row * P.C + c, act_in, v, idx, ok);
+            if (ok) v = (float)fmin(fmax(x, 0.0), 1.0);      // (out of range: the value keeps its bits, the bin is 6)
+            else atomicOr(P.err, XV_DEVERR_ACTION_RANGE);
+            if (AM == XV_ANYHVAC_ACT_DIFF) dl = -3.0 + 0.5 * (double)idx;
+            if (cost_on) {
+              unsigned long long* wp = A.window + (size_t)env * P.C + c;
+              const unsigned long long w = ((*wp << 4) | (unsigned long long)(idx + 1)) & HV_WINDOW_MASK;
+              *wp = w;
+              s_ne[c] = 0.5 * A.table[idx] + 0.5 * ((double)hv_reversals(w) * 0.6);
+            }
+          }
+          if (A.delta) A.delta[row * P.C + c] = dl;
+        }
         if (c == E.rest) v = (float)K.sc[14];
+        if (AM != XV_ANYHVAC_ACT_BOX && A.applied) A.applied[row * P.C + c] = c < K.nC ? v : 0.0f;
         value[c] = v;
         s_energy[c] = 0.0f;
         s_ev[c] = c < K.nC ? K.cool[(size_t)c * 24 + 8] : 0.0;
       }
     }
     __syncthreads();
+    double act_cost = 0.0;      // -mean over the coolers in index order, by every lane (s_ne is free until the loop)
+    if (cost_on) {
+      double cs = 0.0;
+      for (int c = 0; c < K.nC; ++c) cs += s_ne[c];
+      act_cost = -(cs / (double)K.nC);
+    }
     double heat_sum = 0.0;
     for (int h = tid; h < K.nH; h += HV_BLOCK) heat_sum += s_heat[h];
     heat_sum = hv_block_sum(heat_sum, s_red);      // current_heat_power (numpy sums pairwise: last bits may differ)
@@ -554,9 +661,20 @@ __global__ __launch_bounds__(HV_BLOCK) void xv_anyhvac_step_kernel(HvArgs P, xv_
     }
     // -- observation, reward, flags
     double loss, hot;
+    int cnt[XV_ANYHVAC_STAT_COUNTS] = {0, 0, 0, 0, 0, 0, 0, 0};
     hv_obs(P, K, s_grid[cur], E.t, E.rest, value,
            hv_obs_rows(io.sensor_readings, io.heat_readings, io.action_temp, io.timestep, row, P), &loss, &hot,
-           PID ? s_obs : nullptr);
+           PID ? s_obs : nullptr, AM != XV_ANYHVAC_ACT_BOX ? cnt : nullptr);
+    if (AM != XV_ANYHVAC_ACT_BOX && A.counts) {      // four counts (<= 640 each) per fp64 sum, 12 bits apart: exact
+#pragma unroll
+      for (int half = 0; half < 2; ++half) {
+        const int* n = cnt + 4 * half;
+        const double packed = (double)((long long)n[0] | ((long long)n[1] << 12) | ((long long)n[2] << 24) | ((long long)n[3] << 36));
+        const long long tot = (long long)hv_block_sum(packed, s_red);
+        if (tid == 0)
+          for (int i = 0; i < 4; ++i) A.counts[row * XV_ANYHVAC_STAT_COUNTS + 4 * half + i] = (int32_t)((tot >> (12 * i)) & 4095);
+      }
+    }
     if (PID && D.stats) {      // e = reading - target in float32, over the real sensors (this lane's entries of s_obs)
       const float target = (float)K.sc[9], over = (float)(K.sc[9] + 2.0);
       for (int s = tid; s < K.nS; s += HV_BLOCK) {
@@ -596,6 +714,7 @@ __global__ __launch_bounds__(HV_BLOCK) void xv_anyhvac_step_kernel(HvArgs P, xv_
     int term = 0;
     if (E.warning_count > 5) { over_tol = 1; term = 1; reward = -30.0; }
     else reward = (double)(1.0f + target_cost) + 0.0 + energy_cost + 0.0 + (overheat ? -10.0 : 0.0);
+    if (cost_on) reward = reward + act_cost;      // (the failure reward too, as the reference)
     int trunc = E.t >= P.max_t ? 1 : 0;
     if (nonfinite) { reward = NAN; term = 0; trunc = 0; E.warning_count = E0.warning_count; }
     if (PID) st_rew += reward;
@@ -603,6 +722,7 @@ __global__ __launch_bounds__(HV_BLOCK) void xv_anyhvac_step_kernel(HvArgs P, xv_
       io.reward[row] = reward;
       io.terminated[row] = (uint8_t)term;
       io.truncated[row] = (uint8_t)trunc;
+      if (AM != XV_ANYHVAC_ACT_BOX && A.cost) A.cost[row] = act_cost;
       if (io.misc) {
         double* m = io.misc + row * 8;
         m[0] = overheat; m[1] = over_tol; m[2] = energy_cost; m[3] = (double)target_cost; m[4] = E.t; m[5] = E.rest;
@@ -620,6 +740,8 @@ __global__ __launch_bounds__(HV_BLOCK) void xv_anyhvac_step_kernel(HvArgs P, xv_
              hv_obs_rows(io.sensor_readings, io.heat_readings, io.action_temp, io.timestep, row, P), nullptr, nullptr,
              PID ? s_obs : nullptr);
       if (PID) hv_pid_clear(P, D, env);      // the new episode starts with a fresh controller
+      if (AM != XV_ANYHVAC_ACT_BOX)          // ... and an empty window (each lane its own coolers' words)
+        for (int c = tid; c < P.C; c += HV_BLOCK) A.window[(size_t)env * P.C + c] = 0ull;
     } else {
       if (fin.sensor) for (int s = tid; s < P.S; s += HV_BLOCK) fin.sensor[s] = 0.0f;
       if (fin.heat) for (int h = tid; h < P.H; h += HV_BLOCK) fin.heat[h] = 0.0f;
@@ -659,7 +781,7 @@ extern "C" int xv_anyhvac_destroy(xv_anyhvac* h) {
   (void)hipStreamSynchronize(h->eng->stream);
   HvArgs& a = h->a;
   void* ps[] = {a.grid, a.t, a.last_call, a.episode_step, a.warning_count, a.rest_idx, a.rest_start, a.value, a.filter,
-                a.ring_t, a.ring_v, a.head, a.tail, h->pid_acc, h->pid_last_obs, h->pid_fresh};
+                a.ring_t, a.ring_v, a.head, a.tail, h->pid_acc, h->pid_last_obs, h->pid_fresh, h->act_window, h->act_table};
   for (void* q : ps) if (q) (void)hipFree(q);
   delete h;
   return XV_OK;
@@ -727,6 +849,11 @@ static int hv_reset_call(xv_anyhvac* h, const uint8_t* mask, const double* grid,
   hipLaunchKernelGGL((xv_anyhvac_reset_kernel<INJECT>), dim3(h->a.n_env), dim3(HV_BLOCK), 0, h->eng->stream, h->a, mask, grid,
                      o);
   XV_LAUNCH_CHECK();
+  if (h->act_window) {      // a reset env starts with an empty action window
+    hipLaunchKernelGGL(xv_anyhvac_act_reset_kernel, dim3(h->a.n_env), dim3(HV_BLOCK), 0, h->eng->stream, h->act_window, h->a.C,
+                       mask);
+    XV_LAUNCH_CHECK();
+  }
   return XV_OK;
 }
 
@@ -742,15 +869,93 @@ template <bool INJECT>
 static int hv_step_call(xv_anyhvac* h, const xv_anyhvac_io* io, const double* reset_grid, int mode, int T) {
   XV_CHECK_ARG(h && h->a.tables && io && io->action && io->reward && io->terminated && io->truncated && T > 0);
   XV_CHECK_ARG(reset_grid || !INJECT);
+  XV_CHECK_ARG(h->act_mode == XV_ANYHVAC_ACT_BOX);      // (a mapped mode steps through xv_anyhvac_step_mapped)
   if (mode != XV_AUTORESET_DISABLED && mode != XV_AUTORESET_SAME_STEP) {
     xv_set_error("xv_anyhvac: autoreset mode %d is not built (disabled and same_step are)", mode);
     return XV_ERR_UNSUPPORTED;
   }
   hv_bind_rng(h, INJECT ? 0 : (uint64_t)T);
-  hipLaunchKernelGGL((xv_anyhvac_step_kernel<INJECT, false>), dim3(h->a.n_env), dim3(HV_BLOCK), 0, h->eng->stream, h->a, *io,
-                     reset_grid, mode, T, HvPid{});
+  hipLaunchKernelGGL((xv_anyhvac_step_kernel<INJECT, false, XV_ANYHVAC_ACT_BOX>), dim3(h->a.n_env), dim3(HV_BLOCK), 0,
+                     h->eng->stream, h->a, *io, reset_grid, mode, T, HvPid{}, HvAct{});
   XV_LAUNCH_CHECK();
   return XV_OK;
+}
+
+// ---- the mapped action modes -------------------------------------------------------------------------------------------
+extern "C" int xv_anyhvac_set_action_mode(xv_anyhvac* h, int mode, int flags, const double* cost_table) {
+  XV_CHECK_ARG(h && mode >= XV_ANYHVAC_ACT_BOX && mode <= XV_ANYHVAC_ACT_DIFF);
+  XV_CHECK_ARG((flags & ~(XV_ANYHVAC_ACT_COST | XV_ANYHVAC_ACT_TOO_COLD_LIMIT)) == 0);
+  XV_CHECK_ARG(mode == XV_ANYHVAC_ACT_DIFF || flags == 0);
+  XV_CHECK_ARG(cost_table || !(flags & XV_ANYHVAC_ACT_COST));
+  XV_HIP(hipSetDevice(h->eng->device));
+  if (mode != XV_ANYHVAC_ACT_BOX) {
+    const size_t bytes = (size_t)h->a.n_env * h->a.C * sizeof(unsigned long long);
+    const bool fresh = !h->act_window || mode != h->act_mode;      // (a change of flags alone keeps the windows)
+    if (!h->act_window) XV_HIP(hipMalloc((void**)&h->act_window, bytes));
+    if (!h->act_table) XV_HIP(hipMalloc((void**)&h->act_table, XV_ANYHVAC_ACT_BINS * sizeof(double)));
+    if (fresh) XV_HIP(hipMemsetAsync(h->act_window, 0, bytes, h->eng->stream));
+    XV_HIP(hipStreamSynchronize(h->eng->stream));
+    if (cost_table) XV_HIP(hipMemcpy(h->act_table, cost_table, XV_ANYHVAC_ACT_BINS * sizeof(double), hipMemcpyHostToDevice));
+    else XV_HIP(hipMemset(h->act_table, 0, XV_ANYHVAC_ACT_BINS * sizeof(double)));
+  }
+  h->act_mode = mode;
+  h->act_flags = flags;
+  return XV_OK;
+}
+
+template <bool INJECT>
+static int hv_step_mapped_call(xv_anyhvac* h, const xv_anyhvac_io* io, const xv_anyhvac_act_io* act, const double* reset_grid,
+                               int mode, int T) {
+  XV_CHECK_ARG(h && h->a.tables && io && act && io->reward && io->terminated && io->truncated && T > 0);
+  XV_CHECK_ARG(h->act_mode != XV_ANYHVAC_ACT_BOX && h->act_window && h->act_table);
+  XV_CHECK_ARG(io->action || (act->action_index && h->act_mode == XV_ANYHVAC_ACT_DIFF));
+  XV_CHECK_ARG(!act->action_index || h->act_mode == XV_ANYHVAC_ACT_DIFF);
+  XV_CHECK_ARG(reset_grid || !INJECT);
+  if (mode != XV_AUTORESET_DISABLED && mode != XV_AUTORESET_SAME_STEP) {
+    xv_set_error("xv_anyhvac: autoreset mode %d is not built (disabled and same_step are)", mode);
+    return XV_ERR_UNSUPPORTED;
+  }
+  HvAct A = {};
+  A.index = act->action_index; A.applied = act->applied_value; A.delta = act->delta; A.cost = act->action_cost;
+  A.counts = act->stat_counts; A.window = h->act_window; A.table = h->act_table; A.flags = h->act_flags;
+  hv_bind_rng(h, INJECT ? 0 : (uint64_t)T);
+  const dim3 grid(h->a.n_env), block(HV_BLOCK);
+  if (h->act_mode == XV_ANYHVAC_ACT_DIFF)
+    hipLaunchKernelGGL((xv_anyhvac_step_kernel<INJECT, false, XV_ANYHVAC_ACT_DIFF>), grid, block, 0, h->eng->stream, h->a, *io,
+                       reset_grid, mode, T, HvPid{}, A);
+  else
+    hipLaunchKernelGGL((xv_anyhvac_step_kernel<INJECT, false, XV_ANYHVAC_ACT_DISCRETE>), grid, block, 0, h->eng->stream, h->a, *io,
+                       reset_grid, mode, T, HvPid{}, A);
+  XV_LAUNCH_CHECK();
+  return XV_OK;
+}
+
+extern "C" int xv_anyhvac_step_mapped(xv_anyhvac* h, const xv_anyhvac_io* io, const xv_anyhvac_act_io* act, int autoreset_mode) {
+  return hv_step_mapped_call<false>(h, io, act, nullptr, autoreset_mode, 1);
+}
+
+extern "C" int xv_anyhvac_step_mapped_injected(xv_anyhvac* h, const xv_anyhvac_io* io, const xv_anyhvac_act_io* act,
+                                               const double* reset_grid, int autoreset_mode) {
+  return hv_step_mapped_call<true>(h, io, act, reset_grid, autoreset_mode, 1);
+}
+
+extern "C" int xv_anyhvac_rollout_mapped(xv_anyhvac* h, int T, const xv_anyhvac_io* io, const xv_anyhvac_act_io* act,
+                                         int autoreset_mode) {
+  return hv_step_mapped_call<false>(h, io, act, nullptr, autoreset_mode, T);
+}
+
+template <bool SET>
+static int hv_act_state_copy(xv_anyhvac* h, uint64_t* window) {
+  XV_CHECK_ARG(h && h->act_window && window);
+  const size_t bytes = (size_t)h->a.n_env * h->a.C * sizeof(unsigned long long);
+  XV_HIP(hipMemcpyAsync(SET ? (void*)h->act_window : (void*)window, SET ? (void*)window : (void*)h->act_window, bytes,
+                        hipMemcpyDeviceToDevice, h->eng->stream));
+  return XV_OK;
+}
+
+extern "C" int xv_anyhvac_act_get_state(xv_anyhvac* h, uint64_t* window) { return hv_act_state_copy<false>(h, window); }
+extern "C" int xv_anyhvac_act_set_state(xv_anyhvac* h, const uint64_t* window) {
+  return hv_act_state_copy<true>(h, const_cast<uint64_t*>(window));
 }
 
 extern "C" int xv_anyhvac_step(xv_anyhvac* h, const xv_anyhvac_io* io, int autoreset_mode) {
@@ -835,13 +1040,15 @@ extern "C" int xv_anyhvac_pid_action(xv_anyhvac* h, const float* readings, float
 extern "C" int xv_anyhvac_rollout_pid(xv_anyhvac* h, int T, const xv_anyhvac_io* io, float* action_out, double* stats,
                                       int autoreset_mode) {
   XV_CHECK_ARG(h && h->a.tables && h->pid_acc && io && io->reward && io->terminated && io->truncated && action_out && T > 0);
+  XV_CHECK_ARG(h->act_mode == XV_ANYHVAC_ACT_BOX);      // (the teachers put out box actions)
   if (autoreset_mode != XV_AUTORESET_DISABLED && autoreset_mode != XV_AUTORESET_SAME_STEP) {
     xv_set_error("xv_anyhvac: autoreset mode %d is not built (disabled and same_step are)", autoreset_mode);
     return XV_ERR_UNSUPPORTED;
   }
   hv_bind_rng(h, (uint64_t)T);
-  hipLaunchKernelGGL((xv_anyhvac_step_kernel<false, true>), dim3(h->a.n_env), dim3(HV_BLOCK), 0, h->eng->stream, h->a, *io,
-                     (const double*)nullptr, autoreset_mode, T, hv_pid_args(h, action_out, nullptr, stats));
+  hipLaunchKernelGGL((xv_anyhvac_step_kernel<false, true, XV_ANYHVAC_ACT_BOX>), dim3(h->a.n_env), dim3(HV_BLOCK), 0,
+                     h->eng->stream, h->a, *io, (const double*)nullptr, autoreset_mode, T,
+                     hv_pid_args(h, action_out, nullptr, stats), HvAct{});
   XV_LAUNCH_CHECK();
   return XV_OK;
 }
