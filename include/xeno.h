@@ -892,6 +892,67 @@ int xv_maze_set_raycast_mapping(xv_maze* h, int mapping);
 #define XV_MAZE_TYPING_NUMBA 1
 int xv_maze_set_typing(xv_maze* h, int typing);
 
+/* MazeWorld tasks made on the device (additions within ABI 12; csrc/maze_sampler.hip) — reference:
+ * xenoverse/mazeworld/envs/task_sampler.py sample_task :92-177, resample_task :179-225; xenoverse/utils/grid_ops.py
+ * genmaze_largeroom :49-72, genmaze_by_primwall :74-162.  One launch over candidates [cand_base, cand_base + n_cand), one
+ * wave64 per candidate, the grid in LDS: head, rooms, wall release, textures, landmarks, start, commands, written into the
+ * slots xv_maze_create consumes (layout and padding of mazeworld.tables.build_tables: walls 1, texts 0, landmarks -1 beyond
+ * a task's n; dbl[7] = tan(fol_angle / 2) is left 0 for the host's numpy.tan).  Every slot of every candidate is written;
+ * a candidate without a table (status != 0) is all padding and zeros.
+ *
+ * The wall release is genmaze_by_primwall pass by pass.  Nothing changes during a pass until it breaks, so each standing
+ * interior wall is tested on the grid as the pass found it: P1 it joins >= 2 regions and no region touches it twice; P2 it
+ * joins >= 2 regions, some region touches it twice, loops allowed; P3 one region left, loops allowed, its own uniform < 0.2.
+ * With one key per (pass, wall) the first passing wall of a shuffled order is the passing wall with the smallest (key, cell)
+ * and the last wall of the order the standing wall with the largest (key, cell); the wall the pass ended on is released if
+ * it touches an open cell (it joins the smallest neighbouring region id, the others are relabelled), else the pass is idle.
+ * Passes run while more than one region is left, or loops are allowed and the interior wall count exceeds
+ * (n-2)^2 * wall_density — at most 4 (n-2)^2 of them, idle ones included; then status 1 (pass_cap).
+ *
+ * Randomness: Philox4x32-10, key = seed, counter = {candidate lo, candidate hi, sub, purpose | tick << 8}; one call gives two
+ * uniforms (words 0,1 and words 2,3, xv_u53); element q of a block of uniforms is half q & 1 of call q >> 1; integers are
+ * floor(u * m) (not numpy's masked rejection).  Purposes: 0 head (sub 0 cell_size, wall_height; 1 agent_height, wall_density;
+ * 2 landmarks_number, n; 3 ground_text, ceiling_text; 4 fol_angle, room count); 1 rooms (sub 2 (5 room + try): h, w; + 1:
+ * placement); 2 passes (tick = pass, sub = cell i * n + j: key, P3 uniform); 3 textures, 4 landmarks, 5 start (blocks over
+ * cells); 6 commands (sub i: draw, fix-up); 7 colour shuffle (block over landmarks).  The resampler uses purposes 4..7 | 0x10
+ * with index = task index and tick = episode (< 2^24).  A candidate is a pure function of (seed, params, candidate index).
+ *
+ * 7 <= n_lo < n_hi <= 64 (n = n_lo + floor(u (n_hi - n_lo)), raised to odd); NG odd, == ((n_hi - 1) | 1), the largest n the
+ * range gives; 2 <= landmarks_lo < landmarks_hi (capped at 15); 1 <= n_cmd <= 2048.
+ * status int32[n_cand]: 0 accepted, 1 pass_cap, 2 no_room (fewer open cells than landmarks + 1). */
+typedef struct xv_maze_sampler_params {
+  int32_t n_lo, n_hi, allow_loops, landmarks_lo, landmarks_hi, n_cmd;
+  int32_t n_wall_textures, n_ground_textures, n_ceiling_textures, has_goal_reward;
+  double cell_size[2], wall_height[2], agent_height[2], wall_density[2], fol_angle[2];   /* [lo, hi) */
+  double step_reward, collision_reward, goal_reward;   /* goal_reward: n sqrt(n) / 60 unless has_goal_reward */
+} xv_maze_sampler_params;
+typedef struct xv_maze_task_slots {   /* the first seven members of xv_maze_tables, writable, [n][...] leading */
+  int8_t* walls;
+  int32_t* texts;
+  int8_t* landmarks;
+  int32_t* ints;
+  double* dbl;
+  int32_t* commands;
+  int32_t* lm_coord;
+} xv_maze_task_slots;
+typedef struct xv_maze_cand_info {
+  int32_t status, n, rooms, passes, idle, released;   /* rooms placed; passes run; idle passes; walls released */
+} xv_maze_cand_info;
+int xv_maze_sample_tasks(xv_engine* e, uint64_t seed, int64_t cand_base, int n_cand, int NG, const xv_maze_sampler_params* p,
+                         const xv_maze_task_slots* out, xv_maze_cand_info* info /* nullable */, int32_t* status);
+/* the argument checks of xv_maze_sample_tasks alone (host code, touches no device) */
+int xv_maze_sampler_check(int64_t cand_base, int n_cand, int NG, const xv_maze_sampler_params* p,
+                          const xv_maze_task_slots* out, const int32_t* status);
+/* The reference's Resampler over n_task device tables, in place: reads walls, ints[:, 0] (n) and ints[:, 5] (landmarks);
+ * writes landmarks, lm_coord (LANDMARKS: new landmarks; else COLOR: the same cells, ids permuted by key rank), ints[:, 1:3]
+ * (START) and commands (CMD); texts and dbl may be null.  Draws are a function of (seed, index_base + task, episode). */
+#define XV_MAZE_RESAMPLE_CMD 1
+#define XV_MAZE_RESAMPLE_START 2
+#define XV_MAZE_RESAMPLE_LANDMARKS 4
+#define XV_MAZE_RESAMPLE_COLOR 8
+int xv_maze_resample_tasks(xv_engine* e, uint64_t seed, int64_t index_base, int64_t episode, int n_task, int NG, int n_cmd,
+                           int flags, const xv_maze_task_slots* io);
+
 /* ---------------------------------------------------------------------------------------------
  * MazeWorld rule-based teachers — reference: xenoverse/mazeworld/agents
  *   AgentBase.__init__ / update_common_info / valid_neighbors   agent_base.py:10-107

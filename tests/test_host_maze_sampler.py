@@ -1,0 +1,230 @@
+"""The numpy restatement of the device MazeWorld task sampler and resampler (mazeworld/sampler_host.py): structure of what
+it makes, the pass cap as a condition, the parallel pass against the same pass walked sequentially, the population against
+the host MazeTaskSampler's, and the resampler's contract.  No GPU; tests/test_gpu_maze_sampler.py holds the device to
+this module bit for bit."""
+import os
+
+import numpy as np
+import pytest
+
+from xenoverse_amd.mazeworld import MazeTaskSampler, build_tables
+from xenoverse_amd.mazeworld import sampler_host as sh
+from xenoverse_amd.mazeworld.textures import REFERENCE_TEXTURE_COUNTS
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+SIZES = (7, 9, 15, 25)
+PER_CELL = {7: 40, 9: 40, 15: 30, 25: 10}       # candidates per (n, allow_loops): 240 in all
+
+
+def _open_degrees(walls):
+    """per open cell, how many of its four neighbours are open"""
+    o = (np.asarray(walls) < 1).astype(np.int64)
+    p = np.pad(o, 1)
+    deg = p[:-2, 1:-1] + p[2:, 1:-1] + p[1:-1, :-2] + p[1:-1, 2:]
+    return deg[o > 0]
+
+
+def _connected(walls):
+    o = np.asarray(walls) < 1
+    seen = np.zeros_like(o)
+    start = tuple(np.argwhere(o)[0])
+    seen[start] = True
+    stack = [start]
+    while stack:
+        i, j = stack.pop()
+        for a, b in ((i - 1, j), (i + 1, j), (i, j - 1), (i, j + 1)):
+            if o[a, b] and not seen[a, b]:
+                seen[a, b] = True
+                stack.append((a, b))
+    return bool((seen == o).all())
+
+
+@pytest.fixture(scope="module")
+def population():
+    """[(n, allow_loops, wall_density, task, info)]: 240 candidates over n in {7, 9, 15, 25} and both allow_loops values"""
+    out = []
+    for n in SIZES:
+        for loops in (True, False):
+            for c in range(PER_CELL[n]):
+                task, info = sh.sample_candidate_host(11, 1000 * n + c, n_range=(n, n + 1), allow_loops=loops)
+                d = sh.Draws(11, 1000 * n + c)
+                wd = sh._uniform(d.pairs(sh.P_HEAD, 1)[1], sh.DEFAULTS["wall_density_range"])
+                out.append((n, loops, float(wd), task, info))
+    assert len(out) >= 200
+    return out
+
+
+def test_pass_cap_is_a_condition(population):
+    for n, loops, wd, task, info in population:
+        assert info["status"] == 0 and task is not None, (n, loops, info)
+        assert info["n"] == n and info["passes"] <= 4 * (n - 2) ** 2
+        assert info["passes"] == info["idle"] + info["released"]
+
+
+def test_structure(population):
+    nw, ng, nc = REFERENCE_TEXTURE_COUNTS
+    for n, loops, wd, task, info in population:
+        w = task["cell_walls"]
+        assert w.shape == (n, n) and set(np.unique(w)) <= {0, 1}
+        assert w[0].all() and w[-1].all() and w[:, 0].all() and w[:, -1].all()
+        assert _connected(w)
+        if loops:
+            assert w[1:-1, 1:-1].sum() <= (n - 2) ** 2 * wd
+        lm = task["landmarks_coordinates"]
+        k = len(lm)
+        assert 5 <= k <= 14 and len(set(lm)) == k
+        assert all(w[c] == 0 for c in lm)
+        cl = task["cell_landmarks"]
+        assert sorted(cl[cl >= 0].tolist()) == list(range(k)) and all(cl[c] == q for q, c in enumerate(lm))
+        assert w[task["start"]] == 0
+        cmd = np.asarray(task["commands_sequence"])
+        assert cmd.shape == (200,) and cmd.min() >= 0 and cmd.max() < k and (cmd[1:] != cmd[:-1]).all()
+        t = task["cell_texts"]
+        assert t.min() >= 0 and t.max() < nw and not t[1:-1, 1:-1][w[1:-1, 1:-1] < 1].any()
+        assert 0 <= task["ground_text"] < ng and 0 <= task["ceiling_text"] < nc
+        assert task["goal_reward"] == n * np.sqrt(n) / 60.0
+        tab = build_tables([task])
+        assert tab["NG"] == n and tab["ints"][0, 5] == k
+
+
+def _walk_sequentially(walls, region, order, allow_loops, n_regions, u3):
+    """genmaze's loop body (task_sampler.genmaze) over the walls in `order`, each wall with its own P3 draw
+    -> (the wall the walk ended on, keep, losers)"""
+    n = walls.shape[0]
+    keep, losers = -1, {}
+    i = j = 0
+    for i, j in order:
+        keep, losers, seen, most = -1, {}, {}, 1
+        for a, b in ((i - 1, j), (i + 1, j), (i, j - 1), (i, j + 1)):
+            if 0 < a < n and 0 < b < n and walls[a, b] < 1:
+                rid = int(region[a, b])
+                seen[rid] = seen.get(rid, 0) + 1
+                most = max(most, seen[rid])
+                if rid < keep or keep < 0:
+                    if keep >= 0:
+                        losers[keep] = True
+                    keep = rid
+                elif rid != keep:
+                    losers[rid] = True
+        if losers and most < 2:
+            break
+        if losers and most > 1 and allow_loops:
+            break
+        if allow_loops and n_regions < 2 and u3[i - 1, j - 1] < 0.2:
+            break
+    return (i, j), keep, sorted(losers)
+
+
+def test_parallel_pass_equals_the_sequential_walk():
+    """One pass in parallel form (every wall tested, argmin / argmax over keys) ends on the wall, with the keep id and the
+    losers, of genmaze's loop body walked over the walls in key order: on every 5th pass of 12 generations (both
+    allow_loops values, before and after the regions are joined)."""
+    states = []
+    for c, (n, loops) in enumerate([(9, True), (9, False), (15, True), (15, False), (25, True), (25, False)] * 2):
+        seen = []
+        sh.sample_candidate_host(5, 77 + c, n_range=(n, n + 1), allow_loops=loops,
+                                 on_pass=lambda s: seen.append(s) if s["index"] % 5 == 0 else None)
+        states += [(n, loops, s) for s in seen]
+    assert len(states) >= 50
+    assert any(s["n_regions"] < 2 for _, _, s in states) and any(s["n_regions"] > 1 for _, _, s in states)
+    for n, loops, s in states:
+        standing = np.argwhere(s["walls"][1:-1, 1:-1] > 0)
+        keys = s["keys"][standing[:, 0], standing[:, 1]]
+        order = standing[np.lexsort((standing[:, 0] * n + standing[:, 1], keys))] + 1
+        (i, j), keep, losers = _walk_sequentially(s["walls"], s["region"], [tuple(c) for c in order], loops,
+                                                  s["n_regions"], s["u3"])
+        t = s["tests"]
+        assert s["pick"] == (i - 1, j - 1)
+        assert int(t["keep"][s["pick"]]) == keep
+        ids = t["ids"][(slice(None),) + s["pick"]]
+        assert sorted(set(int(v) for v in ids if v >= 0 and v != keep)) == losers
+        assert int(t["distinct"][s["pick"]]) == len(losers) + (1 if keep >= 0 else 0)
+
+
+def _density_and_degrees(tasks):
+    dens = np.array([t["cell_walls"][1:-1, 1:-1].mean() for t in tasks])
+    hist = np.array([np.bincount(_open_degrees(t["cell_walls"]), minlength=5)[:5] / float((t["cell_walls"] < 1).sum())
+                     for t in tasks])
+    return dens, hist
+
+
+def test_same_population_as_the_host_sampler():
+    """n = 15, 300 tasks each: the mean interior wall density and the mean open-cell degree histogram of
+    sample_candidate_host against the host MazeTaskSampler's, both measured here; the margin is three standard errors of
+    the difference, from the two samples' own variances."""
+    N = 300
+    mine = [sh.sample_candidate_host(2, c, n_range=(15, 16))[0] for c in range(N)]
+    assert all(t is not None for t in mine)
+    ref = [MazeTaskSampler(n_range=(15, 16), seed=100 + c, commands_sequence=4) for c in range(N)]
+    d0, h0 = _density_and_degrees(mine)
+    d1, h1 = _density_and_degrees(ref)
+    se = np.sqrt(d0.var(ddof=1) / N + d1.var(ddof=1) / N)
+    print("density %.4f vs %.4f, 3 se %.4f" % (d0.mean(), d1.mean(), 3 * se))
+    assert abs(d0.mean() - d1.mean()) <= 3 * se
+    seh = np.sqrt(h0.var(0, ddof=1) / N + h1.var(0, ddof=1) / N)
+    print("degrees", h0.mean(0), h1.mean(0), 3 * seh)
+    assert (np.abs(h0.mean(0) - h1.mean(0)) <= 3 * seh).all()
+
+
+def _same(a, b, keys):
+    return all(np.array_equal(np.asarray(a[k]), np.asarray(b[k])) for k in keys)
+
+
+def test_resampler_contract():
+    task, _ = sh.sample_candidate_host(4, 9, n_range=(15, 16))
+    fixed = ("cell_walls", "cell_texts", "cell_size", "wall_height", "agent_height", "fol_angle", "ground_text",
+             "ceiling_text", "goal_reward")
+    lm, st, cmd = ("landmarks_coordinates", "cell_landmarks"), ("start",), ("commands_sequence",)
+    off = dict(resample_cmd=False, resample_start=False, resample_landmarks=False, resample_landmarks_color=False)
+    for flag, changed in (("resample_cmd", cmd), ("resample_start", st), ("resample_landmarks", lm),
+                          ("resample_landmarks_color", lm)):
+        new = sh.resample_host(task, 8, 3, 5, **dict(off, **{flag: True}))
+        assert _same(new, task, fixed)
+        for group in (lm, st, cmd):
+            assert _same(new, task, group) == (group is not changed), (flag, group)
+        again = sh.resample_host(task, 8, 3, 5, **dict(off, **{flag: True}))
+        assert _same(new, again, lm + st + cmd)
+        for other in ((9, 3, 5), (8, 4, 5), (8, 3, 6)):      # seed, index, episode each matter
+            assert not _same(new, sh.resample_host(task, *other, **dict(off, **{flag: True})), changed)
+    new = sh.resample_host(task, 8, 3, 5, **dict(off, resample_landmarks_color=True))
+    assert sorted(new["landmarks_coordinates"]) == sorted(task["landmarks_coordinates"])
+    k = len(task["landmarks_coordinates"])
+    assert sorted(new["cell_landmarks"][new["cell_landmarks"] >= 0].tolist()) == list(range(k))
+    new = sh.resample_host(task, 8, 3, 5, **dict(off, resample_landmarks=True, resample_start=True))
+    assert task["cell_walls"][new["start"]] == 0 and new["cell_landmarks"][new["start"]] < 0
+    assert all(task["cell_walls"][c] == 0 for c in new["landmarks_coordinates"])
+    assert _same(sh.resample_host(task, 8, 3, 5, **off), task, fixed + lm + st + cmd)
+
+
+def test_arguments_are_checked():
+    for bad in (dict(n_range=(5, 9)), dict(n_range=(9, 66)), dict(n_range=(9, 9)), dict(landmarks_number_range=(1, 5)),
+                dict(commands_sequence=0), dict(n_wall_textures=0)):
+        with pytest.raises(ValueError):
+            sh.sampler_arguments(**bad)
+    with pytest.raises(TypeError):
+        sh.sampler_arguments(no_such_argument=1)
+    assert sh.grid_pitch((9, 25)) == 25 and sh.grid_pitch((63, 64)) == 63 and sh.grid_pitch((7, 8)) == 7
+
+
+def test_info_record_matches_the_header():
+    """xv_maze_cand_info (include/xeno.h) and its numpy dtype list the same int32 fields"""
+    import re
+    txt = open(os.path.join(os.path.dirname(GOLDEN), "..", "include", "xeno.h")).read()
+    body = re.search(r"typedef struct xv_maze_cand_info \{(.*?)\} xv_maze_cand_info;", txt, flags=re.S).group(1)
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    names = [v.strip() for v in re.search(r"int32_t([^;]*);", body).group(1).split(",")]
+    assert tuple(names) == sh.INFO_DTYPE.names and sh.INFO_DTYPE.itemsize == 4 * len(names)
+
+
+@pytest.mark.parametrize("name", ["default", "n63"])
+def test_recorded_host_results_are_the_host_samplers(name):
+    """tests/golden/sampler_maze_host_<name>.npz records sample_slots_host over 256 candidates (info records in full, the
+    slots as digests: the n = 63 batch takes minutes of numpy), for the device test to compare with; here two candidates
+    of each file are made again and must be the recorded ones."""
+    g = np.load(os.path.join(GOLDEN, "sampler_maze_host_%s.npz" % name))
+    kwargs = dict(n_range=tuple(int(v) for v in g["n_range"]))
+    assert g["digest"].shape == (256, 32) and g["info_words"].shape == (256, 6)
+    for q in ((3, 200) if name == "default" else (17,)):
+        s = sh.sample_slots_host(int(g["seed"]), q, 1, **kwargs)
+        assert np.array_equal(np.frombuffer(s["info"].tobytes(), np.int32), g["info_words"][q])
+        assert np.array_equal(sh.slots_digest(s, 0), g["digest"][q])

@@ -129,6 +129,9 @@ SIGNATURES = {
     "xv_maze_set_raycast_mapping": [c_void_p, c_int],
     "xv_maze_set_typing": [c_void_p, c_int],
     "xv_maze_set_move_kernel": [c_void_p, c_int],
+    "xv_maze_sample_tasks": [c_void_p, c_u64, c_i64, c_int, c_int] + [c_void_p] * 4,
+    "xv_maze_sampler_check": [c_i64, c_int, c_int] + [c_void_p] * 3,
+    "xv_maze_resample_tasks": [c_void_p, c_u64, c_i64, c_i64] + [c_int] * 4 + [c_void_p],
     "xv_maze_agent_create": [c_void_p, c_int, C.c_double, c_int, c_int, c_int, c_void_p],
     "xv_maze_agent_destroy": [c_void_p],
     "xv_maze_agent_act": [c_void_p, c_void_p, c_void_p],

@@ -77,8 +77,16 @@ class MazeWorldVecEnv(VectorEnv):
         tex = self._textures if self._textures is not None else make_texture_library()
         check_texture_library(tex)      # the kernels address 256 x 256 x 3 texels: any other size is an out-of-bounds read
         d = self.device
-        dev = {k: torch.from_numpy(np.ascontiguousarray(tab[k])).to(d) for k in
-               ("walls", "texts", "landmarks", "ints", "dbl", "commands", "lm_coord")}
+        dev = {}
+        for k, dt in (("walls", torch.int8), ("texts", torch.int32), ("landmarks", torch.int8), ("ints", torch.int32),
+                      ("dbl", torch.float64), ("commands", torch.int32), ("lm_coord", torch.int32)):
+            v = tab[k]
+            if torch.is_tensor(v):      # tables made on the device (mazeworld.device_sampler) are taken as they are
+                if v.dtype != dt:
+                    raise ValueError("table %r must be %s" % (k, dt))
+                dev[k] = v.to(d).contiguous()
+            else:
+                dev[k] = torch.from_numpy(np.ascontiguousarray(v)).to(d)
         for k, name in (("tex_walls", "walls"), ("tex_grounds", "grounds"), ("tex_ceilings", "ceilings")):
             v = tex[name]
             dev[k] = (v.to(d, torch.float32) if torch.is_tensor(v)
