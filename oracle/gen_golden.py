@@ -1,6 +1,6 @@
 """Generate tests/golden/*.npz by running the REFERENCE itself (build container only).
 
-usage:  python oracle/gen_golden.py [anymdp] [linds] [maze] [cartpole] ...   (default: all available)
+usage:  python oracle/gen_golden.py [anymdp] [linds] [linds_wide] [maze] [cartpole] ...   (default: all available)
 
 Each fixture holds inputs and the reference's outputs for one family.  The
 reference is stochastic through numpy's *global* legacy RandomState and reseeds it from OS entropy at
@@ -245,16 +245,18 @@ def _linds_task_arrays(task):
     return out
 
 
-def gen_linds_one(name, task, T=512, seed0=5000, act_scale=1.5):
+def gen_linds_one(name, task, T=512, seed0=5000, act_scale=1.5, pads=None):
     """G-L for one task: a T-step trajectory through the reference LinearDSEnv.step()/reset(), manual reset on
     done.  numpy's global RNG is seeded before every step (process noise) and the stdlib RNG before every reset
-    (linds_env.py:117 uses random.choice); both draws are replayed and stored."""
+    (linds_env.py:117 uses random.choice); both draws are replayed and stored.  `pads`: keyword arguments of the
+    reference env (pad_observation_dim, pad_command_dim, pad_action_dim); the recorded rows take those widths."""
     import random as pyrandom
     LinearDSEnv, _ = _refimport.linds()
     import xenoverse.linds.linds_env as envmod
     envmod.pseudo_random_seed = lambda *a, **k: 12345   # reset()'s reseeding of numpy: irrelevant, made inert
 
-    env = LinearDSEnv()   # dt=0.1, pads 16/16/8 (linds_env.py:16-19)
+    env = LinearDSEnv(**(pads or {}))   # dt=0.1, default pads 16/16/8 (linds_env.py:16-19)
+    wo, wc = env.pad_observation_dim, env.pad_command_dim
     env.set_task(task)
     ns = int(task["state_dim"])
     n_init = len(task["initial_states"])
@@ -269,10 +271,10 @@ def gen_linds_one(name, task, T=512, seed0=5000, act_scale=1.5):
 
     acts = rng.uniform(-act_scale, act_scale, size=(T, env.pad_action_dim))
     acts[rng.random_sample(T) < 0.3] *= 0.5
-    z = np.zeros((T, ns)); x_after = np.zeros((T, ns)); obs = np.zeros((T, 16)); cmd = np.zeros((T, 16))
+    z = np.zeros((T, ns)); x_after = np.zeros((T, ns)); obs = np.zeros((T, wo)); cmd = np.zeros((T, wc))
     reward = np.zeros(T); error = np.zeros(T); term = np.zeros(T, np.uint8); trunc = np.zeros(T, np.uint8)
     steps = np.zeros(T, np.int64)
-    reset_idx = np.full(T, -1, np.int64); reset_obs = np.zeros((T, 16)); reset_cmd = np.zeros((T, 16))
+    reset_idx = np.full(T, -1, np.int64); reset_obs = np.zeros((T, wo)); reset_cmd = np.zeros((T, wc))
     reset_err = np.zeros(T)
     init_idx, init_obs, init_cmd, init_err = ref_reset(seed0 + 1)
     for t in range(T):
@@ -290,6 +292,8 @@ def gen_linds_one(name, task, T=512, seed0=5000, act_scale=1.5):
                tr_term=term, tr_trunc=trunc, tr_steps=steps, tr_reset_idx=reset_idx, tr_reset_obs=reset_obs,
                tr_reset_cmd=reset_cmd, tr_reset_err=reset_err,
                init_idx=np.int64(init_idx), init_obs=init_obs, init_cmd=init_cmd, init_err=np.float64(init_err))
+    if pads:
+        out.update(pad_action_dim=np.int64(env.pad_action_dim), pad_observation_dim=np.int64(wo))
     path = os.path.join(GOLD, name + ".npz")
     np.savez_compressed(path, **out)
     print("wrote", path, os.path.getsize(path) // 1024, "KiB; type", str(task["target_type"]), "delay",
@@ -329,6 +333,44 @@ def gen_linds():
                 initial_states=[0.3 * np.random.randn(32) for _ in range(3)], noise_drift=0.01,
                 command=ts.RandomFourier(8), target_delay=7)
     gen_linds_one("linds_32x8x8_0", task, T=384, seed0=9000)
+
+
+def _linds_wide_task(ts, seed, ns, na, no, all_live, n_init=3, **kw):
+    """a task from the reference sampler's building blocks (its rejection loop over initial states does not end at 24 or
+    32 observations): the first draw after `seed` whose B and C have full rank, as the sampler demands, and, with
+    `all_live`, whose A, X and target_valid have no zero entry (no trimmed A, X factor > 0, every target tracked).  The
+    command is the reference's RandomFourier with a smaller box, and the hand-made initial states start near it (the
+    least-squares state of the first tracked command plus noise), so that episodes run to max_steps instead of ending at
+    error > 10 in their first step."""
+    np.random.seed(seed)
+    while True:
+        A, B, Cm, X, Y = ts.sample_variants_(ns, na, no)
+        valid = ts.sample_target_spaces_(no)
+        if np.linalg.matrix_rank(B) < min(na, ns) or np.linalg.matrix_rank(Cm) < min(no, ns):
+            continue
+        if all_live and not (np.all(A != 0) and np.all(X != 0) and np.all(valid != 0)):
+            continue
+        break
+    task = dict(state_dim=ns, observation_dim=no, action_dim=na, ld_A=A, ld_B=B, ld_C=Cm, ld_X=X, ld_Y=Y,
+                target_valid=valid, target_type="dynamic_target", command=ts.RandomFourier(no, box_size=0.25))
+    task.update(kw)
+    x_cmd = np.linalg.lstsq(Cm, task["command"](-task["target_delay"]) - Y, rcond=None)[0]
+    task["initial_states"] = [x_cmd + 0.1 * np.random.randn(ns) for _ in range(n_init)]
+    return task
+
+
+def gen_linds_wide():
+    """the reference at pad_observation_dim = pad_command_dim = 32, pad_action_dim = 16 (files lindswide_*: the prefix keeps
+    them out of golden_files("linds_")): one task zero-padded in both widths, one that fills them"""
+    _, ts = _refimport.linds()
+    pads = dict(pad_observation_dim=32, pad_command_dim=32, pad_action_dim=16)
+    task = _linds_wide_task(ts, 1224, 16, 12, 24, False, max_steps=45, action_cost=0.02, reward_base=0.1,
+                            terminate_punish=2.0, reward_factor=0.4, noise_drift=0.015, target_delay=5)
+    task["initial_states"].append(6.0 * np.random.RandomState(4).randn(16))     # ends its episode at once: terminated
+    gen_linds_one("lindswide_16x12x24_0", task, T=256, seed0=21000, pads=pads)
+    task = _linds_wide_task(ts, 3216, 32, 16, 32, True, max_steps=30, action_cost=0.01, reward_base=0.1,
+                            terminate_punish=3.0, reward_factor=0.5, noise_drift=0.01, target_delay=7)
+    gen_linds_one("lindswide_32x16x32_0", task, T=240, seed0=22000, act_scale=1.1, pads=pads)
 
 
 def _maze_task_arrays(task):
@@ -837,7 +879,7 @@ def gen_maze_texture_names():
     print("sampler_reftexture_names.npz", len(names), "names")
 
 
-FAMILIES = {"anymdp": gen_anymdp, "linds": gen_linds, "maze": gen_maze, "acrobot": gen_acrobot, "garnet": gen_garnet,
+FAMILIES = {"anymdp": gen_anymdp, "linds": gen_linds, "linds_wide": gen_linds_wide, "maze": gen_maze, "acrobot": gen_acrobot, "garnet": gen_garnet,
             "anymdp_vi": gen_anymdp_vi, "anymdp_sampled": gen_anymdp_sampled, "maze_sampled": gen_maze_sampled,
             "linds_sampled": gen_linds_sampled, "maze_agent": gen_maze_agent, "maze_refcounts": gen_maze_refcounts,
             "anymdp_accept": gen_anymdp_accept, "maze_texture_names": gen_maze_texture_names,

@@ -1,16 +1,23 @@
 """Randomised soak of the LinDS step kernels against the CPU oracle (not collected by pytest; run as a script on a GPU box,
 `PYTHONPATH=.:tests python tests/soak_linds.py [seconds]`): tasks drawn by the package's seed-compatible sampler with random
-dimensions, random env -> task maps and counts (partial tiles, one-env tasks), both kernels, the three auto-reset modes, injected
-draws — state and observation bit for bit, command / error / reward within 1e-5 as the unit tests."""
+dimensions — up to 32 states, 16 actions and 32 observations, the env padded to the compiled sizes that hold them, so that a
+run visits all eight (NS, NA, NO) kernel keys — random env -> task maps and counts (partial tiles, one-env tasks), both
+kernels, the three auto-reset modes, injected draws — state and observation bit for bit, command / error / reward within 1e-5
+as the unit tests."""
 import sys
 import time
 
 import numpy as np
 
 import oracle
-from xenoverse_amd.linds import LinDSVecEnv, build_tables, pad_tables
+from xenoverse_amd.linds import LinDSVecEnv, build_tables, pad_tables, task_sampler
 from xenoverse_amd.linds.task_sampler import LinearDSSampler
+from xenoverse_amd.linds.vec_env import _pad_to
 from util import close_rel
+
+# With 20 or more tracked observations hardly any draw of initial states starts within 3 of the command, and the sampler's
+# 20,000 rejected draws per task would be the soak's whole run time: it goes to its shrinking fallback after 200 here.
+task_sampler.MAX_DRAWS = 200
 
 MODES = {"disabled": 0, "next_step": 1, "same_step": 2}
 
@@ -32,13 +39,19 @@ def soak(rng, seed):
     n_task = int(rng.randint(1, 7))
     ns = int(rng.choice([rng.randint(2, 17), rng.randint(17, 33)]))
     same_dims = rng.random_sample() < 0.5
+    na_top, no_top = int(rng.randint(1, 17)), int(rng.randint(1, 33))      # this configuration's largest dims
     tasks = []
     for k in range(n_task):
         d = ns if same_dims else int(rng.randint(2, ns + 1))
-        t = LinearDSSampler(state_dim=d, action_dim=int(rng.randint(1, 9)), observation_dim=int(rng.randint(1, 17)), seed=seed + k)
+        t = LinearDSSampler(state_dim=d, action_dim=int(rng.randint(1, na_top + 1)), observation_dim=int(rng.randint(1, no_top + 1)),
+                            seed=seed + k)
         t["max_steps"] = int(rng.randint(5, 40))
         tasks.append(t)
-    tab = pad_tables(build_tables(tasks))
+    NA = _pad_to(max(t["action_dim"] for t in tasks), (8, 16))
+    NO = _pad_to(max(t["observation_dim"] for t in tasks), (16, 32))
+    pads = dict(pad_action_dim=NA, pad_observation_dim=NO, pad_command_dim=NO)
+    tab = pad_tables(build_tables(tasks, **pads))
+    key = (4 if tab["NS"] == 32 else 0) | (2 if NA == 16 else 0) | (1 if NO == 32 else 0)      # csrc/linds.hip: LINDS_DISPATCH
     counts = [int(rng.choice([1, rng.randint(1, 20), 64, rng.randint(20, 200)])) for _ in range(n_task)]
     env_task = np.repeat(np.arange(n_task, dtype=np.int32), counts)
     layout = str(rng.choice(["grouped", "shuffled"]))
@@ -47,9 +60,10 @@ def soak(rng, seed):
     n = len(env_task)
     mode = str(rng.choice(list(MODES)))
     path = str(rng.choice(["mfma", "mfma", "scalar"]))
-    env = LinDSVecEnv(n, autoreset_mode=mode, seed=seed)
+    env = LinDSVecEnv(n, autoreset_mode=mode, seed=seed, **pads)
     env.set_task(tasks, env_task_index=env_task)
     env.set_path(path)
+    _check((env.NS, env.NA, env.NO) == (tab["NS"], NA, NO), "kernel key")
     ora = oracle.LinDSOracle(tab, env_task)
     n_init = tab["ints"][env_task, 2]
     idx0 = (rng.random_sample(n) * n_init).astype(np.int32)
@@ -81,16 +95,17 @@ def soak(rng, seed):
         if mode == "disabled" and done.any():
             env.reset_injected(idx, mask=done.astype(np.uint8))
             ora.reset_injected(idx, mask=done.astype(np.uint8))
+    _check(env.check_errors() == 0, "device error flags")
     env.close()
-    return "linds tasks=%d ns<=%d (NS %d NA %d NO %d) envs=%d %s path=%s mode=%s steps=%d" % (
-        n_task, ns, tab["NS"], tab["NA"], tab["NO"], n, layout, path, mode, T)
+    return "linds tasks=%d ns<=%d (NS %d NA %d NO %d key %d) envs=%d %s path=%s mode=%s steps=%d" % (
+        n_task, ns, tab["NS"], tab["NA"], tab["NO"], key, n, layout, path, mode, T)
 
 
 if __name__ == "__main__":
     budget = float(sys.argv[1]) if len(sys.argv) > 1 else 120.0
     t_end = time.time() + budget
     master = np.random.RandomState(int(sys.argv[2]) if len(sys.argv) > 2 else 5)
-    n = 0
+    n, keys = 0, set()
     while time.time() < t_end:
         seed = int(master.randint(1, 1 << 30))
         try:
@@ -99,5 +114,6 @@ if __name__ == "__main__":
             print("MISMATCH with seed %d: %s" % (seed, ex), flush=True)
             sys.exit(1)
         n += 1
+        keys.add(int(line.split(" key ")[1].split(")")[0]))
         print("ok seed=%d %s" % (seed, line), flush=True)
-    print("TOTAL %d configurations, 0 mismatches" % n)
+    print("TOTAL %d configurations, 0 mismatches, keys visited %s" % (n, sorted(keys)))

@@ -570,21 +570,26 @@ __global__ __launch_bounds__(256) void linds_step_kernel(LinDSArgs P, LinDSStepI
           }
         }
       }
+      // The results leave INSIDE the pass that made them.  A lane that has left the waterfall is masked off while the other
+      // tasks' passes run, and what it holds in registers first written inside its own pass (y, crep, fobs) is not live on
+      // the loop's back edge as hipcc sees it.  At (32, 16, 32) the kernel spills ~6,000 SGPRs into VGPR lanes and parks those
+      // VGPRs in AGPRs with every lane enabled (s_or_saveexec -1; v_accvgpr_write) — in the AGPRs that held crep[0..9] of
+      // the lanes that had left: the free-running scalar step returned command rows made of table entries in every wave
+      // that holds more than one task.
+#pragma unroll
+      for (int k = 0; k < NS; ++k) P.x[linds_xidx(si, k, MT)] = xs[k];
+      P.sn[si] = (int32_t)((uint32_t)steps | (nr ? XV_LINDS_NR_BIT : 0u));
+      linds_store_row<NO>(io.obs + (size_t)i * NO, y);
+      linds_store_row<NO>(io.cmd + (size_t)i * NO, crep);
+      io.reward[i] = o_r;
+      io.error[i] = o_err;
+      io.terminated[i] = (uint8_t)o_term;
+      io.truncated[i] = (uint8_t)o_trunc;
+      if (io.final_obs && wrote_fobs) linds_store_row<NO>(io.final_obs + (size_t)i * NO, fobs);   // rows of finished envs only
+      if (err) atomicOr(P.err, err);
       break;
     }
   }
-
-#pragma unroll
-  for (int k = 0; k < NS; ++k) P.x[linds_xidx(si, k, MT)] = xs[k];
-  P.sn[si] = (int32_t)((uint32_t)steps | (nr ? XV_LINDS_NR_BIT : 0u));
-  linds_store_row<NO>(io.obs + (size_t)i * NO, y);
-  linds_store_row<NO>(io.cmd + (size_t)i * NO, crep);
-  io.reward[i] = o_r;
-  io.error[i] = o_err;
-  io.terminated[i] = (uint8_t)o_term;
-  io.truncated[i] = (uint8_t)o_trunc;
-  if (io.final_obs && wrote_fobs) linds_store_row<NO>(io.final_obs + (size_t)i * NO, fobs);   // rows of finished envs only
-  if (err) atomicOr(P.err, err);
 }
 
 template <int NS, int NO, bool INJECT>
@@ -607,15 +612,16 @@ __global__ __launch_bounds__(256) void linds_reset_kernel(LinDSArgs P, const uin
       const int n_init = in[2], nf = in[3];
       const int idx = INJECT ? init_index[i] : linds_draw_init(P, P.gid_base + (uint64_t)i, xv_launch_tick(P.tick, P.tick_dev), n_init);
       linds_reset_env<NS, NO>(P, tu, nf, n_init, idx, xs, y, c, e);
+      // stored inside the pass: nothing made here may wait in a masked-off lane for the other passes (see linds_step_kernel)
+#pragma unroll
+      for (int k = 0; k < NS; ++k) P.x[linds_xidx(si, k, NS / 16)] = xs[k];
+      P.sn[si] = 0;
+      if (obs) linds_store_row<NO>(obs + (size_t)i * NO, y);
+      if (cmd) linds_store_row<NO>(cmd + (size_t)i * NO, c);
+      if (error) error[i] = e;
       break;
     }
   }
-#pragma unroll
-  for (int k = 0; k < NS; ++k) P.x[linds_xidx(si, k, NS / 16)] = xs[k];
-  P.sn[si] = 0;
-  if (obs) linds_store_row<NO>(obs + (size_t)i * NO, y);
-  if (cmd) linds_store_row<NO>(cmd + (size_t)i * NO, c);
-  if (error) error[i] = e;
 }
 
 // ------------------------------------------------------------------------------------------------
