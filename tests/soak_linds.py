@@ -12,7 +12,7 @@ import numpy as np
 import oracle
 from xenoverse_amd.linds import LinDSVecEnv, build_tables, pad_tables, task_sampler
 from xenoverse_amd.linds.task_sampler import LinearDSSampler
-from xenoverse_amd.linds.vec_env import _pad_to
+from xenoverse_amd.linds.tables import _pad_to
 from util import close_rel
 
 # With 20 or more tracked observations hardly any draw of initial states starts within 3 of the command, and the sampler's

@@ -83,21 +83,15 @@ class HVACVecEnv(VectorEnv):
         n_task, n, d = len(tasks), self.num_envs, self.device
         for t in tasks:
             check_ring(t["cooler_delay_seconds"], self.sec_per_iter)
-        if env_task_index is None:
-            if n % n_task != 0:
-                raise ValueError("num_envs is not a multiple of the task count; pass env_task_index")
-            env_task = np.arange(n, dtype=np.int32) // (n // n_task)
-        else:
-            env_task = np.asarray(torch.as_tensor(env_task_index).cpu(), np.int32)
-            if env_task.shape != (n,) or env_task.min() < 0 or env_task.max() >= n_task:
-                raise ValueError("env_task_index must be (num_envs,) with entries in [0, n_task)")
+        env_task_dev = self._env_task(n_task, env_task_index)
+        env_task = env_task_dev.cpu().numpy()      # (the per-env counts and targets below are host arrays)
         tab = build_tables(tasks, self.lower_bound, self.upper_bound, generate_task)
         self.dims = NW, NL, Cc, S, H, KS, KH = tab["dims"]
         self.avg_total_heat = tab["avg_total_heat"]
         cs = tab["counts"]
         self.counts = {k: np.array([cs[i][q] for i in env_task], np.int32) for k, q in
                        (("coolers", "C"), ("sensors", "S"), ("heaters", "H"), ("n_width", "nw"), ("n_length", "nl"))}
-        self._tab = dict(table=torch.from_numpy(tab["table"]).to(d), env_task=torch.from_numpy(env_task).to(d))
+        self._tab = dict(table=torch.from_numpy(tab["table"]).to(d), env_task=env_task_dev)
         self.close_extras()
         h = C.c_void_p()
         max_t = int(self.max_steps * self.iter_per_step * self.sec_per_iter)
@@ -148,20 +142,16 @@ class HVACVecEnv(VectorEnv):
     # -- buffers --------------------------------------------------------------------------------------------------
     def _buffers(self, lead, final):
         NW, NL, Cc, S, H, _, _ = self.dims
-        d, n = self.device, self.num_envs
-        shape = tuple(lead) + (n,)
-        z = lambda tail, dt: torch.zeros(shape + tail, dtype=dt, device=d)  # noqa: E731
-        b = dict(sensor_readings=z((S,), torch.float32), heat_readings=z((H,), torch.float32),
-                 action_temp=z((Cc,), torch.float32), timestep=z((), torch.int32), reward=z((), torch.float64),
-                 terminated=z((), torch.uint8), truncated=z((), torch.uint8), cool_power=z((Cc,), torch.float32),
-                 heat_power=z((H,), torch.float64), misc=z((8,), torch.float64))
+        f32, f64, i32, u8 = torch.float32, torch.float64, torch.int32, torch.uint8
+        spec = [("sensor_readings", f32, (S,)), ("heat_readings", f32, (H,)), ("action_temp", f32, (Cc,)), ("timestep", i32, ()),
+                ("reward", f64, ()), ("terminated", u8, ()), ("truncated", u8, ()), ("cool_power", f32, (Cc,)),
+                ("heat_power", f64, (H,)), ("misc", f64, (8,))]      # (the first four: OBS_KEYS)
         if self.action_mode != "box":
-            b.update(applied_value=z((Cc,), torch.float32), delta=z((Cc,), torch.float64), action_cost=z((), torch.float64),
-                     stat_counts=z((len(STAT_KEYS),), torch.int32))
+            spec += [("applied_value", f32, (Cc,)), ("delta", f64, (Cc,)), ("action_cost", f64, ()),
+                     ("stat_counts", i32, (len(STAT_KEYS),))]
         if final:
-            for k, dt in zip(OBS_KEYS, (torch.float32, torch.float32, torch.float32, torch.int32)):
-                b["final_" + k] = z(b[k].shape[len(shape):], dt)
-        return b
+            spec += [("final_" + f[0],) + f[1:] for f in spec[:len(OBS_KEYS)]]
+        return self._alloc([f + (0,) for f in spec], lead)      # zero-filled: the padded columns are never written
 
     def _io(self, b, action=None):
         io = _lib.AnyHVACIO()
@@ -266,12 +256,7 @@ class HVACVecEnv(VectorEnv):
 
     # -- episode --------------------------------------------------------------------------------------------------
     def reset(self, *, seed=None, options=None):
-        self._require_task()
-        if seed is not None:
-            self.engine.tick = (int(seed) & 0xFFFFFFFF) << 24
-        mask = None
-        if options is not None and options.get("reset_mask") is not None:
-            mask = self._dev(options["reset_mask"], torch.uint8)
+        mask = self._reset_prelude(seed, options)
         b = self._buffers((), False)
         io = self._io(b)
         _lib.check(self.lib.xv_anyhvac_reset(self._h, _lib.ptr(mask), C.byref(io)))
@@ -292,10 +277,6 @@ class HVACVecEnv(VectorEnv):
         if self._pid is not None:
             self.pid_reset(m)
         return self._obs(b)
-
-    def _require_reset(self):
-        if (not self.task_set) or self.need_reset:
-            raise Exception("Must \"set_task\" and \"reset\" before doing any actions")
 
     def step(self, actions):
         self._require_reset()

@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from .. import _lib
-from ..engine import Engine
+from ..device_sampling import collect_accepted, engine_scope, sampler_stats
 from .tables import row_lines
 
 STATUS = ("accepted", "unrepairable", "value_gap", "occupancy", "no_convergence")
@@ -81,44 +81,28 @@ def sample_tasks_device(n_tasks, state_space=64, action_space=5, seed=0, device=
     if task_type not in ("MDP", "POMDP", "MTPOMDP"):
         raise NotImplementedError(f"Unknown task type: {task_type}")
     S, A = int(state_space), int(action_space)
-    own = engine is None
-    eng = Engine(device) if own else engine
-    try:
-        if batch is None:
-            per = S * A * row_lines(S) * 128 + (3 * S * A * S * 8 if dense else 0)
-            if S > 64 or S * A > 512:      # the candidate's scratch: transposed transition rows + two S x S matrices
-                per += ((S * A + 63) // 64 * 64 * S + 2 * S * S) * 8
-            batch = int(max(64, min(8192, (6 << 30) // per, 4 * n_tasks + 64)))
-        keys = ["rows", "state_map", "term_mask", "s0_cdf", "s0_ids", "max_steps"] + \
-            (["transition", "reward", "reward_noise"] if dense else [])
-        got = {k: [] for k in keys}
-        hist = np.zeros(len(STATUS), np.int64)
-        n_acc, base, t0 = 0, 0, time.perf_counter()
-        while n_acc < n_tasks:
-            if max_candidates is not None and base >= max_candidates:
-                raise RuntimeError("only %d of %d tasks accepted within %d candidates" % (n_acc, n_tasks, base))
-            r = sample_candidates(eng, seed, base, batch, S, A, s0_max, tables=True, dense=dense)
-            st = r["status"]
-            acc = torch.nonzero(st == 0).flatten()[: n_tasks - n_acc]
-            last = int(acc[-1]) + 1 if len(acc) and n_acc + len(acc) >= n_tasks else batch
-            hist += np.bincount(st[:last].cpu().numpy(), minlength=len(STATUS))[: len(STATUS)]
-            for k in keys:
-                got[k].append(r[k].index_select(0, acc))
-            n_acc += int(len(acc))
-            base += batch
-        out = dict(S=S, A=A, s0_max=s0_max, **{k: torch.cat(v) for k, v in got.items()})
+    if batch is None:
+        per = S * A * row_lines(S) * 128 + (3 * S * A * S * 8 if dense else 0)
+        if S > 64 or S * A > 512:      # the candidate's scratch: transposed transition rows + two S x S matrices
+            per += ((S * A + 63) // 64 * 64 * S + 2 * S * S) * 8
+        batch = int(max(64, min(8192, (6 << 30) // per, 4 * n_tasks + 64)))
+    keys = ["rows", "state_map", "term_mask", "s0_cdf", "s0_ids", "max_steps"] + \
+        (["transition", "reward", "reward_noise"] if dense else [])
+    with engine_scope(engine, device) as eng:
+        t0 = time.perf_counter()
+        # (no info records: one is ~4 KB per candidate; the status comes back as one int32 per candidate)
+        got, _, hist = collect_accepted(
+            lambda base, n: sample_candidates(eng, seed, base, n, S, A, s0_max, tables=True, dense=dense),
+            n_tasks, batch, keys, STATUS, max_candidates)
+        out = dict(S=S, A=A, s0_max=s0_max, **got)
         if task_type != "MDP":
             d_obs, d_act = (int(observation_tokens), int(action_tokens)) if task_type == "MTPOMDP" else (1, 1)
             out.update(task_type=task_type, n_obs=int(observation_space), d_obs=d_obs, d_act=d_act,
                        obs_cdf=sample_observation_model_device(eng, seed, n_tasks, S, observation_space, d_obs, density,
                                                                maximum_distribution))
         eng.sync()
-        out["stats"] = dict(candidates=int(hist.sum()), accepted=int(hist[0]), seconds=time.perf_counter() - t0,
-                            status={STATUS[i]: int(hist[i]) for i in range(len(STATUS))}, batch=batch)
+        out["stats"] = sampler_stats(hist, STATUS, batch, t0)
         return out
-    finally:
-        if own:
-            eng.close()
 
 
 def task_dict_from_dense(transition, reward, reward_noise, info_row, S, A):

@@ -101,20 +101,7 @@ class AnyMDPVecEnv(VectorEnv):
         for k, shp in want.items():      # the device reads these extents: a short table is an out-of-bounds read
             if tuple(dev[k].shape) != shp:
                 raise ValueError("table %r has shape %s, expected %s" % (k, tuple(dev[k].shape), shp))
-        if env_task_index is None:
-            if self.num_envs % n_task != 0:
-                raise ValueError("num_envs (%d) is not a multiple of the task count (%d); pass "
-                                 "env_task_index" % (self.num_envs, n_task))
-            per = self.num_envs // n_task
-            env_task = torch.arange(self.num_envs, device=self.device, dtype=torch.int32) // per
-        else:
-            env_task = self._dev(env_task_index, torch.int32)
-            if env_task.shape != (self.num_envs,):
-                raise ValueError("env_task_index must have shape (num_envs,)")
-            lo, hi = int(env_task.min()), int(env_task.max())
-            if lo < 0 or hi >= n_task:
-                raise ValueError("env_task_index out of range")
-        dev["env_task"] = env_task.contiguous()
+        dev["env_task"] = self._env_task(n_task, env_task_index)
         if self._parent is not None:
             raise ValueError("set_task on a sub-batch made by split(): set the task on the env it was split from")
         self._drop_views()
@@ -256,12 +243,7 @@ class AnyMDPVecEnv(VectorEnv):
     def reset(self, *, seed=None, options=None):
         """gymnasium VectorEnv.reset.  options={"reset_mask": bool[N]} resets a subset (autoreset
         DISABLED); seed (int) re-keys this engine's Philox stream position deterministically."""
-        self._require_task()
-        if seed is not None:
-            self.engine.tick = (int(seed) & 0xFFFFFFFF) << 24
-        mask = None
-        if options is not None and options.get("reset_mask") is not None:
-            mask = self._dev(options["reset_mask"], torch.uint8)
+        mask = self._reset_prelude(seed, options)
         self._adopt_latest(**{"_obs" if self._tok is None else "_tobs": "obs"})
         if self._tok is not None:
             self._detach("_tobs")      # a masked reset writes part of it: never into the tensor the last step handed out
@@ -334,8 +316,7 @@ class AnyMDPVecEnv(VectorEnv):
     # ---- step -------------------------------------------------------------------------------------
     def _check_step(self):
         if (not self.task_set) or self.need_reset:
-            # reference message, anymdp_env.py:93-94
-            raise Exception("Must \"set_task\" and \"reset\" before doing any actions")
+            self._require_reset()      # raises, with the reference's message (anymdp_env.py:93-94)
         if self._parent is not None or self._views:
             self._sync_tick()
 
@@ -400,6 +381,11 @@ class AnyMDPVecEnv(VectorEnv):
                                                     AUTORESET[self.autoreset_mode]))
         return self._finish(self._steps_and_done(s), a)
 
+    # what a roll-out / step_many slot holds per step (VectorEnv._alloc): every entry is written by the launch
+    _ROLLOUT = (("obs", torch.int32, ()), ("reward", torch.float32, ()), ("reward_gt", torch.float32, ()),
+                ("terminated", torch.uint8, ()), ("truncated", torch.uint8, ()), ("final_obs", torch.int32, ()))
+    _ROLLOUT_ACTED = (("action", torch.int32, ()),) + _ROLLOUT      # the teacher's / learner's roll-outs
+
     def rollout(self, actions, out=None):
         """Fused open-loop rollout: actions int32[T, N] -> dict of [T, N] device tensors, one launch.
         Equals T calls of step() with SAME_STEP auto-reset, bit for bit."""
@@ -407,14 +393,8 @@ class AnyMDPVecEnv(VectorEnv):
         a = self._dev(actions, torch.int32)
         T = int(a.shape[0])
         assert a.shape == (T, self.num_envs)
-        d = self.device
         if out is None:
-            out = dict(obs=torch.empty((T, self.num_envs), dtype=torch.int32, device=d),
-                       reward=torch.empty((T, self.num_envs), dtype=torch.float32, device=d),
-                       reward_gt=torch.empty((T, self.num_envs), dtype=torch.float32, device=d),
-                       terminated=torch.empty((T, self.num_envs), dtype=torch.uint8, device=d),
-                       truncated=torch.empty((T, self.num_envs), dtype=torch.uint8, device=d),
-                       final_obs=torch.empty((T, self.num_envs), dtype=torch.int32, device=d))
+            out = self._alloc(self._ROLLOUT, (T,))
         _lib.check(self.lib.xv_anymdp_rollout(
             self._h, T, _lib.ptr(a), _lib.ptr(out["obs"]), _lib.ptr(out["reward"]), _lib.ptr(out["reward_gt"]),
             _lib.ptr(out["terminated"]), _lib.ptr(out["truncated"]), _lib.ptr(out.get("final_obs"))))
@@ -444,14 +424,7 @@ class AnyMDPVecEnv(VectorEnv):
             greedy = self._greedy_cache[1]
         g = self._dev(greedy, torch.uint8)
         assert g.shape == (self.n_task, self.S)
-        d, n = self.device, self.num_envs
-        out = dict(action=torch.empty((T, n), dtype=torch.int32, device=d),
-                   obs=torch.empty((T, n), dtype=torch.int32, device=d),
-                   reward=torch.empty((T, n), dtype=torch.float32, device=d),
-                   reward_gt=torch.empty((T, n), dtype=torch.float32, device=d),
-                   terminated=torch.empty((T, n), dtype=torch.uint8, device=d),
-                   truncated=torch.empty((T, n), dtype=torch.uint8, device=d),
-                   final_obs=torch.empty((T, n), dtype=torch.int32, device=d))
+        out = self._alloc(self._ROLLOUT_ACTED, (T,))
         _lib.check(self.lib.xv_anymdp_rollout_teacher(
             self._h, int(T), _lib.ptr(g), float(epsilon), _lib.ptr(out["action"]), _lib.ptr(out["obs"]),
             _lib.ptr(out["reward"]), _lib.ptr(out["reward_gt"]), _lib.ptr(out["terminated"]),
@@ -492,13 +465,7 @@ class AnyMDPVecEnv(VectorEnv):
                 shape = learner._shape(learner._U_POLICY, T) if k == "u_policy" else (T, n)
                 if tuple(dr[j].shape) != shape:
                     raise ValueError("rollout_learner: draws[%r] has shape %s, expected %s" % (k, tuple(dr[j].shape), shape))
-        out = dict(action=torch.empty((T, n), dtype=torch.int32, device=d),
-                   obs=torch.empty((T, n), dtype=torch.int32, device=d),
-                   reward=torch.empty((T, n), dtype=torch.float32, device=d),
-                   reward_gt=torch.empty((T, n), dtype=torch.float32, device=d),
-                   terminated=torch.empty((T, n), dtype=torch.uint8, device=d),
-                   truncated=torch.empty((T, n), dtype=torch.uint8, device=d),
-                   final_obs=torch.empty((T, n), dtype=torch.int32, device=d))
+        out = self._alloc(self._ROLLOUT_ACTED, (T,))
         _lib.check(getattr(self.lib, learner._ROLLOUT)(
             self._h, learner._h, T, 1 if greedy else 0, *(_lib.ptr(x) for x in dr), _lib.ptr(out["action"]),
             _lib.ptr(out["obs"]), _lib.ptr(out["reward"]), _lib.ptr(out["reward_gt"]), _lib.ptr(out["terminated"]),
@@ -526,12 +493,7 @@ class AnyMDPVecEnv(VectorEnv):
             assert a.shape == (P, self.num_envs)
             d = self.device
             if out is None:
-                out = dict(obs=torch.empty((P, self.num_envs), dtype=torch.int32, device=d),
-                           reward=torch.empty((P, self.num_envs), dtype=torch.float32, device=d),
-                           reward_gt=torch.empty((P, self.num_envs), dtype=torch.float32, device=d),
-                           terminated=torch.empty((P, self.num_envs), dtype=torch.uint8, device=d),
-                           truncated=torch.empty((P, self.num_envs), dtype=torch.uint8, device=d),
-                           final_obs=torch.empty((P, self.num_envs), dtype=torch.int32, device=d))
+                out = self._alloc(self._ROLLOUT, (P,))
             for k in self._MANY_KEYS[:5]:
                 assert tuple(out[k].shape) == (P, self.num_envs) and out[k].device == d, k
             args = (P, _lib.ptr(a), _lib.ptr(out["obs"]), _lib.ptr(out["reward"]), _lib.ptr(out["reward_gt"]),
@@ -634,14 +596,9 @@ class AnyMDPVecEnv(VectorEnv):
         P = int(a.shape[0])
         assert a.shape == (P, self.num_envs, d_act)
         a = a.contiguous()
-        d, n = self.device, self.num_envs
-        if out is None:
-            out = dict(obs=torch.empty((P, n, d_obs), dtype=torch.int32, device=d),
-                       reward=torch.empty((P, n), dtype=torch.float32, device=d),
-                       reward_gt=torch.empty((P, n), dtype=torch.float32, device=d),
-                       terminated=torch.empty((P, n), dtype=torch.uint8, device=d),
-                       truncated=torch.empty((P, n), dtype=torch.uint8, device=d),
-                       final_obs=torch.full((P, n, d_obs), -1, dtype=torch.int32, device=d))
+        if out is None:      # (token steps write final_obs for finished envs only: -1 elsewhere)
+            out = self._alloc([("obs", torch.int32, (d_obs,))] + list(self._ROLLOUT[1:5]) + [("final_obs", torch.int32, (d_obs,), -1)],
+                              (P,))
         _lib.check(self.lib.xv_anymdp_step_tokens_many(
             self._h, int(n_steps), P, _lib.ptr(a), _lib.ptr(out["obs"]), _lib.ptr(out["reward"]), _lib.ptr(out["reward_gt"]),
             _lib.ptr(out["terminated"]), _lib.ptr(out["truncated"]), _lib.ptr(out.get("final_obs")),

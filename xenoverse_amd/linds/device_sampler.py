@@ -19,10 +19,9 @@ import numpy as np
 import torch
 
 from .. import _lib
-from ..engine import Engine
+from ..device_sampling import collect_accepted, engine_scope, sampler_stats
 from . import sampler_host as sh
-from .tables import KMAX, NA_MAX, NO_MAX, NS_MAX, fourier_terms
-from .vec_env import _Tables, _pad_to
+from .tables import KMAX, _Tables, _pack, _pad_to
 
 STATUS = sh.STATUS
 
@@ -104,47 +103,26 @@ def sample_tasks_device(n_tasks, state_dim=16, action_dim=8, observation_dim=8, 
     host; with dense=True also the fp64 tensors) + "stats": candidates tried, status histogram, histogram of the accepted
     attempt index (bin b: attempts in [2^b - 1, 2^(b+1) - 1)), seconds.  Task k is the k-th accepted candidate in candidate
     order, whatever `batch` is.  `LinDSVecEnv.set_task(tables)` takes the result as it is."""
-    own = engine is None
-    eng = Engine(device) if own else engine
-    try:
-        if batch is None:
-            batch = int(max(64, min(4096, 2 * n_tasks)))
-        keys = list(TABLE_KEYS) + (list(DENSE_KEYS) if dense else [])
-        got = {k: [] for k in keys}
-        infos = []
-        hist = np.zeros(len(STATUS), np.int64)
-        n_acc, base, t0 = 0, 0, time.perf_counter()
-        pads = None
-        while n_acc < n_tasks:
-            if max_candidates is not None and base >= max_candidates:
-                raise RuntimeError("only %d of %d tasks accepted within %d candidates" % (n_acc, n_tasks, base))
-            r = sample_candidates(eng, seed, base, batch, state_dim, action_dim, observation_dim, random_dim, dt,
-                                  pad_observation_dim, pad_action_dim, max_init, max_draws, tables=True, dense=dense, info=True)
-            pads = {k: r[k] for k in ("NS", "NA", "NO", "NI", "dt")}
-            st = r["info"]["status"]
-            acc = np.nonzero(st == 0)[0][: n_tasks - n_acc]
-            last = int(acc[-1]) + 1 if len(acc) and n_acc + len(acc) >= n_tasks else batch
-            hist += np.bincount(st[:last], minlength=len(STATUS))[: len(STATUS)]
-            sel = torch.as_tensor(acc, device=eng.device)
-            for k in keys:
-                got[k].append(r[k].index_select(0, sel))
-            infos.append(r["info"][acc])
-            n_acc += int(len(acc))
-            base += batch
-        out = dict(pads, **{k: torch.cat(v) for k, v in got.items()})
-        info = np.concatenate(infos)
+    if batch is None:
+        batch = int(max(64, min(4096, 2 * n_tasks)))
+    keys = list(TABLE_KEYS) + (list(DENSE_KEYS) if dense else [])
+    NS, NA, NO = default_pads(state_dim, action_dim, observation_dim, random_dim, pad_action_dim, pad_observation_dim)
+    with engine_scope(engine, device) as eng:
+        t0 = time.perf_counter()
+        got, info, hist = collect_accepted(
+            lambda base, n: sample_candidates(eng, seed, base, n, state_dim, action_dim, observation_dim, random_dim, dt,
+                                              pad_observation_dim, pad_action_dim, max_init, max_draws, tables=True,
+                                              dense=dense, info=True),
+            n_tasks, batch, keys, STATUS, max_candidates)
+        out = dict(NS=NS, NA=NA, NO=NO, NI=int(max_init), dt=float(dt), **got)      # as sample_candidates has them
         out["info"] = info
         out["action_dims"] = info["na"].astype(np.int32)
         eng.sync()
-        out["stats"] = dict(candidates=int(hist.sum()), accepted=int(hist[0]), seconds=time.perf_counter() - t0,
-                            status={STATUS[i]: int(hist[i]) for i in range(len(STATUS))}, batch=batch,
-                            attempts_total=int(info["attempt"].astype(np.int64).sum() + len(info)),
-                            attempts_log2=np.bincount(np.floor(np.log2(info["attempt"].astype(np.float64) + 1.0)).astype(np.int64),
-                                                      minlength=1).tolist())
+        attempts = info["attempt"]
+        out["stats"] = sampler_stats(
+            hist, STATUS, batch, t0, attempts_total=int(attempts.astype(np.int64).sum() + len(info)),
+            attempts_log2=np.bincount(np.floor(np.log2(attempts.astype(np.float64) + 1.0)).astype(np.int64), minlength=1).tolist())
         return out
-    finally:
-        if own:
-            eng.close()
 
 
 def task_dicts_from_device(out):
@@ -193,66 +171,7 @@ def build_zoh_device(engine, A, B, X, ns, dt=0.1, dense=False):
 def build_tables_device(tasks, engine, dt=0.1, pad_observation_dim=16, pad_action_dim=8, pad_command_dim=16):
     """`linds.tables.build_tables` (same arguments, same dict of host arrays) with its per-task expm replaced by one
     xv_linds_build_zoh launch over all tasks.  Opt-in: `LinDSVecEnv.set_task` keeps using the host builder."""
-    if isinstance(tasks, dict):
-        tasks = [tasks]
-    if pad_command_dim != pad_observation_dim:
-        raise ValueError("pad_command_dim must equal pad_observation_dim on the device path")
-    n_task = len(tasks)
-    NS = max(int(t["state_dim"]) for t in tasks)
-    NA, NO = int(pad_action_dim), int(pad_observation_dim)
-    for t in tasks:
-        assert t["observation_dim"] <= NO, \
-            f"Padded observation dimension {NO} is smaller than actual observation dimension {t['observation_dim']}"
-        assert t["action_dim"] <= NA, \
-            f"Padded action dimension {NA} is smaller than actual action dimension {t['action_dim']}"
-    if NS > NS_MAX or NA > NA_MAX or NO > NO_MAX:
-        raise ValueError("unsupported dims: state %d (<=%d), action %d (<=%d), observation %d (<=%d)"
-                         % (NS, NS_MAX, NA, NA_MAX, NO, NO_MAX))
-    NI = max(len(t["initial_states"]) for t in tasks)
-    A = np.zeros((n_task, NS, NS))
-    B = np.zeros((n_task, NS, NA))
-    X = np.zeros((n_task, NS))
-    nsv = np.zeros(n_task, np.int32)
-    cT = np.zeros((n_task, NS, NO), np.float32)
-    y0 = np.zeros((n_task, NO), np.float32)
-    valid = np.zeros((n_task, NO), np.float32)
-    cmd0 = np.zeros((n_task, NO), np.float32)
-    four_coef = np.zeros((n_task, KMAX, NO, 2), np.float32)
-    four_omega = np.zeros((n_task, KMAX), np.float64)
-    four_period = np.ones(n_task, np.float64)
-    scal = np.zeros((n_task, 8), np.float32)
-    ints = np.zeros((n_task, 4), np.int32)
-    init = np.zeros((n_task, NI, NS), np.float32)
-    action_dims = np.zeros(n_task, np.int32)
-    for i, t in enumerate(tasks):
-        ns, na, no = int(t["state_dim"]), int(t["action_dim"]), int(t["observation_dim"])
-        nsv[i] = ns
-        A[i, :ns, :ns] = np.asarray(t["ld_A"], np.float64)
-        B[i, :ns, :na] = np.asarray(t["ld_B"], np.float64)
-        X[i, :ns] = np.asarray(t["ld_X"], np.float64)
-        cT[i, :ns, :no] = np.asarray(t["ld_C"], np.float64).T
-        y0[i, :no] = np.asarray(t["ld_Y"], np.float64)
-        valid[i, :no] = np.asarray(t["target_valid"], np.float64)
-        ttype = str(t["target_type"])
-        n_terms = 0
-        if ttype == "static_target":
-            cmd0[i, :no] = np.asarray(t["command"], np.float64)
-        elif ttype == "dynamic_target":
-            orders, coeffs, period = fourier_terms(t["command"])
-            n_terms = len(orders)
-            if n_terms > KMAX:
-                raise ValueError("command has %d Fourier terms (max %d)" % (n_terms, KMAX))
-            four_omega[i, :n_terms] = orders
-            four_coef[i, :n_terms, :no, :] = coeffs
-            four_period[i] = period
-        else:
-            raise Exception("Unknown target type: {}".format(ttype))
-        scal[i, :6] = [t["action_cost"], t["reward_base"], t["terminate_punish"], t["reward_factor"],
-                       float(t["noise_drift"]) * dt, dt]
-        ints[i] = [int(t["max_steps"]), int(t["target_delay"]), len(t["initial_states"]), n_terms]
-        action_dims[i] = na
-        for k, x0 in enumerate(t["initial_states"]):
-            init[i, k, :ns] = np.asarray(x0, np.float64)
+    _, tab, (A, B, X, nsv) = _pack(tasks, dt, pad_observation_dim, pad_action_dim, pad_command_dim)
     z = build_zoh_device(engine, A, B, X, nsv, dt)
     engine.sync()
     status = z["status"].cpu().numpy()
@@ -260,6 +179,5 @@ def build_tables_device(tasks, engine, dt=0.1, pad_observation_dim=16, pad_actio
         bad = np.nonzero(status)[0]
         raise ValueError("zero-order hold failed for task(s) %s (status %s: 1 non-finite, 2 scale cap)"
                          % (bad.tolist(), status[bad].tolist()))
-    return dict(NS=NS, NA=NA, NO=NO, NI=NI, dt=float(dt), phiT=z["phiT"].cpu().numpy(), gamT=z["gamT"].cpu().numpy(), cT=cT,
-                xt=z["xt"].cpu().numpy(), y0=y0, valid=valid, cmd0=cmd0, four_coef=four_coef, four_omega=four_omega,
-                four_period=four_period, scal=scal, ints=ints, init=init, action_dims=action_dims)
+    tab.update(phiT=z["phiT"].cpu().numpy(), gamT=z["gamT"].cpu().numpy(), xt=z["xt"].cpu().numpy())
+    return tab

@@ -14,52 +14,16 @@ from .. import _lib
 from ..engine import AUTORESET
 from ..spaces import Box
 from ..vector import VectorEnv
-from .tables import build_tables
+from .tables import _Tables, build_tables, pad_tables
 
 _F32 = ("phiT", "gamT", "cT", "xt", "y0", "valid", "cmd0", "four_coef", "scal", "init")
 _F64 = ("four_omega", "four_period")
-
-
-class _Tables(C.Structure):   # xv_linds_tables (include/xeno.h)
-    _fields_ = [(k, C.c_void_p) for k in ("phiT", "gamT", "cT", "xt", "y0", "valid", "cmd0", "four_coef",
-                                          "four_omega", "four_period", "scal", "ints", "init")]
 
 
 class _MPCTables(C.Structure):   # xv_linds_mpc_tables (include/xeno.h)
     _fields_ = [("n_pad", C.c_int), ("n_in", C.c_int), ("NOc", C.c_int)] + \
         [(k, C.c_void_p) for k in ("mfrag", "gfrag", "g0", "rho", "mnorm", "nu")] + \
         [(k, C.c_float) for k in ("sigma", "alpha", "eps_abs", "eps_rel")]
-
-
-def _pad_to(n, choices):
-    for c in choices:
-        if n <= c:
-            return c
-    raise ValueError("dimension %d exceeds the supported maximum %d" % (n, choices[-1]))
-
-
-def pad_tables(tab):
-    """Zero-pad the batch dims to the kernel's compiled sizes (NS in {16,32}, NA in {8,16}, NO in {16,32}).
-    Zero padding is exact: fmaf(0, x, acc) == acc."""
-    NS, NA, NO = _pad_to(tab["NS"], (16, 32)), _pad_to(tab["NA"], (8, 16)), _pad_to(tab["NO"], (16, 32))
-    if (NS, NA, NO) == (tab["NS"], tab["NA"], tab["NO"]):
-        return tab
-    n = tab["phiT"].shape[0]
-    out = dict(tab, NS=NS, NA=NA, NO=NO)
-
-    def z(shape, dt=np.float32):
-        return np.zeros(shape, dt)
-    s, a, o = tab["NS"], tab["NA"], tab["NO"]
-    out["phiT"] = z((n, NS, NS)); out["phiT"][:, :s, :s] = tab["phiT"]
-    out["gamT"] = z((n, NA, NS)); out["gamT"][:, :a, :s] = tab["gamT"]
-    out["cT"] = z((n, NS, NO)); out["cT"][:, :s, :o] = tab["cT"]
-    out["xt"] = z((n, NS)); out["xt"][:, :s] = tab["xt"]
-    out["y0"] = z((n, NO)); out["y0"][:, :o] = tab["y0"]
-    out["valid"] = z((n, NO)); out["valid"][:, :o] = tab["valid"]
-    out["cmd0"] = z((n, NO)); out["cmd0"][:, :o] = tab["cmd0"]
-    out["four_coef"] = z(tab["four_coef"].shape[:2] + (NO, 2)); out["four_coef"][:, :, :o] = tab["four_coef"]
-    out["init"] = z((n, tab["NI"], NS)); out["init"][:, :, :s] = tab["init"]
-    return out
 
 
 class LinDSVecEnv(VectorEnv):
@@ -90,32 +54,16 @@ class LinDSVecEnv(VectorEnv):
                                pad_action_dim=self.pad_action_dim, pad_command_dim=self.pad_command_dim)
         self.user_dims = (int(tab["NA"]), int(tab["NO"]))
         tab = pad_tables(tab)
-        d = self.device
-        dev = {}
-        for k in _F32:
-            dev[k] = torch.as_tensor(np.ascontiguousarray(tab[k], np.float32)).to(d) if not torch.is_tensor(tab[k]) \
-                else tab[k].to(d, torch.float32).contiguous()
-        for k in _F64:
-            dev[k] = torch.as_tensor(np.ascontiguousarray(tab[k], np.float64)).to(d) if not torch.is_tensor(tab[k]) \
-                else tab[k].to(d, torch.float64).contiguous()
-        dev["ints"] = torch.as_tensor(np.ascontiguousarray(tab["ints"], np.int32)).to(d) \
-            if not torch.is_tensor(tab["ints"]) else tab["ints"].to(d, torch.int32).contiguous()
+        dev = {k: self._dev(tab[k], torch.float32) for k in _F32}
+        dev.update((k, self._dev(tab[k], torch.float64)) for k in _F64)
+        dev["ints"] = self._dev(tab["ints"], torch.int32)
         n_task = int(dev["phiT"].shape[0])
-        if env_task_index is None:
-            if self.num_envs % n_task != 0:
-                raise ValueError("num_envs is not a multiple of the task count; pass env_task_index")
-            env_task = torch.arange(self.num_envs, device=d, dtype=torch.int32) // (self.num_envs // n_task)
-        else:
-            env_task = self._dev(env_task_index, torch.int32)
-            if env_task.shape != (self.num_envs,) or int(env_task.min()) < 0 or int(env_task.max()) >= n_task:
-                raise ValueError("env_task_index must be (num_envs,) with entries in [0, n_task)")
-        dev["env_task"] = env_task.contiguous()
+        dev["env_task"] = self._env_task(n_task, env_task_index)
         self.NS, self.NA, self.NO, self.NI = int(tab["NS"]), int(tab["NA"]), int(tab["NO"]), int(tab["NI"])
         if self._h is not None:
             self.lib.xv_linds_destroy(self._h)
             self._h = None
-        ct = _Tables(*[_lib.ptr(dev[k]) for k in ("phiT", "gamT", "cT", "xt", "y0", "valid", "cmd0", "four_coef",
-                                                   "four_omega", "four_period", "scal", "ints", "init")])
+        ct = _Tables(*[_lib.ptr(dev[k]) for k, _ in _Tables._fields_])
         h = C.c_void_p()
         _lib.check(self.lib.xv_linds_create(self.engine.handle, self.num_envs, n_task, self.NS, self.NA, self.NO,
                                             self.NI, C.byref(ct), _lib.ptr(dev["env_task"]), C.byref(h)))
@@ -155,17 +103,27 @@ class LinDSVecEnv(VectorEnv):
     def _user_obs(self, t):
         return t[:, :self.user_dims[1]]
 
-    def _action(self, actions):
+    def _action(self, actions, lead=()):
+        """actions float[lead..., N, na_user] (lead: () for one step, (P,) for a ring or a roll-out) -> contiguous
+        float32[lead..., N, NA] on the device, zero in the padded columns"""
         a = self._dev(actions, torch.float32)
         na_user = self.user_dims[0]
-        if a.shape != (self.num_envs, na_user):
+        want = tuple(lead) + (self.num_envs, na_user)
+        if a.shape != want:
             # reference: assert numpy.shape(action) == (self.pad_action_dim,) (linds_env.py:137)
-            raise AssertionError(f"Action shape mismatch: expected {(self.num_envs, na_user)}, got {tuple(a.shape)}")
+            raise AssertionError(f"Action shape mismatch: expected {want}, got {tuple(a.shape)}")
         if na_user != self.NA:
-            p = torch.zeros((self.num_envs, self.NA), dtype=torch.float32, device=self.device)
-            p[:, :na_user] = a
+            p = torch.zeros(want[:-1] + (self.NA,), dtype=torch.float32, device=self.device)
+            p[..., :na_user] = a
             a = p
         return a.contiguous()
+
+    def _rollout_spec(self):
+        """what a roll-out / step_many slot holds per step, as _alloc takes it: the first four without infos.  final_obs is
+        zero-filled: the kernels write the rows of finished envs only"""
+        f32, u8, NO = torch.float32, torch.uint8, self.NO
+        return [("obs", f32, (NO,)), ("reward", f32, ()), ("terminated", u8, ()), ("truncated", u8, ()),
+                ("command", f32, (NO,)), ("error", f32, ()), ("final_obs", f32, (NO,), 0)]
 
     def _steps_now(self):
         st = torch.empty(self.num_envs, dtype=torch.int32, device=self.device)
@@ -177,12 +135,7 @@ class LinDSVecEnv(VectorEnv):
 
     # -- API ----------------------------------------------------------------------------------------
     def reset(self, *, seed=None, options=None):
-        self._require_task()
-        if seed is not None:
-            self.engine.tick = (int(seed) & 0xFFFFFFFF) << 24
-        mask = None
-        if options is not None and options.get("reset_mask") is not None:
-            mask = self._dev(options["reset_mask"], torch.uint8)
+        mask = self._reset_prelude(seed, options)
         self._adopt_latest(_obs="obs", _cmd="cmd", _error="error")
         self._detach("_obs", "_cmd", "_error")
         _lib.check(self.lib.xv_linds_reset(self._h, _lib.ptr(mask), _lib.ptr(self._obs), _lib.ptr(self._cmd),
@@ -204,9 +157,7 @@ class LinDSVecEnv(VectorEnv):
         self.need_reset = False
         return self._o(self._user_obs(self._obs)), self._reset_infos()
 
-    def _check_step(self):
-        if (not self.task_set) or self.need_reset:
-            raise Exception("Must \"set_task\" and \"reset\" before doing any actions")   # linds_env.py:134-135
+    _check_step = VectorEnv._require_reset
 
     def _steps_and_done(self, s):
         """after a launch that writes the first seven outputs only (the scalar test kernel, step_injected): `steps` and the done
@@ -261,25 +212,10 @@ class LinDSVecEnv(VectorEnv):
         step k uses slot k % P and writes slot k % P of the returned dict of [P, N(, NO)] device tensors.  Equals n_steps
         calls of step(); `final_obs` rows are written for finished envs only."""
         self._check_step()
-        a = self._dev(actions, torch.float32)
-        P = int(a.shape[0])
-        na_user = self.user_dims[0]
-        if a.shape != (P, self.num_envs, na_user):
-            raise AssertionError(f"Action shape mismatch: expected {(P, self.num_envs, na_user)}, got {tuple(a.shape)}")
-        if na_user != self.NA:
-            p = torch.zeros((P, self.num_envs, self.NA), dtype=torch.float32, device=self.device)
-            p[..., :na_user] = a
-            a = p
-        a = a.contiguous()
-        d, n = self.device, self.num_envs
+        P = len(actions)
+        a = self._action(actions, (P,))
         if out is None:
-            out = dict(obs=torch.empty((P, n, self.NO), dtype=torch.float32, device=d),
-                       reward=torch.empty((P, n), dtype=torch.float32, device=d),
-                       terminated=torch.empty((P, n), dtype=torch.uint8, device=d),
-                       truncated=torch.empty((P, n), dtype=torch.uint8, device=d),
-                       command=torch.empty((P, n, self.NO), dtype=torch.float32, device=d),
-                       error=torch.empty((P, n), dtype=torch.float32, device=d),
-                       final_obs=torch.zeros((P, n, self.NO), dtype=torch.float32, device=d))
+            out = self._alloc(self._rollout_spec(), (P,))
         _lib.check(self.lib.xv_linds_step_many(self._h, int(n_steps), P, _lib.ptr(a), _lib.ptr(out["obs"]),
                                                _lib.ptr(out["reward"]), _lib.ptr(out["terminated"]),
                                                _lib.ptr(out["truncated"]), _lib.ptr(out["command"]), _lib.ptr(out["error"]),
@@ -290,27 +226,10 @@ class LinDSVecEnv(VectorEnv):
         """Fused open-loop roll-out: actions float32[T, N, na] -> dict of [T, N(, NO)] device tensors, one launch with the
         state resident in registers between the steps.  Equals T calls of step() with SAME_STEP auto-reset, bit for bit."""
         self._check_step()
-        a = self._dev(actions, torch.float32)
-        T = int(a.shape[0])
-        na_user = self.user_dims[0]
-        if a.shape != (T, self.num_envs, na_user):
-            raise AssertionError(f"Action shape mismatch: expected {(T, self.num_envs, na_user)}, got {tuple(a.shape)}")
-        if na_user != self.NA:
-            p = torch.zeros((T, self.num_envs, self.NA), dtype=torch.float32, device=self.device)
-            p[..., :na_user] = a
-            a = p
-        a = a.contiguous()
-        d, n = self.device, self.num_envs
-        if out is None:
-            out = dict(obs=torch.empty((T, n, self.NO), dtype=torch.float32, device=d),
-                       reward=torch.empty((T, n), dtype=torch.float32, device=d),
-                       terminated=torch.empty((T, n), dtype=torch.uint8, device=d),
-                       truncated=torch.empty((T, n), dtype=torch.uint8, device=d))
-            if with_info:
-                out.update(command=torch.empty((T, n, self.NO), dtype=torch.float32, device=d),
-                           error=torch.empty((T, n), dtype=torch.float32, device=d),
-                           final_obs=torch.zeros((T, n, self.NO), dtype=torch.float32, device=d))   # written for
-                # finished envs only; a caller-supplied `out` keeps its other rows
+        T = len(actions)
+        a = self._action(actions, (T,))
+        if out is None:      # (a caller-supplied `out` keeps the final_obs rows of unfinished envs)
+            out = self._alloc(self._rollout_spec() if with_info else self._rollout_spec()[:4], (T,))
         _lib.check(self.lib.xv_linds_rollout(self._h, T, _lib.ptr(a), _lib.ptr(out["obs"]), _lib.ptr(out["reward"]),
                                              _lib.ptr(out["terminated"]), _lib.ptr(out["truncated"]),
                                              _lib.ptr(out.get("command")), _lib.ptr(out.get("error")),
@@ -451,17 +370,9 @@ class LinDSVecEnv(VectorEnv):
         self._check_step()
         T = int(T)
         h, _ = self._mpc(K, gamma, max_iter)
-        d, n = self.device, self.num_envs
-        out = dict(action=torch.empty((T, n, self.NA), dtype=torch.float32, device=d),
-                   obs=torch.empty((T, n, self.NO), dtype=torch.float32, device=d),
-                   reward=torch.empty((T, n), dtype=torch.float32, device=d),
-                   terminated=torch.empty((T, n), dtype=torch.uint8, device=d),
-                   truncated=torch.empty((T, n), dtype=torch.uint8, device=d),
-                   command=torch.empty((T, n, self.NO), dtype=torch.float32, device=d),
-                   error=torch.empty((T, n), dtype=torch.float32, device=d),
-                   final_obs=torch.zeros((T, n, self.NO), dtype=torch.float32, device=d),
-                   status=torch.empty((T, n), dtype=torch.int32, device=d),
-                   iters=torch.empty((T, n), dtype=torch.int32, device=d))
+        i32 = torch.int32
+        out = self._alloc([("action", torch.float32, (self.NA,))] + self._rollout_spec() + [("status", i32, ()), ("iters", i32, ())],
+                          (T,))
         _lib.check(self.lib.xv_linds_rollout_mpc(h, T, *[_lib.ptr(out[k]) for k in (
             "action", "obs", "reward", "terminated", "truncated", "command", "error", "final_obs", "status", "iters")]))
         return out

@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from .. import _lib
-from ..engine import Engine
+from ..device_sampling import collect_accepted, engine_scope, sampler_stats
 from . import sampler_host as sh
 from .tables import LMAX
 
@@ -96,40 +96,19 @@ def sample_tasks_device(n_tasks, seed=0, engine=None, device="cuda:0", batch=Non
     texts, landmarks, ints, dbl, commands, lm_coord) + `info` (host records) and `stats`: candidates tried, status
     histogram, seconds.  Task k is the k-th accepted candidate in candidate order, whatever `batch` is.
     `MazeWorldVecEnv.set_task(tables)` takes the result as it is.  Keyword arguments: MazeTaskSampler's."""
-    own = engine is None
-    eng = Engine(device) if own else engine
-    try:
-        if batch is None:
-            batch = int(max(64, min(4096, n_tasks)))
-        got = {k: [] for k in SLOT_KEYS}
-        infos = []
-        hist = np.zeros(len(STATUS), np.int64)
-        n_acc, base, t0 = 0, 0, time.perf_counter()
-        NG = n_cmd = None
-        while n_acc < n_tasks:
-            if max_candidates is not None and base >= max_candidates:
-                raise RuntimeError("only %d of %d tasks accepted within %d candidates" % (n_acc, n_tasks, base))
-            r = sample_candidates(eng, seed, base, batch, info=True, **sampler_kwargs)
-            NG, n_cmd = r["NG"], r["n_cmd"]
-            st = r["info"]["status"]
-            acc = np.nonzero(st == 0)[0][: n_tasks - n_acc]
-            last = int(acc[-1]) + 1 if len(acc) and n_acc + len(acc) >= n_tasks else batch
-            hist += np.bincount(st[:last], minlength=len(STATUS))[: len(STATUS)]
-            sel = torch.as_tensor(acc, device=eng.device)
-            for k in SLOT_KEYS:
-                got[k].append(r[k].index_select(0, sel))
-            infos.append(r["info"][acc])
-            n_acc += int(len(acc))
-            base += batch
-        out = dict(NG=NG, n_cmd=n_cmd, **{k: torch.cat(v) for k, v in got.items()})
-        out["info"] = np.concatenate(infos)
+    if batch is None:
+        batch = int(max(64, min(4096, n_tasks)))
+    a = sh.sampler_arguments(**sampler_kwargs)
+    with engine_scope(engine, device) as eng:
+        t0 = time.perf_counter()
+        got, info, hist = collect_accepted(
+            lambda base, n: sample_candidates(eng, seed, base, n, info=True, **sampler_kwargs),
+            n_tasks, batch, SLOT_KEYS, STATUS, max_candidates)
+        out = dict(NG=sh.grid_pitch(a["n_range"]), n_cmd=int(a["commands_sequence"]), **got)      # as sample_candidates has them
+        out["info"] = info
         eng.sync()
-        out["stats"] = dict(candidates=int(hist.sum()), accepted=int(hist[0]), seconds=time.perf_counter() - t0,
-                            status={STATUS[i]: int(hist[i]) for i in range(len(STATUS))}, batch=batch)
+        out["stats"] = sampler_stats(hist, STATUS, batch, t0)
         return out
-    finally:
-        if own:
-            eng.close()
 
 
 def resample_tasks_device(tables, seed=0, episode=0, resample_cmd=True, resample_start=True, resample_landmarks=False,
@@ -146,9 +125,7 @@ def resample_tasks_device(tables, seed=0, episode=0, resample_cmd=True, resample
     for k, shape in shapes.items():      # the kernel addresses the tables by these pitches
         if tuple(tables[k].shape) != shape or tables[k].dtype != dtypes[k] or tables[k].device != w.device:
             raise ValueError("table %r must be %s%s on %s" % (k, dtypes[k], list(shape), w.device))
-    own = engine is None
-    eng = Engine(str(w.device)) if own else engine
-    try:
+    with engine_scope(engine, str(w.device)) as eng:
         new = dict(tables)
         for k in ("landmarks", "lm_coord", "ints", "commands"):
             new[k] = tables[k].contiguous().clone()
@@ -162,9 +139,6 @@ def resample_tasks_device(tables, seed=0, episode=0, resample_cmd=True, resample
                                                   C.cast(C.byref(slots), C.c_void_p)))
         eng.sync()
         return new
-    finally:
-        if own:
-            eng.close()
 
 
 def task_dicts_from_device(tables):

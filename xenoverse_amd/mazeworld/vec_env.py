@@ -96,15 +96,7 @@ class MazeWorldVecEnv(VectorEnv):
                 int(dev["ints"][:, 3].max()) >= dev["tex_grounds"].shape[0] or \
                 int(dev["ints"][:, 4].max()) >= dev["tex_ceilings"].shape[0]:
             raise ValueError("task texture ids exceed the texture library size")
-        if env_task_index is None:
-            if self.num_envs % n_task != 0:
-                raise ValueError("num_envs is not a multiple of the task count; pass env_task_index")
-            env_task = torch.arange(self.num_envs, device=d, dtype=torch.int32) // (self.num_envs // n_task)
-        else:
-            env_task = self._dev(env_task_index, torch.int32)
-            if env_task.shape != (self.num_envs,) or int(env_task.min()) < 0 or int(env_task.max()) >= n_task:
-                raise ValueError("env_task_index must be (num_envs,) with entries in [0, n_task)")
-        dev["env_task"] = env_task.contiguous()
+        dev["env_task"] = self._env_task(n_task, env_task_index)
         self._close_agents()
         if self._h is not None:
             self.lib.xv_maze_destroy(self._h)
@@ -144,9 +136,7 @@ class MazeWorldVecEnv(VectorEnv):
     def reset(self, *, seed=None, options=None):
         if not self.task_set:
             raise Exception("Must call \"set_task\" before reset")   # maze_env.py:35-36
-        mask = None
-        if options is not None and options.get("reset_mask") is not None:
-            mask = self._dev(options["reset_mask"], torch.uint8)
+        mask = self._reset_mask(options)      # (`seed` is not applied here)
         self._detach("_frames", "_cmd_rgb")
         _lib.check(self.lib.xv_maze_reset(self._h, _lib.ptr(mask), _lib.ptr(self._frames), _lib.ptr(self._cmd_rgb)))
         self.need_reset = False

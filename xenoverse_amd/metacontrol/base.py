@@ -53,16 +53,8 @@ class ControlVecEnv(VectorEnv):
         params = np.array([[t[k] for k in self.TASK_KEYS] for t in tasks], np.float64)
         d = self.device
         n_task = len(tasks)
-        if env_task_index is None:
-            if self.num_envs % n_task != 0:
-                raise ValueError("num_envs is not a multiple of the task count; pass env_task_index")
-            env_task = torch.arange(self.num_envs, device=d, dtype=torch.int32) // (self.num_envs // n_task)
-        else:
-            env_task = self._dev(env_task_index, torch.int32)
-            if env_task.shape != (self.num_envs,) or int(env_task.min()) < 0 or int(env_task.max()) >= n_task:
-                raise ValueError("env_task_index must be (num_envs,) with entries in [0, n_task)")
         self._tab = dict(params=torch.from_numpy(params).to(d), scale=torch.from_numpy(self.reset_bounds_scale).to(d),
-                         env_task=env_task.contiguous())
+                         env_task=self._env_task(n_task, env_task_index))
         self.close_extras()
         h = C.c_void_p()
         _lib.check(self._c_create(self.engine.handle, self.num_envs, n_task, self.frameskip, self.max_steps,
@@ -78,12 +70,7 @@ class ControlVecEnv(VectorEnv):
         self.need_reset = True
 
     def reset(self, *, seed=None, options=None):
-        self._require_task()
-        if seed is not None:
-            self.engine.tick = (int(seed) & 0xFFFFFFFF) << 24
-        mask = None
-        if options is not None and options.get("reset_mask") is not None:
-            mask = self._dev(options["reset_mask"], torch.uint8)
+        mask = self._reset_prelude(seed, options)
         self._adopt_latest(_obs="obs")
         self._detach("_obs")
         _lib.check(self._c_reset(self._h, _lib.ptr(mask), _lib.ptr(self._obs)))
@@ -112,10 +99,6 @@ class ControlVecEnv(VectorEnv):
             return self._numpy(t["obs"], t["reward"], t["term"], t["trunc"], infos)
         return t["obs"], t["reward"], t["term"], t["trunc"], infos
 
-    def _require_reset(self):
-        if (not self.task_set) or self.need_reset:
-            raise Exception("Must \"set_task\" and \"reset\" before doing any actions")
-
     def step(self, actions):
         self._require_reset()
         a = self._dev(actions, torch.int32)
@@ -129,14 +112,11 @@ class ControlVecEnv(VectorEnv):
         the state in registers between the steps; equals T calls of step() bit for bit."""
         self._require_reset()
         a = self._dev(actions, torch.int32).contiguous()
-        T, n, w, d = int(a.shape[0]), self.num_envs, self.OBS_DIM, self.device
-        assert a.shape == (T, n)
+        T, w, f32, u8 = int(a.shape[0]), self.OBS_DIM, torch.float32, torch.uint8
+        assert a.shape == (T, self.num_envs)
         if out is None:
-            out = dict(obs=torch.empty((T, n, w), dtype=torch.float32, device=d),
-                       reward=torch.empty((T, n), dtype=torch.float32, device=d),
-                       terminated=torch.empty((T, n), dtype=torch.uint8, device=d),
-                       truncated=torch.empty((T, n), dtype=torch.uint8, device=d),
-                       final_obs=torch.empty((T, n, w), dtype=torch.float32, device=d))
+            out = self._alloc((("obs", f32, (w,)), ("reward", f32, ()), ("terminated", u8, ()), ("truncated", u8, ()),
+                               ("final_obs", f32, (w,))), (T,))
         _lib.check(self._c_rollout(self._h, T, _lib.ptr(a), _lib.ptr(out["obs"]), _lib.ptr(out["reward"]),
                                    _lib.ptr(out["terminated"]), _lib.ptr(out["truncated"]),
                                    _lib.ptr(out.get("final_obs")), AUTORESET[self.autoreset_mode]))

@@ -209,6 +209,20 @@ class StepOutputs(object):
         return s
 
 
+def env_task_map(num_envs, n_task, index=None, device="cpu"):
+    """The task of every env as a contiguous int32[num_envs] tensor on `device`.  index None: the envs split evenly and
+    contiguously over the tasks (num_envs must be a multiple of n_task); else `index` (tensor / ndarray / list), checked:
+    the kernels read their task's tables by it."""
+    if index is None:
+        if num_envs % n_task != 0:
+            raise ValueError("num_envs is not a multiple of the task count; pass env_task_index")
+        return torch.arange(num_envs, device=device, dtype=torch.int32) // (num_envs // n_task)
+    t = torch.as_tensor(index).to(device=device, dtype=torch.int32).contiguous()
+    if t.shape != (num_envs,) or int(t.min()) < 0 or int(t.max()) >= n_task:
+        raise ValueError("env_task_index must be (num_envs,) with entries in [0, n_task)")
+    return t
+
+
 class VectorEnv(_GymVectorEnv):
     metadata = {"autoreset_mode": "same_step"}
     render_mode = None
@@ -315,14 +329,47 @@ class VectorEnv(_GymVectorEnv):
     def _obf(self, t):
         return self._out(t.bool() if self.to_numpy else t.view(torch.bool))
 
-    def _ob(self, t):
-        """a uint8 0/1 flag buffer -> bool tensor (zero-copy view when copy=False)"""
-        return self._out(t.bool() if (self.copy or self.to_numpy) else t.view(torch.bool))
-
     def _require_task(self):
         if not self.task_set:
             # reference: raise Exception("Must call \"set_task\" first") (anymdp_env.py:83, linds_env.py:110)
             raise Exception("Must call \"set_task\" first")
+
+    def _require_reset(self):
+        if (not self.task_set) or self.need_reset:
+            # reference message (anymdp_env.py:93-94, linds_env.py:134-135)
+            raise Exception("Must \"set_task\" and \"reset\" before doing any actions")
+
+    def _env_task(self, n_task, env_task_index):
+        """set_task's env -> task mapping on this env's device (env_task_map above)"""
+        return env_task_map(self.num_envs, n_task, env_task_index, self.device)
+
+    def _reset_mask(self, options):
+        """reset(options={"reset_mask": ...}) -> uint8[N] device tensor, or None: every env"""
+        if options is not None and options.get("reset_mask") is not None:
+            return self._dev(options["reset_mask"], torch.uint8)
+        return None
+
+    def _reset_prelude(self, seed, options):
+        """the head of reset(): a task must be set; `seed` (int) re-keys the engine's Philox stream position; -> the mask"""
+        self._require_task()
+        if seed is not None:
+            self.engine.tick = (int(seed) & 0xFFFFFFFF) << 24
+        return self._reset_mask(options)
+
+    def _alloc(self, spec, lead=()):
+        """spec: [(name, torch dtype, trailing shape[, fill])] -> {name: tensor[lead..., N, trailing...]} on the device, in
+        spec order.  Without `fill` the tensor is uninitialised (the launch writes every entry); with it, filled (outputs a
+        launch writes only in part)."""
+        shape, out = tuple(lead) + (self.num_envs,), {}
+        for f in spec:
+            size = shape + tuple(f[2])
+            if len(f) < 4:
+                out[f[0]] = torch.empty(size, dtype=f[1], device=self.device)
+            elif f[3] == 0:
+                out[f[0]] = torch.zeros(size, dtype=f[1], device=self.device)
+            else:
+                out[f[0]] = torch.full(size, f[3], dtype=f[1], device=self.device)
+        return out
 
     def _capture_hold(self, on):
         """while a captured loop exists: pins whatever the family alternates between step() calls (output sets) and,
