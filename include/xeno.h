@@ -1340,6 +1340,75 @@ int xv_anyhvac_rollout_mapped(xv_anyhvac* h, int T, const xv_anyhvac_io* io, con
 int xv_anyhvac_act_get_state(xv_anyhvac* h, uint64_t* window);
 int xv_anyhvac_act_set_state(xv_anyhvac* h, const uint64_t* window);
 
+/* AnyHVAC tasks made on the device (additions within ABI 12; csrc/anyhvac_sampler.hip) — reference:
+ * xenoverse/anyhvac/anyhvac_sampler.py HVACTaskSampler, anyhvac_utils.py (node classes, wind_diffuser), utils/random_nn.py
+ * RandomFourier.  One launch over candidates [cand_base, cand_base + n_cand), one 256-lane workgroup per candidate: head
+ * scalars, convection coefficients and heat capacities, placement by rejection, Fourier rows, cooler unification, the
+ * diffusers (wind_diffuser as a fixed point: whole-grid passes until nothing changes, walls from the final values, numpy's
+ * pairwise order for the normalising sum), the bilinear reads, the week-long average heat (skipped under generate_task:
+ * 10000).  `table` rows are complete in the layout above, padded exactly as anyhvac.tables.build_tables pads (heat capacity
+ * 1, periods 1, column 20 of a cooler row 1, zeros elsewhere); a candidate without a task (status != 0) is all padding.
+ * `extras` rows keep what the table does not: sensor_loc[S][2], heater_loc[H][2], cooler_loc[C][2], heater sigma[H], cooler
+ * sigma[C], the unify coefficient, the smallest relative margin of the bias rejection (|s| against its bound) and of the
+ * diffusers' `k > 1e-3` (+inf where none), 0.
+ *
+ * Randomness: Philox4x32-10, key = seed, counter = {candidate lo, candidate hi, sub, purpose | tick << 8}; one call gives two
+ * uniforms (words 0,1 and words 2,3, xv_u53) or one fp64 Box-Muller pair (radius sqrt(-2 log(1 - u_a)), angle 2 pi u_b:
+ * cos first, sin second); element q of a block of uniforms is half q & 1 of call q >> 1; integers are floor(u * m), an
+ * exponential is -log(1 - u) * scale.  Purposes (tick 0 unless said): 0 head (sub 0 n_width, n_length; 1 cell_size,
+ * floor_height; 2 wall chtc, floorceil chtc; 3 sensor, heater density; 4 cooler density, ambient bucket; 5 ambient, target;
+ * 6 drift std, unify draw; 7 unify_ratio); 1 convection coefficients (block over walls (i (nl + 1) + j) 2 + d); 2 heat
+ * capacities (block over cells i nl + j); 3 / 4 / 5 sensor / heater / cooler placement (tick = node, sub = attempt: x, y);
+ * 6 sensor (tick = sensor: sub 0 period, box; Fourier block from sub 1); 7 base heater (sub 0 period, scale; 1 heat_base;
+ * Fourier block from 2); 8 heater (tick = heater: as 7; sub 128 sigma, base_factor; 129 equipment heat capacity); 9 cooler
+ * (tick = cooler: sub 0 power_eff_vent, eer_base; 1 eer_decay_start, eer_zero_point; 2 eer_reverse, sigma; 3 decay_ub,
+ * decay_lb; 4 max_cooling_power, power_vent_min; 5 fixed-ratio decision, ratio or power; 6 sign, delay; 16 + a: the normal
+ * of bias attempt a < 256); 10 unification keys (block over coolers, 53-bit integers).  A Fourier block from sub f: f
+ * n_items; term t at f + 1 + 4 t: + 0 order integer, + 1 order normal, + 2 coefficient normals, + 3 coefficient exponentials.
+ * Ticks stay below 2^24.  A candidate is a pure function of (seed, params, dimensions, candidate index).
+ *
+ * Placement: attempt a of node i draws (x = floor(u int(dw)), y = dl u); it passes when its cell exists and no earlier node
+ * of the kind is closer than min_dist (squared distances); the lowest passing attempt wins; 4096 attempts, then status 1.
+ * Unification: draw < 0.4 all coolers take cooler 0's parameters; < 0.8 the n coolers of index >= 1 with the smallest keys
+ * (ties by index) do, n = max(1, int((coolers - 1) unify_ratio)); with one cooler that is status 2.
+ * status int32[n_cand]: 0 accepted, 1 placement_cap, 2 unify_empty, 3 too_big (a count above NW, NL, C, S or H). */
+enum {
+  XV_ANYHVAC_R_CELL_SIZE = 0, XV_ANYHVAC_R_FLOOR_HEIGHT, XV_ANYHVAC_R_INTERNAL_CHTC, XV_ANYHVAC_R_WALL_CHTC,
+  XV_ANYHVAC_R_FLOOR_CHTC, XV_ANYHVAC_R_GRID_HC, XV_ANYHVAC_R_EQUIPMENT_HC, XV_ANYHVAC_R_SENSOR_DENSITY,
+  XV_ANYHVAC_R_HEATER_DENSITY, XV_ANYHVAC_R_COOLER_DENSITY, XV_ANYHVAC_R_TARGET, XV_ANYHVAC_R_HEAT_SIGMA,
+  XV_ANYHVAC_R_COOLER_SIGMA, XV_ANYHVAC_R_VENT_EFFICIENCY, XV_ANYHVAC_R_EER_BASE, XV_ANYHVAC_R_EER_DECAY_START,
+  XV_ANYHVAC_R_EER_ZERO_POINT, XV_ANYHVAC_R_EER_REVERSE, XV_ANYHVAC_R_DECAY_UB, XV_ANYHVAC_R_DECAY_LB,
+  XV_ANYHVAC_R_MAX_COOLING_POWER, XV_ANYHVAC_R_POWER_VENT_MIN, XV_ANYHVAC_R_FIXED_RATIO, XV_ANYHVAC_R_FIXED_POWER,
+  XV_ANYHVAC_R_DELAY, XV_ANYHVAC_R_BASE_FACTOR, XV_ANYHVAC_R_HEAT_SCALE, XV_ANYHVAC_R_HEAT_BASE,
+  XV_ANYHVAC_SAMPLER_RANGES
+};
+#define XV_ANYHVAC_EXTRAS(C, S, H) (2 * (S) + 3 * (H) + 3 * (C) + 4)
+typedef struct xv_anyhvac_sampler_params {
+  int32_t nw_lo, nw_hi, nl_lo, nl_hi;            /* cells: lo + floor(u (hi - lo)) */
+  int32_t n_ambient, has_target, generate_task;  /* ambient buckets (<= 4); target given, not drawn; avg_total_heat = 10000 */
+  int32_t sensor_period_lo, sensor_period_hi;    /* minutes */
+  int32_t heat_period_lo, heat_period_hi;        /* minutes */
+  int32_t sensor_max_order, sensor_max_items, heat_max_order, heat_max_item;
+  int32_t reserved;
+  double ambient_low, ambient_pt[4], ambient_w[4];
+  double target, set_lower, set_upper;
+  double sensor_drift_mean, sensor_drift_ub, vent_fixed_factor, bias_mean, sign_prob;
+  double range[XV_ANYHVAC_SAMPLER_RANGES][2];    /* [lo, hi) of the uniform draws, by XV_ANYHVAC_R_* */
+} xv_anyhvac_sampler_params;
+typedef struct xv_anyhvac_cand_info {
+  int32_t status, n_width, n_length, coolers, sensors, heaters;
+  int32_t place_max, passes, unified, bias_max;   /* most attempts a node took; most diffuser passes; coolers unified */
+} xv_anyhvac_cand_info;
+int xv_anyhvac_sample_tasks(xv_engine* e, uint64_t seed, int64_t cand_base, int n_cand, int NW, int NL, int C, int S, int H,
+                            int KS, int KH, const xv_anyhvac_sampler_params* params,
+                            double* table   /* [n_cand][XV_ANYHVAC_TASK_DOUBLES(...)] */,
+                            double* extras  /* [n_cand][XV_ANYHVAC_EXTRAS(C, S, H)] */,
+                            xv_anyhvac_cand_info* info /* nullable */, int32_t* status);
+/* the argument checks of xv_anyhvac_sample_tasks alone (host code, touches no device) */
+int xv_anyhvac_sampler_check(int64_t cand_base, int n_cand, int NW, int NL, int C, int S, int H, int KS, int KH,
+                             const xv_anyhvac_sampler_params* params, const double* table, const double* extras,
+                             const int32_t* status);
+
 #ifdef __cplusplus
 }
 #endif

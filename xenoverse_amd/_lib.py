@@ -176,6 +176,8 @@ SIGNATURES = {
     "xv_anyhvac_rollout_mapped": [c_void_p, c_int, c_void_p, c_void_p, c_int],
     "xv_anyhvac_act_get_state": [c_void_p, c_void_p],
     "xv_anyhvac_act_set_state": [c_void_p, c_void_p],
+    "xv_anyhvac_sample_tasks": [c_void_p, c_u64, c_i64] + [c_int] * 8 + [c_void_p] * 5,
+    "xv_anyhvac_sampler_check": [c_i64] + [c_int] * 8 + [c_void_p] * 4,
 }
 for _p in ("xv_cartpole", "xv_acrobot"):      # the control families share one set of entry points (csrc/xv_control.h)
     SIGNATURES.update({

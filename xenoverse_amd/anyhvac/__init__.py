@@ -7,10 +7,14 @@ bit for bit to recorded runs of the reference (host.py); HVACVecEnv / HVACEnv: t
 PIDHost / pid_weights / pid_search_host: the reference's PID teachers restated on the host (pid.py);
 HVACSolverGTPID / HVACSolverLOCPID / HVACSolverGridSearchPID: the teachers on the device (vec_env.py);
 DiscreteActionHost / DiffActionHost: the reference's RL action spaces restated on the host (actions.py);
-HVACEnvDiscreteAction / HVACEnvDiffAction: the same on the device, HVACVecEnv(action_mode=...) batched (vec_env.py).
+HVACEnvDiscreteAction / HVACEnvDiffAction: the same on the device, HVACVecEnv(action_mode=...) batched (vec_env.py);
+sample_tasks_device / sample_candidates / task_dicts_from_device: tasks made on the device as the table rows set_task
+borrows (device_sampler.py), sample_candidate_host / sample_rows_host: their numpy restatement (sampler_host.py).
 """
 from .actions import ActionMapHost, DiffActionHost, DiscreteActionHost            # noqa: F401
 from .config import DEFAULTS                                                      # noqa: F401
+from .device_sampler import sample_candidates, sample_tasks_device, task_dicts_from_device   # noqa: F401
+from .sampler_host import sample_candidate_host, sample_rows_host, table_dims, wind_diffuser_host   # noqa: F401
 from .host import HVACHost, average_total_heat, check_settings, heater_powers    # noqa: F401
 from .pid import PIDHost, pid_search_host, pid_weights                            # noqa: F401
 from .task_sampler import HVACTaskSampler, task_from_reference, wind_diffuser    # noqa: F401

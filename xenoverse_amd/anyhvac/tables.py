@@ -33,13 +33,17 @@ def _nodes(loc, cell_size, nw, nl):
     return np.concatenate([sn, dn, k], axis=1).astype(np.float64), nloc
 
 
-def build_tables(tasks, set_lower_bound=16, set_upper_bound=32, generate_task=False):
+def build_tables(tasks, set_lower_bound=16, set_upper_bound=32, generate_task=False, dims=None):
     """-> dict(dims=(NW, NL, C, S, H, KS, KH), table=float64[n_task, task_doubles(*dims)], counts=[per task dict],
-    avg_total_heat=[per task])"""
+    avg_total_heat=[per task]).  dims: pad to these dimensions (the device sampler's) instead of the batch's own maxima."""
     cs = [counts(t) for t in tasks]
     for t in tasks:
         check_settings(control_type=t.get("control_type", "Temperature"))
     NW, NL, C, S, H, KS, KH = (max(c[k] for c in cs) for k in ("nw", "nl", "C", "S", "H", "KS", "KH"))
+    if dims is not None:
+        if any(a > b for a, b in zip((NW, NL, C, S, H, KS, KH), dims)):
+            raise ValueError("a task exceeds the dimensions asked for: %s > %s" % ((NW, NL, C, S, H, KS, KH), tuple(dims)))
+        NW, NL, C, S, H, KS, KH = (int(v) for v in dims)
     if NW > MAX_GRID or NL > MAX_GRID or C > MAX_COOLERS or S > MAX_SENSORS or H > MAX_HEATERS:
         raise ValueError("a task exceeds the device tables: %d x %d cells (<= %d), %d coolers (<= %d), %d sensors (<= %d), "
                          "%d heaters (<= %d)" % (NW, NL, MAX_GRID, C, MAX_COOLERS, S, MAX_SENSORS, H, MAX_HEATERS))

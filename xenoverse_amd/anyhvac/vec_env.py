@@ -33,7 +33,7 @@ from .actions import ACTION_MODES, COST_TABLE, N_BINS, STAT_KEYS, RunningStat
 from .config import RING_CAPACITY
 from .host import check_ring, check_settings
 from .pid import DEFAULT_GAINS, GAINS, first_strict_minimum, pid_weights, search_score
-from .tables import build_tables
+from .tables import build_tables, task_doubles
 
 OBS_KEYS = ("sensor_readings", "heat_readings", "action_temp", "timestep")
 MISC = ("over_heat", "over_tolerace", "energy_cost", "target_cost", "time", "rest_idx", "warning_count", "episode_step")
@@ -71,31 +71,49 @@ class HVACVecEnv(VectorEnv):
         self.too_cold_limit = bool(too_cold_limit)
         self._h = None
         self._pid = None
+        self._task_list = self._task_tables = None
         self.need_reset = True
 
     # -- tasks ----------------------------------------------------------------------------------------------------
     def set_task(self, tasks, env_task_index=None, generate_task=False):
         """tasks: one flat task dict (task_sampler.py) or a list; envs share tasks through env_task_index (default: equal
         blocks).  generate_task=True takes avg_total_heat = 10000 as the reference does, False forms the reference's
-        week-long average (host.average_total_heat)."""
+        week-long average (host.average_total_heat).
+        A dict with a `table` key is the result of anyhvac.sample_tasks_device: its device rows are borrowed as they are (no
+        host copy); its set bounds and generate_task must be this call's, and flat dicts are made from it only when
+        something asks for them (set_pid(weights=None), the solver classes)."""
+        if isinstance(tasks, dict) and "table" in tasks:
+            return self._set_task_device(tasks, env_task_index, generate_task)
         if isinstance(tasks, dict):
             tasks = [tasks]
-        n_task, n, d = len(tasks), self.num_envs, self.device
+        n_task, d = len(tasks), self.device
         for t in tasks:
             check_ring(t["cooler_delay_seconds"], self.sec_per_iter)
         env_task_dev = self._env_task(n_task, env_task_index)
         env_task = env_task_dev.cpu().numpy()      # (the per-env counts and targets below are host arrays)
         tab = build_tables(tasks, self.lower_bound, self.upper_bound, generate_task)
-        self.dims = NW, NL, Cc, S, H, KS, KH = tab["dims"]
+        self.dims = tab["dims"]
         self.avg_total_heat = tab["avg_total_heat"]
         cs = tab["counts"]
         self.counts = {k: np.array([cs[i][q] for i in env_task], np.int32) for k, q in
                        (("coolers", "C"), ("sensors", "S"), ("heaters", "H"), ("n_width", "nw"), ("n_length", "nl"))}
         self._tab = dict(table=torch.from_numpy(tab["table"]).to(d), env_task=env_task_dev)
+        self._bind_tables(n_task)
+        self.default_action_value = np.array([(float(tasks[i]["target_temperature"]) - self.lower_bound)
+                                              / (self.upper_bound - self.lower_bound) for i in env_task])
+        self._targets = np.array([float(tasks[i]["target_temperature"]) for i in env_task])
+        self._task_tables = None
+        self._tasks, self._generate_task = list(tasks), bool(generate_task)
+        self.task_set = True
+        self.need_reset = True
+
+    def _bind_tables(self, n_task):
+        """a handle for self.dims over self._tab, the spaces: what both set_task paths end with"""
+        NW, NL, Cc, S, H, KS, KH = self.dims
         self.close_extras()
         h = C.c_void_p()
         max_t = int(self.max_steps * self.iter_per_step * self.sec_per_iter)
-        _lib.check(self.lib.xv_anyhvac_create(self.engine.handle, n, NW, NL, Cc, S, H, KS, KH, self.iter_per_step,
+        _lib.check(self.lib.xv_anyhvac_create(self.engine.handle, self.num_envs, NW, NL, Cc, S, H, KS, KH, self.iter_per_step,
                                               self.sec_per_iter, float(self.lower_bound), float(self.upper_bound),
                                               float(max_t), self.reward_mode, C.byref(h)))
         self._h = h
@@ -108,12 +126,53 @@ class HVACVecEnv(VectorEnv):
         self.single_observation_spaces = dict(
             sensor_readings=Box(10, 50, shape=(S,), dtype=np.float32), heat_readings=Box(0.0, 50000.0, shape=(H,)),
             action_temp=Box(-1, 33, shape=(Cc,)), timestep=Box(0, 30000, shape=(1,), dtype=np.int32))
-        self.default_action_value = np.array([(float(tasks[i]["target_temperature"]) - self.lower_bound)
-                                              / (self.upper_bound - self.lower_bound) for i in env_task])
-        self._targets = np.array([float(tasks[i]["target_temperature"]) for i in env_task])
-        self._tasks, self._generate_task = list(tasks), bool(generate_task)
+
+    def _set_task_device(self, tables, env_task_index, generate_task):
+        """set_task over the device tables of anyhvac.sample_tasks_device"""
+        table = tables["table"]
+        dims = tuple(int(v) for v in tables["dims"])
+        # (self.device is the engine's: a torch.device with its index resolved, also when the env was built with 'cuda')
+        if not torch.is_tensor(table) or table.dtype != torch.float64 or table.device != self.device \
+                or not table.is_contiguous() or table.ndim != 2 or table.shape[1] != task_doubles(*dims):
+            raise ValueError("tables['table'] must be a contiguous float64 tensor [n_task, %d] on %s"
+                             % (task_doubles(*dims), self.device))
+        check_settings(control_type=tables.get("control_type", "Temperature"))
+        if float(tables["set_lower_bound"]) != float(self.lower_bound) or \
+                float(tables["set_upper_bound"]) != float(self.upper_bound):
+            raise ValueError("the tables were sampled for set bounds (%g, %g), this env has (%g, %g)"
+                             % (tables["set_lower_bound"], tables["set_upper_bound"], self.lower_bound, self.upper_bound))
+        if bool(tables["generate_task"]) != bool(generate_task):
+            raise ValueError("the tables were sampled with generate_task=%r, set_task was called with generate_task=%r"
+                             % (bool(tables["generate_task"]), bool(generate_task)))
+        check_ring(float(tables["delay_high"]), self.sec_per_iter)
+        n_task = int(table.shape[0])
+        env_task_dev = self._env_task(n_task, env_task_index)
+        # one small read-back: the counts, and the target / average heat / default action columns of the rows
+        small = torch.cat([tables["counts"].to(torch.float64), table[:, [9, 10, 14]]], dim=1).cpu().numpy()
+        env_task = env_task_dev.cpu().numpy()
+        self.dims = dims
+        self.avg_total_heat = [float(v) for v in small[:, 6]]
+        self.counts = {k: small[env_task, j].astype(np.int32) for j, k in
+                       enumerate(("n_width", "n_length", "coolers", "sensors", "heaters"))}
+        self._tab = dict(table=table, env_task=env_task_dev)
+        self._bind_tables(n_task)
+        self.default_action_value = small[env_task, 7].copy()
+        self._targets = small[env_task, 5].copy()
+        self._task_list, self._task_tables, self._generate_task = None, tables, bool(generate_task)
         self.task_set = True
         self.need_reset = True
+
+    @property
+    def _tasks(self):
+        """the flat task dicts; made from device tables the first time something needs them"""
+        if self._task_list is None and self._task_tables is not None:
+            from .device_sampler import task_dicts_from_device
+            self._task_list = task_dicts_from_device(self._task_tables)
+        return self._task_list
+
+    @_tasks.setter
+    def _tasks(self, tasks):
+        self._task_list = tasks
 
     def _push_action_mode(self):
         if self.action_mode == "box":
