@@ -1340,6 +1340,43 @@ int xv_anyhvac_rollout_mapped(xv_anyhvac* h, int T, const xv_anyhvac_io* io, con
 int xv_anyhvac_act_get_state(xv_anyhvac* h, uint64_t* window);
 int xv_anyhvac_act_set_state(xv_anyhvac* h, const uint64_t* window);
 
+/* The episode protocol of the reference's RL trainer (run_rl.py:38-48) — reference: anyhvac_env.py HVACEnv.reset :296-371,
+ * _save / _restore / _reset_cooler_state_history :256-294, reward :519-524, step :648-649 (no_switch_action=True,
+ * control_type 'Temperature'); host restatement xenoverse_amd/anyhvac/host.py.  Per env one byte of flags, runtime data:
+ *   XV_ANYHVAC_START_RANDOM        random_start_t: a reset takes, in this order,
+ *     with XV_ANYHVAC_START_RECORD   (generate_record) t = k * iter_per_step * sec_per_iter, k uniform in [0, max_steps);
+ *                                    the history is emptied
+ *     last_fail > 0 and the env's    t = max(0, last_fail - 100 steps); the resting cooler is the history's entry at
+ *     t before the reset < max_t     max(0, len - 100) (cooler 0 if it is empty); the history is kept and goes on growing
+ *     otherwise                      the history is emptied, the resting cooler is 0 and, from two uniforms u0, u1:
+ *                                    u0 < 0.5: t = int((1 - sqrt(1 - u1)) * max_t), the square root correctly rounded;
+ *                                    else numpy.random.choice(arange(max_t + 1), p ~ 1 / (s + 1)^2): the number of
+ *                                    entries of choice_cdf that are <= u1 (searchsorted, side='right'), by one lane
+ *     and rest_start[rest] = t.  Without the flag a reset is what it was (t = 0, cooler 0 rests, the history untouched).
+ *   XV_ANYHVAC_START_NO_TERMINATE  overheat_no_termiated_training_only: a failing step still returns -30,
+ *                                  over_tolerace = 1 and sets last_fail, but terminated = 0: no autoreset follows.
+ * Every failing step sets last_fail = its rounded t (never cleared by a reset, -1 in a new handle); every other step
+ * appends the resting cooler's index to the history.  The reference keeps 1,000 entries and reads only the one at
+ * max(0, len - 100): the handle keeps the last XV_ANYHVAC_HISTORY in a ring of int16 and a count that saturates (count %
+ * XV_ANYHVAC_HISTORY stays the next slot; min(count, 1000) is the reference's len).  The start logic is part of every
+ * reset there is: xv_anyhvac_reset, _reset_injected and the same-step autoreset of every step and rollout call.
+ * Free-running draws are one Philox block per (engine seed, env_id_base + env, tick) of a purpose the grid noise does not
+ * use: the grid of a reset does not depend on the flags.  New symbols only: no ABI bump. */
+#define XV_ANYHVAC_START_RANDOM 1
+#define XV_ANYHVAC_START_RECORD 2
+#define XV_ANYHVAC_START_NO_TERMINATE 4
+#define XV_ANYHVAC_HISTORY 128
+/* flags uint8[n_env] and choice_cdf float64[n_cdf] (n_cdf = max_t + 1) on the HOST, both copied; choice_cdf may be NULL
+ * when the handle has its table already or no env can reach the choice branch.  max_steps: the record branch's range. */
+int xv_anyhvac_set_start_mode(xv_anyhvac* h, const uint8_t* flags, int64_t max_steps, const double* choice_cdf,
+                              int64_t n_cdf);
+/* u float64[n_env][2] (u0, u1), device pointer, borrowed; NULL = off.  While set, every *_injected call takes its start
+ * draws from it; under XV_ANYHVAC_START_RECORD k = floor(u1 * max_steps). */
+int xv_anyhvac_set_start_draws(xv_anyhvac* h, const double* u);
+/* last_fail float64[n_env], ring int16[n_env][XV_ANYHVAC_HISTORY], count int32[n_env]: device pointers, every one nullable */
+int xv_anyhvac_start_get_state(xv_anyhvac* h, double* last_fail, int16_t* ring, int32_t* count);
+int xv_anyhvac_start_set_state(xv_anyhvac* h, const double* last_fail, const int16_t* ring, const int32_t* count);
+
 /* AnyHVAC tasks made on the device (additions within ABI 12; csrc/anyhvac_sampler.hip) — reference:
  * xenoverse/anyhvac/anyhvac_sampler.py HVACTaskSampler, anyhvac_utils.py (node classes, wind_diffuser), utils/random_nn.py
  * RandomFourier.  One launch over candidates [cand_base, cand_base + n_cand), one 256-lane workgroup per candidate: head

@@ -176,6 +176,10 @@ SIGNATURES = {
     "xv_anyhvac_rollout_mapped": [c_void_p, c_int, c_void_p, c_void_p, c_int],
     "xv_anyhvac_act_get_state": [c_void_p, c_void_p],
     "xv_anyhvac_act_set_state": [c_void_p, c_void_p],
+    "xv_anyhvac_set_start_mode": [c_void_p, c_void_p, c_i64, c_void_p, c_i64],  # (handle, host flags, max_steps, host cdf, n)
+    "xv_anyhvac_set_start_draws": [c_void_p, c_void_p],
+    "xv_anyhvac_start_get_state": [c_void_p, c_void_p, c_void_p, c_void_p],     # (handle, last_fail, ring, count)
+    "xv_anyhvac_start_set_state": [c_void_p, c_void_p, c_void_p, c_void_p],
     "xv_anyhvac_sample_tasks": [c_void_p, c_u64, c_i64] + [c_int] * 8 + [c_void_p] * 5,
     "xv_anyhvac_sampler_check": [c_i64] + [c_int] * 8 + [c_void_p] * 4,
 }

@@ -132,9 +132,9 @@ class DiffActionHost(ActionMapHost):
         self.add_action_cost = add_action_cost
         self.too_cold_limit = too_cold_limit
 
-    def reset(self, state=None):
+    def reset(self, state=None, start_u=None):
         self.bins = None
-        return super().reset(state)
+        return super().reset(state, start_u)
 
     def action_indices(self, action):
         """the bin per cooler: the integers themselves under the MultiDiscrete space, else round(v * 12) clipped"""

@@ -16,6 +16,12 @@ the observations, and the reward's target term.  The accumulator follows numpy's
 where the controller's ratio is interpolated the power is a numpy.float64 and power * dt is added in fp64, the sum rounded
 back to float32; where the ratio is clamped to 0 or 1, or the cooler rests, the power is a Python float (the sampler's
 draws are Python floats), which numpy rounds to float32 BEFORE a float32 addition.
+
+The episode protocol of the reference's RL trainer (run_rl.py:38-48) is three setters, as there: set_random_start_t,
+set_generate_record, set_overheat_no_termiated_training_only.  reset() then follows anyhvac_env.py:301-323 branch for
+branch (see reset), every failing step remembers its time, every other step appends the resting cooler's index to a
+history the restart-before-failure branch reads 100 entries back.  BoundedHistory is the device's form of that history
+(a ring and a saturating count); tests/test_host_anyhvac_start.py proves it against the literal list.
 """
 import numpy as np
 
@@ -27,6 +33,11 @@ EXCLUDED = dict(control_type="Temperature", no_switch_action=True, action_space_
 REST_SECONDS = 3600
 FAILURE_REWARD, OVERHEAT_REWARD, ENERGY_WHT, TARGET_WHT, BASE_REWARD, WARNING_TOLERANCE = -30, -10, -3.0, -0.5, 1.0, 5
 HEAT_AVG_INTERVAL, HEAT_AVG_MAX_TIME = 30, 604800
+HISTORY_LENGTH, STEPS_BACK = 1000, 100      # the reference's cap of the history, and how far a restart goes back
+HISTORY_RING = 128                          # what the device keeps of it (include/xeno.h XV_ANYHVAC_HISTORY)
+HISTORY_WRAP = 1024 + HISTORY_RING
+START_RANDOM, START_RECORD, START_NO_TERMINATE = 1, 2, 4      # include/xeno.h XV_ANYHVAC_START_*
+SETTERS = ("random_start_t", "generate_record", "overheat_no_termiated_training_only")
 
 
 def check_settings(**settings):
@@ -37,7 +48,8 @@ def check_settings(**settings):
         ok = EXCLUDED[k]
         same = (str(v).lower() == ok.lower()) if isinstance(ok, str) else (bool(v) == ok)
         if not same:
-            raise ValueError("%s=%r is not supported by xenoverse_amd.anyhvac (only %s=%r is built)" % (k, v, k, ok))
+            hint = " as a keyword (the reference has none either): call set_%s()" % k if k in SETTERS else ""
+            raise ValueError("%s=%r is not supported by xenoverse_amd.anyhvac%s (only %s=%r is built)" % (k, v, hint, k, ok))
 
 
 def check_ring(delay_seconds, sec_per_iter):
@@ -105,6 +117,90 @@ def average_total_heat(task):
     return float(np.cumsum(step_heat)[-1] / len(ts))      # cumsum adds sequentially
 
 
+def start_cdf(max_t):
+    """the table numpy.random.choice(arange(max_t + 1), p=weights) searches, formed with the reference's own expressions
+    (anyhvac_env.py:320-321) and numpy's (cdf = p.cumsum(); cdf /= cdf[-1]): float64 [max_t + 1]"""
+    weights = 1.0 / ((np.arange(max_t + 1) + 1) ** 2)
+    weights = weights / weights.sum()
+    cdf = weights.cumsum()
+    cdf /= cdf[-1]
+    return cdf
+
+
+def choice_from_cdf(cdf, u):
+    """numpy's choice on its uniform u: the number of entries <= u"""
+    return int(np.searchsorted(cdf, u, side="right"))
+
+
+def inverse_start(u, max_t):
+    """anyhvac_env.py:315-317 on its uniform u"""
+    start_ratio = 1 - np.sqrt(1 - u)
+    return int(start_ratio * max_t)
+
+
+def start_t_probability(cdf, max_t, lo, hi):
+    """P(lo <= t <= hi) of the reference's mixed start draw (no record, no failure behind it): half the inverse-CDF
+    branch — t = int((1 - sqrt(1 - u)) max_t) >= a exactly when u >= 1 - (1 - a / max_t)^2, up to a rounding on u's
+    2^-53 grid — and half the choice branch, whose probabilities are the table's differences"""
+    def inv_at_least(a):
+        return 1.0 if a <= 0 else (0.0 if a >= max_t else (1.0 - a / max_t) ** 2)
+    below = float(cdf[lo - 1]) if lo > 0 else 0.0
+    return 0.5 * (inv_at_least(lo) - inv_at_least(hi + 1)) + 0.5 * (float(cdf[min(hi, len(cdf) - 1)]) - below)
+
+
+class BoundedHistory(object):
+    """the reference's cooler_state_history as the device keeps it.  The reference appends one rest index per step that
+    does not fail, pops the oldest beyond 1,000 entries, and reads ONE entry, at index max(0, len - 100): the 100th
+    newest once there are 100, the oldest since the last clear before.  Both lie among the last 100 appends, so a ring of
+    128 entries (int16: a room has up to 320 coolers) and the number of appends since the clear give the same entry.  The
+    count need not run on for ever: from 1152 it steps back by one ring, which keeps count % 128 — the next slot — and
+    keeps it >= 1000, so min(count, 1000) is the reference's len."""
+
+    def __init__(self):
+        self.ring = np.zeros(HISTORY_RING, np.int16)
+        self.count = 0
+
+    def clear(self):
+        self.count = 0
+
+    def append(self, rest_idx):
+        self.ring[self.count & (HISTORY_RING - 1)] = rest_idx
+        self.count = self.count + 1 - HISTORY_RING if self.count + 1 >= HISTORY_WRAP else self.count + 1
+
+    def __len__(self):
+        return min(self.count, HISTORY_LENGTH)
+
+    def restore(self, steps_back=STEPS_BACK):
+        """-> the entry at max(0, len - steps_back), None when empty"""
+        if self.count == 0:
+            return None
+        at = self.count - steps_back if self.count >= steps_back else 0
+        return int(self.ring[at & (HISTORY_RING - 1)])
+
+
+class ListHistory(object):
+    """the reference's list, literally (_save / _restore / _reset_cooler_state_history): what HVACHost keeps"""
+
+    def __init__(self):
+        self.items = []
+
+    def clear(self):
+        self.items = []
+
+    def append(self, rest_idx):
+        self.items.append(rest_idx)
+        if len(self.items) > HISTORY_LENGTH:
+            self.items.pop(0)
+
+    def __len__(self):
+        return len(self.items)
+
+    def restore(self, steps_back=STEPS_BACK):
+        if len(self.items) > 0:
+            return self.items[max(0, len(self.items) - steps_back)]
+        return None
+
+
 class HVACHost(object):
     def __init__(self, max_steps=20160, iter_per_step=200, sec_per_iter=0.15, set_lower_bound=16, set_upper_bound=32,
                  reward_mode=0, include_heat_in_observation=True, include_last_action_in_observation=True,
@@ -117,6 +213,24 @@ class HVACHost(object):
         self.include = (bool(include_heat_in_observation), bool(include_last_action_in_observation),
                         bool(include_timestep_in_observation))
         self.task_set = False
+        self.random_start_t = self.generate_record = self.overheat_no_termiated_training_only = False
+        self.last_fail_timestemp = -1
+        self.history = ListHistory()      # cooler_state_history['current_rest_cooler_idx']
+        self.t = 0.0                      # (the reference's reset reads self.t only behind last_fail > 0)
+
+    def set_random_start_t(self, random_start_t):
+        self.random_start_t = random_start_t
+
+    def set_generate_record(self, generate_record):
+        self.generate_record = generate_record
+
+    def set_overheat_no_termiated_training_only(self, overheat_no_termiated_training_only):
+        self.overheat_no_termiated_training_only = overheat_no_termiated_training_only
+
+    def _start_cdf(self):
+        if getattr(self, "_cdf", (None, None))[0] != self.max_t:
+            self._cdf = (self.max_t, start_cdf(self.max_t))
+        return self._cdf[1]
 
     def set_task(self, task, generate_task=False):
         check_settings(control_type=task.get("control_type", "Temperature"))
@@ -146,22 +260,47 @@ class HVACHost(object):
         self.task_set = True
 
     # -- episode --------------------------------------------------------------------------------------------------
-    def reset(self, state=None):
+    def reset(self, state=None, start_u=None):
         """state: the initial grid [nw, nl] (tests inject the recorded one); None draws ambient + 2 N(0, 1) from numpy's
-        global stream, as the reference does"""
+        global stream, as the reference does.  start_u: (u0, u1), the uniforms of the start draw (under generate_record
+        u1 alone: k = floor(u1 max_steps)); None takes them from numpy's global stream with the reference's own calls.
+        Under random_start_t, anyhvac_env.py:301-323 in its order: generate_record -> a uniform step, the history
+        emptied; a failure behind and t < max_t -> 100 steps before it, with the rest index of 100 history entries ago;
+        else the history emptied and the mixed draw.  Without it t = 0 and cooler 0 rests; the history is not touched."""
         if state is None:
             state = np.full((self.nw, self.nl), self.ambient_temp) + np.random.normal(0, 2.0, (self.nw, self.nl))
         self.state = np.array(state, np.float64).reshape(self.nw, self.nl)
         self.max_t = int(self.max_steps * self.iter_per_step * self.sec_per_iter)
-        self.t = 0.0
+        rest = 0
+        if self.random_start_t:
+            if self.generate_record:
+                k = np.random.randint(0, self.max_steps) if start_u is None else int(np.floor(start_u[1] * self.max_steps))
+                self.t = k * self.iter_per_step * self.sec_per_iter
+                self.history.clear()
+            elif self.last_fail_timestemp > 0 and self.t < self.max_t:
+                self.t = max(0, self.last_fail_timestemp - STEPS_BACK * self.iter_per_step * self.sec_per_iter)
+                if len(self.history) > 0:
+                    rest = self.history.restore(STEPS_BACK)
+            else:
+                self.history.clear()
+                if (np.random.random() if start_u is None else start_u[0]) < 0.5:
+                    self.t = inverse_start(np.random.random() if start_u is None else start_u[1], self.max_t)
+                elif start_u is None:
+                    weights = 1.0 / ((np.arange(self.max_t + 1) + 1) ** 2)
+                    weights = weights / weights.sum()
+                    self.t = np.random.choice(np.arange(self.max_t + 1), p=weights)
+                else:
+                    self.t = choice_from_cdf(self._start_cdf(), start_u[1])
+        else:
+            self.t = 0.0
         self.episode_step = 0
         self.warning_count = 0
         self.rest_start = np.zeros(self.n_coolers)
-        self.rest_idx = 0
-        self.rest_start[0] = self.t
+        self.rest_idx = rest
+        self.rest_start[rest] = self.t
         self.default_action_value = (self.target_temperature - self.lower_bound) / (self.upper_bound - self.lower_bound)
         self.switch = np.ones(self.n_coolers, np.int8)
-        self.switch[0] = 0
+        self.switch[rest] = 0
         self.value = np.full(self.n_coolers, self.default_action_value, np.float32)
         obs = self._obs()
         self.filter_out = [0.0] * self.n_coolers      # cooler.reset(): last_output = 0.0, the queue empty, no last call
@@ -294,6 +433,8 @@ class HVACHost(object):
         reward, terminated, info = self._reward(obs["sensor_readings"], average_power, heat_power)
         truncated = self.t >= self.max_t
         info.update(time=self.t, heat_power=np.copy(equip_heat), cool_power=powers, state=self.state.copy())
+        if self.overheat_no_termiated_training_only:      # (the failure's reward, info and last_fail stand)
+            terminated = False
         return obs, reward, terminated, truncated, info
 
     def _reward(self, obs_arr, power, heat_power):
@@ -316,5 +457,7 @@ class HVACHost(object):
         info = {"over_heat": overheat, "over_tolerace": 0, "energy_cost": energy_cost, "target_cost": target_cost}
         if self.warning_count > WARNING_TOLERANCE:
             info["over_tolerace"] = 1
+            self.last_fail_timestemp = self.t
             return FAILURE_REWARD, True, info
+        self.history.append(self.rest_idx)      # _save_cooler_state_history: a failing step returns before it
         return BASE_REWARD + target_cost + 0.0 + energy_cost + 0.0 + overheat_cost, False, info

@@ -18,6 +18,10 @@ maps every step's raw actions inside the step kernel — float32 [N, C], or unde
 discretize_rl_action_space=True an integer tensor of bins 0...12 — and adds info["applied_value"], info["delta"],
 info["action_cost"] (with add_action_cost) and info["step_stat"].  HVACEnvDiscreteAction / HVACEnvDiffAction are the
 reference-shaped one-room classes.
+
+The episode protocol of the reference's RL trainer: set_random_start_t, set_generate_record and
+set_overheat_no_termiated_training_only take a bool or a bool[num_envs] and hold from the next reset (the last: the next
+step) on; the start logic runs inside every reset the device makes, same-step autoresets included (host.py restates it).
 """
 import itertools
 import ctypes as C
@@ -31,15 +35,17 @@ from ..spaces import Box, MultiDiscrete
 from ..vector import VectorEnv
 from .actions import ACTION_MODES, COST_TABLE, N_BINS, STAT_KEYS, RunningStat
 from .config import RING_CAPACITY
-from .host import check_ring, check_settings
+from .host import (HISTORY_RING, START_NO_TERMINATE, START_RANDOM, START_RECORD, check_ring, check_settings, start_cdf)
 from .pid import DEFAULT_GAINS, GAINS, first_strict_minimum, pid_weights, search_score
 from .tables import build_tables, task_doubles
 
 OBS_KEYS = ("sensor_readings", "heat_readings", "action_temp", "timestep")
 MISC = ("over_heat", "over_tolerace", "energy_cost", "target_cost", "time", "rest_idx", "warning_count", "episode_step")
+_START_STATE = dict(last_fail=torch.float64, history=torch.int16, history_count=torch.int32)
 _STATE_DTYPES = dict(grid=torch.float64, t=torch.float64, last_call=torch.float64, episode_step=torch.int32,
                      warning_count=torch.int32, rest_idx=torch.int32, rest_start=torch.float64, value=torch.float32,
-                     filter=torch.float64, ring_t=torch.float64, ring_v=torch.float64, head=torch.int32, tail=torch.int32)
+                     filter=torch.float64, ring_t=torch.float64, ring_v=torch.float64, head=torch.int32, tail=torch.int32,
+                     **_START_STATE)
 
 
 class HVACVecEnv(VectorEnv):
@@ -73,6 +79,52 @@ class HVACVecEnv(VectorEnv):
         self._pid = None
         self._task_list = self._task_tables = None
         self.need_reset = True
+        self._start_flags = np.zeros(self.num_envs, np.uint8)
+        self._start_cdf = self._start_u = None
+
+    # -- the episode start ----------------------------------------------------------------------------------------
+    def _set_start_flag(self, bit, on):
+        on = np.broadcast_to(np.asarray(on, bool), (self.num_envs,))
+        self._start_flags = np.where(on, self._start_flags | bit, self._start_flags & ~np.uint8(bit)).astype(np.uint8)
+        if self._h is not None:
+            self._push_start_mode()
+
+    def set_random_start_t(self, random_start_t):
+        """a bool or bool[num_envs]: from the next reset on an episode starts as the reference's does under random_start_t
+        (100 steps before the last failure, else at a random time of the week)"""
+        self._set_start_flag(START_RANDOM, random_start_t)
+
+    def set_generate_record(self, generate_record):
+        """a bool or bool[num_envs]: with random_start_t, every reset starts at a uniform step and forgets the history"""
+        self._set_start_flag(START_RECORD, generate_record)
+
+    def set_overheat_no_termiated_training_only(self, overheat_no_termiated_training_only):
+        """a bool or bool[num_envs]: a failing step still returns -30 and over_tolerace = 1 but terminated = False"""
+        self._set_start_flag(START_NO_TERMINATE, overheat_no_termiated_training_only)
+
+    def _push_start_mode(self):
+        """the flags, and with the first env that may take the choice branch the table of numpy's choice (once per
+        handle: max_t + 1 doubles, shared among the envs), to the handle"""
+        cdf, n = None, 0
+        if ((self._start_flags & (START_RANDOM | START_RECORD)) == START_RANDOM).any() and not self._cdf_on_handle:
+            if self._start_cdf is None:
+                self._start_cdf = np.ascontiguousarray(start_cdf(int(self.max_steps * self.iter_per_step * self.sec_per_iter)))
+            cdf, n = self._start_cdf.ctypes.data_as(C.c_void_p), len(self._start_cdf)
+        flags = np.ascontiguousarray(self._start_flags)
+        _lib.check(self.lib.xv_anyhvac_set_start_mode(self._h, flags.ctypes.data_as(C.c_void_p), self.max_steps, cdf, n))
+        self._cdf_on_handle = self._cdf_on_handle or cdf is not None
+
+    def _start_draws(self, start_u):
+        """start_u float64 [N, 2] (u0, u1) or None -> the handle's injected start draws for the next *_injected call"""
+        u = None
+        if start_u is not None:
+            u = self._dev(start_u, torch.float64)
+            if tuple(u.shape) != (self.num_envs, 2):
+                raise ValueError("start_u must have shape %s" % ((self.num_envs, 2),))
+            u = u.contiguous()
+        if u is not None or self._start_u is not None:
+            _lib.check(self.lib.xv_anyhvac_set_start_draws(self._h, _lib.ptr(u)))
+        self._start_u = u      # (borrowed by the handle: alive until the next call replaces it)
 
     # -- tasks ----------------------------------------------------------------------------------------------------
     def set_task(self, tasks, env_task_index=None, generate_task=False):
@@ -117,6 +169,8 @@ class HVACVecEnv(VectorEnv):
                                               self.sec_per_iter, float(self.lower_bound), float(self.upper_bound),
                                               float(max_t), self.reward_mode, C.byref(h)))
         self._h = h
+        self._cdf_on_handle = False      # (a new handle: no failure behind any env, empty histories, no table)
+        self._push_start_mode()
         _lib.check(self.lib.xv_anyhvac_set_task(h, n_task, _lib.ptr(self._tab["table"]), _lib.ptr(self._tab["env_task"])))
         self._push_action_mode()
         if self.action_mode == "diff" and self.discretize_rl_action_space:
@@ -261,7 +315,7 @@ class HVACVecEnv(VectorEnv):
             raise ValueError("actions must have shape %s" % (tuple(lead) + (self.num_envs, self.dims[2]),))
         return a
 
-    def _mapped(self, actions, T=None, reset_state=None):
+    def _mapped(self, actions, T=None, reset_state=None, start_u=None):
         """one launch of a mapped mode: step (T None), step_injected (reset_state given) or rollout (T steps)"""
         lead = () if T is None else (T,)
         shape = tuple(lead) + (self.num_envs, self.dims[2])
@@ -287,6 +341,7 @@ class HVACVecEnv(VectorEnv):
             _lib.check(self.lib.xv_anyhvac_rollout_mapped(self._h, T, C.byref(io), C.byref(act), mode))
         elif reset_state is not None:
             g = self._pad_grid(reset_state)
+            self._start_draws(start_u)
             _lib.check(self.lib.xv_anyhvac_step_mapped_injected(self._h, C.byref(io), C.byref(act), _lib.ptr(g), mode))
         else:
             _lib.check(self.lib.xv_anyhvac_step_mapped(self._h, C.byref(io), C.byref(act), mode))
@@ -324,10 +379,12 @@ class HVACVecEnv(VectorEnv):
             self.pid_reset(mask)
         return self._obs(b), {}
 
-    def reset_injected(self, state, mask=None):
-        """reset with the initial grid given: state [N, nw, nl] (rooms smaller than the batch's largest: zero-padded)"""
+    def reset_injected(self, state, mask=None, start_u=None):
+        """reset with the initial grid given: state [N, nw, nl] (rooms smaller than the batch's largest: zero-padded);
+        start_u float64 [N, 2]: the uniforms (u0, u1) of the start draw under random_start_t (default: the engine's)"""
         self._require_task()
         g = self._pad_grid(state)
+        self._start_draws(start_u)
         m = None if mask is None else self._dev(mask, torch.uint8)
         b = self._buffers((), False)
         io = self._io(b)
@@ -348,11 +405,12 @@ class HVACVecEnv(VectorEnv):
         self._pid_follow(b)
         return self._result(b)
 
-    def step_injected(self, actions, reset_state):
+    def step_injected(self, actions, reset_state, start_u=None):
         self._require_reset()
         if self.action_mode != "box":
-            return self._mapped(actions, reset_state=reset_state)
+            return self._mapped(actions, reset_state=reset_state, start_u=start_u)
         a, g = self._actions(actions), self._pad_grid(reset_state)
+        self._start_draws(start_u)
         b = self._buffers((), self.autoreset_mode == "same_step")
         io = self._io(b, a)
         _lib.check(self.lib.xv_anyhvac_step_injected(self._h, C.byref(io), _lib.ptr(g), AUTORESET[self.autoreset_mode]))
@@ -503,19 +561,27 @@ class HVACVecEnv(VectorEnv):
         n, R = self.num_envs, RING_CAPACITY
         return dict(grid=(n, NW * NL), t=(n,), last_call=(n,), episode_step=(n,), warning_count=(n,), rest_idx=(n,),
                     rest_start=(n, Cc), value=(n, Cc), filter=(n, Cc), ring_t=(n, R), ring_v=(n, R, Cc), head=(n, Cc),
-                    tail=(n,))
+                    tail=(n,), last_fail=(n,), history=(n, HISTORY_RING), history_count=(n,))
 
-    def get_state(self):
-        """-> dict of device tensors: grid [N, NW * NL], t, last_call (NaN: none since the reset), episode_step,
+    def get_state(self, only=None):
+        """only: a subset of the entries' names (default all).  -> dict of device tensors: grid [N, NW * NL], t, last_call
+        (NaN: none since the reset), episode_step,
         warning_count, rest_idx, rest_start [N, C], value [N, C] (the current action), filter [N, C], the delay rings
-        ring_t [N, 256], ring_v [N, 256, C] with head [N, C] and tail [N].  (The energy accumulator lives within a step.)"""
+        ring_t [N, 256], ring_v [N, 256, C] with head [N, C] and tail [N]; last_fail [N] (-1: none yet), history int16
+        [N, 128] — the rest indices of the last steps that did not fail, a ring whose next slot is history_count % 128 — and
+        history_count [N] (min(count, 1000) is the reference's history length).  (The energy accumulator lives within a
+        step.)"""
         self._require_task()
         st = _lib.AnyHVACState()
         out = {}
         for k, shape in self._state_shapes().items():
+            if only is not None and k not in only:
+                continue
             out[k] = torch.empty(shape, dtype=_STATE_DTYPES[k], device=self.device)
-            setattr(st, k, out[k].data_ptr())
+            if k not in _START_STATE:
+                setattr(st, k, out[k].data_ptr())
         _lib.check(self.lib.xv_anyhvac_get_state(self._h, C.byref(st)))
+        _lib.check(self.lib.xv_anyhvac_start_get_state(self._h, *[_lib.ptr(out.get(k)) for k in _START_STATE]))
         self.engine.sync()
         return out
 
@@ -523,7 +589,7 @@ class HVACVecEnv(VectorEnv):
         """any subset of get_state()'s entries"""
         self._require_task()
         st = _lib.AnyHVACState()
-        shapes, keep = self._state_shapes(), []
+        shapes, keep, start = self._state_shapes(), [], {}
         for k, v in state.items():
             if k not in shapes:
                 raise ValueError("unknown state entry %r" % (k,))
@@ -531,10 +597,19 @@ class HVACVecEnv(VectorEnv):
             if tuple(t.shape) != shapes[k]:
                 raise ValueError("state entry %s must have shape %s" % (k, shapes[k]))
             keep.append(t)
-            setattr(st, k, t.data_ptr())
+            if k in _START_STATE:
+                start[k] = t
+            else:
+                setattr(st, k, t.data_ptr())
         _lib.check(self.lib.xv_anyhvac_set_state(self._h, C.byref(st)))
+        if start:
+            _lib.check(self.lib.xv_anyhvac_start_set_state(self._h, *[_lib.ptr(start.get(k)) for k in _START_STATE]))
         self.engine.sync()
         self.need_reset = False
+
+    def time(self):
+        """-> the envs' t as a float64 numpy array [N] (one small read-back)"""
+        return self.get_state(only=("t",))["t"].cpu().numpy()
 
     def sample_action(self, mode="constant"):
         """anyhvac_env.py:653-678 for the C value columns: 'max' (all zeros: the lowest set temperature), 'constant' (the
@@ -584,6 +659,15 @@ class HVACEnv(object):
         self.action_space = self.vec.single_action_space
         self.task_set = True
 
+    def set_random_start_t(self, random_start_t):
+        self.vec.set_random_start_t(bool(random_start_t))
+
+    def set_generate_record(self, generate_record):
+        self.vec.set_generate_record(bool(generate_record))
+
+    def set_overheat_no_termiated_training_only(self, overheat_no_termiated_training_only):
+        self.vec.set_overheat_no_termiated_training_only(bool(overheat_no_termiated_training_only))
+
     def _np(self, obs):
         c = self.vec.counts
         width = dict(sensor_readings=c["sensors"][0], heat_readings=c["heaters"][0], action_temp=c["coolers"][0])
@@ -595,13 +679,15 @@ class HVACEnv(object):
             out[k] = v[:width[k]] if k in width else v.reshape(1)
         return out
 
-    def reset(self, *args, state=None, **kwargs):
-        """state: the initial grid [n_width, n_length] (otherwise ambient + 2 N(0, 1) from the engine's Philox stream)"""
+    def reset(self, *args, state=None, start_u=None, **kwargs):
+        """state: the initial grid [n_width, n_length] (otherwise ambient + 2 N(0, 1) from the engine's Philox stream);
+        start_u: with it, the uniforms (u0, u1) of the start draw under random_start_t"""
         if state is None:
             obs, _ = self.vec.reset()
         else:
-            obs = self.vec.reset_injected(np.asarray(state, np.float64)[None])
-        return self._np(obs), {"time": 0.0}
+            obs = self.vec.reset_injected(np.asarray(state, np.float64)[None],
+                                          start_u=None if start_u is None else np.asarray(start_u, np.float64)[None])
+        return self._np(obs), {"time": float(self.vec.time()[0])}
 
     def step(self, action):
         n = int(self.vec.counts["coolers"][0])

@@ -26,6 +26,14 @@
 // value the env applied at the step before, in the host's operations and order; the action cost keeps each cooler's last
 // ten bins in one 64-bit word; the eight stat() counts are taken on the float32 readings of the observation.  All of it sits
 // outside the iteration loop and uses the LDS the box kernel has (s_ne before the loop, s_red after it).
+//
+// The episode protocol of the reference's RL trainer (anyhvac_env.py reset :296-371, the cooler state history :256-294,
+// reward :519-524, step :648-649; host restatement in host.py) is hv_reset: under an env's random-start flag one lane
+// picks the start time — a uniform step, 100 steps before the env's last failure with the rest index of 100 history
+// entries ago, or the reference's mixed draw (inverse CDF, or an upper-bound search of numpy's choice table) — and hands
+// it to the workgroup through LDS.  The step's epilogue appends the rest index of every step that does not fail to a
+// ring of XV_ANYHVAC_HISTORY int16 per env, remembers the time of every failing one, and under the no-terminate flag
+// reports such a step as not terminated.  The flags are runtime data: the instantiations stay <INJECT, PID, AM>.
 #include <cmath>
 #include <new>
 
@@ -39,6 +47,10 @@
 #define HV_MAX_K 16
 #define HV_MAX_WALL (17 * 17 * 2)
 #define HV_DRAW_GRID 7u      // Philox purpose of the reset grid (sub-index: the cell)
+#define HV_DRAW_START 8u     // ... of the episode start: (u0, u1) from one block of its own, so the grid does not move
+#define HV_STEPS_BACK 100    // reset: restart this many steps before the last failure, from the rest index of then
+#define HV_HIST_MASK (XV_ANYHVAC_HISTORY - 1)
+#define HV_HIST_WRAP (1024 + XV_ANYHVAC_HISTORY)      // the count goes back by one ring here: it saturates, its slot does not move
 #define HV_REST_SECONDS 3600.0
 #define HV_MAX_HEAT 20000.0
 #define HV_WINDOW_MASK ((1ull << 40) - 1)      // ten 4-bit entries: bin + 1, 0 = empty; the newest in the low bits
@@ -59,6 +71,14 @@ struct HvArgs {
   uint32_t* err;
   uint64_t seed, gid_base, tick;
   const uint64_t* tick_dev;
+  // the episode start (xv_anyhvac_set_start_mode / _set_start_draws): flags per env, the choice table, injected draws;
+  // the time of the last failure and the rest indices of the last steps that did not fail
+  const uint8_t* start_flags;
+  const double *cdf, *start_u;
+  long long n_cdf, max_steps;
+  double* last_fail;
+  int16_t* hist;
+  int32_t* hist_n;
 };
 
 struct HvAct {      // the mapped action modes' arguments (xv_anyhvac_set_action_mode, xv_anyhvac_act_io)
@@ -83,6 +103,8 @@ struct xv_anyhvac {
   double* pid_acc;
   float* pid_last_obs;
   int32_t* pid_fresh;
+  uint8_t* start_flags;      // what a.start_flags, a.cdf point to (owned)
+  double* cdf;
 };
 
 struct HvTask {      // one task's table, taken apart (layout: include/xeno.h)
@@ -226,10 +248,66 @@ struct HvEnv {      // what every lane carries of its env (uniform) and of its c
   int head[2];
 };
 
-// HVACEnv.reset + Cooler.reset: grid into g (LDS), the rest into E and the env's global rows
+// the time of the env's last failure and the count of its history, in LDS: lane 0 keeps them (the step's epilogue, the
+// reset), every lane reads last_fail at a reset; they stay out of the registers the iteration loop carries
+struct HvHist {
+  double last_fail;
+  int n;
+};
+
+// reset :301-323 under random_start_t, by ONE lane: the start time and the resting cooler of env; E holds the time and hs
+// the last failure and the history count from before the reset.
+//   generate_record             t = randint(0, max_steps) (iter_per_step sec_per_iter)
+//   last_fail > 0, t < max_t    t = max(0, last_fail - 100 steps), the rest index of 100 steps ago (the oldest, if fewer)
+//   otherwise                   u0 < 0.5: t = int((1 - sqrt(1 - u1)) max_t); else numpy's choice over p ~ 1 / (s + 1)^2:
+//                               the count of cdf entries <= u1 (searchsorted, side='right')
+template <bool INJECT>
+__device__ __forceinline__ void hv_start(const HvArgs& P, const HvTask& K, int env, uint64_t tick, unsigned flags, bool back,
+                                         const HvHist& hs, double* out) {
+  double t, rest = 0.0;
+  if (back) {
+    t = fmax(0.0, hs.last_fail - (double)(HV_STEPS_BACK * P.iters) * P.dt);
+    if (hs.n > 0) {
+      const int at = hs.n >= HV_STEPS_BACK ? hs.n - HV_STEPS_BACK : 0;
+      rest = (double)min(max((int)P.hist[(size_t)env * XV_ANYHVAC_HISTORY + (at & HV_HIST_MASK)], 0), K.nC - 1);
+    }
+  } else {
+    double u0, u1;
+    if (INJECT && P.start_u) {
+      u0 = P.start_u[(size_t)env * 2];
+      u1 = P.start_u[(size_t)env * 2 + 1];
+    } else {
+      const xv_u32x4 w = xv_env_draw_sub(P.seed, P.gid_base + (uint64_t)env, tick, HV_DRAW_START, 0u);
+      u0 = xv_u53(w.x, w.y);
+      u1 = xv_u53(w.z, w.w);
+    }
+    u1 = fmin(fmax(u1, 0.0), 0x1.fffffffffffffp-1);      // (an injected draw outside [0, 1), a NaN: into it)
+    if (flags & XV_ANYHVAC_START_RECORD) {
+      const long long k = min((long long)(u1 * (double)P.max_steps), P.max_steps - 1);
+      t = (double)(k * (long long)P.iters) * P.dt;
+    } else if (u0 < 0.5 || !P.cdf) {
+      t = (double)(long long)((1.0 - __dsqrt_rn(1.0 - u1)) * P.max_t);
+    } else {
+      long long lo = 0, hi = P.n_cdf;      // upper bound: the first entry above u1
+      while (lo < hi) {
+        const long long mid = lo + ((hi - lo) >> 1);
+        if (P.cdf[mid] <= u1) lo = mid + 1;
+        else hi = mid;
+      }
+      t = (double)min(lo, P.n_cdf - 1);
+    }
+  }
+  out[0] = t;
+  out[1] = rest;
+}
+
+// HVACEnv.reset + Cooler.reset: grid into g (LDS), the rest into E and the env's global rows.  E.t comes in as the env's
+// time before the reset, hs (LDS, settled by a barrier) as its last failure and history count: the restart-before-failure
+// branch reads them.
 template <bool INJECT>
 __device__ __forceinline__ void hv_reset(const HvArgs& P, const HvTask& K, int env, uint64_t tick, const double* grid_in,
-                                         double* g, HvEnv& E) {
+                                         double* g, HvEnv& E, HvHist& hs) {
+  __shared__ double s_start[2];
   const int tid = threadIdx.x;
   if (tid < K.NC) {
     double v;
@@ -241,8 +319,22 @@ __device__ __forceinline__ void hv_reset(const HvArgs& P, const HvTask& K, int e
     }
     g[tid] = v;
   }
-  E.t = 0.0; E.last_call = NAN; E.rest_since = 0.0;
-  E.episode_step = 0; E.warning_count = 0; E.rest = 0; E.tail = 0;
+  const unsigned flags = P.start_flags[env];
+  const bool random = (flags & XV_ANYHVAC_START_RANDOM) != 0;      // uniform over the workgroup, as is all of E read here
+  const bool back = random && !(flags & XV_ANYHVAC_START_RECORD) && hs.last_fail > 0.0 && E.t < P.max_t;
+  if (random && tid == 0) {
+    hv_start<INJECT>(P, K, env, tick, flags, back, hs, s_start);
+    if (!back) hs.n = 0;      // (no other lane reads the count)
+  }
+  __syncthreads();
+  double t0 = 0.0;
+  int rest = 0;
+  if (random) {
+    t0 = s_start[0];
+    rest = (int)s_start[1];
+  }
+  E.t = t0; E.last_call = NAN; E.rest_since = t0;
+  E.episode_step = 0; E.warning_count = 0; E.rest = rest; E.tail = 0;
   const float dflt = (float)K.sc[14];
 #pragma unroll
   for (int q = 0; q < 2; ++q) {
@@ -250,14 +342,14 @@ __device__ __forceinline__ void hv_reset(const HvArgs& P, const HvTask& K, int e
     E.filt[q] = 0.0; E.head[q] = 0;
     if (c < P.C) {
       P.value[(size_t)env * P.C + c] = dflt;
-      P.rest_start[(size_t)env * P.C + c] = 0.0;
+      P.rest_start[(size_t)env * P.C + c] = c == rest ? t0 : 0.0;
     }
   }
-  __syncthreads();
 }
 
-__device__ __forceinline__ void hv_load(const HvArgs& P, int env, double* g, HvEnv& E) {
+__device__ __forceinline__ void hv_load(const HvArgs& P, int env, double* g, HvEnv& E, HvHist& hs) {
   const int tid = threadIdx.x, NC = P.NW * P.NL;
+  if (tid == 0) { hs.last_fail = P.last_fail[env]; hs.n = P.hist_n[env]; }
   if (tid < NC) g[tid] = P.grid[(size_t)env * NC + tid];
   E.t = P.t[env]; E.last_call = P.last_call[env];
   E.episode_step = P.episode_step[env]; E.warning_count = P.warning_count[env];
@@ -272,7 +364,7 @@ __device__ __forceinline__ void hv_load(const HvArgs& P, int env, double* g, HvE
   __syncthreads();
 }
 
-__device__ __forceinline__ void hv_store(const HvArgs& P, int env, const double* g, const HvEnv& E) {
+__device__ __forceinline__ void hv_store(const HvArgs& P, int env, const double* g, const HvEnv& E, const HvHist& hs) {
   const int tid = threadIdx.x, NC = P.NW * P.NL;
   if (tid < NC) P.grid[(size_t)env * NC + tid] = g[tid];
   if (tid == 0) {
@@ -280,6 +372,7 @@ __device__ __forceinline__ void hv_store(const HvArgs& P, int env, const double*
     P.episode_step[env] = E.episode_step; P.warning_count[env] = E.warning_count;
     P.rest_idx[env] = E.rest; P.tail[env] = E.tail;
     P.rest_start[(size_t)env * P.C + E.rest] = E.rest_since;
+    P.last_fail[env] = hs.last_fail; P.hist_n[env] = hs.n;
   }
 #pragma unroll
   for (int q = 0; q < 2; ++q) {
@@ -304,11 +397,15 @@ __global__ __launch_bounds__(HV_BLOCK) void xv_anyhvac_reset_kernel(HvArgs P, co
   const int env = blockIdx.x;
   if (mask && !mask[env]) return;
   const HvTask K = hv_task(P, env);
+  __shared__ HvHist s_hist;
   HvEnv E;
-  hv_reset<INJECT>(P, K, env, xv_launch_tick(P.tick, P.tick_dev), grid_in, s_grid, E);
+  E.t = P.t[env];
+  if (threadIdx.x == 0) { s_hist.last_fail = P.last_fail[env]; s_hist.n = P.hist_n[env]; }
+  __syncthreads();
+  hv_reset<INJECT>(P, K, env, xv_launch_tick(P.tick, P.tick_dev), grid_in, s_grid, E, s_hist);
   hv_obs(P, K, s_grid, E.t, E.rest, P.value + (size_t)env * P.C,
          hv_obs_rows(io.sensor_readings, io.heat_readings, io.action_temp, io.timestep, (size_t)env, P), nullptr, nullptr);
-  hv_store(P, env, s_grid, E);
+  hv_store(P, env, s_grid, E, s_hist);
 }
 
 
@@ -474,6 +571,7 @@ __global__ __launch_bounds__(HV_BLOCK) void xv_anyhvac_step_kernel(HvArgs P, xv_
   __shared__ double s_heat[HV_MAX_SH];
   __shared__ double s_red[HV_BLOCK];
   __shared__ int s_bad;
+  __shared__ HvHist s_hist;
   __shared__ double s_de[PID ? HV_MAX_SH : 1];
   __shared__ float s_obs[PID ? HV_MAX_SH : 1];      // the readings the next controller call takes
   const int env = blockIdx.x, tid = threadIdx.x;
@@ -489,7 +587,7 @@ __global__ __launch_bounds__(HV_BLOCK) void xv_anyhvac_step_kernel(HvArgs P, xv_
   double* ring_v = P.ring_v + (size_t)env * XV_ANYHVAC_RING * P.C;
   HvEnv E;
   int cur = 0;
-  hv_load(P, env, s_grid[0], E);
+  hv_load(P, env, s_grid[0], E, s_hist);
   const float* act_in = PID ? D.action_out : io.action;
   double st_abs = 0.0, st_max = 0.0, st_sq = 0.0, st_c1 = 0.0, st_c2 = 0.0, st_over = 0.0, st_rew = 0.0, st_n = 0.0;
   if (PID)
@@ -712,8 +810,18 @@ __global__ __launch_bounds__(HV_BLOCK) void xv_anyhvac_step_kernel(HvArgs P, xv_
       E.warning_count = max(E.warning_count - 1, 0);
     }
     int term = 0;
-    if (E.warning_count > 5) { over_tol = 1; term = 1; reward = -30.0; }
-    else reward = (double)(1.0f + target_cost) + 0.0 + energy_cost + 0.0 + (overheat ? -10.0 : 0.0);
+    if (E.warning_count > 5) {      // reward :519-522: the failure is remembered; step :648: a flagged env goes on
+      over_tol = 1; reward = -30.0;
+      term = (P.start_flags[env] & XV_ANYHVAC_START_NO_TERMINATE) ? 0 : 1;
+      if (!nonfinite && tid == 0) s_hist.last_fail = E.t;
+    } else {
+      reward = (double)(1.0f + target_cost) + 0.0 + energy_cost + 0.0 + (overheat ? -10.0 : 0.0);
+      if (!nonfinite && tid == 0) {      // _save_cooler_state_history: a step that did not fail leaves its rest index
+        const int n = s_hist.n;
+        P.hist[(size_t)env * XV_ANYHVAC_HISTORY + (n & HV_HIST_MASK)] = (int16_t)E.rest;
+        s_hist.n = n + 1 >= HV_HIST_WRAP ? n + 1 - XV_ANYHVAC_HISTORY : n + 1;
+      }
+    }
     if (cost_on) reward = reward + act_cost;      // (the failure reward too, as the reference)
     int trunc = E.t >= P.max_t ? 1 : 0;
     if (nonfinite) { reward = NAN; term = 0; trunc = 0; E.warning_count = E0.warning_count; }
@@ -735,7 +843,7 @@ __global__ __launch_bounds__(HV_BLOCK) void xv_anyhvac_step_kernel(HvArgs P, xv_
     if (redo) {
       hv_obs(P, K, s_grid[cur], E.t, E.rest, value, fin, nullptr, nullptr);
       __syncthreads();
-      hv_reset<INJECT>(P, K, env, xv_launch_tick(P.tick, P.tick_dev) + (uint64_t)ts, reset_grid, s_grid[cur], E);
+      hv_reset<INJECT>(P, K, env, xv_launch_tick(P.tick, P.tick_dev) + (uint64_t)ts, reset_grid, s_grid[cur], E, s_hist);
       hv_obs(P, K, s_grid[cur], E.t, E.rest, value,
              hv_obs_rows(io.sensor_readings, io.heat_readings, io.action_temp, io.timestep, row, P), nullptr, nullptr,
              PID ? s_obs : nullptr);
@@ -750,7 +858,7 @@ __global__ __launch_bounds__(HV_BLOCK) void xv_anyhvac_step_kernel(HvArgs P, xv_
     }
     __syncthreads();
   }
-  hv_store(P, env, s_grid[cur], E);
+  hv_store(P, env, s_grid[cur], E, s_hist);
   if (PID && D.stats) {      // lane partials over the T steps, then one fixed tree each: the same bits in any batch
     double* st = D.stats + (size_t)env * XV_ANYHVAC_PID_STATS;
     const double sums[6] = {st_abs, st_sq, st_c1, st_c2, st_over, st_n};
@@ -775,13 +883,24 @@ static void hv_bind_rng(xv_anyhvac* h, uint64_t ticks) {
   h->a.tick_dev = b.tick_dev;
 }
 
+__global__ void xv_anyhvac_fill_kernel(double* p, size_t n, double v) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) p[i] = v;
+}
+
+static hipError_t hv_fill(double* p, size_t n, double v, hipStream_t stream) {
+  hipLaunchKernelGGL(xv_anyhvac_fill_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, p, n, v);
+  return hipGetLastError();
+}
+
 extern "C" int xv_anyhvac_destroy(xv_anyhvac* h) {
   if (!h) return XV_OK;
   (void)hipSetDevice(h->eng->device);
   (void)hipStreamSynchronize(h->eng->stream);
   HvArgs& a = h->a;
   void* ps[] = {a.grid, a.t, a.last_call, a.episode_step, a.warning_count, a.rest_idx, a.rest_start, a.value, a.filter,
-                a.ring_t, a.ring_v, a.head, a.tail, h->pid_acc, h->pid_last_obs, h->pid_fresh, h->act_window, h->act_table};
+                a.ring_t, a.ring_v, a.head, a.tail, h->pid_acc, h->pid_last_obs, h->pid_fresh, h->act_window, h->act_table,
+                a.last_fail, a.hist, a.hist_n, h->start_flags, h->cdf};
   for (void* q : ps) if (q) (void)hipFree(q);
   delete h;
   return XV_OK;
@@ -817,17 +936,21 @@ extern "C" int xv_anyhvac_create(xv_engine* e, int n_env, int NW, int NL, int C,
       {(void**)&a.episode_step, n * 4, 0}, {(void**)&a.warning_count, n * 4, 0}, {(void**)&a.rest_idx, n * 4, 0},
       {(void**)&a.rest_start, n * c * 8, 0}, {(void**)&a.value, n * c * 4, 0}, {(void**)&a.filter, n * c * 8, 0},
       {(void**)&a.ring_t, n * ring * 8, 0}, {(void**)&a.ring_v, n * ring * c * 8, 0}, {(void**)&a.head, n * c * 4, 0},
-      {(void**)&a.tail, n * 4, 0}};
+      {(void**)&a.tail, n * 4, 0}, {(void**)&a.last_fail, n * 8, 0}, {(void**)&a.hist, n * XV_ANYHVAC_HISTORY * 2, 0},
+      {(void**)&a.hist_n, n * 4, 0}, {(void**)&h->start_flags, n, 0}};
   hipError_t r = hipSuccess;
   for (auto& b : bufs) {
     if (r == hipSuccess) r = hipMalloc(b.p, b.bytes);
     if (r == hipSuccess) r = hipMemsetAsync(*b.p, b.fill, b.bytes, e->stream);      // (0xFF bytes: a NaN, "no last call")
   }
+  if (r == hipSuccess) r = hv_fill(a.last_fail, n, -1.0, e->stream);      // last_fail_timestemp = -1: no failure yet
   if (r != hipSuccess) {
     xv_set_error("xv_anyhvac_create: device allocation failed: %s", hipGetErrorString(r));
     (void)xv_anyhvac_destroy(h);
     return XV_ERR_HIP;
   }
+  a.start_flags = h->start_flags;
+  a.max_steps = 1;
   *out = h;
   return XV_OK;
 }
@@ -838,6 +961,59 @@ extern "C" int xv_anyhvac_set_task(xv_anyhvac* h, int n_task, const double* tabl
   h->a.tables = tables;
   h->a.env_task = env_task;
   return XV_OK;
+}
+
+// ---- the episode start -------------------------------------------------------------------------------------------------
+extern "C" int xv_anyhvac_set_start_mode(xv_anyhvac* h, const uint8_t* flags, int64_t max_steps, const double* choice_cdf,
+                                         int64_t n_cdf) {
+  XV_CHECK_ARG(h && flags && max_steps > 0 && (!choice_cdf || n_cdf > 0));
+  const uint8_t all = XV_ANYHVAC_START_RANDOM | XV_ANYHVAC_START_RECORD | XV_ANYHVAC_START_NO_TERMINATE;
+  bool choice = false;
+  for (int i = 0; i < h->a.n_env; ++i) {
+    XV_CHECK_ARG((flags[i] & ~all) == 0);
+    choice = choice || (flags[i] & (XV_ANYHVAC_START_RANDOM | XV_ANYHVAC_START_RECORD)) == XV_ANYHVAC_START_RANDOM;
+  }
+  XV_CHECK_ARG(!choice || choice_cdf || h->cdf);      // (an env that may take the choice branch needs its table)
+  XV_HIP(hipSetDevice(h->eng->device));
+  XV_HIP(hipStreamSynchronize(h->eng->stream));       // launches in flight keep the flags and the table they were given
+  if (choice_cdf) {
+    if (h->cdf && h->a.n_cdf != n_cdf) {
+      XV_HIP(hipFree(h->cdf));
+      h->cdf = nullptr; h->a.cdf = nullptr; h->a.n_cdf = 0;
+    }
+    if (!h->cdf) XV_HIP(hipMalloc((void**)&h->cdf, (size_t)n_cdf * sizeof(double)));
+    XV_HIP(hipMemcpy(h->cdf, choice_cdf, (size_t)n_cdf * sizeof(double), hipMemcpyHostToDevice));
+    h->a.cdf = h->cdf;
+    h->a.n_cdf = n_cdf;
+  }
+  XV_HIP(hipMemcpy(h->start_flags, flags, (size_t)h->a.n_env, hipMemcpyHostToDevice));
+  h->a.max_steps = max_steps;
+  return XV_OK;
+}
+
+extern "C" int xv_anyhvac_set_start_draws(xv_anyhvac* h, const double* u) {
+  XV_CHECK_ARG(h);
+  h->a.start_u = u;
+  return XV_OK;
+}
+
+template <bool SET>
+static int hv_start_state_copy(xv_anyhvac* h, double* last_fail, int16_t* ring, int32_t* count) {
+  XV_CHECK_ARG(h);
+  const size_t n = (size_t)h->a.n_env;
+  struct { void* user; void* own; size_t bytes; } rows[] = {
+      {last_fail, h->a.last_fail, n * 8}, {ring, h->a.hist, n * XV_ANYHVAC_HISTORY * 2}, {count, h->a.hist_n, n * 4}};
+  for (auto& r : rows)
+    if (r.user)
+      XV_HIP(hipMemcpyAsync(SET ? r.own : r.user, SET ? r.user : r.own, r.bytes, hipMemcpyDeviceToDevice, h->eng->stream));
+  return XV_OK;
+}
+
+extern "C" int xv_anyhvac_start_get_state(xv_anyhvac* h, double* last_fail, int16_t* ring, int32_t* count) {
+  return hv_start_state_copy<false>(h, last_fail, ring, count);
+}
+extern "C" int xv_anyhvac_start_set_state(xv_anyhvac* h, const double* last_fail, const int16_t* ring, const int32_t* count) {
+  return hv_start_state_copy<true>(h, const_cast<double*>(last_fail), const_cast<int16_t*>(ring), const_cast<int32_t*>(count));
 }
 
 template <bool INJECT>
