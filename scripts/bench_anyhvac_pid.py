@@ -9,6 +9,9 @@
 (iii) with --action-mode discrete | diff: rollout(actions) of shape (i) under that action mode (the difference mode with
      integer bins and the action cost on) against the box-mode rollout of the same room, batch and T, alternating.
 
+(iv) the host path of one call: 200 consecutive step() calls at 64 envs of `rot` with iter_per_step = 1 (the kernel is
+     short, so the host side of the call is what the clock sees), in box mode and in the difference mode with integer bins.
+
 Clock: a host clock around calls that end in a device synchronise.  Every timed shape is run once before it is timed;
 each figure is the median of `--repeats` alternated samples, all samples are kept in the output.
 
@@ -107,6 +110,34 @@ def action_mode_cost(room, n, T, repeats, iter_per_step, sec_per_iter, mode):
                 samples_box_s=samples["box"], samples_mapped_s=samples[mode], device_errors=errors)
 
 
+def host_path(repeats, n=64, calls=200):
+    task, grid = load_room("gt_rot")
+    grids = np.repeat(grid[None], n, axis=0)
+    C = len(task["cooler_loc"])
+    rng = np.random.RandomState(0)
+    out = dict(room="gt_rot", envs=n, calls=calls, iter_per_step=1, sec_per_iter=0.15)
+    for mode, opts, acts in (("box", {}, torch.from_numpy(rng.uniform(0, 1, (n, C)).astype(np.float32)).cuda()),
+                             ("diff", dict(action_mode="diff", discretize_rl_action_space=True),
+                              torch.from_numpy(rng.randint(0, 13, (n, C)).astype(np.int32)).cuda())):
+        env = HVACVecEnv(n, iter_per_step=1, sec_per_iter=0.15, autoreset_mode="disabled", **opts)
+        env.set_task([task], generate_task=True)
+
+        def block():
+            for _ in range(calls):
+                env.step(acts)
+        samples = []
+        for i in range(repeats + 1):      # (the first round warms the shape up)
+            env.reset_injected(grids)
+            t = timed(block, env)
+            if i:
+                samples.append(t)
+        out["device_errors_" + mode] = env.check_errors()
+        env.close()
+        out[mode + "_us_per_step"] = statistics.median(samples) / calls * 1e6
+        out["samples_%s_s" % mode] = samples
+    return out
+
+
 def search_time(repeats, max_steps=64, points=10):
     task, grid = load_room("gt_rot")
     env = HVACEnv()
@@ -138,7 +169,7 @@ def main():
     out = dict(device=torch.cuda.get_device_name(0), clock="time.perf_counter around calls ending in a stream synchronise",
                controller_cost=[controller_cost("gt_rot", a.envs, a.T, a.repeats, 200, 0.15),
                                 controller_cost("gt_wide", max(a.envs // 4, 1), max(a.T // 4, 1), a.repeats, 200, 0.15)],
-               search=search_time(a.repeats))
+               search=search_time(a.repeats), host_path=host_path(a.repeats))
     if a.action_mode != "box":
         out["action_mode_cost"] = [action_mode_cost("gt_rot", a.envs, a.T, a.repeats, 200, 0.15, a.action_mode),
                                    action_mode_cost("gt_wide", max(a.envs // 4, 1), max(a.T // 4, 1), a.repeats, 200, 0.15,
@@ -146,7 +177,7 @@ def main():
     with open(a.out, "w") as f:
         json.dump(out, f, indent=1)
         f.write("\n")
-    print(json.dumps({k: out[k] for k in ("controller_cost", "search", "action_mode_cost") if k in out}))
+    print(json.dumps({k: out[k] for k in ("controller_cost", "search", "host_path", "action_mode_cost") if k in out}))
 
 
 if __name__ == "__main__":

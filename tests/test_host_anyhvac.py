@@ -271,3 +271,24 @@ def test_device_table_alone_replays_a_recording(name):
     g, task, settings, gen = U.load(name)
     tab = build_tables([U.load("wide")[1], task], generate_task=gen)
     _replay_from_table(tab["table"][1], tab["dims"], dict(settings, set_lower_bound=16, set_upper_bound=32), g)
+
+
+def test_the_package_keeps_its_names_and_the_moved_classes_say_where_they_live():
+    """every public name of xenoverse_amd.anyhvac before the one-room and solver classes left vec_env.py"""
+    import xenoverse_amd.anyhvac as pkg
+    names = ("ActionMapHost", "DEFAULTS", "DiffActionHost", "DiscreteActionHost", "HVACEnv", "HVACEnvDiffAction",
+             "HVACEnvDiscreteAction", "HVACHost", "HVACSolverGTPID", "HVACSolverGridSearchPID", "HVACSolverLOCPID",
+             "HVACTaskSampler", "HVACVecEnv", "PIDHost", "actions", "average_total_heat", "build_tables", "check_settings",
+             "config", "device_sampler", "heater_powers", "host", "pid", "pid_search_host", "pid_weights",
+             "sample_candidate_host", "sample_candidates", "sample_rows_host", "sample_tasks_device", "sampler_host",
+             "table_dims", "tables", "task_dicts_from_device", "task_from_reference", "task_sampler", "vec_env",
+             "wind_diffuser", "wind_diffuser_host")
+    for k in names:
+        assert hasattr(pkg, k), k
+    where = {"vec_env": ("HVACVecEnv",), "single_env": ("HVACEnv", "HVACEnvDiscreteAction", "HVACEnvDiffAction"),
+             "solvers": ("HVACSolverGTPID", "HVACSolverLOCPID", "HVACSolverGridSearchPID")}
+    for module, classes in where.items():
+        for k in classes:
+            assert getattr(pkg, k).__module__ == "xenoverse_amd.anyhvac." + module, k
+    from xenoverse_amd.anyhvac.single_env import _StatEnv
+    assert _StatEnv.__module__ == "xenoverse_amd.anyhvac.single_env"

@@ -1,6 +1,5 @@
 """HVACVecEnv — batched AnyHVAC rooms on the device (csrc/anyhvac.hip, include/xeno.h xv_anyhvac_*): one launch steps every
-room, one workgroup per room.  HVACEnv — the one-room wrapper with the reference's constructor keywords and numpy outputs
-of the room's true sizes.
+room, one workgroup per room.  (HVACEnv, the one-room wrapper with the reference's surface: single_env.py.)
 
 Observations are dicts of tensors padded to the batch's largest room — sensor_readings[N, S], heat_readings[N, H],
 action_temp[N, C] (float32), timestep[N] (int32) — with `counts` (per env: coolers, sensors, heaters, n_width, n_length)
@@ -10,20 +9,19 @@ autoreset_mode="disabled" goes on stepping as the reference's env would; "next_s
 
 The PID teachers (pid.py restates the reference's solvers on the host): set_pid() puts a controller with per-env gains on
 the device, pid_action() makes one controller call, rollout_teacher(T) runs T controller-driven steps in ONE launch.
-HVACSolverGTPID / HVACSolverLOCPID / HVACSolverGridSearchPID are the reference-shaped classes over the one-room HVACEnv;
-the grid search evaluates its candidates as the envs of one batch.
+HVACSolverGTPID / HVACSolverLOCPID / HVACSolverGridSearchPID (solvers.py) are the reference-shaped classes over the one-room
+HVACEnv; the grid search evaluates its candidates as the envs of one batch.
 
 The RL action spaces (actions.py restates the reference's classes on the host): HVACVecEnv(action_mode="discrete" | "diff")
 maps every step's raw actions inside the step kernel — float32 [N, C], or under action_mode="diff" with
 discretize_rl_action_space=True an integer tensor of bins 0...12 — and adds info["applied_value"], info["delta"],
-info["action_cost"] (with add_action_cost) and info["step_stat"].  HVACEnvDiscreteAction / HVACEnvDiffAction are the
-reference-shaped one-room classes.
+info["action_cost"] (with add_action_cost) and info["step_stat"].  HVACEnvDiscreteAction / HVACEnvDiffAction
+(single_env.py) are the reference-shaped one-room classes.
 
 The episode protocol of the reference's RL trainer: set_random_start_t, set_generate_record and
 set_overheat_no_termiated_training_only take a bool or a bool[num_envs] and hold from the next reset (the last: the next
 step) on; the start logic runs inside every reset the device makes, same-step autoresets included (host.py restates it).
 """
-import itertools
 import ctypes as C
 
 import numpy as np
@@ -33,19 +31,32 @@ from .. import _lib
 from ..engine import AUTORESET
 from ..spaces import Box, MultiDiscrete
 from ..vector import VectorEnv
-from .actions import ACTION_MODES, COST_TABLE, N_BINS, STAT_KEYS, RunningStat
+from .actions import ACTION_MODES, COST_TABLE, N_BINS, STAT_KEYS
 from .config import RING_CAPACITY
 from .host import (HISTORY_RING, START_NO_TERMINATE, START_RANDOM, START_RECORD, check_ring, check_settings, start_cdf)
-from .pid import DEFAULT_GAINS, GAINS, first_strict_minimum, pid_weights, search_score
+from .pid import DEFAULT_GAINS, GAINS, pid_weights
 from .tables import build_tables, task_doubles
 
 OBS_KEYS = ("sensor_readings", "heat_readings", "action_temp", "timestep")
 MISC = ("over_heat", "over_tolerace", "energy_cost", "target_cost", "time", "rest_idx", "warning_count", "episode_step")
-_START_STATE = dict(last_fail=torch.float64, history=torch.int16, history_count=torch.int32)
-_STATE_DTYPES = dict(grid=torch.float64, t=torch.float64, last_call=torch.float64, episode_step=torch.int32,
-                     warning_count=torch.int32, rest_idx=torch.int32, rest_start=torch.float64, value=torch.float32,
-                     filter=torch.float64, ring_t=torch.float64, ring_v=torch.float64, head=torch.int32, tail=torch.int32,
-                     **_START_STATE)
+_COST_TABLE = np.ascontiguousarray(COST_TABLE, np.float64)
+_f64, _f32, _i64, _i32, _i16 = torch.float64, torch.float32, torch.int64, torch.int32, torch.int16
+# Every entry of the handle's state: name -> (group, dtype, shape behind [num_envs] from dims d = (NW, NL, C, S, H, KS, KH)).
+# Within a group the entries stand in the order of the C call's pointers: xv_anyhvac_state's fields for "env", the
+# arguments of xv_anyhvac_<group>_get_state / _set_state for "start", "act" and "pid".
+_STATE = {
+    "grid": ("env", _f64, lambda d: (d[0] * d[1],)), "t": ("env", _f64, lambda d: ()), "last_call": ("env", _f64, lambda d: ()),
+    "episode_step": ("env", _i32, lambda d: ()), "warning_count": ("env", _i32, lambda d: ()),
+    "rest_idx": ("env", _i32, lambda d: ()), "rest_start": ("env", _f64, lambda d: (d[2],)),
+    "value": ("env", _f32, lambda d: (d[2],)), "filter": ("env", _f64, lambda d: (d[2],)),
+    "ring_t": ("env", _f64, lambda d: (RING_CAPACITY,)), "ring_v": ("env", _f64, lambda d: (RING_CAPACITY, d[2])),
+    "head": ("env", _i32, lambda d: (d[2],)), "tail": ("env", _i32, lambda d: ()),
+    "last_fail": ("start", _f64, lambda d: ()), "history": ("start", _i16, lambda d: (HISTORY_RING,)),
+    "history_count": ("start", _i32, lambda d: ()),
+    "window": ("act", _i64, lambda d: (d[2],)),
+    "acc_diff": ("pid", _f64, lambda d: (d[3],)), "last_obs": ("pid", _f32, lambda d: (d[3],)), "fresh": ("pid", _i32, lambda d: ()),
+}
+assert tuple(k for k, v in _STATE.items() if v[0] == "env") == _lib.AnyHVACState.FIELDS
 
 
 class HVACVecEnv(VectorEnv):
@@ -142,25 +153,31 @@ class HVACVecEnv(VectorEnv):
         for t in tasks:
             check_ring(t["cooler_delay_seconds"], self.sec_per_iter)
         env_task_dev = self._env_task(n_task, env_task_index)
-        env_task = env_task_dev.cpu().numpy()      # (the per-env counts and targets below are host arrays)
         tab = build_tables(tasks, self.lower_bound, self.upper_bound, generate_task)
-        self.dims = tab["dims"]
-        self.avg_total_heat = tab["avg_total_heat"]
-        cs = tab["counts"]
-        self.counts = {k: np.array([cs[i][q] for i in env_task], np.int32) for k, q in
-                       (("coolers", "C"), ("sensors", "S"), ("heaters", "H"), ("n_width", "nw"), ("n_length", "nl"))}
-        self._tab = dict(table=torch.from_numpy(tab["table"]).to(d), env_task=env_task_dev)
-        self._bind_tables(n_task)
-        self.default_action_value = np.array([(float(tasks[i]["target_temperature"]) - self.lower_bound)
-                                              / (self.upper_bound - self.lower_bound) for i in env_task])
-        self._targets = np.array([float(tasks[i]["target_temperature"]) for i in env_task])
-        self._task_tables = None
-        self._tasks, self._generate_task = list(tasks), bool(generate_task)
+        targets = np.array([float(t["target_temperature"]) for t in tasks])
+        self._finish_task(tab["dims"], torch.from_numpy(tab["table"]).to(d), env_task_dev,
+                          {k: np.array([c[q] for c in tab["counts"]], np.int32) for k, q in
+                           (("coolers", "C"), ("sensors", "S"), ("heaters", "H"), ("n_width", "nw"), ("n_length", "nl"))},
+                          targets, np.array([(v - self.lower_bound) / (self.upper_bound - self.lower_bound) for v in targets]),
+                          tab["avg_total_heat"], generate_task)
+        self._task_list, self._task_tables = list(tasks), None
+
+    def _finish_task(self, dims, table, env_task_dev, counts, targets, default_action_value, avg_total_heat, generate_task):
+        """what both set_task paths end with.  counts {name: int32 [n_task]}, targets and default_action_value float64
+        [n_task], avg_total_heat [n_task]: per task; the per-env attributes are read off them through the env -> task map"""
+        env_task = env_task_dev.cpu().numpy()      # (the per-env counts and targets are host arrays)
+        self.dims = dims
+        self.avg_total_heat = avg_total_heat
+        self.counts = {k: v[env_task] for k, v in counts.items()}
+        self._tab = dict(table=table, env_task=env_task_dev)
+        self._bind_tables(int(table.shape[0]))
+        self.default_action_value, self._targets = default_action_value[env_task], targets[env_task]
+        self._generate_task = bool(generate_task)
         self.task_set = True
         self.need_reset = True
 
     def _bind_tables(self, n_task):
-        """a handle for self.dims over self._tab, the spaces: what both set_task paths end with"""
+        """a handle for self.dims over self._tab, the spaces"""
         NW, NL, Cc, S, H, KS, KH = self.dims
         self.close_extras()
         h = C.c_void_p()
@@ -199,22 +216,14 @@ class HVACVecEnv(VectorEnv):
             raise ValueError("the tables were sampled with generate_task=%r, set_task was called with generate_task=%r"
                              % (bool(tables["generate_task"]), bool(generate_task)))
         check_ring(float(tables["delay_high"]), self.sec_per_iter)
-        n_task = int(table.shape[0])
-        env_task_dev = self._env_task(n_task, env_task_index)
+        env_task_dev = self._env_task(int(table.shape[0]), env_task_index)
         # one small read-back: the counts, and the target / average heat / default action columns of the rows
         small = torch.cat([tables["counts"].to(torch.float64), table[:, [9, 10, 14]]], dim=1).cpu().numpy()
-        env_task = env_task_dev.cpu().numpy()
-        self.dims = dims
-        self.avg_total_heat = [float(v) for v in small[:, 6]]
-        self.counts = {k: small[env_task, j].astype(np.int32) for j, k in
-                       enumerate(("n_width", "n_length", "coolers", "sensors", "heaters"))}
-        self._tab = dict(table=table, env_task=env_task_dev)
-        self._bind_tables(n_task)
-        self.default_action_value = small[env_task, 7].copy()
-        self._targets = small[env_task, 5].copy()
-        self._task_list, self._task_tables, self._generate_task = None, tables, bool(generate_task)
-        self.task_set = True
-        self.need_reset = True
+        self._finish_task(dims, table, env_task_dev,
+                          {k: small[:, j].astype(np.int32) for j, k in
+                           enumerate(("n_width", "n_length", "coolers", "sensors", "heaters"))},
+                          small[:, 5], small[:, 7], [float(v) for v in small[:, 6]], generate_task)
+        self._task_list, self._task_tables = None, tables
 
     @property
     def _tasks(self):
@@ -234,9 +243,8 @@ class HVACVecEnv(VectorEnv):
         flags = 0
         if self.action_mode == "diff":
             flags = (1 if self.add_action_cost else 0) | (2 if self.too_cold_limit else 0)
-        table = np.ascontiguousarray(COST_TABLE, np.float64)
         _lib.check(self.lib.xv_anyhvac_set_action_mode(self._h, ACTION_MODES.index(self.action_mode), flags,
-                                                       table.ctypes.data_as(C.c_void_p)))
+                                                       _COST_TABLE.ctypes.data_as(C.c_void_p)))
 
     def set_too_cold_limit(self, too_cold_limit):
         """the reference's setter: from the next step on; the action windows are kept"""
@@ -309,64 +317,91 @@ class HVACVecEnv(VectorEnv):
         out[:, :g.shape[1], :g.shape[2]] = g.to(self.device)
         return out.reshape(self.num_envs, NW * NL)
 
-    def _actions(self, actions, lead=()):
-        a = self._dev(actions, torch.float32)
-        if a.shape != tuple(lead) + (self.num_envs, self.dims[2]):
-            raise ValueError("actions must have shape %s" % (tuple(lead) + (self.num_envs, self.dims[2]),))
-        return a
-
-    def _mapped(self, actions, T=None, reset_state=None, start_u=None):
-        """one launch of a mapped mode: step (T None), step_injected (reset_state given) or rollout (T steps)"""
-        lead = () if T is None else (T,)
-        shape = tuple(lead) + (self.num_envs, self.dims[2])
-        integer = (actions.dtype in (torch.int32, torch.int64)) if torch.is_tensor(actions) else \
-            np.issubdtype(np.asarray(actions).dtype, np.integer)
-        a = idx = None
-        if integer:
-            if not (self.action_mode == "diff" and self.discretize_rl_action_space):
-                raise ValueError("integer actions need action_mode='diff' with discretize_rl_action_space=True")
-            idx = self._dev(actions, torch.int32)
+    def _run(self, actions=None, rollout=False, injected=False, reset_state=None, start_u=None, teacher=None):
+        """THE step-family call, one launch: step(), step_injected() (injected), rollout() (actions [T, N, C]) or
+        rollout_teacher() (teacher = (T, action_out, stats): the controller acts, there are no actions)"""
+        a = idx = g = None
+        if teacher is not None:
+            lead = (teacher[0],)
         else:
-            a = self._dev(actions, torch.float32)
-        if (idx if integer else a).shape != shape:
-            raise ValueError("actions must have shape %s" % (shape,))
-        b = self._buffers(lead, self.autoreset_mode == "same_step")
-        io = self._io(b, a)
-        act = _lib.AnyHVACActIO()
-        act.action_index = _lib.ptr(idx)
-        for k in _lib.AnyHVACActIO.FIELDS[1:]:
-            setattr(act, k, b[k].data_ptr())
-        mode = AUTORESET[self.autoreset_mode]
-        if T is not None:
-            _lib.check(self.lib.xv_anyhvac_rollout_mapped(self._h, T, C.byref(io), C.byref(act), mode))
-        elif reset_state is not None:
+            integer = self.action_mode != "box" and (
+                (actions.dtype in (torch.int32, torch.int64)) if torch.is_tensor(actions) else
+                np.issubdtype(np.asarray(actions).dtype, np.integer))
+            if integer and not (self.action_mode == "diff" and self.discretize_rl_action_space):
+                raise ValueError("integer actions need action_mode='diff' with discretize_rl_action_space=True")
+            a = self._dev(actions, torch.int32 if integer else torch.float32)
+            lead = (int(a.shape[0]),) if rollout else ()
+            if a.shape != lead + (self.num_envs, self.dims[2]):
+                raise ValueError("actions must have shape %s" % (lead + (self.num_envs, self.dims[2]),))
+            if integer:
+                a, idx = None, a
+        if injected:
             g = self._pad_grid(reset_state)
             self._start_draws(start_u)
-            _lib.check(self.lib.xv_anyhvac_step_mapped_injected(self._h, C.byref(io), C.byref(act), _lib.ptr(g), mode))
-        else:
-            _lib.check(self.lib.xv_anyhvac_step_mapped(self._h, C.byref(io), C.byref(act), mode))
+        b = self._buffers(lead, self.autoreset_mode == "same_step")
+        io = self._io(b, a)
+        name, args = "rollout" if lead else "step", list(lead) + [C.byref(io)]
+        if self.action_mode != "box":
+            act = _lib.AnyHVACActIO()
+            act.action_index = _lib.ptr(idx)
+            for k in _lib.AnyHVACActIO.FIELDS[1:]:
+                setattr(act, k, b[k].data_ptr())
+            name, args = name + "_mapped", args + [C.byref(act)]
+        elif teacher is not None:
+            name, args = name + "_pid", args + [_lib.ptr(teacher[1]), _lib.ptr(teacher[2])]
+        if injected:
+            name, args = name + "_injected", args + [_lib.ptr(g)]
+        _lib.check(getattr(self.lib, "xv_anyhvac_" + name)(self._h, *args, AUTORESET[self.autoreset_mode]))
+        if teacher is None:
+            self._pid_follow(b)      # (box mode alone has a controller to follow)
         return self._result(b)
+
+    # -- state ----------------------------------------------------------------------------------------------------
+    def _state_call(self, verb, ts):
+        """one xv_anyhvac_[<group>_]<verb>_state call per group that has an entry in ts (name -> tensor), then a sync"""
+        for group in dict.fromkeys(_STATE[k][0] for k in ts):
+            names = [k for k, v in _STATE.items() if v[0] == group]
+            if group == "env":
+                st = _lib.AnyHVACState()
+                for k in names:
+                    setattr(st, k, _lib.ptr(ts.get(k)))
+                _lib.check(getattr(self.lib, "xv_anyhvac_%s_state" % verb)(self._h, C.byref(st)))
+            else:
+                _lib.check(getattr(self.lib, "xv_anyhvac_%s_%s_state" % (group, verb))(self._h, *[_lib.ptr(ts.get(k)) for k in names]))
+        self.engine.sync()
+
+    def _get_state(self, groups, only=None):
+        out = {k: torch.empty((self.num_envs,) + shape(self.dims), dtype=dtype, device=self.device)
+               for k, (group, dtype, shape) in _STATE.items() if group in groups and (only is None or k in only)}
+        self._state_call("get", out)
+        return out
+
+    def _set_state(self, groups, what, state):
+        """what: how the error texts call an entry of these groups"""
+        ts = {}
+        for k, v in state.items():
+            if k not in _STATE or _STATE[k][0] not in groups:
+                raise ValueError("unknown %s%r" % (what, k))
+            ts[k] = self._dev(v, _STATE[k][1])
+            shape = (self.num_envs,) + _STATE[k][2](self.dims)
+            if tuple(ts[k].shape) != shape:
+                raise ValueError("%s%s must have shape %s" % (what, k, shape))
+        self._state_call("set", ts)
+
+    def _require_act_state(self):
+        self._require_task()
+        if self.action_mode == "box":
+            raise ValueError("action_mode='box' keeps no action state")
 
     def get_act_state(self):
         """-> dict(window int64 [N, C]): per cooler the last <= 10 bins of the action cost's window, 4 bits per entry holding
         bin + 1, the newest lowest, 0 = empty"""
-        self._require_task()
-        if self.action_mode == "box":
-            raise ValueError("action_mode='box' keeps no action state")
-        w = torch.empty((self.num_envs, self.dims[2]), dtype=torch.int64, device=self.device)
-        _lib.check(self.lib.xv_anyhvac_act_get_state(self._h, _lib.ptr(w)))
-        self.engine.sync()
-        return dict(window=w)
+        self._require_act_state()
+        return self._get_state(("act",))
 
     def set_act_state(self, window):
-        self._require_task()
-        if self.action_mode == "box":
-            raise ValueError("action_mode='box' keeps no action state")
-        w = self._dev(window, torch.int64)
-        if tuple(w.shape) != (self.num_envs, self.dims[2]):
-            raise ValueError("window must have shape %s" % ((self.num_envs, self.dims[2]),))
-        _lib.check(self.lib.xv_anyhvac_act_set_state(self._h, _lib.ptr(w)))
-        self.engine.sync()
+        self._require_act_state()
+        self._set_state(("act",), "", dict(window=window))
 
     # -- episode --------------------------------------------------------------------------------------------------
     def reset(self, *, seed=None, options=None):
@@ -396,40 +431,17 @@ class HVACVecEnv(VectorEnv):
 
     def step(self, actions):
         self._require_reset()
-        if self.action_mode != "box":
-            return self._mapped(actions)
-        a = self._actions(actions)
-        b = self._buffers((), self.autoreset_mode == "same_step")
-        io = self._io(b, a)
-        _lib.check(self.lib.xv_anyhvac_step(self._h, C.byref(io), AUTORESET[self.autoreset_mode]))
-        self._pid_follow(b)
-        return self._result(b)
+        return self._run(actions)
 
     def step_injected(self, actions, reset_state, start_u=None):
         self._require_reset()
-        if self.action_mode != "box":
-            return self._mapped(actions, reset_state=reset_state, start_u=start_u)
-        a, g = self._actions(actions), self._pad_grid(reset_state)
-        self._start_draws(start_u)
-        b = self._buffers((), self.autoreset_mode == "same_step")
-        io = self._io(b, a)
-        _lib.check(self.lib.xv_anyhvac_step_injected(self._h, C.byref(io), _lib.ptr(g), AUTORESET[self.autoreset_mode]))
-        self._pid_follow(b)
-        return self._result(b)
+        return self._run(actions, injected=True, reset_state=reset_state, start_u=start_u)
 
     def rollout(self, actions):
         """actions float32[T, N, C] -> (obs, reward, terminated, truncated, info) with a leading T on every tensor, from ONE
         launch; bit-equal to T calls of step()"""
         self._require_reset()
-        T = int(torch.as_tensor(actions).shape[0]) if not torch.is_tensor(actions) else int(actions.shape[0])
-        if self.action_mode != "box":
-            return self._mapped(actions, T=T)
-        a = self._actions(actions, (T,))
-        b = self._buffers((T,), self.autoreset_mode == "same_step")
-        io = self._io(b, a)
-        _lib.check(self.lib.xv_anyhvac_rollout(self._h, T, C.byref(io), AUTORESET[self.autoreset_mode]))
-        self._pid_follow(b)
-        return self._result(b)
+        return self._run(actions, rollout=True)
 
     # -- the PID teacher -------------------------------------------------------------------------------------------
     def set_pid(self, kind="gt", kp=DEFAULT_GAINS["kp"], ki=DEFAULT_GAINS["ki"], kd=DEFAULT_GAINS["kd"], gains="python",
@@ -499,17 +511,13 @@ class HVACVecEnv(VectorEnv):
         self._require_pid()
         self._require_reset()
         T = int(T)
-        b = self._buffers((T,), self.autoreset_mode == "same_step")
-        io = self._io(b)
         act = torch.zeros((T, self.num_envs, self.dims[2]), dtype=torch.float32, device=self.device)
         if stats is None and return_stats:
             stats = torch.zeros((self.num_envs, 8), dtype=torch.float64, device=self.device)
         if stats is not None and (stats.shape != (self.num_envs, 8) or stats.dtype != torch.float64
                                   or stats.device != self.device or not stats.is_contiguous()):
             raise ValueError("stats must be a contiguous float64 [num_envs, 8] tensor on the env's device")
-        _lib.check(self.lib.xv_anyhvac_rollout_pid(self._h, T, C.byref(io), _lib.ptr(act), _lib.ptr(stats),
-                                                   AUTORESET[self.autoreset_mode]))
-        out = self._result(b)
+        out = self._run(teacher=(T, act, stats))
         out[4]["action"] = self._out(act)
         if stats is not None:
             out[4]["pid_stats"] = self._out(stats)
@@ -529,39 +537,16 @@ class HVACVecEnv(VectorEnv):
             done = b["terminated"] | b["truncated"]
             self.pid_reset(done if done.dim() == 1 else done.amax(0))
 
-    def _pid_state_shapes(self):
-        n, S = self.num_envs, self.dims[3]
-        return dict(acc_diff=((n, S), torch.float64), last_obs=((n, S), torch.float32), fresh=((n,), torch.int32))
-
     def get_pid_state(self):
         """-> dict of device tensors: acc_diff float64 [N, S], last_obs float32 [N, S], fresh int32 [N] (1 from a reset
         to the first controller call)"""
         self._require_pid()
-        out = {k: torch.empty(shape, dtype=dt, device=self.device) for k, (shape, dt) in self._pid_state_shapes().items()}
-        _lib.check(self.lib.xv_anyhvac_pid_get_state(self._h, *[_lib.ptr(out[k]) for k in ("acc_diff", "last_obs", "fresh")]))
-        self.engine.sync()
-        return out
+        return self._get_state(("pid",))
 
     def set_pid_state(self, **state):
         """any subset of get_pid_state()'s entries"""
         self._require_pid()
-        shapes, ts = self._pid_state_shapes(), {}
-        for k, v in state.items():
-            if k not in shapes:
-                raise ValueError("unknown PID state entry %r" % (k,))
-            ts[k] = self._dev(v, shapes[k][1])
-            if tuple(ts[k].shape) != shapes[k][0]:
-                raise ValueError("PID state entry %s must have shape %s" % (k, shapes[k][0]))
-        _lib.check(self.lib.xv_anyhvac_pid_set_state(self._h, *[_lib.ptr(ts.get(k)) for k in ("acc_diff", "last_obs", "fresh")]))
-        self.engine.sync()
-
-    # -- state ----------------------------------------------------------------------------------------------------
-    def _state_shapes(self):
-        NW, NL, Cc = self.dims[:3]
-        n, R = self.num_envs, RING_CAPACITY
-        return dict(grid=(n, NW * NL), t=(n,), last_call=(n,), episode_step=(n,), warning_count=(n,), rest_idx=(n,),
-                    rest_start=(n, Cc), value=(n, Cc), filter=(n, Cc), ring_t=(n, R), ring_v=(n, R, Cc), head=(n, Cc),
-                    tail=(n,), last_fail=(n,), history=(n, HISTORY_RING), history_count=(n,))
+        self._set_state(("pid",), "PID state entry ", state)
 
     def get_state(self, only=None):
         """only: a subset of the entries' names (default all).  -> dict of device tensors: grid [N, NW * NL], t, last_call
@@ -572,39 +557,12 @@ class HVACVecEnv(VectorEnv):
         history_count [N] (min(count, 1000) is the reference's history length).  (The energy accumulator lives within a
         step.)"""
         self._require_task()
-        st = _lib.AnyHVACState()
-        out = {}
-        for k, shape in self._state_shapes().items():
-            if only is not None and k not in only:
-                continue
-            out[k] = torch.empty(shape, dtype=_STATE_DTYPES[k], device=self.device)
-            if k not in _START_STATE:
-                setattr(st, k, out[k].data_ptr())
-        _lib.check(self.lib.xv_anyhvac_get_state(self._h, C.byref(st)))
-        _lib.check(self.lib.xv_anyhvac_start_get_state(self._h, *[_lib.ptr(out.get(k)) for k in _START_STATE]))
-        self.engine.sync()
-        return out
+        return self._get_state(("env", "start"), only)
 
     def set_state(self, **state):
         """any subset of get_state()'s entries"""
         self._require_task()
-        st = _lib.AnyHVACState()
-        shapes, keep, start = self._state_shapes(), [], {}
-        for k, v in state.items():
-            if k not in shapes:
-                raise ValueError("unknown state entry %r" % (k,))
-            t = self._dev(v, _STATE_DTYPES[k])
-            if tuple(t.shape) != shapes[k]:
-                raise ValueError("state entry %s must have shape %s" % (k, shapes[k]))
-            keep.append(t)
-            if k in _START_STATE:
-                start[k] = t
-            else:
-                setattr(st, k, t.data_ptr())
-        _lib.check(self.lib.xv_anyhvac_set_state(self._h, C.byref(st)))
-        if start:
-            _lib.check(self.lib.xv_anyhvac_start_set_state(self._h, *[_lib.ptr(start.get(k)) for k in _START_STATE]))
-        self.engine.sync()
+        self._set_state(("env", "start"), "state entry ", state)
         self.need_reset = False
 
     def time(self):
@@ -631,271 +589,3 @@ class HVACVecEnv(VectorEnv):
             self.lib.xv_anyhvac_destroy(self._h)
             self._h = None
         self._pid = None
-
-
-class HVACEnv(object):
-    """one room with the reference's surface: HVACEnv(**keywords); set_task(task, generate_task=False); reset() ->
-    (obs, info); step(action[C]) -> (obs, reward, terminated, truncated, info), numpy arrays of the room's true sizes.
-    The episode is not reset behind the caller's back (autoreset_mode='disabled')."""
-    ACTION_MODE = "box"
-
-    def __init__(self, max_steps=20160, iter_per_step=200, sec_per_iter=0.15, set_lower_bound=16, set_upper_bound=32,
-                 verbose=False, action_space_format='box', include_heat_in_observation=True,
-                 include_switch_in_observation=False, include_last_action_in_observation=True,
-                 include_timestep_in_observation=True, no_switch_action=True, reward_mode=0, device="cuda:0", seed=0):
-        self.vec = HVACVecEnv(1, action_mode=self.ACTION_MODE, max_steps=max_steps, iter_per_step=iter_per_step, sec_per_iter=sec_per_iter,
-                              set_lower_bound=set_lower_bound, set_upper_bound=set_upper_bound, reward_mode=reward_mode,
-                              include_heat_in_observation=include_heat_in_observation,
-                              include_last_action_in_observation=include_last_action_in_observation,
-                              include_timestep_in_observation=include_timestep_in_observation, device=device, seed=seed,
-                              autoreset_mode="disabled", action_space_format=action_space_format,
-                              include_switch_in_observation=include_switch_in_observation,
-                              no_switch_action=no_switch_action)
-        self.verbose = verbose
-        self.task_set = False
-
-    def set_task(self, task, generate_task=False):
-        self.vec.set_task([task], generate_task=generate_task)
-        self.action_space = self.vec.single_action_space
-        self.task_set = True
-
-    def set_random_start_t(self, random_start_t):
-        self.vec.set_random_start_t(bool(random_start_t))
-
-    def set_generate_record(self, generate_record):
-        self.vec.set_generate_record(bool(generate_record))
-
-    def set_overheat_no_termiated_training_only(self, overheat_no_termiated_training_only):
-        self.vec.set_overheat_no_termiated_training_only(bool(overheat_no_termiated_training_only))
-
-    def _np(self, obs):
-        c = self.vec.counts
-        width = dict(sensor_readings=c["sensors"][0], heat_readings=c["heaters"][0], action_temp=c["coolers"][0])
-        out = {}
-        for k, v in obs.items():
-            if k == "counts":
-                continue
-            v = v[0].cpu().numpy()
-            out[k] = v[:width[k]] if k in width else v.reshape(1)
-        return out
-
-    def reset(self, *args, state=None, start_u=None, **kwargs):
-        """state: the initial grid [n_width, n_length] (otherwise ambient + 2 N(0, 1) from the engine's Philox stream);
-        start_u: with it, the uniforms (u0, u1) of the start draw under random_start_t"""
-        if state is None:
-            obs, _ = self.vec.reset()
-        else:
-            obs = self.vec.reset_injected(np.asarray(state, np.float64)[None],
-                                          start_u=None if start_u is None else np.asarray(start_u, np.float64)[None])
-        return self._np(obs), {"time": float(self.vec.time()[0])}
-
-    def step(self, action):
-        n = int(self.vec.counts["coolers"][0])
-        action = np.asarray(action)
-        integer = self.ACTION_MODE == "diff" and self.vec.discretize_rl_action_space and np.issubdtype(action.dtype, np.integer)
-        a = np.zeros((1, self.vec.dims[2]), np.int32 if integer else np.float32)
-        a[0, :n] = action.reshape(-1)[:n]
-        obs, r, term, trunc, info = self.vec.step(a)
-        self._last = info
-        c = self.vec.counts
-        out = {k: float(info[k][0]) for k in ("energy_cost", "target_cost", "time")}
-        out.update(over_heat=int(info["over_heat"][0]), over_tolerace=int(info["over_tolerace"][0]),
-                   cool_power=info["cool_power"][0, :n].cpu().numpy(),
-                   heat_power=info["heat_power"][0, :int(c["heaters"][0])].cpu().numpy())
-        return self._np(obs), float(r[0]), bool(term[0]), bool(trunc[0]), out
-
-    def sample_action(self, mode="constant"):
-        a = self.vec.sample_action(mode)
-        return a[0, :int(self.vec.counts["coolers"][0])].cpu().numpy()
-
-    def check_errors(self, clear=True):
-        return self.vec.check_errors(clear)
-
-    def close(self):
-        self.vec.close()
-
-
-class _StatEnv(HVACEnv):
-    """HVACEnv + stat(): info["step_stat"] with the reference's keys and its running averages as attributes"""
-
-    def __init__(self, *args, **kwargs):
-        super().__init__(*args, **kwargs)
-        self.stats = RunningStat()
-
-    def _finish(self, out):
-        obs, reward, terminated, truncated, info = out
-        raw = self._last
-        n = int(self.vec.counts["coolers"][0])
-        info["last_control"] = {"value": raw["applied_value"][0, :n].cpu().numpy()}
-        if self.vec.add_action_cost:
-            info["action_cost"] = float(raw["action_cost"][0])
-        cnt = [int(raw["step_stat"][k][0]) for k in STAT_KEYS]
-        info["step_stat"] = self.stats.update(int(raw["episode_step"][0]), int(self.vec.counts["sensors"][0]), cnt[:4], cnt[4:],
-                                              info["cool_power"], terminated, reward)
-        return obs, reward, terminated, truncated, info
-
-
-for _k in ("avg_reward", "avg_cooler_power_per_step", "over_heat_percentage", "over_cool_percentage", "fail_percentage"):
-    setattr(_StatEnv, _k, property(lambda self, k=_k: getattr(self.stats, k)))
-
-
-class HVACEnvDiscreteAction(_StatEnv):
-    """the reference's HVACEnvDiscreteAction: absolute actions rounded to 0.1 K on the device, info["step_stat"]"""
-    ACTION_MODE = "discrete"
-
-    def step(self, action):
-        return self._finish(super().step(action))
-
-
-class HVACEnvDiffAction(_StatEnv):
-    """the reference's HVACEnvDiffAction: each action is one of 13 temperature steps on the cooler's previous set-point"""
-    ACTION_MODE = "diff"
-
-    def set_too_cold_limit(self, too_cold_limit):
-        self.vec.set_too_cold_limit(too_cold_limit)
-
-    def set_task(self, task, discretize_rl_action_space=False, add_action_cost=False, too_cold_limit=True,
-                 generate_task=False):
-        vec = self.vec      # (the options go to the device with the handle set_task builds)
-        vec.discretize_rl_action_space, vec.add_action_cost = bool(discretize_rl_action_space), bool(add_action_cost)
-        vec.too_cold_limit = bool(too_cold_limit)
-        super().set_task(task, generate_task=generate_task)
-
-    def step(self, action, call_diff_action=True):
-        if not call_diff_action:
-            raise ValueError("call_diff_action=False is not supported by xenoverse_amd.anyhvac (the mapping runs on the device)")
-        return self._finish(super().step(action))
-
-
-class HVACSolverGTPID(object):
-    """the reference's HVACSolverGTPID over the one-room HVACEnv (set_task and reset first): .policy(observation) -> the flat
-    float32 [2C] action (switch columns, value columns), computed on the device; the env's action is 1 - policy(obs)[C:].
-    kp, ki, kd and corr_sensor_cooler are attributes as there; gains that are numpy.float64 scalars take the float64
-    arithmetic numpy gives the reference with them."""
-    kind = "gt"
-
-    def __init__(self, env):
-        if not getattr(env, "task_set", False):
-            raise Exception("Must call \"set_task\" first")
-        self.env = env
-        vec = env.vec
-        task = vec._tasks[0]
-        self.target_temperature = float(task["target_temperature"])
-        self.sec_per_step = vec.iter_per_step * vec.sec_per_iter
-        self.lower_bound, self.upper_bound = vec.lower_bound, vec.upper_bound
-        self.delta_t = self.sec_per_step / 60
-        self.kp, self.ki, self.kd = DEFAULT_GAINS["kp"], DEFAULT_GAINS["ki"], DEFAULT_GAINS["kd"]
-        self.corr_sensor_cooler = pid_weights(task, self.kind)
-        self.n_sensors, self.n_coolers = self.corr_sensor_cooler.shape
-        self._on_device = None
-        self._push(keep_state=False)
-
-    def _gains_mode(self):
-        kinds = {isinstance(g, np.floating) for g in (self.kp, self.ki, self.kd)}
-        if len(kinds) != 1:
-            raise ValueError("kp, ki and kd must be all Python floats or all numpy.float64 scalars")
-        return "float64" if kinds.pop() else "python"
-
-    def _push(self, keep_state=True):
-        """the gains and weights as the attributes have them now -> the device (the controller's state is kept)"""
-        want = (float(self.kp), float(self.ki), float(self.kd), self._gains_mode(), self.corr_sensor_cooler.tobytes())
-        if want == self._on_device and self.env.vec._pid is not None:
-            return
-        vec = self.env.vec
-        state = vec.get_pid_state() if keep_state and vec._pid is not None else None
-        vec.set_pid(kp=self.kp, ki=self.ki, kd=self.kd, gains=want[3], weights=[self.corr_sensor_cooler])
-        if state is not None:
-            vec.set_pid_state(**state)
-        self._on_device = want
-
-    def reset(self):
-        self._push()
-        self.env.vec.pid_reset()
-
-    def policy(self, observation):
-        obs = np.array(observation)[:self.n_sensors]
-        if obs.dtype != np.float32 or obs.shape != (self.n_sensors,):
-            raise ValueError("the observation must be the env's float32 sensor readings")
-        self._push()
-        _, flat = self.env.vec.pid_action(obs[None], return_flat=True)
-        return flat[0, :, :self.n_coolers].reshape(-1).cpu().numpy()
-
-
-class HVACSolverLOCPID(HVACSolverGTPID):
-    """HVACSolverGTPID with the inverse-distance weight matrix"""
-    kind = "loc"
-
-
-class HVACSolverGridSearchPID(HVACSolverGTPID):
-    """the reference's HVACSolverGridSearchPID: .search() evaluates every (kp, ki, kd) of the three linspaces for max_steps
-    controller-driven steps and returns the candidate with the lowest score.  Here the candidates are the envs of ONE batch
-    (a private HVACVecEnv), each with its own gains, all with the env's task and the SAME initial grid (the reference
-    draws a new one per candidate)."""
-    MAX_T = 64      # steps per launch
-
-    def __init__(self, env, kp_range=(1e-3, 5e-2, 10), ki_range=(1e-2, 1e-1, 10), kd_range=(1e-3, 2e-2, 10)):
-        super().__init__(env)
-        self.kp_values, self.ki_values, self.kd_values = (np.linspace(r[0], r[1], r[2]) for r in (kp_range, ki_range, kd_range))
-        self.kp_range, self.ki_range, self.kd_range = kp_range, ki_range, kd_range
-        self.search_results, self.best_params = [], None
-        self.search_rollouts, self.search_stats = [], np.zeros((0, 8))
-
-    @staticmethod
-    def metrics_from_stats(st, max_steps):
-        """a pid_stats row -> the reference's metrics (std from the two sums)"""
-        n = st[7]
-        mean = st[0] / n
-        return {"mean_error": mean, "max_error": st[1], "std_error": float(np.sqrt(max(st[2] / n - mean * mean, 0.0))),
-                "error_within_2C": st[4] / n * 100, "error_within_1C": st[3] / n * 100, "mean_reward": st[6] / max_steps,
-                "mean_overshoot": st[5] / max_steps}
-
-    def search(self, max_steps=1000, apply_best=True, chunk=None, init_grid=None, keep_rollouts=False):
-        """-> best_params (the reference's dict).  chunk: candidates per batch (default all at once); init_grid [nw, nl]:
-        the grid every candidate starts from; without it the caller's env IS RESET (as the reference's search resets it)
-        and its new grid taken; keep_rollouts: rollout_teacher()'s tuples, per chunk a list of calls, stay in
-        self.search_rollouts.  search_stats: the candidates' pid_stats rows, float64 [n, 8]."""
-        vec0 = self.env.vec
-        task = vec0._tasks[0]
-        nw, nl = int(task["n_width"]), int(task["n_length"])
-        if init_grid is None:
-            vec0.reset()
-            init_grid = vec0.get_state()["grid"][0].reshape(vec0.dims[0], vec0.dims[1])[:nw, :nl].cpu().numpy()
-        init_grid = np.asarray(init_grid, np.float64).reshape(nw, nl)
-        cands = list(itertools.product(self.kp_values, self.ki_values, self.kd_values))
-        chunk = len(cands) if chunk is None else max(1, int(chunk))
-        self.search_results, self.search_rollouts, rows = [], [], []
-        for lo in range(0, len(cands), chunk):
-            part = np.array(cands[lo:lo + chunk])
-            vec = HVACVecEnv(len(part), max_steps=vec0.max_steps, iter_per_step=vec0.iter_per_step,
-                             sec_per_iter=vec0.sec_per_iter, set_lower_bound=vec0.lower_bound,
-                             set_upper_bound=vec0.upper_bound, reward_mode=vec0.reward_mode, device=str(self.env.vec.device),
-                             autoreset_mode="disabled")
-            vec.set_task([task], generate_task=vec0._generate_task)
-            vec.reset_injected(np.repeat(init_grid[None], len(part), axis=0))
-            vec.set_pid(kp=part[:, 0], ki=part[:, 1], kd=part[:, 2], gains="float64", weights=[self.corr_sensor_cooler])
-            stats, calls = None, []
-            for t0 in range(0, max_steps, self.MAX_T):
-                out = vec.rollout_teacher(min(self.MAX_T, max_steps - t0), stats=stats, return_stats=True)
-                stats = out[4]["pid_stats"]
-                if keep_rollouts:
-                    calls.append(out)
-            rows.append(stats.cpu().numpy())
-            self.search_rollouts.append(calls)
-            vec.close()
-        self.search_stats = np.concatenate(rows)
-        for (kp, ki, kd), st in zip(cands, self.search_stats):
-            m = dict(kp=kp, ki=ki, kd=kd, **self.metrics_from_stats(st, max_steps))
-            m["score"] = search_score(m)
-            self.search_results.append(m)
-        self.best_params = first_strict_minimum(self.search_results)
-        if apply_best and self.best_params:
-            self.apply_params(self.best_params["kp"], self.best_params["ki"], self.best_params["kd"])
-        return self.best_params
-
-    def apply_params(self, kp=None, ki=None, kd=None):
-        if kp is not None:
-            self.kp = kp
-        if ki is not None:
-            self.ki = ki
-        if kd is not None:
-            self.kd = kd

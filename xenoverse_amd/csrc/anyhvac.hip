@@ -875,6 +875,9 @@ __global__ __launch_bounds__(HV_BLOCK) void xv_anyhvac_step_kernel(HvArgs P, xv_
 
 #ifndef XV_KERNELS_ONLY
 // ---- host side of the C-ABI ---------------------------------------------------------------------------------------
+#include <cstddef>
+#include <initializer_list>
+
 static void hv_bind_rng(xv_anyhvac* h, uint64_t ticks) {
   h->a.seed = h->eng->seed;
   h->a.gid_base = h->eng->env_id_base;
@@ -893,15 +896,103 @@ static hipError_t hv_fill(double* p, size_t n, double v, hipStream_t stream) {
   return hipGetLastError();
 }
 
+// ---- the handle's device buffers ---------------------------------------------------------------------------------------
+// Every buffer the handle owns, once: create, the lazy allocations of set_action_mode and set_pid, destroy and the four
+// get/set copies all walk this table.  A buffer with `state` is one of its group's get/set pointers, in the table's order
+// (the env group: xv_anyhvac_state's fields; the others: the positional arguments of xv_anyhvac_<group>_get_state).
+enum { HV_ENV, HV_START, HV_ACT, HV_PID };
+struct HvBuf {
+  size_t slot;                         // where the handle keeps the pointer
+  size_t (*bytes)(const HvArgs& a);    // of the whole buffer, from the handle's dims
+  int fill;                            // the byte a new buffer is filled with; -1: who allocates it writes every entry
+  int group;
+  bool state;
+};
+#define HV_SLOT(member) offsetof(xv_anyhvac, member)
+#define HV_PER_ENV(x) [](const HvArgs& a) -> size_t { return (size_t)a.n_env * (size_t)(x); }
+#define HV_SHARED(x) [](const HvArgs& a) -> size_t { return (size_t)(x); }
+static const HvBuf HV_BUFS[] = {
+    {HV_SLOT(a.grid), HV_PER_ENV(a.NW * a.NL * 8), 0, HV_ENV, true},
+    {HV_SLOT(a.t), HV_PER_ENV(8), 0, HV_ENV, true},
+    {HV_SLOT(a.last_call), HV_PER_ENV(8), 0xFF, HV_ENV, true},      // (0xFF bytes: a NaN, "no last call")
+    {HV_SLOT(a.episode_step), HV_PER_ENV(4), 0, HV_ENV, true},
+    {HV_SLOT(a.warning_count), HV_PER_ENV(4), 0, HV_ENV, true},
+    {HV_SLOT(a.rest_idx), HV_PER_ENV(4), 0, HV_ENV, true},
+    {HV_SLOT(a.rest_start), HV_PER_ENV(a.C * 8), 0, HV_ENV, true},
+    {HV_SLOT(a.value), HV_PER_ENV(a.C * 4), 0, HV_ENV, true},
+    {HV_SLOT(a.filter), HV_PER_ENV(a.C * 8), 0, HV_ENV, true},
+    {HV_SLOT(a.ring_t), HV_PER_ENV(XV_ANYHVAC_RING * 8), 0, HV_ENV, true},
+    {HV_SLOT(a.ring_v), HV_PER_ENV(XV_ANYHVAC_RING * a.C * 8), 0, HV_ENV, true},
+    {HV_SLOT(a.head), HV_PER_ENV(a.C * 4), 0, HV_ENV, true},
+    {HV_SLOT(a.tail), HV_PER_ENV(4), 0, HV_ENV, true},
+    {HV_SLOT(a.last_fail), HV_PER_ENV(8), 0, HV_START, true},       // (create goes on to fill it with -1.0)
+    {HV_SLOT(a.hist), HV_PER_ENV(XV_ANYHVAC_HISTORY * 2), 0, HV_START, true},
+    {HV_SLOT(a.hist_n), HV_PER_ENV(4), 0, HV_START, true},
+    {HV_SLOT(start_flags), HV_PER_ENV(1), 0, HV_START, false},
+    {HV_SLOT(cdf), HV_SHARED(a.n_cdf * 8), -1, HV_START, false},    // (no bytes until xv_anyhvac_set_start_mode brings a table)
+    {HV_SLOT(act_window), HV_PER_ENV(a.C * 8), 0, HV_ACT, true},
+    {HV_SLOT(act_table), HV_SHARED(XV_ANYHVAC_ACT_BINS * 8), -1, HV_ACT, false},      // (set_action_mode writes it)
+    {HV_SLOT(pid_acc), HV_PER_ENV(a.S * 8), -1, HV_PID, true},      // (xv_anyhvac_pid_reset writes the three)
+    {HV_SLOT(pid_last_obs), HV_PER_ENV(a.S * 4), -1, HV_PID, true},
+    {HV_SLOT(pid_fresh), HV_PER_ENV(4), -1, HV_PID, true},
+};
+#undef HV_SLOT
+#undef HV_PER_ENV
+#undef HV_SHARED
+static const int HV_N_BUFS = (int)(sizeof(HV_BUFS) / sizeof(HV_BUFS[0]));
+static_assert(sizeof(HV_BUFS) / sizeof(HV_BUFS[0]) <= 32, "hv_free and hv_alloc keep a bit per buffer in 32");
+
+static void** hv_slot(xv_anyhvac* h, const HvBuf& b) { return (void**)((char*)h + b.slot); }
+
+static void hv_free(xv_anyhvac* h, uint32_t which) {      // which: a bit per entry of HV_BUFS
+  for (int i = 0; i < HV_N_BUFS; ++i) {
+    void** p = hv_slot(h, HV_BUFS[i]);
+    if ((which >> i & 1u) && *p) { (void)hipFree(*p); *p = nullptr; }
+  }
+}
+
+// Allocate what `group` still lacks and fill what is new, with `clear` every buffer of the group that has a fill byte.
+// A failure frees what this call allocated: the group is then as it was.
+static hipError_t hv_alloc(xv_anyhvac* h, int group, bool clear) {
+  uint32_t made = 0;
+  hipError_t r = hipSuccess;
+  for (int i = 0; i < HV_N_BUFS && r == hipSuccess; ++i) {
+    const HvBuf& b = HV_BUFS[i];
+    const size_t bytes = b.bytes(h->a);
+    void** p = hv_slot(h, b);
+    if (b.group != group || bytes == 0) continue;
+    bool fill = clear;
+    if (!*p) {
+      r = hipMalloc(p, bytes);
+      if (r != hipSuccess) { *p = nullptr; break; }
+      made |= 1u << i;
+      fill = true;
+    }
+    if (fill && b.fill >= 0) r = hipMemsetAsync(*p, b.fill, bytes, h->eng->stream);
+  }
+  if (r != hipSuccess) hv_free(h, made);
+  return r;
+}
+
+// get (set false) or set a group's state: user[i] goes with the group's i-th state buffer, a null pointer is skipped
+static int hv_copy(xv_anyhvac* h, int group, std::initializer_list<const void*> user, bool set) {
+  XV_CHECK_ARG(h);
+  const void* const* u = user.begin();
+  for (const HvBuf& b : HV_BUFS) {
+    if (b.group != group || !b.state) continue;
+    void* own = *hv_slot(h, b);
+    void* usr = const_cast<void*>(*u++);
+    XV_CHECK_ARG(own != nullptr);      // (the act and pid groups exist from xv_anyhvac_set_action_mode / _set_pid on)
+    if (usr) XV_HIP(hipMemcpyAsync(set ? own : usr, set ? usr : own, b.bytes(h->a), hipMemcpyDeviceToDevice, h->eng->stream));
+  }
+  return XV_OK;
+}
+
 extern "C" int xv_anyhvac_destroy(xv_anyhvac* h) {
   if (!h) return XV_OK;
   (void)hipSetDevice(h->eng->device);
   (void)hipStreamSynchronize(h->eng->stream);
-  HvArgs& a = h->a;
-  void* ps[] = {a.grid, a.t, a.last_call, a.episode_step, a.warning_count, a.rest_idx, a.rest_start, a.value, a.filter,
-                a.ring_t, a.ring_v, a.head, a.tail, h->pid_acc, h->pid_last_obs, h->pid_fresh, h->act_window, h->act_table,
-                a.last_fail, a.hist, a.hist_n, h->start_flags, h->cdf};
-  for (void* q : ps) if (q) (void)hipFree(q);
+  hv_free(h, ~0u);
   delete h;
   return XV_OK;
 }
@@ -930,20 +1021,9 @@ extern "C" int xv_anyhvac_create(xv_engine* e, int n_env, int NW, int NL, int C,
   a.n_env = n_env; a.iters = iter_per_step; a.reward_mode = reward_mode;
   a.dt = sec_per_iter; a.lb = set_lower_bound; a.ub = set_upper_bound; a.max_t = max_t;
   a.err = e->d_err;
-  const size_t n = (size_t)n_env, nc = (size_t)NW * NL, c = (size_t)C, ring = XV_ANYHVAC_RING;
-  struct { void** p; size_t bytes; int fill; } bufs[] = {
-      {(void**)&a.grid, n * nc * 8, 0}, {(void**)&a.t, n * 8, 0}, {(void**)&a.last_call, n * 8, 0xFF},
-      {(void**)&a.episode_step, n * 4, 0}, {(void**)&a.warning_count, n * 4, 0}, {(void**)&a.rest_idx, n * 4, 0},
-      {(void**)&a.rest_start, n * c * 8, 0}, {(void**)&a.value, n * c * 4, 0}, {(void**)&a.filter, n * c * 8, 0},
-      {(void**)&a.ring_t, n * ring * 8, 0}, {(void**)&a.ring_v, n * ring * c * 8, 0}, {(void**)&a.head, n * c * 4, 0},
-      {(void**)&a.tail, n * 4, 0}, {(void**)&a.last_fail, n * 8, 0}, {(void**)&a.hist, n * XV_ANYHVAC_HISTORY * 2, 0},
-      {(void**)&a.hist_n, n * 4, 0}, {(void**)&h->start_flags, n, 0}};
-  hipError_t r = hipSuccess;
-  for (auto& b : bufs) {
-    if (r == hipSuccess) r = hipMalloc(b.p, b.bytes);
-    if (r == hipSuccess) r = hipMemsetAsync(*b.p, b.fill, b.bytes, e->stream);      // (0xFF bytes: a NaN, "no last call")
-  }
-  if (r == hipSuccess) r = hv_fill(a.last_fail, n, -1.0, e->stream);      // last_fail_timestemp = -1: no failure yet
+  hipError_t r = hv_alloc(h, HV_ENV, false);
+  if (r == hipSuccess) r = hv_alloc(h, HV_START, false);
+  if (r == hipSuccess) r = hv_fill(a.last_fail, (size_t)n_env, -1.0, e->stream);      // last_fail_timestemp = -1: no failure yet
   if (r != hipSuccess) {
     xv_set_error("xv_anyhvac_create: device allocation failed: %s", hipGetErrorString(r));
     (void)xv_anyhvac_destroy(h);
@@ -997,23 +1077,11 @@ extern "C" int xv_anyhvac_set_start_draws(xv_anyhvac* h, const double* u) {
   return XV_OK;
 }
 
-template <bool SET>
-static int hv_start_state_copy(xv_anyhvac* h, double* last_fail, int16_t* ring, int32_t* count) {
-  XV_CHECK_ARG(h);
-  const size_t n = (size_t)h->a.n_env;
-  struct { void* user; void* own; size_t bytes; } rows[] = {
-      {last_fail, h->a.last_fail, n * 8}, {ring, h->a.hist, n * XV_ANYHVAC_HISTORY * 2}, {count, h->a.hist_n, n * 4}};
-  for (auto& r : rows)
-    if (r.user)
-      XV_HIP(hipMemcpyAsync(SET ? r.own : r.user, SET ? r.user : r.own, r.bytes, hipMemcpyDeviceToDevice, h->eng->stream));
-  return XV_OK;
-}
-
 extern "C" int xv_anyhvac_start_get_state(xv_anyhvac* h, double* last_fail, int16_t* ring, int32_t* count) {
-  return hv_start_state_copy<false>(h, last_fail, ring, count);
+  return hv_copy(h, HV_START, {last_fail, ring, count}, false);
 }
 extern "C" int xv_anyhvac_start_set_state(xv_anyhvac* h, const double* last_fail, const int16_t* ring, const int32_t* count) {
-  return hv_start_state_copy<true>(h, const_cast<double*>(last_fail), const_cast<int16_t*>(ring), const_cast<int32_t*>(count));
+  return hv_copy(h, HV_START, {last_fail, ring, count}, true);
 }
 
 template <bool INJECT>
@@ -1041,22 +1109,6 @@ extern "C" int xv_anyhvac_reset_injected(xv_anyhvac* h, const uint8_t* mask, con
   return hv_reset_call<true>(h, mask, grid, io);
 }
 
-template <bool INJECT>
-static int hv_step_call(xv_anyhvac* h, const xv_anyhvac_io* io, const double* reset_grid, int mode, int T) {
-  XV_CHECK_ARG(h && h->a.tables && io && io->action && io->reward && io->terminated && io->truncated && T > 0);
-  XV_CHECK_ARG(reset_grid || !INJECT);
-  XV_CHECK_ARG(h->act_mode == XV_ANYHVAC_ACT_BOX);      // (a mapped mode steps through xv_anyhvac_step_mapped)
-  if (mode != XV_AUTORESET_DISABLED && mode != XV_AUTORESET_SAME_STEP) {
-    xv_set_error("xv_anyhvac: autoreset mode %d is not built (disabled and same_step are)", mode);
-    return XV_ERR_UNSUPPORTED;
-  }
-  hv_bind_rng(h, INJECT ? 0 : (uint64_t)T);
-  hipLaunchKernelGGL((xv_anyhvac_step_kernel<INJECT, false, XV_ANYHVAC_ACT_BOX>), dim3(h->a.n_env), dim3(HV_BLOCK), 0,
-                     h->eng->stream, h->a, *io, reset_grid, mode, T, HvPid{}, HvAct{});
-  XV_LAUNCH_CHECK();
-  return XV_OK;
-}
-
 // ---- the mapped action modes -------------------------------------------------------------------------------------------
 extern "C" int xv_anyhvac_set_action_mode(xv_anyhvac* h, int mode, int flags, const double* cost_table) {
   XV_CHECK_ARG(h && mode >= XV_ANYHVAC_ACT_BOX && mode <= XV_ANYHVAC_ACT_DIFF);
@@ -1065,11 +1117,7 @@ extern "C" int xv_anyhvac_set_action_mode(xv_anyhvac* h, int mode, int flags, co
   XV_CHECK_ARG(cost_table || !(flags & XV_ANYHVAC_ACT_COST));
   XV_HIP(hipSetDevice(h->eng->device));
   if (mode != XV_ANYHVAC_ACT_BOX) {
-    const size_t bytes = (size_t)h->a.n_env * h->a.C * sizeof(unsigned long long);
-    const bool fresh = !h->act_window || mode != h->act_mode;      // (a change of flags alone keeps the windows)
-    if (!h->act_window) XV_HIP(hipMalloc((void**)&h->act_window, bytes));
-    if (!h->act_table) XV_HIP(hipMalloc((void**)&h->act_table, XV_ANYHVAC_ACT_BINS * sizeof(double)));
-    if (fresh) XV_HIP(hipMemsetAsync(h->act_window, 0, bytes, h->eng->stream));
+    XV_HIP(hv_alloc(h, HV_ACT, mode != h->act_mode));      // (new windows are empty; a change of flags alone keeps them)
     XV_HIP(hipStreamSynchronize(h->eng->stream));
     if (cost_table) XV_HIP(hipMemcpy(h->act_table, cost_table, XV_ANYHVAC_ACT_BINS * sizeof(double), hipMemcpyHostToDevice));
     else XV_HIP(hipMemset(h->act_table, 0, XV_ANYHVAC_ACT_BINS * sizeof(double)));
@@ -1079,92 +1127,24 @@ extern "C" int xv_anyhvac_set_action_mode(xv_anyhvac* h, int mode, int flags, co
   return XV_OK;
 }
 
-template <bool INJECT>
-static int hv_step_mapped_call(xv_anyhvac* h, const xv_anyhvac_io* io, const xv_anyhvac_act_io* act, const double* reset_grid,
-                               int mode, int T) {
-  XV_CHECK_ARG(h && h->a.tables && io && act && io->reward && io->terminated && io->truncated && T > 0);
-  XV_CHECK_ARG(h->act_mode != XV_ANYHVAC_ACT_BOX && h->act_window && h->act_table);
-  XV_CHECK_ARG(io->action || (act->action_index && h->act_mode == XV_ANYHVAC_ACT_DIFF));
-  XV_CHECK_ARG(!act->action_index || h->act_mode == XV_ANYHVAC_ACT_DIFF);
-  XV_CHECK_ARG(reset_grid || !INJECT);
-  if (mode != XV_AUTORESET_DISABLED && mode != XV_AUTORESET_SAME_STEP) {
-    xv_set_error("xv_anyhvac: autoreset mode %d is not built (disabled and same_step are)", mode);
-    return XV_ERR_UNSUPPORTED;
-  }
-  HvAct A = {};
-  A.index = act->action_index; A.applied = act->applied_value; A.delta = act->delta; A.cost = act->action_cost;
-  A.counts = act->stat_counts; A.window = h->act_window; A.table = h->act_table; A.flags = h->act_flags;
-  hv_bind_rng(h, INJECT ? 0 : (uint64_t)T);
-  const dim3 grid(h->a.n_env), block(HV_BLOCK);
-  if (h->act_mode == XV_ANYHVAC_ACT_DIFF)
-    hipLaunchKernelGGL((xv_anyhvac_step_kernel<INJECT, false, XV_ANYHVAC_ACT_DIFF>), grid, block, 0, h->eng->stream, h->a, *io,
-                       reset_grid, mode, T, HvPid{}, A);
-  else
-    hipLaunchKernelGGL((xv_anyhvac_step_kernel<INJECT, false, XV_ANYHVAC_ACT_DISCRETE>), grid, block, 0, h->eng->stream, h->a, *io,
-                       reset_grid, mode, T, HvPid{}, A);
-  XV_LAUNCH_CHECK();
-  return XV_OK;
+extern "C" int xv_anyhvac_act_get_state(xv_anyhvac* h, uint64_t* window) {
+  XV_CHECK_ARG(window);
+  return hv_copy(h, HV_ACT, {window}, false);
 }
-
-extern "C" int xv_anyhvac_step_mapped(xv_anyhvac* h, const xv_anyhvac_io* io, const xv_anyhvac_act_io* act, int autoreset_mode) {
-  return hv_step_mapped_call<false>(h, io, act, nullptr, autoreset_mode, 1);
-}
-
-extern "C" int xv_anyhvac_step_mapped_injected(xv_anyhvac* h, const xv_anyhvac_io* io, const xv_anyhvac_act_io* act,
-                                               const double* reset_grid, int autoreset_mode) {
-  return hv_step_mapped_call<true>(h, io, act, reset_grid, autoreset_mode, 1);
-}
-
-extern "C" int xv_anyhvac_rollout_mapped(xv_anyhvac* h, int T, const xv_anyhvac_io* io, const xv_anyhvac_act_io* act,
-                                         int autoreset_mode) {
-  return hv_step_mapped_call<false>(h, io, act, nullptr, autoreset_mode, T);
-}
-
-template <bool SET>
-static int hv_act_state_copy(xv_anyhvac* h, uint64_t* window) {
-  XV_CHECK_ARG(h && h->act_window && window);
-  const size_t bytes = (size_t)h->a.n_env * h->a.C * sizeof(unsigned long long);
-  XV_HIP(hipMemcpyAsync(SET ? (void*)h->act_window : (void*)window, SET ? (void*)window : (void*)h->act_window, bytes,
-                        hipMemcpyDeviceToDevice, h->eng->stream));
-  return XV_OK;
-}
-
-extern "C" int xv_anyhvac_act_get_state(xv_anyhvac* h, uint64_t* window) { return hv_act_state_copy<false>(h, window); }
 extern "C" int xv_anyhvac_act_set_state(xv_anyhvac* h, const uint64_t* window) {
-  return hv_act_state_copy<true>(h, const_cast<uint64_t*>(window));
+  XV_CHECK_ARG(window);
+  return hv_copy(h, HV_ACT, {window}, true);
 }
 
-extern "C" int xv_anyhvac_step(xv_anyhvac* h, const xv_anyhvac_io* io, int autoreset_mode) {
-  return hv_step_call<false>(h, io, nullptr, autoreset_mode, 1);
+// ---- the env's state ---------------------------------------------------------------------------------------------------
+static int hv_env_copy(xv_anyhvac* h, const xv_anyhvac_state* s, bool set) {
+  XV_CHECK_ARG(s);
+  return hv_copy(h, HV_ENV, {s->grid, s->t, s->last_call, s->episode_step, s->warning_count, s->rest_idx, s->rest_start, s->value,
+                             s->filter, s->ring_t, s->ring_v, s->head, s->tail}, set);
 }
 
-extern "C" int xv_anyhvac_step_injected(xv_anyhvac* h, const xv_anyhvac_io* io, const double* reset_grid, int autoreset_mode) {
-  return hv_step_call<true>(h, io, reset_grid, autoreset_mode, 1);
-}
-
-extern "C" int xv_anyhvac_rollout(xv_anyhvac* h, int T, const xv_anyhvac_io* io, int autoreset_mode) {
-  return hv_step_call<false>(h, io, nullptr, autoreset_mode, T);
-}
-
-template <bool SET>
-static int hv_state_copy(xv_anyhvac* h, const xv_anyhvac_state* s) {
-  XV_CHECK_ARG(h && s);
-  const HvArgs& a = h->a;
-  const size_t n = (size_t)a.n_env, nc = (size_t)a.NW * a.NL, c = (size_t)a.C, ring = XV_ANYHVAC_RING;
-  struct { void* user; void* own; size_t bytes; } rows[] = {
-      {s->grid, a.grid, n * nc * 8}, {s->t, a.t, n * 8}, {s->last_call, a.last_call, n * 8},
-      {s->episode_step, a.episode_step, n * 4}, {s->warning_count, a.warning_count, n * 4}, {s->rest_idx, a.rest_idx, n * 4},
-      {s->rest_start, a.rest_start, n * c * 8}, {s->value, a.value, n * c * 4}, {s->filter, a.filter, n * c * 8},
-      {s->ring_t, a.ring_t, n * ring * 8}, {s->ring_v, a.ring_v, n * ring * c * 8}, {s->head, a.head, n * c * 4},
-      {s->tail, a.tail, n * 4}};
-  for (auto& r : rows)
-    if (r.user)
-      XV_HIP(hipMemcpyAsync(SET ? r.own : r.user, SET ? r.user : r.own, r.bytes, hipMemcpyDeviceToDevice, h->eng->stream));
-  return XV_OK;
-}
-
-extern "C" int xv_anyhvac_get_state(xv_anyhvac* h, const xv_anyhvac_state* out) { return hv_state_copy<false>(h, out); }
-extern "C" int xv_anyhvac_set_state(xv_anyhvac* h, const xv_anyhvac_state* in) { return hv_state_copy<true>(h, in); }
+extern "C" int xv_anyhvac_get_state(xv_anyhvac* h, const xv_anyhvac_state* out) { return hv_env_copy(h, out, false); }
+extern "C" int xv_anyhvac_set_state(xv_anyhvac* h, const xv_anyhvac_state* in) { return hv_env_copy(h, in, true); }
 
 // ---- the PID teacher ---------------------------------------------------------------------------------------------------
 static HvPid hv_pid_args(const xv_anyhvac* h, float* action_out, float* flat_out, double* stats) {
@@ -1186,18 +1166,10 @@ extern "C" int xv_anyhvac_pid_reset(xv_anyhvac* h, const uint8_t* mask) {
 extern "C" int xv_anyhvac_set_pid(xv_anyhvac* h, const double* weights, const double* gains, int kind_flags) {
   XV_CHECK_ARG(h && h->a.tables && weights && gains && (kind_flags & ~XV_ANYHVAC_PID_FLOAT64) == 0);
   XV_HIP(hipSetDevice(h->eng->device));
-  if (!h->pid_acc) {
-    const size_t n = (size_t)h->a.n_env, s = (size_t)h->a.S;
-    hipError_t r = hipMalloc((void**)&h->pid_acc, n * s * 8);
-    if (r == hipSuccess) r = hipMalloc((void**)&h->pid_last_obs, n * s * 4);
-    if (r == hipSuccess) r = hipMalloc((void**)&h->pid_fresh, n * 4);
-    if (r != hipSuccess) {
-      xv_set_error("xv_anyhvac_set_pid: device allocation failed: %s", hipGetErrorString(r));
-      void* ps[] = {h->pid_acc, h->pid_last_obs, h->pid_fresh};
-      for (void* q : ps) if (q) (void)hipFree(q);
-      h->pid_acc = nullptr; h->pid_last_obs = nullptr; h->pid_fresh = nullptr;
-      return XV_ERR_HIP;
-    }
+  const hipError_t r = hv_alloc(h, HV_PID, false);      // (all three or, after a failure, none)
+  if (r != hipSuccess) {
+    xv_set_error("xv_anyhvac_set_pid: device allocation failed: %s", hipGetErrorString(r));
+    return XV_ERR_HIP;
   }
   h->pid_weights = weights;
   h->pid_gains = gains;
@@ -1213,38 +1185,86 @@ extern "C" int xv_anyhvac_pid_action(xv_anyhvac* h, const float* readings, float
   return XV_OK;
 }
 
-extern "C" int xv_anyhvac_rollout_pid(xv_anyhvac* h, int T, const xv_anyhvac_io* io, float* action_out, double* stats,
-                                      int autoreset_mode) {
-  XV_CHECK_ARG(h && h->a.tables && h->pid_acc && io && io->reward && io->terminated && io->truncated && action_out && T > 0);
-  XV_CHECK_ARG(h->act_mode == XV_ANYHVAC_ACT_BOX);      // (the teachers put out box actions)
-  if (autoreset_mode != XV_AUTORESET_DISABLED && autoreset_mode != XV_AUTORESET_SAME_STEP) {
-    xv_set_error("xv_anyhvac: autoreset mode %d is not built (disabled and same_step are)", autoreset_mode);
+extern "C" int xv_anyhvac_pid_get_state(xv_anyhvac* h, double* acc_diff, float* last_obs, int32_t* fresh) {
+  return hv_copy(h, HV_PID, {acc_diff, last_obs, fresh}, false);
+}
+extern "C" int xv_anyhvac_pid_set_state(xv_anyhvac* h, const double* acc_diff, const float* last_obs, const int32_t* fresh) {
+  return hv_copy(h, HV_PID, {acc_diff, last_obs, fresh}, true);
+}
+
+// ---- the step family ---------------------------------------------------------------------------------------------------
+// What the seven entry points below ask of the one launch.  mapped: the call is one of a mapped action mode's (act: its
+// arguments); pid: the teacher acts in front of every step (action_out, stats: its outputs).
+struct HvRun {
+  int T, mode;
+  bool inject = false;
+  const double* reset_grid = nullptr;
+  bool mapped = false;
+  const xv_anyhvac_act_io* act = nullptr;
+  bool pid = false;
+  float* action_out = nullptr;
+  double* stats = nullptr;
+};
+
+typedef void (*HvStepKernel)(HvArgs, xv_anyhvac_io, const double*, int, int, HvPid, HvAct);
+
+static int hv_run(xv_anyhvac* h, const xv_anyhvac_io* io, const HvRun& r) {
+  XV_CHECK_ARG(h && h->a.tables && io && io->reward && io->terminated && io->truncated && r.T > 0);
+  XV_CHECK_ARG(r.reset_grid || !r.inject);
+  // a handle in a mapped mode steps through the _mapped entry points, a box handle through the others (the teachers put
+  // out box actions)
+  XV_CHECK_ARG((h->act_mode != XV_ANYHVAC_ACT_BOX) == r.mapped);
+  HvAct A = {};
+  if (r.mapped) {
+    const xv_anyhvac_act_io* act = r.act;
+    XV_CHECK_ARG(act && h->act_window && h->act_table);
+    XV_CHECK_ARG(io->action || (act->action_index && h->act_mode == XV_ANYHVAC_ACT_DIFF));
+    XV_CHECK_ARG(!act->action_index || h->act_mode == XV_ANYHVAC_ACT_DIFF);
+    A.index = act->action_index; A.applied = act->applied_value; A.delta = act->delta; A.cost = act->action_cost;
+    A.counts = act->stat_counts; A.window = h->act_window; A.table = h->act_table; A.flags = h->act_flags;
+  } else if (r.pid) {
+    XV_CHECK_ARG(h->pid_acc && r.action_out);
+  } else {
+    XV_CHECK_ARG(io->action);
+  }
+  if (r.mode != XV_AUTORESET_DISABLED && r.mode != XV_AUTORESET_SAME_STEP) {
+    xv_set_error("xv_anyhvac: autoreset mode %d is not built (disabled and same_step are)", r.mode);
     return XV_ERR_UNSUPPORTED;
   }
-  hv_bind_rng(h, (uint64_t)T);
-  hipLaunchKernelGGL((xv_anyhvac_step_kernel<false, true, XV_ANYHVAC_ACT_BOX>), dim3(h->a.n_env), dim3(HV_BLOCK), 0,
-                     h->eng->stream, h->a, *io, (const double*)nullptr, autoreset_mode, T,
-                     hv_pid_args(h, action_out, nullptr, stats), HvAct{});
+  const HvPid D = r.pid ? hv_pid_args(h, r.action_out, nullptr, r.stats) : HvPid{};
+  hv_bind_rng(h, r.inject ? 0 : (uint64_t)r.T);
+  static const HvStepKernel plain[3][2] = {      // [the handle's action mode][inject]
+      {xv_anyhvac_step_kernel<false, false, XV_ANYHVAC_ACT_BOX>, xv_anyhvac_step_kernel<true, false, XV_ANYHVAC_ACT_BOX>},
+      {xv_anyhvac_step_kernel<false, false, XV_ANYHVAC_ACT_DISCRETE>, xv_anyhvac_step_kernel<true, false, XV_ANYHVAC_ACT_DISCRETE>},
+      {xv_anyhvac_step_kernel<false, false, XV_ANYHVAC_ACT_DIFF>, xv_anyhvac_step_kernel<true, false, XV_ANYHVAC_ACT_DIFF>}};
+  const HvStepKernel kernel = r.pid ? xv_anyhvac_step_kernel<false, true, XV_ANYHVAC_ACT_BOX> : plain[h->act_mode][r.inject ? 1 : 0];
+  hipLaunchKernelGGL(kernel, dim3(h->a.n_env), dim3(HV_BLOCK), 0, h->eng->stream, h->a, *io, r.reset_grid, r.mode, r.T, D, A);
   XV_LAUNCH_CHECK();
   return XV_OK;
 }
 
-template <bool SET>
-static int hv_pid_state_copy(xv_anyhvac* h, double* acc_diff, float* last_obs, int32_t* fresh) {
-  XV_CHECK_ARG(h && h->pid_acc);
-  const size_t n = (size_t)h->a.n_env, s = (size_t)h->a.S;
-  struct { void* user; void* own; size_t bytes; } rows[] = {
-      {acc_diff, h->pid_acc, n * s * 8}, {last_obs, h->pid_last_obs, n * s * 4}, {fresh, h->pid_fresh, n * 4}};
-  for (auto& r : rows)
-    if (r.user)
-      XV_HIP(hipMemcpyAsync(SET ? r.own : r.user, SET ? r.user : r.own, r.bytes, hipMemcpyDeviceToDevice, h->eng->stream));
-  return XV_OK;
+extern "C" int xv_anyhvac_step(xv_anyhvac* h, const xv_anyhvac_io* io, int autoreset_mode) {
+  return hv_run(h, io, {1, autoreset_mode});
 }
-
-extern "C" int xv_anyhvac_pid_get_state(xv_anyhvac* h, double* acc_diff, float* last_obs, int32_t* fresh) {
-  return hv_pid_state_copy<false>(h, acc_diff, last_obs, fresh);
+extern "C" int xv_anyhvac_step_injected(xv_anyhvac* h, const xv_anyhvac_io* io, const double* reset_grid, int autoreset_mode) {
+  return hv_run(h, io, {1, autoreset_mode, true, reset_grid});
 }
-extern "C" int xv_anyhvac_pid_set_state(xv_anyhvac* h, const double* acc_diff, const float* last_obs, const int32_t* fresh) {
-  return hv_pid_state_copy<true>(h, const_cast<double*>(acc_diff), const_cast<float*>(last_obs), const_cast<int32_t*>(fresh));
+extern "C" int xv_anyhvac_rollout(xv_anyhvac* h, int T, const xv_anyhvac_io* io, int autoreset_mode) {
+  return hv_run(h, io, {T, autoreset_mode});
+}
+extern "C" int xv_anyhvac_step_mapped(xv_anyhvac* h, const xv_anyhvac_io* io, const xv_anyhvac_act_io* act, int autoreset_mode) {
+  return hv_run(h, io, {1, autoreset_mode, false, nullptr, true, act});
+}
+extern "C" int xv_anyhvac_step_mapped_injected(xv_anyhvac* h, const xv_anyhvac_io* io, const xv_anyhvac_act_io* act,
+                                               const double* reset_grid, int autoreset_mode) {
+  return hv_run(h, io, {1, autoreset_mode, true, reset_grid, true, act});
+}
+extern "C" int xv_anyhvac_rollout_mapped(xv_anyhvac* h, int T, const xv_anyhvac_io* io, const xv_anyhvac_act_io* act,
+                                         int autoreset_mode) {
+  return hv_run(h, io, {T, autoreset_mode, false, nullptr, true, act});
+}
+extern "C" int xv_anyhvac_rollout_pid(xv_anyhvac* h, int T, const xv_anyhvac_io* io, float* action_out, double* stats,
+                                      int autoreset_mode) {
+  return hv_run(h, io, {T, autoreset_mode, false, nullptr, false, nullptr, true, action_out, stats});
 }
 #endif  // XV_KERNELS_ONLY
