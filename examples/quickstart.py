@@ -10,7 +10,7 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from xenoverse_amd.anymdp import AnyMDPTaskSampler, AnyMDPVecEnv  # noqa: E402
+from xenoverse_amd.anymdp import AnyMDPTaskSampler, AnyMDPVecEnv, AnyPOMDPTaskSampler  # noqa: E402
 from xenoverse_amd.linds import LinDSVecEnv, LinearDSSampler  # noqa: E402
 from xenoverse_amd.metacontrol import CartPoleVecEnv, sample_cartpole  # noqa: E402
 from xenoverse_amd.mixed import MixedBatch  # noqa: E402
@@ -46,6 +46,14 @@ data = env.rollout_teacher(64, epsilon=0.1)
 print("teacher rollout:", {k: tuple(v.shape) for k, v in data.items()}, "mean reward %.4f" % data["reward"].mean().item())
 print("device error flags:", env.check_errors())
 env.close()
+
+# 3b. the same for POMDP tasks: the teacher acts on the hidden inner state, the data holds the observation tokens
+pomdp = AnyMDPVecEnv(1024, seed=2)
+pomdp.set_task([AnyPOMDPTaskSampler(state_space=16, action_space=4, observation_space=16, seed=k) for k in range(4)])
+pomdp.reset()
+data = pomdp.rollout_teacher(64, epsilon=0.1)
+print("POMDP teacher rollout:", {k: tuple(v.shape) for k, v in data.items()}, "mean reward %.4f" % data["reward"].mean().item())
+pomdp.close()
 
 # 4. several families side by side (BASELINE config 5 in miniature)
 mb = MixedBatch("cuda:0", seed=1)

@@ -414,6 +414,26 @@ int xv_anymdp_rollout_teacher(xv_anymdp* h, int T, const uint8_t* greedy, float 
                               int32_t* obs, float* reward, float* reward_gt, uint8_t* terminated,
                               uint8_t* truncated, int32_t* final_obs);
 
+/* Fused rollouts of POMDP / multi-token POMDP handles (after xv_anymdp_set_observation_model; the two entry points above
+ * serve MDP handles): T token steps of every env in one launch, SAME_STEP auto-reset.  actions int32[T][n_env][d_act];
+ * obs / final_obs int32[T][n_env][d_obs] (final_obs nullable; -1 in the rows of steps that end no episode); reward,
+ * reward_gt, terminated, truncated [T][n_env].  Step ts draws at tick + ts with the purposes of xv_anymdp_step_tokens, so the
+ * call equals T calls of xv_anymdp_step_tokens(.., XV_AUTORESET_SAME_STEP) bit for bit, whatever the search mode, and
+ * splitting T over calls changes nothing.  An action outside [0, A) is clamped and sets XV_DEVERR_ACTION_RANGE.
+ * XV_ERR_INVALID (nothing launched): no observation model, T <= 0, a required pointer missing. */
+int xv_anymdp_rollout_tokens(xv_anymdp* h, int T, const int32_t* actions, int32_t* obs, float* reward, float* reward_gt,
+                             uint8_t* terminated, uint8_t* truncated, int32_t* final_obs);
+/* The same driven by the ground-truth teacher of the reference (AnyMDPSolverOpt.policy, anymdp_solver_opt.py:38-51:
+ * argmax_a Q[env.inner_state] — the teacher reads the hidden state the observations hide): greedy uint8[n_task][S] (e.g. from
+ * xv_anymdp_solve, which reads the task tables and serves token handles as it serves MDP handles), epsilon-greedy with the
+ * draw and arithmetic of xv_anymdp_rollout_teacher; actions_out int32[T][n_env] receives the actions taken.  One action
+ * token per step: XV_ERR_UNSUPPORTED when the handle's d_act > 1 (the reference's solver emits a scalar there; its
+ * multi-token branch tests for the type name 'MTMDP', which no sampler produces).  XV_ERR_INVALID as above, and for epsilon
+ * outside [0, 1].  Nothing is launched on a refusal. */
+int xv_anymdp_rollout_tokens_teacher(xv_anymdp* h, int T, const uint8_t* greedy, float epsilon, int32_t* actions_out,
+                                     int32_t* obs, float* reward, float* reward_gt, uint8_t* terminated,
+                                     uint8_t* truncated, int32_t* final_obs);
+
 /* AnyMDP Q-learning agents — reference: xenoverse/anymdp/anymdp_solver_q.py AnyMDPSolverQ, driven by the training loop of
  * anymdp/test_utils.py (epoch_run :42-60), one agent per env of an MDP handle, in fp64 (xenoverse_amd/anymdp/qlearner.py)
  *   __init__ :8-27   -> xv_anymdp_qlearn_create / xv_anymdp_qlearn_reset (Q = 1 / (1 - gamma), visit counts 1)

@@ -76,6 +76,8 @@ SIGNATURES = {
     "xv_anymdp_step_tokens_injected": [c_void_p] + [c_void_p] * 12 + [c_int],
     "xv_anymdp_step_tokens_many": [c_void_p, c_int, c_int] + [c_void_p] * 7 + [c_int],
     "xv_anymdp_rollout_teacher": [c_void_p, c_int, c_void_p, C.c_float] + [c_void_p] * 7,
+    "xv_anymdp_rollout_tokens": [c_void_p, c_int] + [c_void_p] * 7,
+    "xv_anymdp_rollout_tokens_teacher": [c_void_p, c_int, c_void_p, C.c_float] + [c_void_p] * 7,
     "xv_anymdp_qlearn_create": [c_void_p, C.c_double, C.c_double, c_int, C.POINTER(c_void_p)],
     "xv_anymdp_qlearn_destroy": [c_void_p],
     "xv_anymdp_qlearn_reset": [c_void_p, c_void_p],

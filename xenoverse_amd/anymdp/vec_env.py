@@ -386,10 +386,59 @@ class AnyMDPVecEnv(VectorEnv):
                 ("terminated", torch.uint8, ()), ("truncated", torch.uint8, ()), ("final_obs", torch.int32, ()))
     _ROLLOUT_ACTED = (("action", torch.int32, ()),) + _ROLLOUT      # the teacher's / learner's roll-outs
 
+    def _tok_rollout_out(self, spec, T, out=None):
+        """the [T, ...] outputs of a token rollout as the launch writes them (obs / final_obs [T, N, d_obs]) and as the caller
+        gets them ([T, N] for a POMDP: its observation is its one token, the rule of _tok_obs)"""
+        d_obs, n = self._tok[0], self.num_envs
+        if out is None:
+            raw = self._alloc([(k, dt, (d_obs,)) if k in ("obs", "final_obs") else (k, dt, tail) for k, dt, tail in spec], (T,))
+        else:
+            raw = dict(out)
+            for k in ("obs", "final_obs"):
+                if raw.get(k) is not None:
+                    if raw[k].numel() != T * n * d_obs or not raw[k].is_contiguous():
+                        raise ValueError("rollout: out[%r] must be a contiguous int32 [T, N, d_obs] tensor" % k)
+                    raw[k] = raw[k].view(T, n, d_obs)
+        res = dict(raw)
+        if self.task_type == "POMDP":
+            for k in ("obs", "final_obs"):
+                if res.get(k) is not None:
+                    res[k] = res[k][:, :, 0]
+        return raw, res
+
+    def _tok_rollout_done(self, raw, T):
+        """after a token rollout: the env's current observation is the last step's (a restarted env's: its restart's)"""
+        if self._outputs is not None:
+            self._outputs.take_last()      # (a masked reset keeps the other envs' observation of the ROLLOUT's end)
+        self._tobs = raw["obs"][T - 1].clone()
+
+    def _rollout_tokens(self, actions, out=None):
+        d_act, n = self._tok[1], self.num_envs
+        a = self._dev(actions, torch.int32)
+        if a.dim() == 2 and d_act == 1:
+            a = a[:, :, None]
+        if a.dim() != 3 or a.shape[0] < 1 or tuple(a.shape[1:]) != (n, d_act):
+            raise ValueError("rollout: actions of shape %s, expected [T >= 1, %d, %d]%s" % (
+                tuple(a.shape), n, d_act, " or [T, %d]" % n if d_act == 1 else ""))
+        a = a.contiguous()
+        T = int(a.shape[0])
+        raw, res = self._tok_rollout_out(self._ROLLOUT, T, out)
+        _lib.check(self.lib.xv_anymdp_rollout_tokens(
+            self._h, T, _lib.ptr(a), _lib.ptr(raw["obs"]), _lib.ptr(raw["reward"]), _lib.ptr(raw["reward_gt"]),
+            _lib.ptr(raw["terminated"]), _lib.ptr(raw["truncated"]), _lib.ptr(raw.get("final_obs"))))
+        self._tok_rollout_done(raw, T)
+        return res
+
     def rollout(self, actions, out=None):
         """Fused open-loop rollout: actions int32[T, N] -> dict of [T, N] device tensors, one launch.
-        Equals T calls of step() with SAME_STEP auto-reset, bit for bit."""
+        Equals T calls of step() with SAME_STEP auto-reset, bit for bit.
+
+        POMDP / MTPOMDP tasks: actions int32[T, N, d_act] ([T, N] also when d_act == 1; any other shape raises ValueError
+        before a launch); obs / final_obs are [T, N, d_obs] ([T, N] for a POMDP), final_obs -1 where the step ends no
+        episode.  step(), get_state(), inner_state and engine.tick continue from where the rollout ended."""
         self._check_step()
+        if self._tok is not None:
+            return self._rollout_tokens(actions, out)
         a = self._dev(actions, torch.int32)
         T = int(a.shape[0])
         assert a.shape == (T, self.num_envs)
@@ -416,14 +465,36 @@ class AnyMDPVecEnv(VectorEnv):
     def rollout_teacher(self, T, greedy=None, epsilon=0.0, gamma=0.99):
         """Fused T-step rollout driven on the device by a teacher: greedy uint8[n_task, S] (e.g.
         `teacher.optimal_policy_table(tasks)`; None: solved on the device with `solve(gamma)` and cached),
-        epsilon-greedy.  -> dict of [T, N] device tensors incl. "action"."""
+        epsilon-greedy.  -> dict of [T, N] device tensors incl. "action".
+
+        POMDP / MTPOMDP tasks with one action token per step: the same teacher — it reads the hidden inner state, as the
+        reference's train(env, solver_type='opt') does — with obs / final_obs as rollout() returns them; d_act > 1 raises
+        ValueError."""
         self._check_step()
+        if self._tok is not None:
+            if self._tok[1] != 1:
+                raise ValueError(
+                    "rollout_teacher needs one action token per step (this env takes d_act = %d): the reference's optimal "
+                    "solver emits one action token per step (AnyMDPSolverOpt.policy returns a scalar; its multi-token branch "
+                    "tests for the type name 'MTMDP', which no sampler produces)" % self._tok[1])
+            if int(T) < 1:
+                raise ValueError("rollout_teacher: T must be >= 1")
         if greedy is None:
             if getattr(self, "_greedy_cache", None) is None or self._greedy_cache[0] != (id(self._tab), gamma):
                 self._greedy_cache = ((id(self._tab), gamma), self.solve(gamma, return_q=False)[1])
             greedy = self._greedy_cache[1]
         g = self._dev(greedy, torch.uint8)
         assert g.shape == (self.n_task, self.S)
+        if self._tok is not None:
+            T = int(T)
+            raw, res = self._tok_rollout_out(self._ROLLOUT_ACTED, T)
+            _lib.check(self.lib.xv_anymdp_rollout_tokens_teacher(
+                self._h, T, _lib.ptr(g), float(epsilon), _lib.ptr(raw["action"]), _lib.ptr(raw["obs"]),
+                _lib.ptr(raw["reward"]), _lib.ptr(raw["reward_gt"]), _lib.ptr(raw["terminated"]),
+                _lib.ptr(raw["truncated"]), _lib.ptr(raw["final_obs"])))
+            self._tok_rollout_done(raw, T)
+            self.engine.sync()
+            return res
         out = self._alloc(self._ROLLOUT_ACTED, (T,))
         _lib.check(self.lib.xv_anymdp_rollout_teacher(
             self._h, int(T), _lib.ptr(g), float(epsilon), _lib.ptr(out["action"]), _lib.ptr(out["obs"]),

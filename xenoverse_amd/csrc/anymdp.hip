@@ -2366,5 +2366,6 @@ extern "C" int xv_anymdp_reset_tokens_injected(xv_anymdp* h, const uint8_t* mask
   return XV_OK;
 }
 
+#include "anymdp_tok_rollout.h"   // xv_anymdp_rollout_tokens, xv_anymdp_rollout_tokens_teacher: fused token rollouts and their kernels
 #include "anymdp_many.h"   // xv_anymdp_step_many, xv_anymdp_step_many_chains, xv_anymdp_step_tokens_many, the overlapped path
 #endif   // XV_KERNELS_ONLY
