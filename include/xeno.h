@@ -74,6 +74,7 @@ extern "C" {
 #define XV_DEVERR_NONFINITE 4u      /* a float state left the finite range */
 #define XV_DEVERR_HANDOFF 8u        /* overlapped xv_anymdp_step_many: a wave's bounded wait for the step before it expired */
 #define XV_DEVERR_LENGTH 16u        /* xv_metalm_*: a pass reached max_len tokens without the stop token and was cut there */
+#define XV_DEVERR_EPISODE_RANGE 32u /* maze resampled episodes: an env's episode number reached 2^24; its task was left as it was */
 
 #define XV_STREAM_OWN ((void*)(intptr_t)-1)
 
@@ -999,6 +1000,64 @@ int xv_maze_agent_act(xv_maze_agent* g, const uint8_t* exposed_inject, int32_t* 
 /* state of the last decision, each nullable: _mask_info uint8[n_env][NG][NG], _cost_map double[n_env][NG][NG],
  * path int32[n_env][5] = {len(path), path[0], path[1]}, cell_exposed uint8[n_env][NG][NG] */
 int xv_maze_agent_get(xv_maze_agent* g, uint8_t* mask, double* cost, int32_t* path, uint8_t* exposed);
+
+/* ---------------------------------------------------------------------------------------------
+ * MazeWorld fused rollouts (additions within ABI 12; csrc/maze_rollout.hip) — reference: the data-collection loops
+ * around MazeWorldEnvBase.step (envs/maze_env.py:50-66) and the agents' step (agents/agent_base.py), and the per-episode
+ * re-draw those loops start with (resample_task, envs/task_sampler.py:179-225: xv_maze_set_episode_resample below).
+ * T vector steps issued by ONE call, in the given autoreset mode; every output is stacked over T ([T][n_env]...) and holds
+ * the value AFTER the step, as a loop would read it after each xv_maze_step — except `steps`, the count BEFORE the step
+ * (the info["steps"] quirk of maze_env.py:57).  The move kernels write reward and flags into row t; a one-wave-per-env
+ * kernel after the move writes the rest of the row (and `command`, which otherwise only the ray caster writes).
+ * frame_stride 0: the ray caster is not launched at all; s >= 1: steps t with (t + 1) % s == 0 are painted straight into
+ * frames[(t + 1) / s - 1] (uint8[T / s][n_env][W][H][3]), and final_frames (nullable; SAME_STEP) likewise.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct xv_maze_rollout_out {
+  float* reward;          /* [T][n_env] */
+  uint8_t* terminated;    /* [T][n_env] */
+  uint8_t* truncated;     /* [T][n_env] */
+  int32_t* steps;         /* [T][n_env], before the step */
+  float* command;         /* [T][n_env][3] RGB of the commanded landmark */
+  double* pos;            /* [T][n_env][2] */
+  double* ori;            /* [T][n_env] */
+  int32_t* grid;          /* [T][n_env][2] */
+  int32_t* cmd_idx;       /* [T][n_env] */
+  int32_t* cmd_age;       /* [T][n_env] */
+  double* collision;      /* [T][n_env] */
+  int32_t* target;        /* [T][n_env] id of the commanded landmark */
+  int32_t* episode;       /* [T][n_env] resets of the env so far (0: episodes are not resampled) */
+  double* final_pose;     /* nullable, SAME_STEP: [T][n_env][3] (x, y, ori) before the reset where the step ended an episode, else 0 */
+  uint8_t* frames;        /* null iff frame_stride == 0 or T < frame_stride */
+  uint8_t* final_frames;  /* nullable */
+  int32_t* action;        /* xv_maze_rollout_agent only: [T][n_env] the action executed */
+  int32_t* action_label;  /*   [T][n_env] the label agent's choice, or the behaviour agent's own (un-noised) one */
+  uint8_t* explored;      /*   [T][n_env] 1 where the executed action is the random one */
+} xv_maze_rollout_out;
+/* the argument checks of the two calls below alone (host code, touches no device).  with_agent != 0: those of
+ * xv_maze_rollout_agent (actions null, a Discrete action_mode, SAME_STEP, 0 <= epsilon <= 1). */
+int xv_maze_rollout_check(int n_env, int action_mode, int autoreset_mode, int T, int frame_stride, const void* actions,
+                          const xv_maze_rollout_out* out, int with_agent, double epsilon);
+/* actions: int32[T][n_env] (Discrete16 / 32) or double[T][n_env][2] (Continuous) */
+int xv_maze_rollout(xv_maze* h, const void* actions, int action_mode, int T, int frame_stride, int autoreset_mode,
+                    const xv_maze_rollout_out* out);
+/* Per step: agent acts, label (nullable) acts, the env steps with the behaviour agent's action (SAME_STEP; ticks are
+ * consumed in that order, one per act).  Exploration: w = xv_env_draw(seed, env id, tick of the behaviour agent's act,
+ * purpose 48); the env explores iff u53(w.x, w.y) < epsilon and then executes floor(u53(w.z, w.w) * n_actions); both
+ * agents update their memories every step regardless.  Both agents must belong to the same xv_maze. */
+int xv_maze_rollout_agent(xv_maze_agent* agent, xv_maze_agent* label, int T, double epsilon, int frame_stride,
+                          const xv_maze_rollout_out* out);
+
+/* Resampled episodes.  flags (XV_MAZE_RESAMPLE_*) != 0: from now on EVERY reset of env e — xv_maze_reset (masked ones too)
+ * and the autoreset inside xv_maze_step / xv_maze_rollout / xv_maze_rollout_agent — first applies the Resampler to that
+ * env's task in place, then places the agent at the new start.  The draws of the env's j-th reset since this call are
+ * those of xv_maze_resample_tasks(seed, index_base, episode_base + j, ...) for its task; an episode number that reaches
+ * 2^24 is refused on the device (XV_DEVERR_EPISODE_RANGE, the task stays).  Needs one task per env (n_task == n_env, every
+ * task used once).  own: writable [n_task]-leading copies of landmarks, ints, commands and lm_coord (the other members are
+ * ignored) that the env reads and rewrites from here on instead of the tables xv_maze_create got; episodes int32[n_env]
+ * (zeroed here): the resets so far.  Both stay the caller's memory and must outlive the handle or the next call.
+ * flags == 0: off (own / episodes may be null; the env keeps the tables it has). */
+int xv_maze_set_episode_resample(xv_maze* h, int flags, uint64_t seed, int64_t index_base, int64_t episode_base,
+                                 const xv_maze_task_slots* own, int32_t* episodes);
 
 /* Observation models of AnyPOMDPTaskSampler / MultiTokensAnyPOMDPTaskSampler (task_sampler.py:78-87, :103-117) for the
  * tasks task_base .. task_base + n_task - 1 on the device: per (task, observation token) scipy.sparse.random(S, n_obs,

@@ -138,6 +138,10 @@ SIGNATURES = {
     "xv_maze_agent_destroy": [c_void_p],
     "xv_maze_agent_act": [c_void_p, c_void_p, c_void_p],
     "xv_maze_agent_get": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    "xv_maze_set_episode_resample": [c_void_p, c_int, c_u64, c_i64, c_i64, c_void_p, c_void_p],
+    "xv_maze_rollout_check": [c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, C.c_double],
+    "xv_maze_rollout": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p],
+    "xv_maze_rollout_agent": [c_void_p, c_void_p, c_int, C.c_double, c_int, c_void_p],
     "xv_metalang_create": [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, C.POINTER(c_void_p)],
     "xv_metalang_destroy": [c_void_p],
     "xv_metalang_set_task": [c_void_p, c_int] + [c_void_p] * 8,

@@ -28,12 +28,6 @@ static inline int maze_rc_threads(int W) { return W <= 64 ? 64 : (W <= 128 ? 128
 // 1.09 -> 0.98 ms, 256 x 256: 11.95 -> 11.24 ms); the exact filter, which is bound by fp64 issue and pays for the extra
 // selects (17.1 -> 18.0 ms at 256 x 256), keeps the row-major copy (profiles/r04_j_ab_tex_pairs.txt).
 
-// ray_caster_utils.py:11-25
-__device__ const float MZ_LANDMARK_RGB[XV_MAZE_LMAX][3] = {
-    {0, 255, 0}, {255, 0, 0}, {0, 0, 255}, {0, 255, 255}, {255, 0, 255}, {255, 255, 0}, {128, 128, 255},
-    {128, 255, 128}, {255, 128, 128}, {0, 96, 128}, {96, 0, 128}, {0, 128, 96}, {96, 128, 0}, {128, 96, 0},
-    {128, 0, 96}};
-
 // a / b for a divisor b that is reused: hipcc expands an fp64 division into div_scale / rcp / two Newton steps on
 // the reciprocal / q0 = a*y / r = fma(-b,q0,a) / q = fma(r,y,q0) / div_fixup, and the scale and fixup steps only act
 // on operands near the ends of the exponent range.  Hoisting the refined reciprocal y leaves three instructions per
@@ -140,17 +134,6 @@ __device__ __forceinline__ void mz_collision_force_near(double v0, double v1, do
   f0 = s * o0; f1 = s * o1;
 }
 
-__device__ __forceinline__ void mz_reset_env(const MazeArgs& P, int e, int t) {   // maze_base.py:83-105
-  const int32_t* in = P.T.ints + (size_t)t * 8;
-  const double cs = P.T.dbl[(size_t)t * 8];
-  const size_t N = (size_t)P.n_env;
-  P.grid[e] = in[1]; P.grid[N + e] = in[2];
-  P.pos[e] = in[1] * cs + 0.5 * cs;        // get_cell_center :215-218
-  P.pos[N + e] = in[2] * cs + 0.5 * cs;
-  P.ori[e] = 0.0;
-  P.cmd_idx[e] = 0; P.cmd_age[e] = 0; P.steps[e] = 0; P.need_reset[e] = 0; P.collision[e] = 0.0;
-}
-
 __global__ __launch_bounds__(256) void maze_reset_kernel(MazeArgs P, const uint8_t* mask) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= P.n_env) return;
@@ -226,6 +209,7 @@ __global__ __launch_bounds__(256) void maze_step_kernel(MazeArgs P, const void* 
   P.fin_flag[e] = 0;
   if (mode == XV_AUTORESET_NEXT_STEP && P.need_reset[e]) {
     mz_reset_env(P, e, t);
+    P.fin_flag[e] = 1;      // "this launch reset the env": what the per-step kernel of resampled episodes goes by
     reward[e] = 0.0f; terminated[e] = 0; truncated[e] = 0;
     return;
   }
@@ -485,6 +469,7 @@ __global__ __launch_bounds__(64) void maze_step9_kernel(MazeArgs P, const void* 
   P.fin_flag[e] = 0;
   if (resetting) {
     mz_reset_env(P, e, t);
+    P.fin_flag[e] = 1;      // (as maze_step_kernel)
     reward[e] = 0.0f; terminated[e] = 0; truncated[e] = 0;
     return;
   }
@@ -1549,7 +1534,7 @@ extern "C" int xv_maze_destroy(xv_maze* h) {
   return XV_OK;
 }
 
-static int maze_launch_render(xv_maze* h, uint8_t* frames, float* command_rgb, bool final) {
+int maze_launch_render(xv_maze* h, uint8_t* frames, float* command_rgb, bool final) {
   const MazeArgs& a = h->a;
   const int threads = maze_rc_threads(a.W);
   // which lanes paint what (xv_maze_set_raycast_mapping): AUTO = rows of a column on packed textures, fp32 and exact filter, every
@@ -1632,17 +1617,20 @@ extern "C" int xv_maze_render(xv_maze* h, uint8_t* frames, float* command_rgb) {
 
 extern "C" int xv_maze_reset(xv_maze* h, const uint8_t* mask, uint8_t* frames, float* command_rgb) {
   XV_CHECK_ARG(h != nullptr);
-  hipLaunchKernelGGL(maze_reset_kernel, dim3(xv_div_up(h->a.n_env, 256)), dim3(256), 0, h->eng->stream, h->a, mask);
-  XV_LAUNCH_CHECK();
+  if (h->re_flags != 0) {      // resampled episodes: the Resampler on the env's task first, then the new start
+    const int rc = maze_launch_poststep(h, MzRow{}, true, mask);
+    if (rc != XV_OK) return rc;
+  } else {
+    hipLaunchKernelGGL(maze_reset_kernel, dim3(xv_div_up(h->a.n_env, 256)), dim3(256), 0, h->eng->stream, h->a, mask);
+    XV_LAUNCH_CHECK();
+  }
   if (frames) return maze_launch_render(h, frames, command_rgb, false);
   return XV_OK;
 }
 
-extern "C" int xv_maze_step(xv_maze* h, const void* action, int action_mode, uint8_t* frames, float* reward,
-                            uint8_t* terminated, uint8_t* truncated, float* command_rgb, uint8_t* final_frames,
-                            int autoreset_mode) {
-  XV_CHECK_ARG(h && action && reward && terminated && truncated);
-  XV_CHECK_ARG(action_mode >= 0 && action_mode <= 2 && autoreset_mode >= 0 && autoreset_mode <= 2);
+// the move / collision / rules launch(es) of one vector step (xv_maze_step, and every step of xv_maze_rollout*)
+int maze_launch_move(xv_maze* h, const void* action, int action_mode, float* reward, uint8_t* terminated, uint8_t* truncated,
+                     int autoreset_mode) {
   // lanes per env: enough waves to give every SIMD work, no more (the lanes of an env repeat the position arithmetic)
   // (measured at 16,384 envs: 169 us with nine lanes, 225 us with three, 269 us with the lane-per-env kernel)
   const int lanes = h->move_lanes > 0 ? h->move_lanes : (h->a.n_env <= 32768 ? 9 : 3);
@@ -1674,8 +1662,22 @@ extern "C" int xv_maze_step(xv_maze* h, const void* action, int action_mode, uin
     hipLaunchKernelGGL(maze_step_kernel, dim3(xv_div_up(h->a.n_env, 64)), dim3(64), 0, h->eng->stream, h->a, action,
                        action_mode, reward, terminated, truncated, autoreset_mode);
   XV_LAUNCH_CHECK();
+  return XV_OK;
+}
+
+extern "C" int xv_maze_step(xv_maze* h, const void* action, int action_mode, uint8_t* frames, float* reward,
+                            uint8_t* terminated, uint8_t* truncated, float* command_rgb, uint8_t* final_frames,
+                            int autoreset_mode) {
+  XV_CHECK_ARG(h && action && reward && terminated && truncated);
+  XV_CHECK_ARG(action_mode >= 0 && action_mode <= 2 && autoreset_mode >= 0 && autoreset_mode <= 2);
+  const int mv = maze_launch_move(h, action, action_mode, reward, terminated, truncated, autoreset_mode);
+  if (mv != XV_OK) return mv;
   if (final_frames && autoreset_mode == XV_AUTORESET_SAME_STEP) {
     const int rc = maze_launch_render(h, final_frames, nullptr, true);
+    if (rc != XV_OK) return rc;
+  }
+  if (h->re_flags != 0 && autoreset_mode != XV_AUTORESET_DISABLED) {      // after the final frame: it shows the episode that ended
+    const int rc = maze_launch_poststep(h, MzRow{}, false, nullptr);
     if (rc != XV_OK) return rc;
   }
   if (frames) return maze_launch_render(h, frames, command_rgb, false);

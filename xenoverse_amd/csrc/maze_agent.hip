@@ -68,7 +68,7 @@ __device__ __forceinline__ bool ag_valid(const uint8_t* cls, int n, int NG, int 
 }
 
 __global__ __launch_bounds__(256) void maze_agent_kernel(MazeArgs P, AgentArgs A, const uint8_t* exposed_inject,
-                                                         int32_t* action) {
+                                                         int32_t* action, MazeExplore X) {
   extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
   const int e = blockIdx.x, tid = threadIdx.x, nth = blockDim.x;
   const int NG = P.NG, G2 = NG * NG, WORDS = A.words;
@@ -393,6 +393,13 @@ __global__ __launch_bounds__(256) void maze_agent_kernel(MazeArgs P, AgentArgs A
     int best = 0;
     for (int k = 1; k < A.na; ++k)
       if (sh_u[k] < sh_u[best]) best = k;
+    if (X.own != nullptr) X.own[e] = best;
+    if (X.explored != nullptr) {      // epsilon-greedy (maze_common.h MazeExplore): the memories above were updated either way
+      const xv_u32x4 w = xv_env_draw(A.seed, gid, xv_launch_tick(A.tick, A.tick_dev), XV_DRAW_EXPLORE);
+      const bool explore = xv_u53(w.x, w.y) < X.epsilon;
+      if (explore) best = (int)floor(xv_u53(w.z, w.w) * (double)A.na);
+      X.explored[e] = explore ? 1 : 0;
+    }
     action[e] = best;
   }
   if (A.cost != nullptr)
@@ -477,7 +484,14 @@ extern "C" int xv_maze_agent_destroy(xv_maze_agent* g) {
   return XV_OK;
 }
 
+xv_maze* maze_agent_env(xv_maze_agent* g) { return g->env; }
+int maze_agent_n_actions(xv_maze_agent* g) { return g->a.na; }
+
 extern "C" int xv_maze_agent_act(xv_maze_agent* g, const uint8_t* exposed_inject, int32_t* action) {
+  return maze_agent_launch(g, exposed_inject, action, MazeExplore{0.0, nullptr, nullptr});
+}
+
+int maze_agent_launch(xv_maze_agent* g, const uint8_t* exposed_inject, int32_t* action, const MazeExplore& x) {
   XV_CHECK_ARG(g != nullptr && action != nullptr);
   xv_engine* eng = g->env->eng;
   AgentArgs& a = g->a;
@@ -489,7 +503,7 @@ extern "C" int xv_maze_agent_act(xv_maze_agent* g, const uint8_t* exposed_inject
   const size_t lds = G2 * 8 + (size_t)a.words * 8 + 2 * G2 + 2 + 2 * G2 + 16;
   // small mazes: one wave per env (its barriers cost nothing and four times as many envs are resident per CU)
   const int threads = G2 <= 1024 ? 64 : 256;
-  hipLaunchKernelGGL(maze_agent_kernel, dim3(m.n_env), dim3(threads), lds, eng->stream, m, a, exposed_inject, action);
+  hipLaunchKernelGGL(maze_agent_kernel, dim3(m.n_env), dim3(threads), lds, eng->stream, m, a, exposed_inject, action, x);
   XV_LAUNCH_CHECK();
   return XV_OK;
 }

@@ -408,10 +408,11 @@ struct MsReArgs {
   xv_maze_task_slots o;
 };
 
-__global__ __launch_bounds__(MS_T) void maze_resampler_kernel(MsReArgs P) {
-  __shared__ MsLds L;
-  const int lane = threadIdx.x, ti = blockIdx.x;
-  if (ti >= P.n_task) return;
+// The Resampler on task slot `ti` of P.o for one wave (every lane of it calls this; L is the wave's own): the draws are a
+// function of (P.seed, P.index_base + ti, episode).  Shared by maze_resampler_kernel (one episode for every task) and
+// the per-step kernel of the fused rollouts (maze_rollout.hip: the episode is the env's own reset count).
+__device__ void ms_resample_task(MsLds& L, const MsReArgs& P, int ti, uint32_t episode) {
+  const int lane = threadIdx.x;
   const int NG = P.NG;
   int32_t* ints = P.o.ints + (size_t)ti * 8;
   const int n = ints[0], k = ints[5];
@@ -427,10 +428,10 @@ __global__ __launch_bounds__(MS_T) void maze_resampler_kernel(MsReArgs P) {
   }
   __syncthreads();
   if (P.flags & XV_MAZE_RESAMPLE_LANDMARKS) {
-    ms_landmarks(L, n, seed, index, P.episode, MS_P_LANDMARK | MS_P_RESAMPLE, k, lm_coord);
+    ms_landmarks(L, n, seed, index, episode, MS_P_LANDMARK | MS_P_RESAMPLE, k, lm_coord);
   } else if (P.flags & XV_MAZE_RESAMPLE_COLOR) {
     // a random permutation by key rank: the new landmark r is the old landmark with the r-th smallest (key, id)
-    const uint64_t key = lane < k ? ms_block_k53(seed, index, P.episode, MS_P_SHUFFLE | MS_P_RESAMPLE, (uint32_t)lane) : 0;
+    const uint64_t key = lane < k ? ms_block_k53(seed, index, episode, MS_P_SHUFFLE | MS_P_RESAMPLE, (uint32_t)lane) : 0;
     int ci = 0, cj = 0, rank = 0;
     if (lane < k) {
       ci = lm_coord[2 * lane];
@@ -450,19 +451,25 @@ __global__ __launch_bounds__(MS_T) void maze_resampler_kernel(MsReArgs P) {
     __syncthreads();
   }
   if (P.flags & XV_MAZE_RESAMPLE_START) {
-    const int start = ms_start(L, n, seed, index, P.episode, MS_P_START | MS_P_RESAMPLE);
+    const int start = ms_start(L, n, seed, index, episode, MS_P_START | MS_P_RESAMPLE);
     if (lane == 0 && start >= 0) {
       ints[1] = start / n;
       ints[2] = start % n;
     }
   }
   if (P.flags & XV_MAZE_RESAMPLE_CMD)
-    ms_commands(L, seed, index, P.episode, MS_P_CMD | MS_P_RESAMPLE, k, P.n_cmd, P.o.commands + (size_t)ti * P.n_cmd);
+    ms_commands(L, seed, index, episode, MS_P_CMD | MS_P_RESAMPLE, k, P.n_cmd, P.o.commands + (size_t)ti * P.n_cmd);
   if (P.flags & (XV_MAZE_RESAMPLE_LANDMARKS | XV_MAZE_RESAMPLE_COLOR))
     for (int c = lane; c < nn; c += MS_T) {
       const int i = c / n, j = c - i * n;
       P.o.landmarks[slot + (size_t)i * NG + j] = L.mark[c];
     }
+}
+
+__global__ __launch_bounds__(MS_T) void maze_resampler_kernel(MsReArgs P) {
+  __shared__ MsLds L;
+  if ((int)blockIdx.x >= P.n_task) return;
+  ms_resample_task(L, P, (int)blockIdx.x, P.episode);
 }
 
 }  // namespace

@@ -67,6 +67,7 @@ class MazeWorldVecEnv(VectorEnv):
         self._set_spaces(Box(0, 255, shape=(self.resolution[0], self.resolution[1], 3), dtype=np.uint8), act)
         self._textures = textures
         self._h = None
+        self._own_tables, self._episodes = False, None      # resampled episodes (set_episode_resample)
 
     @property
     def list_actions(self):
@@ -113,6 +114,7 @@ class MazeWorldVecEnv(VectorEnv):
                                            self.visibility_3D, C.byref(ct), _lib.ptr(dev["env_task"]), C.byref(h)))
         self._h = h
         self._tab = dev
+        self._own_tables, self._episodes = False, None      # a new task: episodes are not resampled until asked again
         if self.precision != "exact":
             _lib.check(self.lib.xv_maze_set_precision(h, 1 if self.precision == "f32" else 2))
         if self.typing == "numba":
@@ -165,6 +167,78 @@ class MazeWorldVecEnv(VectorEnv):
             infos["_final_obs"] = self._out((self._term | self._trunc).view(torch.bool))   # flags are 0 / 1 bytes: one op, no conversion
         return (self._of(self._frames), self._of(self._reward), self._obf(self._term),
                 self._obf(self._trunc), infos)
+
+    def set_episode_resample(self, resample_cmd=True, resample_start=True, resample_landmarks=False,
+                             resample_landmarks_color=False, seed=0, index_base=0, episode_base=0):
+        """The reference's per-episode re-draw (`env.set_task(Resampler(task))` before every reset()) on the device: from now
+        on EVERY reset of env e — reset(), masked resets, the autoreset inside step / rollout / rollout_teacher — first
+        applies the Resampler to that env's task, in place, then places the agent at the new start.  The env's j-th reset
+        draws what resample_tasks_device(seed=seed, index_base=index_base, episode=episode_base + j, ...) draws for its
+        task.  Call it after set_task; every task must be used by exactly one env.  The env works on private copies of
+        landmarks, lm_coord, ints and commands (the tables handed to set_task never change): `task_tables()` returns the
+        current ones, `episodes` the resets so far.  All four flags False turns it off, and so does a new set_task."""
+        if self._h is None:
+            raise ValueError("call set_task before set_episode_resample")
+        flags = (1 if resample_cmd else 0) | (2 if resample_start else 0) | (4 if resample_landmarks else 0) | \
+                (8 if resample_landmarks_color else 0)      # XV_MAZE_RESAMPLE_*
+        if flags == 0:
+            _lib.check(self.lib.xv_maze_set_episode_resample(self._h, 0, 0, 0, 0, None, None))
+            return
+        n_task = int(self._tab["ints"].shape[0])
+        used = torch.bincount(self._tab["env_task"].long(), minlength=n_task)
+        if n_task != self.num_envs or not bool((used == 1).all()):
+            raise ValueError("set_episode_resample needs every task to be used by exactly one env (the task is rewritten "
+                             "at that env's resets)")
+        if int(index_base) < 0 or not 0 <= int(episode_base) < (1 << 24):
+            raise ValueError("index_base must be >= 0 and episode_base within 0 .. 2^24 - 1")
+        if not self._own_tables:
+            for k in ("landmarks", "lm_coord", "ints", "commands"):
+                self._tab[k] = self._tab[k].clone()
+            self._own_tables = True
+        self._episodes = torch.zeros(self.num_envs, dtype=torch.int32, device=self.device)
+        slots = (C.c_void_p * 7)(None, None, _lib.ptr(self._tab["landmarks"]), _lib.ptr(self._tab["ints"]), None,
+                                 _lib.ptr(self._tab["commands"]), _lib.ptr(self._tab["lm_coord"]))      # xv_maze_task_slots
+        _lib.check(self.lib.xv_maze_set_episode_resample(self._h, flags, int(seed) & (2**64 - 1), int(index_base),
+                                                         int(episode_base), C.cast(slots, C.c_void_p),
+                                                         _lib.ptr(self._episodes)))
+
+    @property
+    def episodes(self):
+        """int32[N]: the resets of each env since set_episode_resample (zeros while episodes are not resampled)"""
+        if self._episodes is None:
+            return torch.zeros(self.num_envs, dtype=torch.int32, device=self.device)
+        return self._episodes.clone()
+
+    def task_tables(self):
+        """the tables the env reads now (resampled episodes rewrite them), in the build_tables layout with device tensors:
+        what set_task, resample_tasks_device and task_dicts_from_device take"""
+        if self._h is None:
+            raise Exception("Must call \"set_task\" first")
+        out = {k: self._tab[k].clone() for k in ("walls", "texts", "landmarks", "ints", "dbl", "commands", "lm_coord")}
+        out["NG"], out["n_cmd"] = int(self._tab["walls"].shape[-1]), int(self._tab["commands"].shape[1])
+        return out
+
+    def rollout(self, actions, frames=None, out=None):
+        """T steps from given actions (int32[T, N] for Discrete16 / 32, float64[T, N, 2] for Continuous) issued by ONE C call,
+        in this env's autoreset mode: -> dict of device tensors stacked over T, the values a loop reads after each step()
+        — reward, terminated, truncated, steps (BEFORE the step, as info["steps"]), command, and the trajectory record pos
+        [T, N, 2], ori, grid [T, N, 2], cmd_idx, cmd_age, collision, target (id of the commanded landmark), episode; under
+        same-step autoreset also final_pose [T, N, 3] (x, y, ori before the reset; 0 where no episode ended).
+        frames=None: the ray caster is not launched at all; frames=s: the steps t with (t + 1) % s == 0 are painted straight
+        into out["frames"][(t + 1) // s - 1] ([T // s, N, W, H, 3]; with_final_obs: out["final_obs"] likewise).
+        out: a dict a former call returned, to write into its tensors again.  step(), get_state() and the agents go on from
+        where the rollout ended."""
+        from .rollout import rollout
+        return rollout(self, actions, frames, out)
+
+    def rollout_teacher(self, agent, T, epsilon=0.0, label_agent=None, frames=None, out=None):
+        """T steps of [agent acts, label_agent acts if given, the env steps] issued by ONE C call (same-step autoreset, a
+        Discrete action space): rollout()'s results plus action (executed), action_label (label_agent's choice, or the
+        agent's own un-noised one) and explored.  epsilon: per env and step the executed action is uniformly random with
+        that probability (draws: mazeworld.explore_draws_host); both agents update their memories either way.  With
+        epsilon=0 and no label agent this is agents.teacher_rollout(env, agent, T), bit for bit."""
+        from .rollout import rollout_teacher
+        return rollout_teacher(self, agent, T, epsilon, label_agent, frames, out)
 
     def set_move_kernel(self, kernel):
         """"auto" (default: nine or three lanes per env by batch size; from 10,240 envs up the nine-lane kernel walks only the
