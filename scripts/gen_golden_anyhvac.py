@@ -148,6 +148,10 @@ def uniform_actions(seed):
     return lambda k, n: rng.uniform(0, 1, n).astype(np.float32)
 
 
+def _all_above(t, n):
+    return min(len(t["coolers"]), len(t["sensors"]), len(t["equipments"])) > n
+
+
 SLOW = dict(max_steps=20160, iter_per_step=200, sec_per_iter=0.15, reward_mode=0)
 # name -> (room constants, first seed, condition on the task, env settings, generate_task, actions(seed), stop rule)
 RUNS = {
@@ -163,6 +167,11 @@ RUNS = {
               lambda s: uniform_actions(2000 + s), lambda k, te, tr: k >= 6),
     "mode2": (room(5, 7, 1.2, 1.6), 2, lambda t: True, dict(SLOW, iter_per_step=50, sec_per_iter=0.2, reward_mode=2), True,
               lambda s: uniform_actions(3000 + s), lambda k, te, tr: k >= 6),
+    # the sampler's default room sizes: every node count above 256, the step kernel's workgroup size
+    "full": (room(15, 15, 2.9, 3.0), 0, lambda t: _all_above(t, 256), SLOW, True,
+             lambda s: uniform_actions(1000 + s), lambda k, te, tr: k >= 4),
+    "max": (room(16, 16, 2.9, 3.0), 0, lambda t: _all_above(t, 256), SLOW, True,
+            lambda s: uniform_actions(1000 + s), lambda k, te, tr: k >= 4),
 }
 
 
@@ -171,9 +180,10 @@ def save(name, flat, extra):
     d.update(extra)
     path = os.path.join(GOLD, "anyhvac_%s.npz" % name)
     np.savez_compressed(path, **d)
-    print("%-8s %7d bytes  %s" % (name, os.path.getsize(path),
-                                  {k: (float(v) if np.ndim(v) == 0 else np.shape(v)) for k, v in extra.items()
-                                   if k in ("eer_margin", "fail_margin", "n_steps", "seed", "rest_idx")}))
+    print("%-8s %7d bytes  %d coolers %d sensors %d heaters  %s" % (
+        name, os.path.getsize(path), len(flat["cooler_loc"]), len(flat["sensor_loc"]), len(flat["heater_loc"]),
+        {k: (float(v) if np.ndim(v) == 0 else np.shape(v)) for k, v in extra.items()
+         if k in ("eer_margin", "fail_margin", "n_steps", "seed", "rest_idx")}))
 
 
 def main():

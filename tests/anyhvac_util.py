@@ -16,7 +16,9 @@ import numpy as np
 from util import golden_files
 
 FILES = {os.path.basename(p)[len("anyhvac_"):-4]: p for p in golden_files("anyhvac_")}
-RUNS = ("rot", "hot", "trunc", "wide", "mode1", "mode2")
+RUNS = ("rot", "hot", "trunc", "wide", "mode1", "mode2", "full", "max")
+FULL_SIZE = ("full", "max")      # 15 x 15 and 16 x 16 cells, every node count above the step kernel's 256 lanes
+SIZE_CAP = 811543      # the cap tests/test_host_metalm.py applies to its family's fixtures
 TASKS_ONLY = ("task_s0", "task_s1")
 MIN_EER_MARGIN, MIN_FAIL_MARGIN = 1e-7, 1e-4
 EPS32 = 2.0 ** -24      # half a float32 ulp, relative
@@ -114,6 +116,30 @@ def check_step(g, k, obs, reward, terminated, truncated, info, grid, label=""):
     else:
         assert abs(float(reward) - float(g["reward"][k])) <= r_tol, at + "reward off by %g (bound %g)" % (
             abs(float(reward) - float(g["reward"][k])), r_tol)
+
+
+class HostRecord(object):
+    """steps of an HVACHost (or a subclass) laid out as a fixture is, so that check_step holds a device run to the host
+    where no recording exists: step() advances the host and appends the step, g is the record so far"""
+
+    def __init__(self, host):
+        self.host, self.rows = host, {}
+
+    def step(self, action):
+        h = self.host
+        out = obs, r, term, trunc, info = h.step(action)
+        row = dict(action=h.value, grid=h.state.copy(), t=np.float64(h.t), timestep=obs["timestep"][0], rest_idx=h.rest_idx,
+                   warning_count=h.warning_count, over_heat=info["over_heat"], over_tolerace=info["over_tolerace"],
+                   action_temp=obs["action_temp"], sensor_readings=obs["sensor_readings"], heat_readings=obs["heat_readings"],
+                   heat_power=info["heat_power"], cool_power=info["cool_power"], target_cost=info["target_cost"],
+                   energy_cost=info["energy_cost"], reward=r, terminated=term, truncated=trunc)
+        for k, v in row.items():
+            self.rows.setdefault(k, []).append(np.array(v))
+        return out
+
+    @property
+    def g(self):
+        return dict({k: np.array(v) for k, v in self.rows.items()}, set_iter_per_step=np.int64(self.host.iter_per_step))
 
 
 # ---- device plumbing ------------------------------------------------------------------------------------------------

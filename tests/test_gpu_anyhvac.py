@@ -1,5 +1,7 @@
 """AnyHVAC on the device (csrc/anyhvac.hip) against the reference's recorded runs and the host restatement; the bounds are
-derived in anyhvac_util.py.  The shapes are the fixtures': rooms of 30-99 cells, 3-92 coolers."""
+derived in anyhvac_util.py.  The shapes are the fixtures': rooms of 30-99 cells, 3-92 coolers, and in
+test_replays_the_reference the two full-size rooms of 225 and 256 cells (tests/test_gpu_anyhvac_fullsize.py has the rest at
+that size)."""
 import numpy as np
 import pytest
 import torch

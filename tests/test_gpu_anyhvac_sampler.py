@@ -159,7 +159,8 @@ def test_set_task_borrows_the_device_tables(engine):
 
 
 def test_default_configuration_structure(engine):
-    """the only test at full size: four candidates, no comparison with the host"""
+    """four candidates at full size, no comparison with the host (the step kernel at these sizes against the host:
+    tests/test_gpu_anyhvac_fullsize.py)"""
     r = sample_candidates(engine, 1, 0, 4, info=True)
     dims = r["dims"]
     assert dims == sh.table_dims() == (15, 15, 303, 607, 607, 4, 7)

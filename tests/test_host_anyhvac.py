@@ -1,6 +1,7 @@
 """AnyHVAC without a GPU: the sampler port and the host restatement against the reference's recorded tasks and runs
 (tests/golden/anyhvac_*.npz, scripts/gen_golden_anyhvac.py), bit for bit; the padded device tables; the settings that are
 not built."""
+import os
 import random
 
 import numpy as np
@@ -17,6 +18,8 @@ def test_every_fixture_is_there_with_its_margins():
     for name in U.RUNS:
         g = U.load(name)[0]
         assert float(g["eer_margin"]) >= U.MIN_EER_MARGIN and float(g["fail_margin"]) >= U.MIN_FAIL_MARGIN, name
+    for name in U.FULL_SIZE:
+        assert os.path.getsize(U.FILES[name]) <= U.SIZE_CAP, name
 
 
 @pytest.mark.parametrize("name", U.TASKS_ONLY + U.RUNS)
@@ -83,6 +86,9 @@ def test_host_replays_the_reference_bit_for_bit(name):
         assert n == 8 and g["truncated"][7] and not g["truncated"][:7].any()
     if name in ("mode1", "mode2"):
         assert list(g["t"]) == [10.0 * (k + 1) for k in range(n)]
+    if name in U.FULL_SIZE:      # what these two are for: every lane-strided loop of the step kernel takes a second pass
+        assert host.nw * host.nl == {"full": 225, "max": 256}[name] and n == 4
+        assert host.n_coolers > 256 and host.n_sensors > 256 and host.n_heaters > 256
 
 
 def test_host_raises_on_nan_like_the_reference():
