@@ -221,6 +221,14 @@ def gen_anymdp():
         gen_anymdp_one("anymdp_64x8_seed1", sample_ref_tasks.get(64, 8, 1), seed0=77000)
     else:
         print("skip 64x8: task cache not ready (run oracle/sample_ref_tasks.py 64 8 1; ~9 min)")
+    # 12 actions: the only reference-sampled task with a row wider than 8 (the Q-learner's sums change code there).  A third of
+    # its states are terminal and random actions end an episode within ~2.4 steps; with this seed0 the episode placed 3 steps
+    # before max_steps reaches it (with 91000 it terminates first, and the fixture must cross the truncation boundary)
+    p = sample_ref_tasks.cache_path(24, 12, 0)
+    if os.path.exists(p):
+        gen_anymdp_one("anymdp_24x12_seed0", sample_ref_tasks.get(24, 12, 0), seed0=92000)
+    else:
+        print("skip 24x12: task cache not ready (run oracle/sample_ref_tasks.py 24 12 0; ~8 min)")
 
 
 def _linds_task_arrays(task):

@@ -142,6 +142,8 @@ def main():
     gen("16x4_m1", "anymdp_16x4_seed2", T=2000, seed0=90000, learner_max_steps=1,
         init_sa=1990 + rng.randint(0, 10, (16, 4)).astype(np.float64), test_interval=6, test_epochs=2)
     gen("64x8_seed1", "anymdp_64x8_seed1", T=3000, seed0=60000, test_interval=10)
+    # 12 actions: the row sums of the policy (mean, std, softmax) take numpy's eight partial sums and a tail of four
+    gen("24x12_seed0", "anymdp_24x12_seed0", T=3000, seed0=130000, test_interval=8)
 
 
 if __name__ == "__main__":

@@ -11,6 +11,7 @@ from util import close_f32, golden_files, load_anymdp_golden
 
 pytestmark = pytest.mark.gpu
 FILES = golden_files("anymdp_")
+FILE_16x4_SEED0 = [f for f in FILES if "anymdp_16x4_seed0" in f][0]
 MODES = {"disabled": 0, "next_step": 1, "same_step": 2}
 
 
@@ -61,7 +62,7 @@ def test_golden_reset_draws(path):
     env.close()
 
 
-@pytest.mark.parametrize("path", FILES[:2])
+@pytest.mark.parametrize("path", [f for f in FILES if "anymdp_16x4_seed0" in f or "anymdp_16x4_seed1" in f])
 def test_golden_trajectory_with_truncation_and_transition_gt(path):
     """one env driven exactly like the reference's rollout loop (manual reset on done)"""
     g, task = load_anymdp_golden(path)
@@ -213,11 +214,13 @@ def test_s64_wave_kernel_vs_oracle(n_env, n_task, search):
                                                     (7, 2, 3, 0), (112, 3, 2, 0), (113, 3, 2, 0), (128, 5, 2, 0),
                                                     (224, 2, 2, 0), (225, 2, 2, 0),
                                                     (300, 4, 2, 0), (336, 2, 2, 0), (337, 3, 2, 0), (449, 2, 2, 0), (512, 2, 2, 100),
-                                                    (64, 8, 4, 65000), (64, 8, 4, 70000)])
+                                                    (64, 8, 4, 65000), (64, 8, 4, 70000),
+                                                    (16, 33, 3, 0), (16, 64, 3, 0)])
 def test_generic_kernel_other_sizes_vs_oracle(S, A, n_task, obs_offset):
     """block-count boundaries of the fence path (S = 7: one block; S = 112: 16 blocks, one per fence entry; S = 113
     .. 224: two blocks per fence entry; S = 225 .. 336: three; .. 448: four; .. 512: five — the reference's samplers take
-    any state_space, task_sampler.py:15-19,90-100) and observation ids at the 16-bit metadata limit (ids < 65536 stay on
+    any state_space, task_sampler.py:15-19,90-100), the row index ((t * S + s) * A + a) at wide rows of actions (A = 33 and
+    the largest A = 64) and observation ids at the 16-bit metadata limit (ids < 65536 stay on
     the fence path, larger ones fall back to the per-lane binary search); every case is also run with search = bucket
     (where the fence layout exists) and search = binary"""
     tab = oracle.anymdp_synth(seed=5, task_index_base=0, n_task=n_task, S=S, A=A, s0_max=3)
@@ -354,7 +357,7 @@ def test_sharding_invariance_env_id_base():
 
 
 def test_error_flags_and_misuse_messages():
-    _, task = load_anymdp_golden(FILES[0])
+    _, task = load_anymdp_golden(FILE_16x4_SEED0)
     env = AnyMDPVecEnv(2, autoreset_mode="disabled")
     with pytest.raises(Exception, match="Must call \"set_task\" first"):
         env.reset()
@@ -491,7 +494,7 @@ def test_full_size_config_2a_properties_and_subset_vs_oracle(search):
 
 def test_gt_transition_and_reward_accessors():
     """get_gt_transition / get_gt_reward (anymdp_env.py:161-165): tensors re-indexed by observation id"""
-    g, task = load_anymdp_golden(FILES[0])
+    g, task = load_anymdp_golden(FILE_16x4_SEED0)
     env = AnyMDPVecEnv(4)
     env.set_task(task)
     sm = g["state_mapping"]
@@ -557,6 +560,35 @@ def test_teacher_rollout_on_device():
     rnd = float(env.rollout_teacher(200, greedy, 1.0)["reward_gt"].mean())
     assert opt > rnd
     env.close()
+
+
+@pytest.mark.parametrize("A", [3, 12, 33, 64])
+def test_teacher_rollout_vs_oracle_at_wide_action_counts(A):
+    """the epsilon-greedy teacher against the oracle's restatement draw for draw (word 1 of the draw -> action, modulo A) on
+    synthetic tasks of 16 states and A actions, the greedy table from the device's own value iteration"""
+    S, n, T, n_task = 16, 128, 40, 4
+    tab = oracle.anymdp_synth(seed=31, task_index_base=0, n_task=n_task, S=S, A=A, s0_max=3)
+    env_task = np.repeat(np.arange(n_task, dtype=np.int32), n // n_task)
+    greedy = None
+    for eps in (0.0, 0.3):
+        env = AnyMDPVecEnv(n, seed=11, env_id_base=4000, autoreset_mode="same_step")
+        env.set_task(_dev_tables(tab), env_task_index=env_task)
+        if greedy is None:
+            greedy = _np(env.solve(return_q=False)[1])
+        ora = oracle.AnyMDPOracle(tab, env_task)
+        tick = env.engine.tick
+        obs, _ = env.reset()
+        assert np.array_equal(_np(obs), ora.reset(11, 4000, tick))
+        tick = env.engine.tick
+        dev = env.rollout_teacher(T, greedy, epsilon=eps)
+        ref = ora.rollout_teacher(11, 4000, tick, T, greedy, epsilon=eps)
+        for k in ("action", "obs", "terminated", "truncated", "final_obs"):
+            assert np.array_equal(_np(dev[k]), ref[k]), (eps, k)
+        assert np.allclose(_np(dev["reward"]), ref["reward"], rtol=1e-5, atol=2e-6)
+        if eps > 0.0:
+            assert len(np.unique(ref["action"])) > min(A, 8) // 2     # the uniform actions spread over the row
+        assert env.check_errors() == 0
+        env.close()
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -715,32 +747,23 @@ def test_engine_timing_events_bracket_a_burst_of_steps():
     env.close()
 
 
-@pytest.mark.parametrize("case", ["golden16", "synth64", "synth100", "sampled64"])
-def test_device_value_iteration_vs_oracle_and_numpy(case):
-    """xv_anymdp_solve (register path for S <= 64, S*A <= 512; strided path otherwise) against the oracle's restatement
-    (xo_anymdp_solve: same tables, same sweeps) and the host value iteration: sweep counts equal, Q to 1e-9, greedy
-    actions equal wherever the best two Q values are not within 1e-7 of each other"""
+def _solve_vs_oracle_and_numpy(tab, gamma):
+    """env.solve(gamma) of an env over the tables `tab` against the oracle's restatement and the host value iteration: sweep
+    counts within 1, Q to 1e-9, greedy actions equal wherever the best two Q values are not within 1e-7 of each other
+    -> (the env, sweeps)"""
     from xenoverse_amd.anymdp.task_sampler import value_iteration
     from xenoverse_amd.anymdp import from_blocked
-    if case == "golden16":
-        tasks = [load_anymdp_golden(p)[1] for p in FILES if "16x4" in p]
-        tab = build_tables(tasks)
-    elif case == "sampled64":
-        tab = build_tables([load_anymdp_golden(p)[1] for p in FILES if "64x8" in p])
-    else:
-        S, A = (64, 8) if case == "synth64" else (100, 5)
-        tab = oracle.anymdp_synth(seed=21, task_index_base=0, n_task=6, S=S, A=A, s0_max=3)
     S, A = tab["S"], tab["A"]
     n_task = len(tab["max_steps"])
     env = AnyMDPVecEnv(n_task * 2)
     env.set_task(_dev_tables(tab) if "rows" not in tab else tab)
-    q, g, it = env.solve(gamma=0.99)
+    q, g, it = env.solve(gamma=gamma)
     q, g, it = _np(q), _np(g), _np(it)
     cdf, rs = from_blocked(_np(env._tab["rows"]), S)
     otab = dict(S=S, A=A, s0_max=int(tab["s0_max"]), cdf=cdf, rs=rs, state_map=_np(env._tab["state_map"]),
                 term_mask=_np(env._tab["term_mask"]).view(np.uint64), s0_cdf=_np(env._tab["s0_cdf"]),
                 s0_ids=_np(env._tab["s0_ids"]), max_steps=_np(env._tab["max_steps"]))
-    qo, go, ito = oracle.AnyMDPOracle(otab, np.zeros(1, np.int32)).solve(0.99)
+    qo, go, ito = oracle.AnyMDPOracle(otab, np.zeros(1, np.int32)).solve(gamma)
     assert np.max(np.abs(it.astype(np.int64) - ito)) <= 1 and np.allclose(q, qo, rtol=1e-9, atol=1e-9)
     srt_o = np.sort(qo, -1)
     clear_o = (srt_o[..., -1] - srt_o[..., -2]) > 1e-7
@@ -749,17 +772,74 @@ def test_device_value_iteration_vs_oracle_and_numpy(case):
         T = np.diff(np.concatenate([np.zeros((S, A, 1)), cdf[t]], -1), axis=-1)
         term = np.array([(int(np.asarray(tab["term_mask"]).view(np.uint64)[t][s >> 6]) >> (s & 63)) & 1 for s in range(S)], bool)
         T[term] = 0.0
-        Qh = value_iteration(T, rs[t][..., 0].astype(np.float64), 0.99)
+        Qh = value_iteration(T, rs[t][..., 0].astype(np.float64), gamma)
         assert np.allclose(q[t], Qh, rtol=1e-9, atol=1e-9), np.abs(q[t] - Qh).max()
         srt = np.sort(Qh, 1)
         clear = (srt[:, -1] - srt[:, -2]) > 1e-7
         assert np.array_equal(g[t][clear], Qh.argmax(1)[clear])
+    return env, it
+
+
+@pytest.mark.parametrize("case", ["golden16", "synth64", "synth100", "sampled64"])
+def test_device_value_iteration_vs_oracle_and_numpy(case):
+    """xv_anymdp_solve (register path for S <= 64, S*A <= 512; strided path otherwise) against the oracle's restatement
+    (xo_anymdp_solve: same tables, same sweeps) and the host value iteration: sweep counts equal, Q to 1e-9, greedy
+    actions equal wherever the best two Q values are not within 1e-7 of each other"""
+    if case == "golden16":
+        tasks = [load_anymdp_golden(p)[1] for p in FILES if "16x4" in p]
+        tab = build_tables(tasks)
+    elif case == "sampled64":
+        tab = build_tables([load_anymdp_golden(p)[1] for p in FILES if "64x8" in p])
+    else:
+        S, A = (64, 8) if case == "synth64" else (100, 5)
+        tab = oracle.anymdp_synth(seed=21, task_index_base=0, n_task=6, S=S, A=A, s0_max=3)
+    n_task = len(tab["max_steps"])
+    env, it = _solve_vs_oracle_and_numpy(tab, 0.99)
     assert it.min() > 10 and it.max() < 20000
     # the teacher rollout solves on the device when no table is given
     env.reset()
     out = env.rollout_teacher(8)
     st = _np(env.get_state()[0])
     assert out["action"].shape == (8, n_task * 2) and st.shape == (n_task * 2,)
+    env.close()
+
+
+@pytest.mark.parametrize("S,A,gamma", [
+    (8, 64, 0.99), (7, 64, 0.99), (21, 24, 0.99), (64, 7, 0.99),    # register path: S*A = 512 at the largest A; 448; 504 (a
+    #                                                                 partial last wave); 448 at S = 64 — no power of two
+    (57, 9, 0.99), (65, 2, 0.99),                                   # strided path just over each limit: S*A = 513; S = 65
+    (128, 24, 0.9), (128, 30, 0.9)])                                # strided path, 54,272 B and 66,560 B of LDS: above the
+#                                                                     48 KiB default and above 64 KiB
+def test_device_value_iteration_at_the_edges_of_its_two_paths(S, A, gamma):
+    """the register path maps thread tid to (tid / A, tid % A) and lets every lane join the readlane chain; the strided
+    path's LDS grows with 2 S A doubles and needs its limit raised above 48 KiB.  Same assertions as
+    test_device_value_iteration_vs_oracle_and_numpy, two synthetic tasks each (gamma = 0.9 at the two large ones keeps the
+    sweep count small)"""
+    tab = oracle.anymdp_synth(seed=23, task_index_base=0, n_task=2, S=S, A=A, s0_max=3)
+    env, it = _solve_vs_oracle_and_numpy(tab, gamma)
+    assert it.max() < 20000          # converged, not stopped at max_iter
+    env.close()
+
+
+def test_device_value_iteration_refuses_what_does_not_fit_lds():
+    """512 x 18 needs 155,648 B of LDS, more than the 150 KiB xv_anymdp_solve allows: XV_ERR_UNSUPPORTED with its message
+    before any launch, and the env steps afterwards"""
+    from xenoverse_amd import _lib
+    S, A, n = 512, 18, 4
+    tab = oracle.anymdp_synth(seed=23, task_index_base=0, n_task=1, S=S, A=A, s0_max=3)
+    env = AnyMDPVecEnv(n, seed=2, autoreset_mode="same_step")
+    env.set_task(_dev_tables(tab))
+    with pytest.raises(_lib.XenoError, match="does not fit the workgroup's LDS") as ex:
+        env.solve()
+    assert ex.value.code == _lib.XV_ERR_UNSUPPORTED
+    ora = oracle.AnyMDPOracle(tab, np.zeros(n, np.int32))
+    tick = env.engine.tick
+    obs, _ = env.reset()
+    assert np.array_equal(_np(obs), ora.reset(2, 0, tick))
+    tick = env.engine.tick
+    a = np.array([0, 17, 9, 3], np.int32)
+    _compare_step(env.step(a), ora.step(2, 0, tick, a, 2), exact_reward=False)
+    assert env.check_errors() == 0
     env.close()
 
 

@@ -8,10 +8,12 @@ import numpy as np
 import pytest
 import torch
 
-from util import anymdp_env as _env, anymdp_tasks16 as _tasks16, to_np as _np
+import oracle
+from util import anymdp_env as _env, anymdp_random_task as _random_task, anymdp_tasks16 as _tasks16, to_np as _np
 from util import golden_files, load_anymdp_golden, load_anymdp_tok_golden
 from xenoverse_amd import _lib
-from xenoverse_amd.anymdp import AnyMDPMBRLLearner, AnyMDPQLearner, AnyMDPVecEnv
+from xenoverse_amd.anymdp import AnyMDPMBRLLearner, AnyMDPQLearner, AnyMDPVecEnv, MBRLHost, QLearnerHost
+from xenoverse_amd.anymdp.qlearner import policy_cdf
 
 pytestmark = pytest.mark.gpu
 
@@ -114,6 +116,82 @@ def test_splitting_T_changes_nothing(kind):
         assert np.array_equal(o1[k], o2[k]), k
     for x, y in zip(s1, s2):
         assert np.array_equal(x, y)
+
+
+def _q_uniforms(seed, gid, tick, A):
+    """anymdp_qlearn.hip: purpose 4 (XV_DRAW_QPOLICY), words 0,1 -> the one uniform numpy.random.choice searches"""
+    w = oracle.env_draw(seed, gid, tick, 4)
+    return oracle.u53(w[0], w[1])
+
+
+def _mbrl_uniforms(seed, gid, tick, A):
+    """anymdp_mbrl.hip: purpose 7 (XV_DRAW_MBRL_POLICY), sub = a >> 1, words 0,1 (a even) or 2,3 (a odd) -> u[a]; an odd
+    A uses only the first word pair of its last draw"""
+    u = np.zeros(A)
+    for sub in range((A + 1) // 2):
+        w = oracle.env_draw_sub(seed, gid, tick, 7, sub)
+        u[2 * sub] = oracle.u53(w[0], w[1])
+        if 2 * sub + 1 < A:
+            u[2 * sub + 1] = oracle.u53(w[2], w[3])
+    return u
+
+
+PHILOX = dict(
+    q=dict(make=AnyMDPQLearner, host=lambda n, S, A: QLearnerHost(n, S, A), uniforms=_q_uniforms,
+           learn=lambda h, s, a, ns, r, term, trunc: h.learn(s, a, ns, r, term)),
+    mbrl=dict(make=AnyMDPMBRLLearner, host=lambda n, S, A: MBRLHost(n, S, A), uniforms=_mbrl_uniforms,
+              learn=lambda h, s, a, ns, r, term, trunc: h.learn(s, a, ns, r, term, trunc)))
+
+
+@pytest.mark.parametrize("kind,A", [("q", 12), ("mbrl", 5), ("mbrl", 12)])
+def test_free_running_policy_draws_are_the_documented_philox_draws(kind, A):
+    """no injected draws, a nonzero engine seed and env_id_base: the policy's uniforms recomputed on the host from the key
+    both kernels document — (engine seed, env_id_base + env, the launch tick of the step that takes the action, purpose,
+    [sub]); step t of a rollout is launched with the tick the engine had before the rollout plus t (a learner launch binds
+    the tick of the NEXT step launch without advancing it, anymdp_learner.h: xv_learner_bind) — and fed to the host
+    restatement along the device's trajectory: every action equal (Q: but for envs from the first step at which the host's
+    own margin to a cut of its CDF is below 1e-9, at most 0.1 % of them; the device's exp may differ from numpy's in the
+    last bit), the learner tables bit-equal at the end; and two calls of T / 2 equal one call of T bit for bit"""
+    K = PHILOX[kind]
+    S, n, T, seed, base = 10, 256, 48, 77, 3000
+    tasks = [_random_task(S, A, seed=40 + A, max_steps=20, n_terminal=2), _random_task(S, A, seed=41 + A, max_steps=20)]
+    res = []
+    for parts in (1, 2):
+        env = _env(tasks, n, seed=seed, env_id_base=base)
+        env.reset()
+        obs0 = _np(env.state).astype(np.int64)
+        lr = K["make"](env)
+        tick0 = env.engine.tick
+        outs = [env.rollout_learner(lr, T // parts) for _ in range(parts)]
+        assert env.engine.tick == tick0 + T          # one tick per step launch, none for a learner launch
+        res.append(({k: np.concatenate([_np(o[k]) for o in outs]) for k in outs[0]}, [_np(x) for x in lr.get_state()]))
+        assert env.check_errors() == 0
+        lr.close()
+        env.close()
+    (out, state), (out2, state2) = res
+    for k in out:
+        assert np.array_equal(out[k], out2[k]), k
+    for x, y in zip(state, state2):
+        assert np.array_equal(x, y)
+    host = K["host"](n, S, A)
+    obs, live, idx = obs0, np.ones(n, bool), np.arange(n)
+    for t in range(T):
+        u = np.array([K["uniforms"](seed, base + i, tick0 + t, A) for i in range(n)])
+        if kind == "q":
+            cdf = policy_cdf(host.q[idx, obs], host.s_visits[idx, obs], host.max_steps)
+            live &= np.abs(cdf[:, :-1] - u[:, None]).min(-1) >= 1e-9
+        a = host.policy(obs, u)
+        bad = np.nonzero((a != out["action"][t]) & live)[0]
+        assert len(bad) == 0, (t, bad[:4], a[bad[:4]], out["action"][t][bad[:4]])
+        term, trunc = out["terminated"][t].astype(bool), out["truncated"][t].astype(bool)
+        K["learn"](host, obs, out["action"][t], np.where(term | trunc, out["final_obs"][t], out["obs"][t]),
+                   out["reward"][t].astype(np.float64), term, trunc)
+        obs = out["obs"][t].astype(np.int64)
+    assert int((~live).sum()) <= n // 1000
+    assert np.array_equal(np.unique(out["action"]), np.arange(A))
+    assert out["terminated"].sum() > 0 and out["truncated"].sum() > 0
+    for name, x, y in zip(K["make"]._TABLES, state, host.get_state()):
+        assert np.array_equal(x[live], y[live]), name[0]
 
 
 @kinds

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from util import anymdp_env as _env, anymdp_fixture_task as _fixture_task, anymdp_tasks16 as _tasks16, to_np as _np
+from util import anymdp_random_task as _random_task
 from util import close_f32, golden_files, load_anymdp_golden
 from xenoverse_amd.anymdp import AnyMDPMBRLLearner, MBRLHost
 
@@ -134,19 +135,6 @@ def test_device_equals_host_restatement(cfg, T):
     # the 20x3 task has no terminal states; the 64x8 task's episodes end by termination within a few steps
     assert (n_term > 0) == (cfg != "20x3") and (n_trunc > 0) == (cfg != "64x8")
     assert most >= 16
-
-
-def _random_task(S, A, seed, max_steps=50):
-    """a random MDP with no terminal states: every (s, a) row reaches 6 next states"""
-    rng = np.random.RandomState(seed)
-    T = np.zeros((S, A, S))
-    for s in range(S):
-        for a in range(A):
-            T[s, a, rng.choice(S, 6, replace=False)] = rng.random_sample(6) + 0.1
-    T /= T.sum(-1, keepdims=True)
-    return dict(ns=S, na=A, max_steps=float(max_steps), state_mapping=rng.permutation(S), task_type="MDP",
-                s_0=np.arange(4), s_0_prob=np.full(4, 0.25), s_e=np.zeros(0, np.int64), transition=T,
-                reward=rng.randn(S, A, S) * (T > 0), reward_noise=np.full((S, A, S), 0.1))
 
 
 @pytest.mark.parametrize("S,A", [(200, 3), (512, 16)])

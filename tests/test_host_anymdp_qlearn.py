@@ -18,8 +18,9 @@ def _learner(g, n=1):
 
 def test_fixtures_present():
     names = [f.rsplit("/", 1)[-1] for f in FILES]
-    assert len(FILES) >= 6, names
+    assert len(FILES) >= 7, names
     assert any("64x8" in n for n in names) and any("m1" in n for n in names)
+    assert any(int(np.load(f)["na"]) > 8 for f in FILES), names      # a row the pairwise sum takes in eight partial sums
 
 
 @pytest.mark.parametrize("path", FILES, ids=lambda p: p.rsplit("/", 1)[-1])
@@ -57,6 +58,10 @@ def test_fixtures_cover_terminal_truncated_greedy_and_caps():
     assert (m1["snap_sa"][-1] > 1000 * (M + 1) - M).any()           # lr = sqrt(1e-3) on these pairs
     assert (m1["snap_s"][-1] >= 9 * M + 10).any()                    # stiffness = 10
     assert int(gs["qlearn_anymdp_64x8_seed1.npz"]["na"]) >= 8
+    wide = [g for g in gs.values() if int(g["na"]) > 8]
+    assert len(wide) >= 1
+    for g in wide:
+        assert int(g["terminated"].sum()) > 0 and int(g["is_test"].sum()) > 0
 
 
 def test_np_sum_matches_numpy():

@@ -8,6 +8,7 @@ from xenoverse_amd.anymdp.tables import build_tables, row_cdf
 from util import golden_files, load_anymdp_golden, close_f32
 
 FILES = golden_files("anymdp_")
+FILE_16x4_SEED0 = [f for f in FILES if "anymdp_16x4_seed0" in f][0]
 DISABLED, NEXT_STEP, SAME_STEP = 0, 1, 2
 
 
@@ -113,7 +114,7 @@ def test_trajectory_same_step_autoreset(path):
 
 
 def test_next_step_autoreset_semantics():
-    g, task = load_anymdp_golden(FILES[0])
+    g, task = load_anymdp_golden(FILE_16x4_SEED0)
     tab = build_tables([task])
     o = oracle.AnyMDPOracle(tab, np.zeros(1, np.int32))
     o.reset_injected(np.array([float(g["init_u"])]))
@@ -134,7 +135,7 @@ def test_next_step_autoreset_semantics():
 
 
 def test_error_flags():
-    g, task = load_anymdp_golden(FILES[0])
+    g, task = load_anymdp_golden(FILE_16x4_SEED0)
     tab = build_tables([task])
     o = oracle.AnyMDPOracle(tab, np.zeros(2, np.int32))
     o.reset_injected(np.array([0.1, 0.1]))

@@ -27,9 +27,29 @@ def anymdp_tasks16():
     return [load_anymdp_golden(p)[1] for p in golden_files("anymdp_16x4")[:4]]
 
 
-def anymdp_env(tasks, n, seed, mode="same_step"):
+def anymdp_random_task(S, A, seed, max_steps=50, n_terminal=0):
+    """a random MDP: every (s, a) row reaches 6 next states; s_0 = the first 4 states.  n_terminal: the last n_terminal
+    states are terminal (s_e; none of them in s_0) and their rows are all zero, as in the reference's tasks (build_tables
+    makes such rows CDF 1.0: they are never sampled from).  The draws do not depend on n_terminal."""
+    assert S >= 6 and S - n_terminal >= 4
+    rng = np.random.RandomState(seed)
+    T = np.zeros((S, A, S))
+    for s in range(S):
+        for a in range(A):
+            T[s, a, rng.choice(S, 6, replace=False)] = rng.random_sample(6) + 0.1
+    T /= T.sum(-1, keepdims=True)
+    s_e = np.arange(S - n_terminal, S, dtype=np.int64)
+    task = dict(ns=S, na=A, max_steps=float(max_steps), state_mapping=rng.permutation(S), task_type="MDP",
+                s_0=np.arange(4), s_0_prob=np.full(4, 0.25), s_e=s_e, transition=T,
+                reward=rng.randn(S, A, S) * (T > 0), reward_noise=np.full((S, A, S), 0.1))
+    task["transition"][s_e] = 0.0
+    task["reward"][s_e] = 0.0
+    return task
+
+
+def anymdp_env(tasks, n, seed, mode="same_step", env_id_base=0):
     from xenoverse_amd.anymdp import AnyMDPVecEnv
-    env = AnyMDPVecEnv(n, seed=seed, autoreset_mode=mode)
+    env = AnyMDPVecEnv(n, seed=seed, env_id_base=env_id_base, autoreset_mode=mode)
     env.set_task(tasks)
     return env
 

@@ -75,6 +75,7 @@ class _DeviceLearner(object):
         _lib.check(self._fn("create")(env._h, *args, C.byref(h)))
         self._h = h
         env._learners.add(self)      # released before the env's handle goes (set_task, close)
+        env._learner_handles[h.value] = (self._fn("destroy"), h)
 
     def _fn(self, op):
         return getattr(self.lib, "%s_%s" % (self._ABI, op))
@@ -139,7 +140,13 @@ class _DeviceLearner(object):
 
     def close(self, why=None):
         if self._h is not None:
-            self._fn("destroy")(self._h)
+            # the C learner borrows the env's handle and, through it, the engine: destroying it reads both.  When the env's
+            # handle went first (only a learner collected together with its env sees that: vec_env.py, _release_learners)
+            # the env has destroyed the C learner already
+            env = self.env
+            if env._h is self._env_h and env.engine.handle is not None:
+                self._fn("destroy")(self._h)
+                env._learner_handles.pop(self._h.value, None)
             self._h = None
             self._closed_why = why or self._closed_why
 

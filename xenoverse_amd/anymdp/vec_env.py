@@ -56,6 +56,7 @@ class AnyMDPVecEnv(VectorEnv):
         self._tab = None
         self._views = []            # sub-batch envs made by split(): they borrow this env's tables
         self._learners = weakref.WeakSet()   # the learners (Q, MBRL) on this env's handle
+        self._learner_handles = {}           # their C handles by address, with the call that destroys each (learner.py: close)
         self._parent = None
 
     # ---- set_task ---------------------------------------------------------------------------------
@@ -762,6 +763,13 @@ class AnyMDPVecEnv(VectorEnv):
         for ql in list(self._learners):
             ql.close("%s: %s" % (type(ql).__name__, why))
         self._learners = weakref.WeakSet()
+        # what is still on record: learners the cyclic collector is taking together with this env.  It clears every weak
+        # reference to them before it runs any finaliser, so the set above no longer names them when this env's finaliser
+        # runs first; their own finalisers then find the env's handle gone and leave the C learner alone
+        if self.engine.handle is not None:
+            for destroy, h in list(self._learner_handles.values()):
+                destroy(h)
+        self._learner_handles = {}
 
     def close_extras(self, **kwargs):
         self._drop_views()
