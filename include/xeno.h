@@ -1250,6 +1250,38 @@ int xv_metalm_stream(xv_metalm* h, int datatype, int L, int max_rounds, const do
                      const int32_t* t_index, const double* u_policy, const double* u_greedy, const double* u_low,
                      const double* u_query, const int32_t* marks, int32_t* data, int32_t* label, int32_t* filled,
                      int32_t* rounds, double* reward, int32_t* t_index_out);
+/* MetaLMV3 tasks made on the device (generator_v3.py sample_and_check_task :25-46 over task_sampler.py TaskSamplerV3 :86-98),
+ * ONE launch, one workgroup per candidate c in [cand_base, cand_base + n_cand): the candidate's networks are generated and
+ * the acceptance protocol reset(), policy(1e4), step(cached), policy(1e-6), step(cached) is run on them.  A pure function
+ * of (seed, c, the sizes, max_len, the stop and function tokens): the call neither reads nor advances the engine's tick
+ * and never sets the engine's error word.
+ *   networks: RandomLM seeds enc, dec and rnn with one seed, so with z the stream of standard normals and
+ *     s(i, o) = sqrt(2 / (i + o)):  enc_w = (s(V,E) z[:V E]).reshape(E,V) 3,  dec_w = (s(H,V) z[:V H]).reshape(V,H) 3,
+ *     rnn_w = (s(E+H,H) z[:H (H+E)]).reshape(H,H+E) 3,  rnn_b = 0.1 z[H (H+E) : H (H+E) + H],  dec_b = 0.
+ *     z[i] is member i & 1 (cos, sin) of the fp64 Box-Muller pair of the Philox call (seed, c, tick 0, purpose 14,
+ *     sub = i >> 1): r = sqrt(-2 log(1 - u53(words 0,1))), angle 2 pi u53(words 2,3).
+ *   tables out (device float64, [n_cand] leading, every candidate's, accepted or not), in xv_metalm_set_task's layouts:
+ *     emb [V][E] (numpy's layer_norm of enc_w's columns, bit for bit), w_h_t [H + E][H], b_h [H], w_d_t [H][V], b_d [V],
+ *     and the raw enc_w [E][V].
+ *   protocol: the draws are those an engine with this seed, env_id_base = c and tick 0 binds in the five calls (ticks 0 ..
+ *     4); temperatures, the cut at max_len and the reward are the existing kernels'.
+ *   status int32 [n_cand], tested in this order: XV_METALM_NONFINITE (a reward is not finite, or a pass raised
+ *     XV_DEVERR_NONFINITE: a deliberate rejection), XV_METALM_REWARD_LOW (the T = 1e4 answer's reward is > 0),
+ *     XV_METALM_REWARD_HIGH (the T = 1e-6 answer's reward is < 2), else XV_METALM_ACCEPTED.
+ *   nullable: reward float64 [n_cand][2] (low, high), ppl float64 [n_cand][2][3] (ppl, ppl_min, ppl_max), query int32
+ *     [n_cand][max_len] with query_len [n_cand], answer int32 [n_cand][2][max_len] with answer_len [n_cand][2] (rows padded
+ *     with 0), flags uint32 [n_cand]: the XV_DEVERR_* bits the candidate's passes raised (XV_DEVERR_LENGTH: a pass was cut).
+ * Refusals are xv_metalm_create's: the size limits (XV_ERR_UNSUPPORTED), a stop or function token outside the vocabulary,
+ * n_cand < 1, cand_base < 0.  function_tokens: n_function HOST ints. */
+#define XV_METALM_ACCEPTED 0
+#define XV_METALM_NONFINITE 1
+#define XV_METALM_REWARD_LOW 2
+#define XV_METALM_REWARD_HIGH 3
+int xv_metalm_sample_tasks(xv_engine* e, uint64_t seed, int64_t cand_base, int n_cand, int n_vocab, int n_emb, int n_hidden,
+                           int max_len, int stop_token, const int32_t* function_tokens, int n_function, double* emb,
+                           double* w_h_t, double* b_h, double* w_d_t, double* b_d, double* enc_w, int32_t* status,
+                           double* reward, double* ppl, int32_t* query, int32_t* query_len, int32_t* answer,
+                           int32_t* answer_len, uint32_t* flags);
 
 /* ------------------------------------------------------------------------------------------------
  * AnyHVAC — reference: xenoverse/anyhvac/anyhvac_env.py HVACEnv :8-651 with control_type 'Temperature',

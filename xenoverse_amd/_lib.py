@@ -160,6 +160,7 @@ SIGNATURES = {
     "xv_metalm_get_state": [c_void_p] * 5,
     "xv_metalm_set_state": [c_void_p] * 5,
     "xv_metalm_stream": [c_void_p, c_int, c_int, c_int, c_void_p, c_int] + [c_void_p] * 12,
+    "xv_metalm_sample_tasks": [c_void_p, c_u64, c_i64] + [c_int] * 6 + [c_void_p, c_int] + [c_void_p] * 14,
     "xv_anyhvac_create": [c_void_p] + [c_int] * 9 + [C.c_double] * 4 + [c_int, C.POINTER(c_void_p)],
     "xv_anyhvac_destroy": [c_void_p],
     "xv_anyhvac_set_task": [c_void_p, c_int, c_void_p, c_void_p],

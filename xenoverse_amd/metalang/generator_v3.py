@@ -11,6 +11,7 @@ import time
 
 import numpy
 
+from .device_sampler import sample_tasks_device, task_dicts_from_device
 from .generator import _text_io
 from .lm_host import TaskSamplerV3
 from .stream_host import CHECK_T_HIGH, CHECK_T_LOW, accepts, sample_tasks_host
@@ -24,19 +25,24 @@ def _max_len(max_len):
 
 def generate_data_v3_batch(tasks, datatype, L, T_choices=None, device="cuda:0", seed=0, max_len=None):
     """one stream per task -> int32 [len(tasks), 2, L]: [:, 0] data, [:, 1] label.  Every task gets an env of its own (all
-    of one size); reset(), then one stream() launch per MAX_ENVS_PER_CALL tasks."""
+    of one size); reset(), then one stream() launch per MAX_ENVS_PER_CALL tasks.  tasks: task dicts, or the tables dict of
+    sample_tasks_device, whose device tensors are sliced per call and set as they are."""
+    from .device_sampler import is_tables, slice_tables
     from .lm_env import MetaLMV3VecEnv
-    tasks = list(tasks)
-    out = numpy.zeros((len(tasks), 2, int(L)), numpy.int32)
-    for base in range(0, len(tasks), MAX_ENVS_PER_CALL):
-        part = tasks[base:base + MAX_ENVS_PER_CALL]
-        env = MetaLMV3VecEnv(len(part), max_len=_max_len(max_len), device=device, seed=seed, env_id_base=base)
+    tables = tasks if is_tables(tasks) else None
+    tasks = None if tables is not None else list(tasks)
+    n = int(tables["emb"].shape[0]) if tables is not None else len(tasks)
+    out = numpy.zeros((n, 2, int(L)), numpy.int32)
+    for base in range(0, n, MAX_ENVS_PER_CALL):
+        top = min(n, base + MAX_ENVS_PER_CALL)
+        part = slice_tables(tables, base, top) if tables is not None else tasks[base:top]
+        env = MetaLMV3VecEnv(top - base, max_len=_max_len(max_len), device=device, seed=seed, env_id_base=base)
         try:
             env.set_task(part)
             env.reset()
             data, label, info = env.stream(datatype, L, T_choices=T_choices)
-            out[base:base + len(part), 0] = data.cpu().numpy()
-            out[base:base + len(part), 1] = label.cpu().numpy()
+            out[base:top, 0] = data.cpu().numpy()
+            out[base:top, 1] = label.cpu().numpy()
             flags = env.check_errors()
         finally:
             env.close()
@@ -115,26 +121,42 @@ def sample_and_check_task(vocab_size=32, embedding_size=16, hidden_size=32, func
                                   device)[0][0]
 
 
+def _sample_tables(samples, seed, device, sizes):
+    return sample_tasks_device(samples, sizes["vocab_size"], sizes["embedding_size"], sizes["hidden_size"], seed=seed,
+                               device=device)
+
+
 def metalang_generator_v3(datatype="QAR", sample_type="sequences", vocab_size=32, embedding_size=16, hidden_size=32,
                           samples=1000, sequence_length=16000, output_type="txt", task_file=None, output=None,
-                          device="cuda:0", seed=None, backend="device"):
+                          device="cuda:0", seed=None, backend="device", sampler=None):
+    """sampler: None — tasks come from sample_and_check_tasks(backend=backend), as ever; "device" — from
+    sample_tasks_device: made and tested on the GPU, handed to the streams as device tables (other tasks than the former's
+    for the same seed; they are drawn independently, so they are not shuffled)"""
     seed_base = int(time.time() * 1000 % 1000000) if seed is None else int(seed)
     assert datatype in ["QAR", "QA", "QARA"], "datatype must be one of QAR, QA, QARA"
     sizes = dict(vocab_size=vocab_size, embedding_size=embedding_size, hidden_size=hidden_size, function_token_number=6)
     if sample_type == "tasks":
         if output is None:
             raise Exception("Must specify --output when sample_type is tasks")
-        tasks, _ = sample_and_check_tasks(samples, seed=seed_base, backend=backend, device=device, **sizes)
+        if sampler == "device":
+            tasks = task_dicts_from_device(_sample_tables(samples, seed_base, device, sizes))
+        else:
+            tasks, _ = sample_and_check_tasks(samples, seed=seed_base, backend=backend, device=device, **sizes)
         name = output if output.endswith(".pkl") else output + ".pkl"
         with open(name, "wb") as f:
             pickle.dump(tasks, f)
         return None
-    if task_file is None:      # a task of its own for every sample
-        tasks, _ = sample_and_check_tasks(samples, seed=seed_base, backend=backend, device=device, **sizes)
+    if task_file is None and sampler == "device":
+        tasks = _sample_tables(samples, seed_base, device, sizes)
+        if backend == "host":
+            tasks = task_dicts_from_device(tasks)
     else:
-        with open(task_file, "rb") as f:
-            tasks = pickle.load(f)
-    random.Random(seed_base).shuffle(tasks)
+        if task_file is None:      # a task of its own for every sample
+            tasks, _ = sample_and_check_tasks(samples, seed=seed_base, backend=backend, device=device, **sizes)
+        else:
+            with open(task_file, "rb") as f:
+                tasks = pickle.load(f)
+        random.Random(seed_base).shuffle(tasks)
     if backend == "host":
         from .stream_host import generate_data_v3_host
         data = numpy.array([generate_data_v3_host(t, datatype, sequence_length)[:2] for t in tasks])
@@ -167,6 +189,8 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=None, help="task seeds and the Philox key; default: from the clock, as the reference")
     ap.add_argument("--backend", type=str, choices=["device", "host"], default="device",
                     help="host: the numpy restatement, no GPU (slow; for checking)")
+    ap.add_argument("--sampler", type=str, choices=["device"], default=None,
+                    help="device: make and test the tasks on the GPU in one launch per batch (metalang.sample_tasks_device)")
     metalang_generator_v3(**vars(ap.parse_args(argv)))
 
 

@@ -17,6 +17,49 @@ def _lm_of(task, what):
     return lm if isinstance(lm, RandomLMHost) else RandomLMHost.from_reference(lm)
 
 
+def env_task_of(n_task, num_envs, env_task_index=None):
+    """the task of every env as int32 [num_envs]: the given indices, checked, or the default (the only task; task i for
+    env i when there are num_envs tasks)"""
+    if env_task_index is None:
+        if n_task == 1:
+            env_task_index = np.zeros(num_envs, np.int32)
+        elif n_task == num_envs:
+            env_task_index = np.arange(num_envs, dtype=np.int32)
+        else:
+            raise ValueError("%d tasks for %d envs: give env_task_index" % (n_task, num_envs))
+    if hasattr(env_task_index, "detach"):
+        env_task_index = env_task_index.detach().cpu().numpy()
+    eti = np.ascontiguousarray(env_task_index, dtype=np.int32)
+    if eti.shape != (num_envs,) or eti.min() < 0 or eti.max() >= n_task:
+        raise ValueError("env_task_index must be int[num_envs] with values in [0, %d)" % n_task)
+    return eti
+
+
+def tables_for_set_task(tables, device):
+    """the tables dict of metalang.sample_tasks_device -> ([emb, w_h_t, b_h, w_d_t, b_d] as the handle borrows them, n_task,
+    (V, E, H, stop, function tokens)).  A float64, contiguous tensor already on `device` is taken as it is."""
+    import torch
+    from .device_sampler import TABLE_KEYS, function_tokens
+    emb = tables["emb"]
+    if not torch.is_tensor(emb) or emb.dim() != 3 or emb.shape[0] < 1:
+        raise ValueError("tables['emb'] must be a tensor [n_task, V, E]")
+    n, V, E = (int(v) for v in emb.shape)
+    H = int(tables["b_h"].shape[-1])
+    shapes = dict(emb=(n, V, E), w_h_t=(n, H + E, H), b_h=(n, H), w_d_t=(n, H, V), b_d=(n, V))
+    dev = []
+    for k in TABLE_KEYS:
+        t = tables[k]
+        if not torch.is_tensor(t) or t.dtype != torch.float64 or tuple(t.shape) != shapes[k]:
+            raise ValueError("tables[%r] must be a float64 tensor of shape %s" % (k, shapes[k]))
+        dev.append(t.to(device).contiguous())
+    for k, v in (("vocabulary", V), ("embedding", E), ("hidden", H)):
+        if k in tables and int(tables[k]) != v:
+            raise ValueError("tables[%r] = %d, the tensors say %d" % (k, int(tables[k]), v))
+        check_lm_limit({"vocabulary": "n_vocab", "embedding": "n_emb", "hidden": "n_hidden"}[k], v)
+    stop, fun = function_tokens(tables.get("function_vocabulary"))
+    return dev, n, (V, E, H, stop, tuple(fun))
+
+
 class MetaLMV3VecEnv(object):
     """num_envs envs, each one RandomLM task with its current query and the hidden state that query left.  Every task of a
     handle has the same (vocabulary, embedding, hidden), stop token and function tokens.
@@ -47,40 +90,37 @@ class MetaLMV3VecEnv(object):
 
     # ---- tasks ----------------------------------------------------------------------------------------------------
     def set_task(self, tasks, env_task_index=None):
-        """tasks: one task dict (TaskSamplerV3) or a list of them; env_task_index int[num_envs]: the task of every env
-        (default: the only task; task i for env i when there are num_envs tasks)"""
+        """tasks: one task dict (TaskSamplerV3), a list of them, or the tables dict of metalang.sample_tasks_device, whose
+        device tensors the handle borrows as they are (no host copy, no RandomLMHost objects); env_task_index
+        int[num_envs]: the task of every env (default: the only task; task i for env i when there are num_envs tasks)"""
         import torch
-        if isinstance(tasks, dict):
-            tasks = [tasks]
-        if not len(tasks):
-            raise ValueError("set_task needs at least one task")
-        lms = [_lm_of(t, "task %d" % k) for k, t in enumerate(tasks)]
-        V, E, H = lms[0].n_vocab, lms[0].n_emb, lms[0].n_hidden
-        stop, fun = lms[0].stop_token, sorted(lms[0].function_token_list)
-        for k, lm in enumerate(lms):
-            if (lm.n_vocab, lm.n_emb, lm.n_hidden) != (V, E, H):
-                raise ValueError("task %d has (vocabulary, embedding, hidden) = %s, task 0 has %s: one handle holds one size"
-                                 % (k, (lm.n_vocab, lm.n_emb, lm.n_hidden), (V, E, H)))
-            if lm.stop_token != stop or sorted(lm.function_token_list) != fun:
-                raise ValueError("task %d has other stop / function tokens than task 0" % k)
-        n_task = len(lms)
-        if env_task_index is None:
-            if n_task == 1:
-                env_task_index = np.zeros(self.num_envs, np.int32)
-            elif n_task == self.num_envs:
-                env_task_index = np.arange(self.num_envs, dtype=np.int32)
-            else:
-                raise ValueError("%d tasks for %d envs: give env_task_index" % (n_task, self.num_envs))
-        eti = np.ascontiguousarray(env_task_index, dtype=np.int32)
-        if eti.shape != (self.num_envs,) or eti.min() < 0 or eti.max() >= n_task:
-            raise ValueError("env_task_index must be int[num_envs] with values in [0, %d)" % n_task)
-        host = [np.stack([lm.emb for lm in lms]),
-                np.stack([lm.rnn_w.T for lm in lms]),      # [H + E][H]: the lanes of a wave own rows of W_h
-                np.stack([lm.rnn_b for lm in lms]),
-                np.stack([lm.dec_w.T for lm in lms]),      # [H][V]: and columns of the logits
-                np.stack([lm.dec_b for lm in lms]), eti]
-        dev = [torch.from_numpy(np.ascontiguousarray(a)).to(self.device) for a in host]
-        sizes = (V, E, H, stop, tuple(fun))
+        from .device_sampler import is_tables
+        if is_tables(tasks):
+            dev, n_task, sizes = tables_for_set_task(tasks, self.device)
+        else:
+            if isinstance(tasks, dict):
+                tasks = [tasks]
+            if not len(tasks):
+                raise ValueError("set_task needs at least one task")
+            lms = [_lm_of(t, "task %d" % k) for k, t in enumerate(tasks)]
+            V, E, H = lms[0].n_vocab, lms[0].n_emb, lms[0].n_hidden
+            stop, fun = lms[0].stop_token, sorted(lms[0].function_token_list)
+            for k, lm in enumerate(lms):
+                if (lm.n_vocab, lm.n_emb, lm.n_hidden) != (V, E, H):
+                    raise ValueError("task %d has (vocabulary, embedding, hidden) = %s, task 0 has %s: one handle holds one "
+                                     "size" % (k, (lm.n_vocab, lm.n_emb, lm.n_hidden), (V, E, H)))
+                if lm.stop_token != stop or sorted(lm.function_token_list) != fun:
+                    raise ValueError("task %d has other stop / function tokens than task 0" % k)
+            n_task = len(lms)
+            host = [np.stack([lm.emb for lm in lms]),
+                    np.stack([lm.rnn_w.T for lm in lms]),      # [H + E][H]: the lanes of a wave own rows of W_h
+                    np.stack([lm.rnn_b for lm in lms]),
+                    np.stack([lm.dec_w.T for lm in lms]),      # [H][V]: and columns of the logits
+                    np.stack([lm.dec_b for lm in lms])]
+            dev = [torch.from_numpy(np.ascontiguousarray(a)).to(self.device) for a in host]
+            sizes = (V, E, H, stop, tuple(fun))
+        dev.append(torch.from_numpy(env_task_of(n_task, self.num_envs, env_task_index)).to(self.device))
+        V, E, H, stop, fun = sizes
         if self._h is not None and sizes != self._sizes:
             self._destroy()
         if self._h is None:
