@@ -31,13 +31,6 @@ def test_jacobi_diffuser_equals_the_fifo_walk_byte_for_byte():
             assert 1 <= passes <= nw * nl + 1 and margin > 0
 
 
-def test_np_sum_order_is_numpys():
-    rng = np.random.RandomState(5)
-    for n in (1, 7, 8, 25, 64, 127, 128, 129, 135, 225, 249, 255, 256):
-        a = rng.random_sample(n) * 10.0 ** rng.randint(-6, 3, n)
-        assert sh.np_sum_order(a) == float(np.sum(a)), n
-
-
 def test_tasks_are_accepted_by_build_tables_and_the_host_env():
     rows = U.host_rows("tiny")
     done = 0

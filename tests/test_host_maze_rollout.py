@@ -4,13 +4,10 @@ import ctypes as C
 import os
 import subprocess
 
-import numpy as np
 import pytest
 
-import oracle
 from xenoverse_amd import _lib
-from xenoverse_amd.mazeworld import explore_draws_host
-from xenoverse_amd.mazeworld.rollout import DRAW_EXPLORE, RECORD, TEACHER, _RolloutOut
+from xenoverse_amd.mazeworld.rollout import RECORD, TEACHER, _RolloutOut
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -78,31 +75,6 @@ def test_rollout_check_refuses_each_bad_argument():
     for kw in bad:
         assert _check(**kw) != 0, kw
         assert b"xv_maze_rollout_check" in _lib.load().xv_last_error()
-
-
-def test_explore_draws_host_is_the_oracles_philox():
-    """1,000 (env, tick) pairs, ticks beyond 2^32 and env ids beyond 2^32 among them"""
-    rng = np.random.RandomState(0)
-    seed, eps, na = 0x1234ABCD5678EF01, 0.3, 32
-    ticks = np.concatenate([rng.randint(0, 1 << 20, 400), rng.randint(0, 1 << 31, 300).astype(np.int64) << 9,
-                            (np.int64(1) << 40) + rng.randint(0, 1000, 300)]).astype(np.uint64)
-    gids = np.concatenate([rng.randint(0, 1 << 16, 700), (np.int64(1) << 33) + rng.randint(0, 1 << 16, 300)]).astype(np.uint64)
-    hits = 0
-    for gid, tick in zip(gids, ticks):
-        w = oracle.env_draw(int(seed), int(gid), int(tick), DRAW_EXPLORE)
-        ex, a = explore_draws_host(seed, int(gid), int(tick), 1, eps, na)
-        assert bool(ex[0]) == (oracle.u53(w[0], w[1]) < eps)
-        assert int(a[0]) == int(np.floor(oracle.u53(w[2], w[3]) * na))
-        hits += int(ex[0])
-    assert 200 < hits < 400
-    # a batch is the envs one by one, a tick per env is accepted, and the two ends of epsilon are all-or-nothing
-    ex, a = explore_draws_host(seed, 5, 77, 64, eps, na)
-    for e in (0, 17, 63):
-        e1, a1 = explore_draws_host(seed, 5 + e, 77, 1, eps, na)
-        assert ex[e] == e1[0] and a[e] == a1[0]
-    exv, av = explore_draws_host(seed, 5, np.full(64, 77), 64, eps, na)
-    assert np.array_equal(exv, ex) and np.array_equal(av, a) and a.dtype == np.int32 and 0 <= a.min() and a.max() < na
-    assert not explore_draws_host(seed, 0, 1, 256, 0.0, 16)[0].any() and explore_draws_host(seed, 0, 1, 256, 1.0, 16)[0].all()
 
 
 def test_rollout_struct_matches_the_header():

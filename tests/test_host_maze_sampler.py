@@ -7,6 +7,7 @@ import os
 import numpy as np
 import pytest
 
+from xenoverse_amd.host_draws import uniform
 from xenoverse_amd.mazeworld import MazeTaskSampler, build_tables
 from xenoverse_amd.mazeworld import sampler_host as sh
 from xenoverse_amd.mazeworld.textures import REFERENCE_TEXTURE_COUNTS
@@ -48,7 +49,7 @@ def population():
             for c in range(PER_CELL[n]):
                 task, info = sh.sample_candidate_host(11, 1000 * n + c, n_range=(n, n + 1), allow_loops=loops)
                 d = sh.Draws(11, 1000 * n + c)
-                wd = sh._uniform(d.pairs(sh.P_HEAD, 1)[1], sh.DEFAULTS["wall_density_range"])
+                wd = uniform(d.pairs(sh.P_HEAD, 1)[1], *sh.DEFAULTS["wall_density_range"])
                 out.append((n, loops, float(wd), task, info))
     assert len(out) >= 200
     return out

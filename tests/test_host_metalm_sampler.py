@@ -3,14 +3,12 @@ against the reference's own constructions, the collector over a fake launch, and
 generator up to the point where a GPU is needed."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 import metalm_sampler_util as U
-import oracle
 from xenoverse_amd import _lib
 from xenoverse_amd.device_sampling import collect_accepted
 from xenoverse_amd.metalang import (RandomLMHost, TaskSamplerV3, device_sampler as ds, generator_v3, sample_candidates,
@@ -48,30 +46,6 @@ def test_layer_norm_rows_is_numpys_for_every_row_length():
         assert np.array_equal(sh.layer_norm_rows(enc_w.T), RandomLMHost(enc_w, np.zeros((H, H + E)), np.zeros(H),
                                                                         np.zeros((V, H))).emb)
     assert rows == 64 * 24
-
-
-def test_philox_words_are_the_oracles_and_the_headers(tmp_path):
-    from xenoverse_amd import build as xb
-    cases = [(5, 7, 2, sh.XV_DRAW_METALM_TASK, 3), (2**64 - 1, 2**40 + 9, 2**33 + 1, sh.XV_DRAW_METALM, (4 << 16) | 511),
-             (0, 0, 0, sh.XV_DRAW_METALM_TASK, 16383), (123456789, 63, 4, sh.XV_DRAW_METALM, (3 << 16) | 0)]
-    got = [sh.env_draw_sub_words(*c[:4], [c[4]])[0] for c in cases]
-    for (seed, gid, tick, purpose, sub), w in zip(cases, got):      # the oracle's Philox under the documented counter layout
-        ctr = np.array([[gid & 0xFFFFFFFF, gid >> 32, tick & 0xFFFFFFFF, purpose | ((tick >> 32) << 8)]], np.uint32)
-        key = np.array([seed & 0xFFFFFFFF, (seed >> 32) ^ (0x80000000 | sub)], np.uint32)
-        assert np.array_equal(w, oracle.philox4x32_10(ctr, key)[0])
-    rs = np.random.RandomState(0)
-    ctr = rs.randint(0, 2**32, size=(6, 4), dtype=np.uint64).astype(np.uint32)
-    key = rs.randint(0, 2**32, size=2, dtype=np.uint64).astype(np.uint32)
-    assert np.array_equal(sh.philox4x32_10(ctr, key), oracle.philox4x32_10(ctr, key))
-    # csrc/philox.h's own host function, compiled for the host alone
-    lines = "".join('  w = xv_env_draw_sub(%dull, %dull, %dull, %du, %du); printf("%%u %%u %%u %%u\\n", w.x, w.y, w.z, w.w);\n' % c
-                    for c in cases)
-    src = tmp_path / "draws.cpp"
-    src.write_text('#include "philox.h"\n#include <cstdio>\nint main() {\n  xv_u32x4 w;\n%s  return 0;\n}\n' % lines)
-    exe = str(tmp_path / "draws")
-    subprocess.check_call([xb._hipcc(), "-x", "hip", "--offload-host-only", "-I", xb.CSRC, str(src), "-o", exe])
-    words = np.array(subprocess.check_output([exe]).split(), np.uint64).astype(np.uint32).reshape(len(cases), 4)
-    assert np.array_equal(words, np.stack(got))
 
 
 def test_normals_and_uniforms_are_counter_based():

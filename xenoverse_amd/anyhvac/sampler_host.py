@@ -8,8 +8,7 @@ utils/random_nn.py RandomFourier; task_sampler.py restates it for numpy's stream
 gives for that seed.
 
 Departures from the reference:
-  * integers are floor(u * m); `exponential` is -log(1 - u) * scale; a normal is the fp64 Box-Muller pair of
-    linds/sampler_host.py (radius sqrt(-2 log(1 - u_a)), angle 2 pi u_b: cos first, sin second);
+  * integers, `exponential` (times its scale) and normals are host_draws' floor_int, expo and box_muller;
   * a node's x coordinate stays the reference's integer, floor(u * int(dw)); y is dl * u;
   * placement compares squared distances, d2 < min_dist * min_dist; attempt a of node i of a kind draws from (the kind's
     purpose, tick = i, sub = a) and the lowest passing attempt wins; an attempt whose cell index x / cell_size, y / cell_size
@@ -44,13 +43,12 @@ normal (cos half), + 2 the coefficients' normals (a: cos, b: sin), + 3 the coeff
 """
 import numpy as np
 
-from ..mazeworld.sampler_host import Draws
+from ..host_draws import Draws, box_muller, expo, floor_int, uniform
 from .config import DEFAULTS, MAX_COOLERS, MAX_GRID, MAX_HEATERS, MAX_SENSORS
 from .host import HEAT_AVG_INTERVAL, HEAT_AVG_MAX_TIME, check_settings
 from .tables import _COOLER_COLUMNS, _nodes, task_doubles
 from .task_sampler import COOLER_PARAMS
 
-TWO_PI = 6.283185307179586
 STATUS = ("accepted", "placement_cap", "unify_empty", "too_big")
 PLACE_TRIES = 4096
 BIAS_TRIES, BIAS_SUB = 256, 16
@@ -116,46 +114,6 @@ def sampler_arguments(control_type='Temperature', target_temperature=None, confi
         raise ValueError("set_upper_bound must exceed set_lower_bound")
     return dict(K=K, dims=table_dims(config), target=None if target_temperature is None else float(target_temperature),
                 lower=set_lower_bound, upper=set_upper_bound, generate_task=bool(generate_task))
-
-
-def _uniform(u, lo, hi):
-    return float(lo) + (float(hi) - float(lo)) * u
-
-
-def _floor_int(u, m):
-    return int(np.floor(u * float(m)))
-
-
-def _normal_pair(ua, ub):
-    r = np.sqrt(-2.0 * np.log(1.0 - ua))
-    ang = TWO_PI * ub
-    return r * np.cos(ang), r * np.sin(ang)
-
-
-def np_sum_order(a):
-    """numpy's pairwise sum of a flat array, spelled out (csrc/anymdp_vi_host.hip np_sum): what the device adds"""
-    a = np.asarray(a, np.float64).reshape(-1)
-    n = len(a)
-    if n < 8:
-        res = 0.0
-        for v in a:
-            res = res + float(v)
-        return res
-    if n <= 128:
-        r = [float(v) for v in a[:8]]
-        i = 8
-        while i < n - (n % 8):
-            for q in range(8):
-                r[q] = r[q] + float(a[i + q])
-            i += 8
-        res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]))
-        while i < n:
-            res = res + float(a[i])
-            i += 1
-        return res
-    half = n // 2
-    half -= half % 8
-    return np_sum_order(a[:half]) + np_sum_order(a[half:])
 
 
 # ---- wind_diffuser as a fixed point ----------------------------------------------------------------------------------
@@ -249,24 +207,24 @@ def place_host(d, purpose, n, dw, dl, cell_size, nw, nl, min_dist, block=32):
 def fourier_host(d, purpose, tick, sub, max_order, max_item, box, width):
     """RandomFourier(ndim=1) -> (n_terms, order[width], coef[width, 2]), padded with zeros"""
     ua, ub = d.pairs(purpose, sub + np.arange(1 + 4 * (max_item + 1)), tick=tick)
-    n_items = 1 + _floor_int(ua[0], max_item)
+    n_items = 1 + int(floor_int(ua[0], max_item))
     scale = box / np.sqrt(float(n_items))
     order, coef = np.zeros(width), np.zeros((width, 2))
     for t in range(n_items + 1):
         b = 1 + 4 * t
         if t:
-            order[t] = (1 + _floor_int(ua[b], max_order)) + _normal_pair(ua[b + 1], ub[b + 1])[0]
-        za, zb = _normal_pair(ua[b + 2], ub[b + 2])
-        coef[t] = za * (-np.log(1.0 - ua[b + 3]) * scale), zb * (-np.log(1.0 - ub[b + 3]) * scale)
+            order[t] = (1 + int(floor_int(ua[b], max_order))) + box_muller(ua[b + 1], ub[b + 1])[0]
+        za, zb = box_muller(ua[b + 2], ub[b + 2])
+        coef[t] = za * (expo(ua[b + 3]) * scale), zb * (expo(ub[b + 3]) * scale)
     return n_items + 1, order, coef
 
 
 def heat_curve_host(d, purpose, tick, K, width):
     (up, uh), (us, _) = d.pairs(purpose, [0, 1], tick=tick)
     lo, hi = int(K["HEAT_SOURCE_PERIOD_RANGE_LOW"]) * 60, int(K["HEAT_SOURCE_PERIOD_RANGE_HIGH"]) * 60
-    period = (lo + _floor_int(up, hi - lo)) * 60
-    scale = _uniform(us, K["HEAT_SOURCE_VARIANT_SCALE_LOW"], K["HEAT_SOURCE_VARIANT_SCALE_HIGH"])
-    heat_base = _uniform(uh, K["BASE_HEAT_SOURCE_PERIOD_RANGE_LOW"], K["BASE_HEAT_SOURCE_PERIOD_RANGE_HIGH"])
+    period = (lo + int(floor_int(up, hi - lo))) * 60
+    scale = uniform(us, K["HEAT_SOURCE_VARIANT_SCALE_LOW"], K["HEAT_SOURCE_VARIANT_SCALE_HIGH"])
+    heat_base = uniform(uh, K["BASE_HEAT_SOURCE_PERIOD_RANGE_LOW"], K["BASE_HEAT_SOURCE_PERIOD_RANGE_HIGH"])
     n, order, coef = fourier_host(d, purpose, tick, 2, int(K["HEAT_SOURCE_FOURIER_MAX_ORDER"]),
                                   int(K["HEAT_SOURCE_FOURIER_MAX_ITEM"]), scale, width)
     return float(period), heat_base, n, order, coef
@@ -306,18 +264,18 @@ def sample_candidate_host(seed, cand, control_type='Temperature', target_tempera
     NW, NL, Cd, Sd, Hd, KS, KH = dims
     d = Draws(seed, cand)
     ua, ub = d.pairs(P_HEAD, np.arange(8))
-    nw = int(K["ROOM_W_GRID_SIZE_LOW"]) + _floor_int(ua[0], int(K["ROOM_W_GRID_SIZE_HIGH"]) - int(K["ROOM_W_GRID_SIZE_LOW"]))
-    nl = int(K["ROOM_L_GRID_SIZE_LOW"]) + _floor_int(ub[0], int(K["ROOM_L_GRID_SIZE_HIGH"]) - int(K["ROOM_L_GRID_SIZE_LOW"]))
-    cell_size = _uniform(ua[1], K["CELL_SIZE_LOW"], K["CELL_SIZE_HIGH"])
-    floor_height = _uniform(ub[1], K["FLOOR_HEIGHT_LOW"], K["FLOOR_HEIGHT_HIGH"])
+    nw = int(K["ROOM_W_GRID_SIZE_LOW"]) + int(floor_int(ua[0], int(K["ROOM_W_GRID_SIZE_HIGH"]) - int(K["ROOM_W_GRID_SIZE_LOW"])))
+    nl = int(K["ROOM_L_GRID_SIZE_LOW"]) + int(floor_int(ub[0], int(K["ROOM_L_GRID_SIZE_HIGH"]) - int(K["ROOM_L_GRID_SIZE_LOW"])))
+    cell_size = uniform(ua[1], K["CELL_SIZE_LOW"], K["CELL_SIZE_HIGH"])
+    floor_height = uniform(ub[1], K["FLOOR_HEIGHT_LOW"], K["FLOOR_HEIGHT_HIGH"])
     dw, dl = nw * cell_size, nl * cell_size
     area = dw * dl
     cell_volume = floor_height * cell_size * cell_size
-    wall_chtc = _uniform(ua[2], K["WALL_CHTC_LOW"], K["WALL_CHTC_HIGH"])
-    floorceil_chtc = _uniform(ub[2], K["FLOOR_CHTC_LOW"], K["FLOOR_CHTC_HIGH"])
-    n_sensors = max(int(min(area * _uniform(ua[3], K["SENSOR_DENSITY_LOW"], K["SENSOR_DENSITY_HIGH"]), COUNT_CAP)), 1)
-    n_heaters = max(int(min(area * _uniform(ub[3], K["HEATER_DENSITY_LOW"], K["HEATER_DENSITY_HIGH"]), COUNT_CAP)), 1)
-    n_coolers = max(int(min(area * _uniform(ua[4], K["COOLER_DENSITY_LOW"], K["COOLER_DENSITY_HIGH"]), COUNT_CAP)), 1)
+    wall_chtc = uniform(ua[2], K["WALL_CHTC_LOW"], K["WALL_CHTC_HIGH"])
+    floorceil_chtc = uniform(ub[2], K["FLOOR_CHTC_LOW"], K["FLOOR_CHTC_HIGH"])
+    n_sensors = max(int(min(area * uniform(ua[3], K["SENSOR_DENSITY_LOW"], K["SENSOR_DENSITY_HIGH"]), COUNT_CAP)), 1)
+    n_heaters = max(int(min(area * uniform(ub[3], K["HEATER_DENSITY_LOW"], K["HEATER_DENSITY_HIGH"]), COUNT_CAP)), 1)
+    n_coolers = max(int(min(area * uniform(ua[4], K["COOLER_DENSITY_LOW"], K["COOLER_DENSITY_HIGH"]), COUNT_CAP)), 1)
     wsum = 0.0
     for _, w in K["AMBIENT_TEMPERATURE_HIGH"]:
         wsum = wsum + float(w)
@@ -325,14 +283,14 @@ def sample_candidate_host(seed, cand, control_type='Temperature', target_tempera
     buckets = list(K["AMBIENT_TEMPERATURE_HIGH"])
     for q, (pt, w) in enumerate(buckets):
         if eps < float(w) or q == len(buckets) - 1:
-            t_ambient = _uniform(ua[5], t_b, pt)
+            t_ambient = uniform(ua[5], t_b, pt)
             break
         eps -= float(w)
         t_b = float(pt)
     target = A["target"]
     if target is None:
-        target = float(np.rint(_uniform(ub[5], K["TARGET_TEMPERATURE_LOW"], K["TARGET_TEMPERATURE_HIGH"]) * 2.0) / 2.0)
-    drift_std = _uniform(ua[6], 1.0, 2.0)
+        target = float(np.rint(uniform(ub[5], K["TARGET_TEMPERATURE_LOW"], K["TARGET_TEMPERATURE_HIGH"]) * 2.0) / 2.0)
+    drift_std = uniform(ua[6], 1.0, 2.0)
     sample_ratio = float(ub[6])
 
     info = np.zeros((), INFO_DTYPE)
@@ -355,8 +313,8 @@ def sample_candidate_host(seed, cand, control_type='Temperature', target_tempera
 
     # convection_coeffs / heat_capacity
     nwall = (nw + 1) * (nl + 1) * 2
-    chtc = _uniform(d.block(P_CHTC, nwall), K["INTERNAL_CHTC_LOW"], K["INTERNAL_CHTC_HIGH"]).reshape(nw + 1, nl + 1, 2)
-    hc = _uniform(d.block(P_HC, nw * nl), K["GRID_HC_LOW"], K["GRID_HC_HIGH"]).reshape(nw, nl) * cell_volume
+    chtc = uniform(d.block(P_CHTC, nwall), K["INTERNAL_CHTC_LOW"], K["INTERNAL_CHTC_HIGH"]).reshape(nw + 1, nl + 1, 2)
+    hc = uniform(d.block(P_HC, nw * nl), K["GRID_HC_LOW"], K["GRID_HC_HIGH"]).reshape(nw, nl) * cell_volume
     chtc[0, :, 0] = wall_chtc
     chtc[nw, :, 0] = wall_chtc
     chtc[:, 0, 1] = wall_chtc
@@ -383,8 +341,8 @@ def sample_candidate_host(seed, cand, control_type='Temperature', target_tempera
     lo, hi = int(K["SENSOR_DRIFT_PERIOD_LOW"]) * 60, int(K["SENSOR_DRIFT_PERIOD_HIGH"]) * 60
     for i in range(n_sensors):
         (up, ue), = zip(*d.pairs(P_SENSOR, [0], tick=i))
-        t["sensor_period"][i] = lo + _floor_int(up, hi - lo)
-        box = min(-np.log(1.0 - ue) * float(K["SENSOR_DRIFT_MEAN"]), float(K["SENSOR_DRIFT_UPPER_BOUND"]))
+        t["sensor_period"][i] = lo + floor_int(up, hi - lo)
+        box = min(expo(ue) * float(K["SENSOR_DRIFT_MEAN"]), float(K["SENSOR_DRIFT_UPPER_BOUND"]))
         t["sensor_n_terms"][i], t["sensor_order"][i], t["sensor_coef"][i] = fourier_host(
             d, P_SENSOR, i, 1, int(K["SENSOR_DRIFT_FOURIER_MAX_ORDER"]), int(K["SENSOR_DRIFT_FOURIER_MAX_ITEMS"]), box, KS)
     # heat curves
@@ -401,13 +359,13 @@ def sample_candidate_host(seed, cand, control_type='Temperature', target_tempera
         (t["heater_period"][i], t["heater_heat_base"][i], t["heater_n_terms"][i], t["heater_order"][i],
          t["heater_coef"][i]) = heat_curve_host(d, P_HEATER, i, K, KH)
         (us, uf), (ue, _) = zip(*d.pairs(P_HEATER, [HEATER_EXTRA_SUB, HEATER_EXTRA_SUB + 1], tick=i))
-        sigma = _uniform(us, K["HEAT_SPACE_INSTANT_DIFFSION_LOW"], K["HEAT_SPACE_INSTANT_DIFFUSION_HIGH"])
+        sigma = uniform(us, K["HEAT_SPACE_INSTANT_DIFFSION_LOW"], K["HEAT_SPACE_INSTANT_DIFFUSION_HIGH"])
         t["heater_diffuse_sigma"][i] = sigma
-        t["heater_base_factor"][i] = _uniform(uf, K["HEAT_SOURCE_BASE_FACTOR_LOW"], K["HEAT_SOURCE_BASE_FACTOR_HIGH"])
+        t["heater_base_factor"][i] = uniform(uf, K["HEAT_SOURCE_BASE_FACTOR_LOW"], K["HEAT_SOURCE_BASE_FACTOR_HIGH"])
         t["heat_diffuse"][i], _, p, m = wind_diffuser_host(cell_walls, locs["heater"][i], cell_size, sigma, True)
         passes, dmargin = max(passes, p), min(dmargin, m)
         nloc = (locs["heater"][i] / cell_size).astype(int)
-        hc[nloc[0], nloc[1]] += _uniform(ue, K["EQUIPMENT_HC_LOW"], K["EQUIPMENT_HC_HIGH"])
+        hc[nloc[0], nloc[1]] += uniform(ue, K["EQUIPMENT_HC_LOW"], K["EQUIPMENT_HC_HIGH"])
     t["heater_timer"] = t["heater_period"].astype(np.int64)
     # coolers
     c = {k: np.zeros(n_coolers) for k in COOLER_PARAMS}
@@ -415,27 +373,27 @@ def sample_candidate_host(seed, cand, control_type='Temperature', target_tempera
     bmargin, bias_max = np.inf, 0
     for i in range(n_coolers):
         ua, ub = d.pairs(P_COOLER, np.arange(7), tick=i)
-        c["power_eff_vent"][i] = _uniform(ua[0], K["COOLER_VENT_EFFICIENCY_LOW"], K["COOLER_VENT_EFFICIENCY_HIGH"])
-        c["cooler_eer_base"][i] = _uniform(ub[0], K["COOLER_EER_BASE_LOW"], K["COOLER_EER_BASE_HIGH"])
-        c["cooler_eer_decay_start"][i] = _uniform(ua[1], K["COOLER_EER_DECAY_START_HIGH"], K["COOLER_EER_DECAY_START_HIGH"])
-        c["cooler_eer_zero_point"][i] = _uniform(ub[1], K["COOLER_EER_ZERO_POINT_LOW"], K["COOLER_EER_ZERO_POINT_HIGH"])
-        c["cooler_eer_reverse"][i] = _uniform(ua[2], K["COOLER_EER_REVERSE_LOW"], K["COOLER_EER_REVERSE_HIGH"])
-        c["cooler_diffuse_sigma"][i] = _uniform(ub[2], K["COOLER_SPACE_INSTANT_DIFFUSION_LOW"],
+        c["power_eff_vent"][i] = uniform(ua[0], K["COOLER_VENT_EFFICIENCY_LOW"], K["COOLER_VENT_EFFICIENCY_HIGH"])
+        c["cooler_eer_base"][i] = uniform(ub[0], K["COOLER_EER_BASE_LOW"], K["COOLER_EER_BASE_HIGH"])
+        c["cooler_eer_decay_start"][i] = uniform(ua[1], K["COOLER_EER_DECAY_START_HIGH"], K["COOLER_EER_DECAY_START_HIGH"])
+        c["cooler_eer_zero_point"][i] = uniform(ub[1], K["COOLER_EER_ZERO_POINT_LOW"], K["COOLER_EER_ZERO_POINT_HIGH"])
+        c["cooler_eer_reverse"][i] = uniform(ua[2], K["COOLER_EER_REVERSE_LOW"], K["COOLER_EER_REVERSE_HIGH"])
+        c["cooler_diffuse_sigma"][i] = uniform(ub[2], K["COOLER_SPACE_INSTANT_DIFFUSION_LOW"],
                                                 K["COOLER_SPACE_INSTANT_DIFFUSION_HIGH"])
-        c["temp_diff_decay_ub"][i] = _uniform(ua[3], K["COOLER_DIFF_DECAY_UB_LOW"], K["COOLER_DIFF_DECAY_UB_HIGH"])
-        c["temp_diff_decay_lb"][i] = _uniform(ub[3], K["COOLER_DIFF_DECAY_LB_LOW"], K["COOLER_DIFF_DECAY_LB_HIGH"])
-        c["max_cooling_power"][i] = _uniform(ua[4], K["COOLER_MAX_COOLING_POWER_LOW"], K["COOLER_MAX_COOLING_POWER_HIGH"])
-        c["power_vent_min"][i] = _uniform(ub[4], K["COOLER_POWER_VENT_MIN_LOW"], K["COOLER_POWER_VENT_MIN_HIGH"])
+        c["temp_diff_decay_ub"][i] = uniform(ua[3], K["COOLER_DIFF_DECAY_UB_LOW"], K["COOLER_DIFF_DECAY_UB_HIGH"])
+        c["temp_diff_decay_lb"][i] = uniform(ub[3], K["COOLER_DIFF_DECAY_LB_LOW"], K["COOLER_DIFF_DECAY_LB_HIGH"])
+        c["max_cooling_power"][i] = uniform(ua[4], K["COOLER_MAX_COOLING_POWER_LOW"], K["COOLER_MAX_COOLING_POWER_HIGH"])
+        c["power_vent_min"][i] = uniform(ub[4], K["COOLER_POWER_VENT_MIN_LOW"], K["COOLER_POWER_VENT_MIN_HIGH"])
         c["min_cooling_power"][i] = c["power_vent_min"][i]
         if ua[5] < float(K["COOLER_VENT_FIXED_RATIO_FACTOR"]):
-            c["power_vent_ratio"][i] = _uniform(ub[5], K["COOLER_VENT_FIXED_RATIO_LOW"], K["COOLER_VENT_FIXED_RATIO_HIGH"])
+            c["power_vent_ratio"][i] = uniform(ub[5], K["COOLER_VENT_FIXED_RATIO_LOW"], K["COOLER_VENT_FIXED_RATIO_HIGH"])
         else:
             c["power_vent_ratio"][i] = 0.0
-            c["power_vent_min"][i] = _uniform(ub[5], K["COOLER_VENT_FIXED_POWER_LOW"], K["COOLER_VENT_FIXED_POWER_HIGH"])
+            c["power_vent_min"][i] = uniform(ub[5], K["COOLER_VENT_FIXED_POWER_LOW"], K["COOLER_VENT_FIXED_POWER_HIGH"])
         sample = 0.0
         for base in range(0, BIAS_TRIES, 16):
             za, zb = d.pairs(P_COOLER, BIAS_SUB + np.arange(base, base + 16), tick=i)
-            s = float(K["COOLER_SENSOR_BIAS_MEAN"]) + drift_std * _normal_pair(za, zb)[0]
+            s = float(K["COOLER_SENSOR_BIAS_MEAN"]) + drift_std * box_muller(za, zb)[0]
             ok = (-bound <= s) & (s <= bound)
             n_eval = int(np.argmax(ok)) + 1 if ok.any() else 16
             bmargin = min(bmargin, float(np.min(np.abs(np.abs(s[:n_eval]) - bound) / bound)))
@@ -444,14 +402,14 @@ def sample_candidate_host(seed, cand, control_type='Temperature', target_tempera
                 bias_max = max(bias_max, base + n_eval)
                 break
         c["base_bias"][i] = abs(sample) if ua[6] < float(K["COOLER_SENSOR_SIGN_POSITIVE_PROB"]) else -abs(sample)
-        c["delay_seconds"][i] = _uniform(ub[6], K["COOLER_SENSOR_DELAY_LOW"], K["COOLER_SENSOR_DELAY_HIGH"])
+        c["delay_seconds"][i] = uniform(ub[6], K["COOLER_SENSOR_DELAY_LOW"], K["COOLER_SENSOR_DELAY_HIGH"])
     # unification
     unified, coefficient = np.zeros(n_coolers, bool), 0.0
     if sample_ratio < 0.4:
         unified[:] = True
         coefficient = 1
     elif sample_ratio < 0.8:
-        n_to_unify = max(1, int((n_coolers - 1) * _uniform(float(d.pairs(P_HEAD, [7])[0][0]), 0.7, 1.0)))
+        n_to_unify = max(1, int((n_coolers - 1) * uniform(float(d.pairs(P_HEAD, [7])[0][0]), 0.7, 1.0)))
         q = np.arange(n_coolers)
         ka, kb = d.ints53(P_UNIFY, q >> 1)
         keys = np.where(q & 1, kb, ka)

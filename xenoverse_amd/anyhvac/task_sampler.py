@@ -27,6 +27,7 @@ import random
 import numpy as np
 from numpy import random as rnd
 
+from ..random_nn import RandomFourier
 from .config import DEFAULTS
 
 COOLER_PARAMS = ("power_eff_vent", "cooler_eer_base", "cooler_eer_decay_start", "cooler_eer_zero_point",
@@ -90,13 +91,8 @@ def _place(dw, dl, others, min_dist):
 
 
 def _fourier(max_order, max_item, box_size):
-    """RandomFourier(ndim=1): [(order, (a, b))], the first term of order 0"""
-    n_items = rnd.randint(1, max_item + 1)
-    terms = [(0, rnd.normal(size=(1, 2)) * rnd.exponential(scale=box_size / np.sqrt(n_items), size=(1, 2)))]
-    for _ in range(n_items):
-        order = rnd.randint(1, max_order + 1) + rnd.normal(scale=1.0)
-        terms.append((order, rnd.normal(size=(1, 2)) * rnd.exponential(scale=box_size / np.sqrt(n_items), size=(1, 2))))
-    return terms
+    """RandomFourier(ndim=1) over numpy's global stream: [(order, (a, b))], the first term of order 0"""
+    return RandomFourier(ndim=1, max_order=max_order, max_item=max_item, box_size=box_size).coeffs
 
 
 def _heat_curve(K):

@@ -24,6 +24,8 @@ same generative model with counter-based randomness on the GPU (not stream-compa
 import numpy as np
 import scipy.sparse as sp
 
+from ..random_nn import RandomFourier
+
 EPS = 1e-10
 
 
@@ -232,12 +234,8 @@ class _ReferenceStream(object):
         else:
             base = np.clip(rng.exponential(1.0), 0.20, 5.0)      # exponential
         box = max(rng.uniform(-base, base), 0.0)                 # uniform
-        # RandomFourier(ndim=1, max_order=5, max_item=3, max_steps=2 ns, box_size=box), utils/random_nn.py:346-359
-        n_items = rng.randint(1, 3 + 1)                          # randint
-        terms = [(0, rng.normal(size=(1, 2)) * rng.exponential(scale=box / np.sqrt(n_items), size=(1, 2)))]
-        for _ in range(n_items):                                 # per term: randint + normal, normal(1,2), exponential(1,2)
-            order = rng.randint(1, 5 + 1) + rng.normal(scale=1.0)
-            terms.append((order, rng.normal(size=(1, 2)) * rng.exponential(scale=box / np.sqrt(n_items), size=(1, 2))))
+        # utils/random_nn.py:346-359 draws: randint; per term randint + normal, normal(1,2), exponential(1,2)
+        terms = RandomFourier(ndim=1, max_order=5, max_item=3, max_steps=2 * ns, box_size=box, rng=rng).coeffs
         pot = []
         for s in range(ns):
             x = s / (ns * 2)

@@ -16,8 +16,8 @@
 // No cross-lane result depends on how work is dealt to lanes, and a candidate does not know its launch.
 #include <climits>
 
-#include "philox.h"
 #include "xv_common.h"
+#include "xv_draws.h"
 
 namespace {
 
@@ -28,7 +28,7 @@ constexpr int HS_WALLS = (HS_MAX_GRID + 1) * (HS_MAX_GRID + 1) * 2;
 constexpr int HS_PLACE_TRIES = 4096, HS_BIAS_TRIES = 256, HS_BIAS_SUB = 16, HS_HEATER_SUB = 128;
 constexpr int HS_HEAT_TIMES = 20160, HS_HEAT_INTERVAL = 30;
 constexpr double HS_COUNT_CAP = 1.0e6;
-constexpr double HS_TWO_PI = 6.283185307179586, HS_CUT = 1.0e-3, HS_MAX_POWER = 20000.0;
+constexpr double HS_CUT = 1.0e-3, HS_MAX_POWER = 20000.0;
 constexpr unsigned long long HS_INF_BITS = 0x7FF0000000000000ull;
 
 enum : uint32_t { HS_P_HEAD = 0, HS_P_CHTC = 1, HS_P_HC = 2, HS_P_SENSOR_LOC = 3, HS_P_HEATER_LOC = 4, HS_P_COOLER_LOC = 5,
@@ -60,34 +60,18 @@ struct HsArgs {
   int32_t* status;
 };
 
-struct HsU2 {
-  double a, b;
-};
 struct HsRng {
   uint64_t seed, index;
 };
-// counter = {candidate lo, candidate hi, sub, purpose | tick << 8}, key = seed
-__device__ __forceinline__ xv_u32x4 hs_draw(const HsRng& g, uint32_t purpose, uint32_t tick, uint32_t sub) {
-  return xv_philox4x32_10((uint32_t)g.index, (uint32_t)(g.index >> 32), sub, (purpose & 0xFFu) | (tick << 8),
-                          (uint32_t)g.seed, (uint32_t)(g.seed >> 32));
-}
-__device__ __forceinline__ HsU2 hs_pair(const HsRng& g, uint32_t purpose, uint32_t tick, uint32_t sub) {
-  const xv_u32x4 w = hs_draw(g, purpose, tick, sub);
-  return HsU2{xv_u53(w.x, w.y), xv_u53(w.z, w.w)};
+__device__ __forceinline__ xv_u2 hs_pair(const HsRng& g, uint32_t purpose, uint32_t tick, uint32_t sub) {
+  return xv_pair(xv_index_draw(g.seed, g.index, tick, purpose, sub));
 }
 // element q of a block of uniforms: half q & 1 of call q >> 1
 __device__ __forceinline__ double hs_block(const HsRng& g, uint32_t purpose, uint32_t q) {
-  const HsU2 u = hs_pair(g, purpose, 0, q >> 1);
+  const xv_u2 u = hs_pair(g, purpose, 0, q >> 1);
   return (q & 1u) ? u.b : u.a;
 }
 __device__ __forceinline__ double hs_uni(double u, const double r[2]) { return r[0] + (r[1] - r[0]) * u; }
-__device__ __forceinline__ int hs_floor_int(double u, int m) { return (int)floor(u * (double)m); }
-__device__ __forceinline__ void hs_normal(const HsU2& u, double* zc, double* zs) {
-  const double r = sqrt(-2.0 * log(1.0 - u.a));
-  const double ang = HS_TWO_PI * u.b;
-  *zc = r * cos(ang);
-  *zs = r * sin(ang);
-}
 // the reference's order of directions: (-1, 0), (0, -1), (1, 0), (0, 1)
 __device__ __forceinline__ int hs_di(int d) { return d == 0 ? -1 : (d == 2 ? 1 : 0); }
 __device__ __forceinline__ int hs_dj(int d) { return d == 1 ? -1 : (d == 3 ? 1 : 0); }
@@ -141,21 +125,21 @@ __device__ void hs_fill_padding(double* row, double* ex, const HsOff& o) {
 // RandomFourier(ndim=1) from sub0: order / a / b rows (term 0 has order 0) -> the number of terms (<= max_item + 1)
 __device__ int hs_fourier(const HsRng& g, uint32_t purpose, uint32_t tick, uint32_t sub0, int max_order, int max_item,
                           double box, double* order, double* ca, double* cb) {
-  const int n_items = 1 + hs_floor_int(hs_pair(g, purpose, tick, sub0).a, max_item);
+  const int n_items = 1 + xv_floor_int(hs_pair(g, purpose, tick, sub0).a, max_item);
   const double scale = box / sqrt((double)n_items);
   for (int t = 0; t <= n_items; ++t) {
     const uint32_t b = sub0 + 1 + 4 * (uint32_t)t;
     double o = 0.0, zc, zs;
     if (t) {
-      const int oi = 1 + hs_floor_int(hs_pair(g, purpose, tick, b).a, max_order);
-      hs_normal(hs_pair(g, purpose, tick, b + 1), &zc, &zs);
+      const int oi = 1 + xv_floor_int(hs_pair(g, purpose, tick, b).a, max_order);
+      xv_normal2(hs_pair(g, purpose, tick, b + 1), &zc, &zs);
       o = (double)oi + zc;
     }
-    hs_normal(hs_pair(g, purpose, tick, b + 2), &zc, &zs);
-    const HsU2 e = hs_pair(g, purpose, tick, b + 3);
+    xv_normal2(hs_pair(g, purpose, tick, b + 2), &zc, &zs);
+    const xv_u2 e = hs_pair(g, purpose, tick, b + 3);
     order[t] = o;
-    ca[t] = zc * (-log(1.0 - e.a) * scale);
-    cb[t] = zs * (-log(1.0 - e.b) * scale);
+    ca[t] = zc * (xv_expo(e.a) * scale);
+    cb[t] = zs * (xv_expo(e.b) * scale);
   }
   return n_items + 1;
 }
@@ -163,9 +147,9 @@ __device__ int hs_fourier(const HsRng& g, uint32_t purpose, uint32_t tick, uint3
 // a heat curve: (period, heat_base, n_terms) and its series
 __device__ int hs_heat_curve(const HsRng& g, const xv_anyhvac_sampler_params& p, uint32_t purpose, uint32_t tick,
                              double* period, double* heat_base, double* order, double* ca, double* cb) {
-  const HsU2 u0 = hs_pair(g, purpose, tick, 0), u1 = hs_pair(g, purpose, tick, 1);
+  const xv_u2 u0 = hs_pair(g, purpose, tick, 0), u1 = hs_pair(g, purpose, tick, 1);
   const int lo = p.heat_period_lo * 60, hi = p.heat_period_hi * 60;
-  *period = (double)((lo + hs_floor_int(u0.a, hi - lo)) * 60);
+  *period = (double)((lo + xv_floor_int(u0.a, hi - lo)) * 60);
   const double scale = hs_uni(u0.b, p.range[XV_ANYHVAC_R_HEAT_SCALE]);
   *heat_base = hs_uni(u1.a, p.range[XV_ANYHVAC_R_HEAT_BASE]);
   return hs_fourier(g, purpose, tick, 2, p.heat_max_order, p.heat_max_item, scale, order, ca, cb);
@@ -201,7 +185,7 @@ __device__ bool hs_place(HsLds& L, const HsRng& g, uint32_t purpose, int n, doub
       if (tid == 0) L.win = INT_MAX;
       __syncthreads();
       const int a = r * HS_T + tid;
-      const HsU2 u = hs_pair(g, purpose, (uint32_t)i, (uint32_t)a);
+      const xv_u2 u = hs_pair(g, purpose, (uint32_t)i, (uint32_t)a);
       const double x = floor(u.a * idw), y = dl * u.b;
       bool ok = (x / cs < (double)nw) && (y / cs < (double)nl);      // the node's cell exists
       for (int j = 0; ok && j < i; ++j) {
@@ -286,10 +270,10 @@ __global__ __launch_bounds__(HS_T) void anyhvac_sampler_kernel(HsArgs P) {
   __syncthreads();      // the padding is down before any lane writes a value over it
 
   // ---- 1. head scalars ----
-  const HsU2 h0 = hs_pair(g, HS_P_HEAD, 0, 0), h1 = hs_pair(g, HS_P_HEAD, 0, 1), h2 = hs_pair(g, HS_P_HEAD, 0, 2),
-             h3 = hs_pair(g, HS_P_HEAD, 0, 3), h4 = hs_pair(g, HS_P_HEAD, 0, 4), h5 = hs_pair(g, HS_P_HEAD, 0, 5),
-             h6 = hs_pair(g, HS_P_HEAD, 0, 6), h7 = hs_pair(g, HS_P_HEAD, 0, 7);
-  const int nw = p.nw_lo + hs_floor_int(h0.a, p.nw_hi - p.nw_lo), nl = p.nl_lo + hs_floor_int(h0.b, p.nl_hi - p.nl_lo);
+  const xv_u2 h0 = hs_pair(g, HS_P_HEAD, 0, 0), h1 = hs_pair(g, HS_P_HEAD, 0, 1), h2 = hs_pair(g, HS_P_HEAD, 0, 2),
+              h3 = hs_pair(g, HS_P_HEAD, 0, 3), h4 = hs_pair(g, HS_P_HEAD, 0, 4), h5 = hs_pair(g, HS_P_HEAD, 0, 5),
+              h6 = hs_pair(g, HS_P_HEAD, 0, 6), h7 = hs_pair(g, HS_P_HEAD, 0, 7);
+  const int nw = p.nw_lo + xv_floor_int(h0.a, p.nw_hi - p.nw_lo), nl = p.nl_lo + xv_floor_int(h0.b, p.nl_hi - p.nl_lo);
   const double cs = hs_uni(h1.a, p.range[XV_ANYHVAC_R_CELL_SIZE]);
   const double floor_height = hs_uni(h1.b, p.range[XV_ANYHVAC_R_FLOOR_HEIGHT]);
   const double dw = (double)nw * cs, dl = (double)nl * cs;
@@ -384,10 +368,10 @@ __global__ __launch_bounds__(HS_T) void anyhvac_sampler_kernel(HsArgs P) {
   // ---- 4. Fourier rows: sensors, the base heater, heaters; equipment heat capacity in heater order ----
   for (int i = tid; i < nS; i += HS_T) {
     double* r = row + o.sens + (size_t)i * o.sens_row;
-    const HsU2 u = hs_pair(g, HS_P_SENSOR, (uint32_t)i, 0);
+    const xv_u2 u = hs_pair(g, HS_P_SENSOR, (uint32_t)i, 0);
     const int lo = p.sensor_period_lo * 60, hi = p.sensor_period_hi * 60;
-    r[6] = (double)(lo + hs_floor_int(u.a, hi - lo));
-    const double box = fmin(-log(1.0 - u.b) * p.sensor_drift_mean, p.sensor_drift_ub);
+    r[6] = (double)(lo + xv_floor_int(u.a, hi - lo));
+    const double box = fmin(xv_expo(u.b) * p.sensor_drift_mean, p.sensor_drift_ub);
     r[7] = (double)hs_fourier(g, HS_P_SENSOR, (uint32_t)i, 1, p.sensor_max_order, p.sensor_max_items, box, r + 8, r + 8 + KS,
                               r + 8 + 2 * KS);
   }
@@ -402,7 +386,7 @@ __global__ __launch_bounds__(HS_T) void anyhvac_sampler_kernel(HsArgs P) {
     double* r = row + o.heat + (size_t)i * o.heat_row;
     double period, heat_base;
     const int n = hs_heat_curve(g, p, HS_P_HEATER, (uint32_t)i, &period, &heat_base, r + 4, r + 4 + KH, r + 4 + 2 * KH);
-    const HsU2 u = hs_pair(g, HS_P_HEATER, (uint32_t)i, HS_HEATER_SUB);
+    const xv_u2 u = hs_pair(g, HS_P_HEATER, (uint32_t)i, HS_HEATER_SUB);
     ex[o.e_hsig + i] = hs_uni(u.a, p.range[XV_ANYHVAC_R_HEAT_SIGMA]);
     r[0] = hs_uni(u.b, p.range[XV_ANYHVAC_R_BASE_FACTOR]);
     r[1] = heat_base;
@@ -427,9 +411,8 @@ __global__ __launch_bounds__(HS_T) void anyhvac_sampler_kernel(HsArgs P) {
   }
   n_unified = mode == 1 ? nC : n_to_unify;
   for (int q = tid; q < nC; q += HS_T) {
-    const xv_u32x4 w = hs_draw(g, HS_P_UNIFY, 0, (uint32_t)q >> 1);
-    L.key[q] = (q & 1) ? (((unsigned long long)(w.z >> 5) << 26) | (unsigned long long)(w.w >> 6))
-                       : (((unsigned long long)(w.x >> 5) << 26) | (unsigned long long)(w.y >> 6));
+    const xv_u32x4 w = xv_index_draw(g.seed, g.index, 0, HS_P_UNIFY, (uint32_t)q >> 1);
+    L.key[q] = (q & 1) ? xv_k53(w.z, w.w) : xv_k53(w.x, w.y);
   }
   __syncthreads();
   for (int q = tid; q < nC; q += HS_T) {
@@ -447,9 +430,9 @@ __global__ __launch_bounds__(HS_T) void anyhvac_sampler_kernel(HsArgs P) {
       double* r = row + o.cool + (size_t)i * 24;
       const uint32_t own = (uint32_t)i, shared = L.unified[i] ? 0u : (uint32_t)i;
       // what a unified cooler takes from cooler 0
-      const HsU2 s0 = hs_pair(g, HS_P_COOLER, shared, 0), s1 = hs_pair(g, HS_P_COOLER, shared, 1),
-                 s2 = hs_pair(g, HS_P_COOLER, shared, 2), s4 = hs_pair(g, HS_P_COOLER, shared, 4),
-                 s5 = hs_pair(g, HS_P_COOLER, shared, 5);
+      const xv_u2 s0 = hs_pair(g, HS_P_COOLER, shared, 0), s1 = hs_pair(g, HS_P_COOLER, shared, 1),
+                  s2 = hs_pair(g, HS_P_COOLER, shared, 2), s4 = hs_pair(g, HS_P_COOLER, shared, 4),
+                  s5 = hs_pair(g, HS_P_COOLER, shared, 5);
       r[8] = hs_uni(s0.a, p.range[XV_ANYHVAC_R_VENT_EFFICIENCY]);
       r[9] = hs_uni(s0.b, p.range[XV_ANYHVAC_R_EER_BASE]);
       r[10] = hs_uni(s1.a, p.range[XV_ANYHVAC_R_EER_DECAY_START]);
@@ -467,13 +450,13 @@ __global__ __launch_bounds__(HS_T) void anyhvac_sampler_kernel(HsArgs P) {
         r[17] = hs_uni(s5.b, p.range[XV_ANYHVAC_R_FIXED_POWER]);
       }
       // its own
-      const HsU2 c3 = hs_pair(g, HS_P_COOLER, own, 3), c6 = hs_pair(g, HS_P_COOLER, own, 6);
+      const xv_u2 c3 = hs_pair(g, HS_P_COOLER, own, 3), c6 = hs_pair(g, HS_P_COOLER, own, 6);
       r[13] = hs_uni(c3.a, p.range[XV_ANYHVAC_R_DECAY_UB]);
       r[14] = hs_uni(c3.b, p.range[XV_ANYHVAC_R_DECAY_LB]);
       double sample = 0.0;
       for (int a = 0; a < HS_BIAS_TRIES; ++a) {
         double zc, zs;
-        hs_normal(hs_pair(g, HS_P_COOLER, own, (uint32_t)(HS_BIAS_SUB + a)), &zc, &zs);
+        xv_normal2(hs_pair(g, HS_P_COOLER, own, (uint32_t)(HS_BIAS_SUB + a)), &zc, &zs);
         const double s = p.bias_mean + drift_std * zc;
         bmargin = fmin(bmargin, fabs(fabs(s) - bound) / bound);
         if (-bound <= s && s <= bound) {

@@ -12,14 +12,13 @@
 #include <cmath>
 #include <cstdint>
 
-#include "philox.h"
 #include "xv_common.h"
+#include "xv_draws.h"
 
 namespace {
 
 constexpr int LS_T = 128;          // threads per candidate: one start attempt per thread and chunk
 constexpr int LS_NS = 32, LS_NA = 16, LS_NO = 32, LS_KMAX = XV_LINDS_KMAX;
-constexpr double LS_TWO_PI = 6.283185307179586;
 
 // head stream (stream 0): draw indices
 constexpr uint32_t H_DIMS = 0, H_DIMS2 = 1, H_SCALE = 2, H_TRIM = 3, H_COST = 4, H_REWARD = 5, H_PUNISH = 6, H_TARGET = 7;
@@ -55,22 +54,18 @@ struct LsKey {
   uint32_t c0, c1, k0, k1;
 };
 
+// LinDS's own layout: counter = {candidate lo, candidate hi, stream, draw}, key = seed
+__device__ __forceinline__ xv_u2 ls_u2(const LsKey& k, uint32_t stream, uint32_t draw) {
+  return xv_pair(xv_philox4x32_10(k.c0, k.c1, stream, draw, k.k0, k.k1));
+}
 __device__ __forceinline__ void ls_pair(const LsKey& k, uint32_t stream, uint32_t draw, double* ua, double* ub) {
-  const xv_u32x4 w = xv_philox4x32_10(k.c0, k.c1, stream, draw, k.k0, k.k1);
-  *ua = xv_u53(w.x, w.y);
-  *ub = xv_u53(w.z, w.w);
+  const xv_u2 u = ls_u2(k, stream, draw);
+  *ua = u.a;
+  *ub = u.b;
 }
-// one Philox call -> a Box-Muller pair in fp64: radius from the first uniform (1 - u in (0, 1]), angle from the second
 __device__ __forceinline__ void ls_normal2(const LsKey& k, uint32_t stream, uint32_t draw, double* z0, double* z1) {
-  double ua, ub;
-  ls_pair(k, stream, draw, &ua, &ub);
-  const double r = sqrt(-2.0 * log(1.0 - ua));
-  const double ang = LS_TWO_PI * ub;
-  *z0 = r * cos(ang);
-  *z1 = r * sin(ang);
+  xv_normal2(ls_u2(k, stream, draw), z0, z1);
 }
-__device__ __forceinline__ double ls_expo(double u) { return -log(1.0 - u); }
-__device__ __forceinline__ int ls_int(double u, int n) { return (int)floor(u * (double)n); }
 
 // ------------------------------------------------------------------------------------------------
 // zero-order hold of one task by the whole workgroup.  A [n][n], B [n][na] in LDS; W: 5 n^2 + n na doubles of LDS.
@@ -256,14 +251,14 @@ __device__ bool ls_attempt(const LsArgs& P, const LsKey& key, const LsHead& H, c
   const int ns = H.ns, no = H.no;
   double ua, ub;
   ls_pair(key, stream, S_BORN, &ua, &ub);
-  const double e = ls_expo(ua);
+  const double e = xv_expo(ua);
   const int born = (int)fmax(e, 1.0);
   if (born > P.NI) return false;
   const double nd = fmin(fmax(-0.02 + 0.04 * ub, 0.0), 0.02);
   ls_pair(key, stream, S_CMD, &ua, &ub);
   int delay = 0, n_terms = 0;
   if (H.type == 0) {
-    const double gate = (double)ls_int(ua, 2);
+    const double gate = (double)xv_floor_int(ua, 2);
     for (int p = 0; 2 * p < no; ++p) {
       double z0, z1;
       ls_normal2(key, stream, S_STATIC + p, &z0, &z1);
@@ -279,8 +274,8 @@ __device__ bool ls_attempt(const LsArgs& P, const LsKey& key, const LsHead& H, c
       if (P.T.four_period) P.T.four_period[ci] = 1.0;
     }
   } else {
-    const int n_items = 1 + ls_int(ua, 5);
-    delay = max(-10 + ls_int(ub, 40), 0);
+    const int n_items = 1 + xv_floor_int(ua, 5);
+    delay = max(-10 + xv_floor_int(ub, 40), 0);
     n_terms = 1 + n_items;
     const double scale = 2.0 / sqrt((double)n_items);
     const double x = -(double)delay / 1000.0;
@@ -291,7 +286,7 @@ __device__ bool ls_attempt(const LsArgs& P, const LsKey& key, const LsHead& H, c
         double oa, ob, z0, z1;
         ls_pair(key, stream, S_ORDER_INT + t, &oa, &ob);
         ls_normal2(key, stream, S_ORDER_Z + t, &z0, &z1);
-        order = (double)(1 + ls_int(oa, 16)) + z0;
+        order = (double)(1 + xv_floor_int(oa, 16)) + z0;
       }
       const double ang = order * x;
       const double sn = sin(ang), cs = cos(ang);
@@ -303,7 +298,7 @@ __device__ bool ls_attempt(const LsArgs& P, const LsKey& key, const LsHead& H, c
         double z0, z1, ea, eb;
         ls_normal2(key, stream, S_FOURIER + 64 * t + o, &z0, &z1);
         ls_pair(key, stream, S_FOURIER + 64 * t + 32 + o, &ea, &eb);
-        const double c0 = z0 * (ls_expo(ea) * scale), c1 = z1 * (ls_expo(eb) * scale);
+        const double c0 = z0 * (xv_expo(ea) * scale), c1 = z1 * (xv_expo(eb) * scale);
         const double term = c0 * sn + c1 * cs;
         cm[o * LS_T] = cm[o * LS_T] + term;
         if (W) {
@@ -370,25 +365,25 @@ __global__ __launch_bounds__(LS_T) void linds_sampler_kernel(LsArgs P) {
     for (int d = 0; d < 8; ++d) ls_pair(key, 0u, (uint32_t)d, &ua[d], &ub[d]);
     int ns = P.ns, na = P.na, no = P.no;
     if (P.random_dim) {      // LinearDSSamplerRandomDim :134-154; P.ns / na / no are the maxima
-      ns = 1 + ls_int(ua[H_DIMS], P.ns);
+      ns = 1 + xv_floor_int(ua[H_DIMS], P.ns);
       const int min_na = max(1, (ns + 1) / 2), hi_na = max(min(P.na, ns * 3 / 2), min_na);
       const int min_no = max(1, ns / 4), hi_no = max(min(P.no, ns * 3 / 2), min_no);
-      na = min_na + ls_int(ub[H_DIMS], hi_na - min_na + 1);
-      no = min_no + ls_int(ua[H_DIMS2], hi_no - min_no + 1);
+      na = min_na + xv_floor_int(ub[H_DIMS], hi_na - min_na + 1);
+      no = min_no + xv_floor_int(ua[H_DIMS2], hi_no - min_no + 1);
     }
     H.ns = ns; H.na = na; H.no = no;
-    H.max_steps = 100 + ls_int(ub[H_DIMS2], 900);
-    H.a_scale = ls_int(ua[H_SCALE], 5);
-    H.x_scale = ls_int(ub[H_SCALE], 3);
-    H.trim = ls_int(ua[H_TRIM], 3);
-    H.width = H.trim == 0 ? 2 + ls_int(ub[H_TRIM], max(ns / 2, 3) - 1)
-                          : (H.trim == 1 ? -1 + ls_int(ub[H_TRIM], max(ns / 4, 2) + 2) : 0);
-    H.action_cost = fmax((-1.0 + 2.0 * ua[H_COST]) * (ls_expo(ub[H_COST]) * 0.05), 0.0);
-    H.reward_base = ls_expo(ua[H_REWARD]) * 0.10;
-    H.terminate_punish = (ls_expo(ub[H_REWARD]) * 5.0) * (ls_int(ua[H_PUNISH], 3) == 0 ? 0.0 : 1.0);
-    H.reward_factor = ls_expo(ub[H_PUNISH]) * 0.50;
+    H.max_steps = 100 + xv_floor_int(ub[H_DIMS2], 900);
+    H.a_scale = xv_floor_int(ua[H_SCALE], 5);
+    H.x_scale = xv_floor_int(ub[H_SCALE], 3);
+    H.trim = xv_floor_int(ua[H_TRIM], 3);
+    H.width = H.trim == 0 ? 2 + xv_floor_int(ub[H_TRIM], max(ns / 2, 3) - 1)
+                          : (H.trim == 1 ? -1 + xv_floor_int(ub[H_TRIM], max(ns / 4, 2) + 2) : 0);
+    H.action_cost = fmax((-1.0 + 2.0 * ua[H_COST]) * (xv_expo(ub[H_COST]) * 0.05), 0.0);
+    H.reward_base = xv_expo(ua[H_REWARD]) * 0.10;
+    H.terminate_punish = (xv_expo(ub[H_REWARD]) * 5.0) * (xv_floor_int(ua[H_PUNISH], 3) == 0 ? 0.0 : 1.0);
+    H.reward_factor = xv_expo(ub[H_PUNISH]) * 0.50;
     H.eps = fmin(0.2 + ua[H_TARGET], 1.0);
-    H.type = ls_int(ub[H_TARGET], 3) < 2 ? 1 : 0;
+    H.type = xv_floor_int(ub[H_TARGET], 3) < 2 ? 1 : 0;
   }
   __syncthreads();
   const int ns = H.ns, na = H.na, no = H.no;

@@ -18,8 +18,8 @@
 // passing wall of a shuffled order" is the passing wall with the smallest (key, cell) and "the last of the order" the
 // standing wall with the largest (key, cell).  A pass = test every wall, one argmin and one argmax, release and relabel.
 // The loop is bounded: 4 (n-2)^2 passes, then status pass_cap.  No loop here depends on data for its termination.
-#include "philox.h"
 #include "xv_common.h"
+#include "xv_draws.h"
 
 namespace {
 
@@ -52,19 +52,11 @@ struct MsArgs {
   int32_t* status;
 };
 
-// counter = {index lo, index hi, sub, purpose | tick << 8}, key = seed
-__device__ __forceinline__ xv_u32x4 ms_draw(uint64_t seed, uint64_t index, uint32_t tick, uint32_t purpose, uint32_t sub) {
-  return xv_philox4x32_10((uint32_t)index, (uint32_t)(index >> 32), sub, (purpose & 0xFFu) | (tick << 8), (uint32_t)seed,
-                          (uint32_t)(seed >> 32));
-}
-__device__ __forceinline__ uint64_t ms_k53(uint32_t a, uint32_t b) { return ((uint64_t)(a >> 5) << 26) | (uint64_t)(b >> 6); }
 // element q of a block of uniforms: half q & 1 of call q >> 1
 __device__ __forceinline__ uint64_t ms_block_k53(uint64_t seed, uint64_t index, uint32_t tick, uint32_t purpose, uint32_t q) {
-  const xv_u32x4 w = ms_draw(seed, index, tick, purpose, q >> 1);
-  return (q & 1u) ? ms_k53(w.z, w.w) : ms_k53(w.x, w.y);
+  const xv_u32x4 w = xv_index_draw(seed, index, tick, purpose, q >> 1);
+  return (q & 1u) ? xv_k53(w.z, w.w) : xv_k53(w.x, w.y);
 }
-__device__ __forceinline__ double ms_u(uint64_t k53) { return (double)k53 * (1.0 / 9007199254740992.0); }
-__device__ __forceinline__ int ms_floor_int(double u, int m) { return (int)floor(u * (double)m); }
 
 // ---- cross-lane choices: the greatest key, equal keys to the lower index; i < 0: no entry ----
 struct MsBest {
@@ -140,7 +132,7 @@ __device__ void ms_landmarks(MsLds& L, int n, uint64_t seed, uint64_t index, uin
     MsBest b{0, -1};
     for (int c = lane; c < nn; c += MS_T) {
       if (L.mark[c] >= 0) continue;
-      const double like = ms_u(ms_block_k53(seed, index, tick, purpose, (uint32_t)c)) - (double)L.walls[c];
+      const double like = xv_k53_u(ms_block_k53(seed, index, tick, purpose, (uint32_t)c)) - (double)L.walls[c];
       const MsBest v{ms_ordered(like), c};
       if (ms_beats(v, b)) b = v;
     }
@@ -160,7 +152,7 @@ __device__ int ms_start(const MsLds& L, int n, uint64_t seed, uint64_t index, ui
   const int lane = threadIdx.x, nn = n * n;
   MsBest b{0, -1};
   for (int c = lane; c < nn; c += MS_T) {
-    const double like = ms_u(ms_block_k53(seed, index, tick, purpose, (uint32_t)c)) - (double)L.walls[c] - (double)L.mark[c];
+    const double like = xv_k53_u(ms_block_k53(seed, index, tick, purpose, (uint32_t)c)) - (double)L.walls[c] - (double)L.mark[c];
     const MsBest v{ms_ordered(like), c};
     if (ms_beats(v, b)) b = v;
   }
@@ -171,9 +163,9 @@ __device__ void ms_commands(MsLds& L, uint64_t seed, uint64_t index, uint32_t ti
                             int32_t* commands) {
   const int lane = threadIdx.x;
   for (int i = lane; i < n_cmd; i += MS_T) {
-    const xv_u32x4 w = ms_draw(seed, index, tick, purpose, (uint32_t)i);
-    L.cx[i] = (int8_t)ms_floor_int(xv_u53(w.x, w.y), k);
-    L.cd[i] = (int8_t)(1 + ms_floor_int(xv_u53(w.z, w.w), k - 1));
+    const xv_u32x4 w = xv_index_draw(seed, index, tick, purpose, (uint32_t)i);
+    L.cx[i] = (int8_t)xv_floor_int(xv_u53(w.x, w.y), k);
+    L.cd[i] = (int8_t)(1 + xv_floor_int(xv_u53(w.z, w.w), k - 1));
   }
   __syncthreads();
   if (lane == 0)
@@ -196,7 +188,7 @@ __global__ __launch_bounds__(MS_T) void maze_sampler_kernel(MsArgs P) {
   double u[10];
 #pragma unroll
   for (int s = 0; s < 5; ++s) {
-    const xv_u32x4 w = ms_draw(seed, cand, 0, MS_P_HEAD, (uint32_t)s);
+    const xv_u32x4 w = xv_index_draw(seed, cand, 0, MS_P_HEAD, (uint32_t)s);
     u[2 * s] = xv_u53(w.x, w.y);
     u[2 * s + 1] = xv_u53(w.z, w.w);
   }
@@ -204,15 +196,15 @@ __global__ __launch_bounds__(MS_T) void maze_sampler_kernel(MsArgs P) {
   const double wall_height = A.wall_height[0] + (A.wall_height[1] - A.wall_height[0]) * u[1];
   const double agent_height = A.agent_height[0] + (A.agent_height[1] - A.agent_height[0]) * u[2];
   const double wall_density = A.wall_density[0] + (A.wall_density[1] - A.wall_density[0]) * u[3];
-  int k = A.landmarks_lo + ms_floor_int(u[4], A.landmarks_hi - A.landmarks_lo);
+  int k = A.landmarks_lo + xv_floor_int(u[4], A.landmarks_hi - A.landmarks_lo);
   k = k > XV_MAZE_LMAX ? XV_MAZE_LMAX : k;
-  int n = A.n_lo + ms_floor_int(u[5], A.n_hi - A.n_lo);
+  int n = A.n_lo + xv_floor_int(u[5], A.n_hi - A.n_lo);
   n |= 1;
   n = n > NG ? NG : n;      // cannot happen with the arguments xv_maze_sample_tasks admits: the LDS grid's bound
-  const int ground_text = ms_floor_int(u[6], A.n_ground_textures), ceiling_text = ms_floor_int(u[7], A.n_ceiling_textures);
+  const int ground_text = xv_floor_int(u[6], A.n_ground_textures), ceiling_text = xv_floor_int(u[7], A.n_ceiling_textures);
   const double fol_angle = A.fol_angle[0] + (A.fol_angle[1] - A.fol_angle[0]) * u[8];
   const int m = n - 2, nn = n * n;
-  const int n_rooms = ms_floor_int(u[9], m * m / 16);
+  const int n_rooms = xv_floor_int(u[9], m * m / 16);
 
   // rooms (_dig_rooms): walls all standing, margins empty
   for (int c = lane; c < nn; c += MS_T) {
@@ -225,8 +217,9 @@ __global__ __launch_bounds__(MS_T) void maze_sampler_kernel(MsArgs P) {
   for (int r = 0; r < n_rooms; ++r) {
     for (int t = 0; t < MS_ROOM_TRIES; ++t) {
       const uint32_t sub = 2u * (uint32_t)(MS_ROOM_TRIES * r + t);
-      const xv_u32x4 w0 = ms_draw(seed, cand, 0, MS_P_ROOM, sub), w1 = ms_draw(seed, cand, 0, MS_P_ROOM, sub + 1);
-      const int h = 2 + ms_floor_int(xv_u53(w0.x, w0.y), 3), w = 2 + ms_floor_int(xv_u53(w0.z, w0.w), 3);
+      const xv_u32x4 w0 = xv_index_draw(seed, cand, 0, MS_P_ROOM, sub),
+                     w1 = xv_index_draw(seed, cand, 0, MS_P_ROOM, sub + 1);
+      const int h = 2 + xv_floor_int(xv_u53(w0.x, w0.y), 3), w = 2 + xv_floor_int(xv_u53(w0.z, w0.w), 3);
       const double uk = xv_u53(w1.x, w1.y);
       const int cols = m - w + 1, places = (m - h + 1) * cols;
       // free placements, 64 at a time in row-major order: ballots count them and find the k-th
@@ -242,7 +235,7 @@ __global__ __launch_bounds__(MS_T) void maze_sampler_kernel(MsArgs P) {
         n_free += __popcll(__ballot(fr));
       }
       if (n_free == 0) continue;
-      const int pick = ms_floor_int(uk, n_free);
+      const int pick = xv_floor_int(uk, n_free);
       int seen = 0, place = -1;
       for (int base = 0; base < places; base += MS_T) {
         const int p = base + lane;
@@ -313,8 +306,8 @@ __global__ __launch_bounds__(MS_T) void maze_sampler_kernel(MsArgs P) {
       const int i = c / n, j = c - i * n;
       if (i < 1 || i > n - 2 || j < 1 || j > n - 2 || L.walls[c] == 0) continue;
       const MsEval e = ms_eval(L, n, c);
-      const xv_u32x4 w = ms_draw(seed, cand, (uint32_t)passes, MS_P_PASS, (uint32_t)c);
-      const uint64_t key = ms_k53(w.x, w.y);
+      const xv_u32x4 w = xv_index_draw(seed, cand, (uint32_t)passes, MS_P_PASS, (uint32_t)c);
+      const uint64_t key = xv_k53(w.x, w.y);
       const bool pass = (e.distinct >= 2 && (e.most < 2 || loops)) || (loops && n_regions < 2 && xv_u53(w.z, w.w) < 0.2);
       const MsBest lo{MS_K53 - key, c}, hi{key, MS_CELLS - 1 - c};      // smallest (key, cell); largest (key, cell)
       if (pass && ms_beats(lo, first)) first = lo;
@@ -377,7 +370,7 @@ __global__ __launch_bounds__(MS_T) void maze_sampler_kernel(MsArgs P) {
       lv = L.mark[c];
       const bool inner = i >= 1 && i <= n - 2 && j >= 1 && j <= n - 2;
       if (!(inner && wv < 1))
-        tv = ms_floor_int(ms_u(ms_block_k53(seed, cand, 0, MS_P_TEXT, (uint32_t)c)), A.n_wall_textures);
+        tv = xv_floor_int(xv_k53_u(ms_block_k53(seed, cand, 0, MS_P_TEXT, (uint32_t)c)), A.n_wall_textures);
     }
     P.o.walls[slot + p] = wv;
     P.o.texts[slot + p] = tv;

@@ -20,6 +20,7 @@
 #define XV_KERNELS_ONLY
 #include "metalm.hip"
 #undef XV_KERNELS_ONLY
+#include "xv_draws.h"
 
 #define XV_DRAW_METALM_TASK 14u
 
@@ -91,11 +92,8 @@ __global__ __launch_bounds__(256) void metalm_sample_kernel(LMArgs P, LMSample S
   const double s_enc = sqrt(2.0 / (double)(V + E)), s_dec = sqrt(2.0 / (double)(H + V)),
                s_rnn = sqrt(2.0 / (double)((E + H) + H));
   for (int p = threadIdx.x; 2 * p < n_z; p += blockDim.x) {
-    const xv_u32x4 w = xv_env_draw_sub(P.seed, gid, 0, XV_DRAW_METALM_TASK, (uint32_t)p);
-    const double ua = xv_u53(w.x, w.y), ub = xv_u53(w.z, w.w);
-    const double r = sqrt(-2.0 * log(1.0 - ua));
-    const double ang = 6.283185307179586 * ub;
-    const double z2[2] = {r * cos(ang), r * sin(ang)};
+    double z2[2];
+    xv_normal2(xv_pair(xv_env_draw_sub(P.seed, gid, 0, XV_DRAW_METALM_TASK, (uint32_t)p)), &z2[0], &z2[1]);
 #pragma unroll
     for (int m = 0; m < 2; ++m) {
       const int i = 2 * p + m;

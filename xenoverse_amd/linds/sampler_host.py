@@ -10,10 +10,8 @@ is member n & 1 of call base + (n >> 1); element q of a block of uniforms is hal
 """
 import numpy as np
 
+from ..host_draws import box_muller, expo, floor_int, interleave, pair, philox4x32_10
 from .tables import KMAX
-
-M32 = np.uint64(0xFFFFFFFF)
-TWO_PI = 6.283185307179586
 
 STATUS = ("accepted", "exhausted", "zoh_failed")
 A_SCALES = (0.01, 0.02, 0.05, 0.1, 0.2)
@@ -33,26 +31,6 @@ ZOH_S_CAP = 40          # more halvings than this: status, not a table
 ZOH_OK, ZOH_NONFINITE, ZOH_SCALE_CAP = 0, 1, 2
 
 
-def philox4x32_10(ctr, key):
-    """ctr uint32[..., 4], key uint32[2] -> uint32[..., 4]  (Salmon et al., SC'11; csrc/philox.h)"""
-    c = np.asarray(ctr, np.uint32).astype(np.uint64)
-    c0, c1, c2, c3 = c[..., 0], c[..., 1], c[..., 2], c[..., 3]
-    key = np.asarray(key, np.uint32).astype(np.uint64).reshape(2)
-    k0, k1 = key[0], key[1]
-    for _ in range(10):
-        p0 = np.uint64(0xD2511F53) * c0
-        p1 = np.uint64(0xCD9E8D57) * c2
-        c0, c1, c2, c3 = (p1 >> np.uint64(32)) ^ c1 ^ k0, p1 & M32, (p0 >> np.uint64(32)) ^ c3 ^ k1, p0 & M32
-        k0 = (k0 + np.uint64(0x9E3779B9)) & M32
-        k1 = (k1 + np.uint64(0xBB67AE85)) & M32
-    return np.stack([c0, c1, c2, c3], axis=-1).astype(np.uint32)
-
-
-def _u53(a, b):
-    return ((a >> np.uint32(5)).astype(np.float64) * 67108864.0 + (b >> np.uint32(6)).astype(np.float64)) * \
-        (1.0 / 9007199254740992.0)
-
-
 class _Stream(object):
     """draws of one (seed, candidate) over an array of streams"""
 
@@ -69,30 +47,17 @@ class _Stream(object):
         ctr[..., 0], ctr[..., 1] = self.c01
         ctr[..., 2] = self.streams.reshape((-1,) + (1,) * d.ndim)
         ctr[..., 3] = d
-        w = philox4x32_10(ctr, self.key)
-        return _u53(w[..., 0], w[..., 1]), _u53(w[..., 2], w[..., 3])
+        return pair(philox4x32_10(ctr, self.key))
 
     def uniforms(self, base, n):
         """block of n uniforms -> float64[n_streams, n]"""
         q = np.arange(n)
-        ua, ub = self.pairs(base + (q >> 1))
-        return np.where(q & 1, ub, ua)
+        return interleave(q, *self.pairs(base + (q >> 1)))
 
     def normals(self, base, n):
         """block of n normals (fp64 Box-Muller) -> float64[n_streams, n]"""
         q = np.arange(n)
-        ua, ub = self.pairs(base + (q >> 1))
-        r = np.sqrt(-2.0 * np.log(1.0 - ua))
-        ang = TWO_PI * ub
-        return np.where(q & 1, r * np.sin(ang), r * np.cos(ang))
-
-
-def _expo(u):
-    return -np.log(1.0 - u)
-
-
-def _floor_int(u, n):
-    return np.floor(u * n).astype(np.int64)
+        return interleave(q, *box_muller(*self.pairs(base + (q >> 1))))
 
 
 def random_dims(u_ns, u_na, u_no, max_ns, max_no, max_na):
@@ -136,10 +101,10 @@ def sample_head(seed, cand, ns=16, na=8, no=8, random_dim=False):
     elif h["trim"] == 1 and h["width"] < ns:
         A = np.where(j < i + h["width"], 0.0, A)
     h.update(A=A, B=np.ascontiguousarray(AB[:, ns:]), C=C, X=X, Y=np.zeros(no))
-    h["action_cost"] = max((-1.0 + 2.0 * ua[H_COST]) * (_expo(ub[H_COST]) * 0.05), 0.0)
-    h["reward_base"] = _expo(ua[H_REWARD]) * 0.10
-    h["terminate_punish"] = (_expo(ub[H_REWARD]) * 5.0) * (0.0 if int(np.floor(ua[H_PUNISH] * 3)) == 0 else 1.0)
-    h["reward_factor"] = _expo(ub[H_PUNISH]) * 0.50
+    h["action_cost"] = max((-1.0 + 2.0 * ua[H_COST]) * (expo(ub[H_COST]) * 0.05), 0.0)
+    h["reward_base"] = expo(ua[H_REWARD]) * 0.10
+    h["terminate_punish"] = (expo(ub[H_REWARD]) * 5.0) * (0.0 if int(np.floor(ua[H_PUNISH] * 3)) == 0 else 1.0)
+    h["reward_factor"] = expo(ub[H_PUNISH]) * 0.50
     h["eps"] = min(0.2 + ua[H_TARGET], 1.0)
     h["type"] = 1 if int(np.floor(ub[H_TARGET] * 3)) < 2 else 0          # 1 dynamic_target, 0 static_target
     for rnd in range(VALID_ROUNDS):
@@ -158,27 +123,27 @@ def eval_attempts(seed, cand, head, attempts, NI=8):
     n = len(attempts)
     st = _Stream(seed, cand, 1 + attempts)
     ua, ub = st.pairs(np.arange(2))
-    e = _expo(ua[:, S_BORN])
+    e = expo(ua[:, S_BORN])
     born = np.maximum(e, 1.0).astype(np.int64)
     r = dict(attempt=attempts, born_e=e, born_loc=born, noise_drift=np.clip(-0.02 + 0.04 * ub[:, S_BORN], 0.0, 0.02))
     if head["type"] == 0:
-        gate = _floor_int(ua[:, S_CMD], 2).astype(np.float64)
+        gate = floor_int(ua[:, S_CMD], 2).astype(np.float64)
         cmd0 = st.normals(S_STATIC, no) * gate[:, None]
         r.update(cmd0=cmd0, delay=np.zeros(n, np.int64), n_terms=np.zeros(n, np.int64))
         cmd = cmd0
     else:
-        n_items = 1 + _floor_int(ua[:, S_CMD], 5)
-        delay = np.maximum(-10 + _floor_int(ub[:, S_CMD], 40), 0)
+        n_items = 1 + floor_int(ua[:, S_CMD], 5)
+        delay = np.maximum(-10 + floor_int(ub[:, S_CMD], 40), 0)
         k = np.arange(1, KMAX)
         oi, _ = st.pairs(S_ORDER_INT + k)
         za, zb = st.pairs(S_ORDER_Z + k)
         orders = np.zeros((n, KMAX))
-        orders[:, 1:] = (1 + _floor_int(oi, 16)) + np.sqrt(-2.0 * np.log(1.0 - za)) * np.cos(TWO_PI * zb)
+        orders[:, 1:] = (1 + floor_int(oi, 16)) + box_muller(za, zb)[0]
         scale = 2.0 / np.sqrt(n_items.astype(np.float64))
         coef = np.empty((n, KMAX, no, 2))
         for t in range(KMAX):
             z = st.normals(S_FOURIER + 64 * t, 2 * no)
-            ex = _expo(st.uniforms(S_FOURIER + 64 * t + 32, 2 * no)) * scale[:, None]
+            ex = expo(st.uniforms(S_FOURIER + 64 * t + 32, 2 * no)) * scale[:, None]
             coef[:, t] = (z * ex).reshape(n, no, 2)
         live = np.arange(KMAX)[None, :] <= n_items[:, None]
         orders = np.where(live, orders, 0.0)

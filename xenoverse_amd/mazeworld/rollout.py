@@ -9,7 +9,7 @@ import torch
 
 from .. import _lib
 from ..engine import AUTORESET
-from .sampler_host import philox4x32_10
+from ..host_draws import env_draw_words, u53
 
 DRAW_EXPLORE = 48      # XV_DRAW_EXPLORE (csrc/maze_common.h)
 
@@ -32,16 +32,8 @@ def explore_draws_host(seed, gid_base, tick, n_env, epsilon, n_actions):
     """The exploration draws of rollout_teacher for envs gid_base .. gid_base + n_env - 1 at `tick` (the tick of the behaviour
     agent's act; a scalar or one per env): w = xv_env_draw(seed, env id, tick, 48); -> (explored bool[n_env] = u53(w0, w1) <
     epsilon, random_action int32[n_env] = floor(u53(w2, w3) * n_actions))."""
-    gid = (np.uint64(int(gid_base)) + np.arange(int(n_env), dtype=np.uint64))
-    tk = np.broadcast_to(np.asarray(tick, dtype=np.uint64), gid.shape)
-    m32, s32 = np.uint64(0xFFFFFFFF), np.uint64(32)
-    ctr = np.stack([gid & m32, gid >> s32, tk & m32, np.uint64(DRAW_EXPLORE) | ((tk >> s32) << np.uint64(8)) & m32],
-                   axis=-1).astype(np.uint32)
-    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-    w = philox4x32_10(ctr, np.array([seed & 0xFFFFFFFF, seed >> 32], np.uint32))
-
-    def u53(a, b):
-        return ((a >> 5).astype(np.float64) * 67108864.0 + (b >> 6).astype(np.float64)) * (1.0 / 9007199254740992.0)
+    gid = np.uint64(int(gid_base)) + np.arange(int(n_env), dtype=np.uint64)
+    w = env_draw_words(seed, gid, tick, DRAW_EXPLORE)
     explored = u53(w[:, 0], w[:, 1]) < float(epsilon)
     return explored, np.floor(u53(w[:, 2], w[:, 3]) * float(n_actions)).astype(np.int32)
 

@@ -15,10 +15,10 @@ otherwise (`pass_tests`, `pass_choice`; tests/test_host_maze_sampler.py walks th
 """
 import numpy as np
 
+from ..host_draws import Draws, floor_int, interleave, uniform
 from .tables import LMAX, NG_MAX
 from .task_sampler import PI
 
-M32 = np.uint64(0xFFFFFFFF)
 STATUS = ("accepted", "pass_cap", "no_room")
 N_MIN, N_MAX = 7, NG_MAX - 1
 CMD_MAX = 2048
@@ -69,57 +69,8 @@ def grid_pitch(n_range):
     return (int(n_range[1]) - 1) | 1
 
 
-def philox4x32_10(ctr, key):
-    """ctr uint32[..., 4], key uint32[2] -> uint32[..., 4]  (Salmon et al., SC'11; csrc/philox.h)"""
-    c = np.asarray(ctr, np.uint32).astype(np.uint64)
-    c0, c1, c2, c3 = c[..., 0], c[..., 1], c[..., 2], c[..., 3]
-    key = np.asarray(key, np.uint32).astype(np.uint64).reshape(2)
-    k0, k1 = key[0], key[1]
-    for _ in range(10):
-        p0 = np.uint64(0xD2511F53) * c0
-        p1 = np.uint64(0xCD9E8D57) * c2
-        c0, c1, c2, c3 = (p1 >> np.uint64(32)) ^ c1 ^ k0, p1 & M32, (p0 >> np.uint64(32)) ^ c3 ^ k1, p0 & M32
-        k0 = (k0 + np.uint64(0x9E3779B9)) & M32
-        k1 = (k1 + np.uint64(0xBB67AE85)) & M32
-    return np.stack([c0, c1, c2, c3], axis=-1).astype(np.uint32)
-
-
-class Draws(object):
-    """the draws of one (seed, index)"""
-
-    def __init__(self, seed, index):
-        seed, index = int(seed) & (2**64 - 1), int(index) & (2**64 - 1)
-        self.key = np.array([seed & 0xFFFFFFFF, seed >> 32], np.uint32)
-        self.c01 = (index & 0xFFFFFFFF, index >> 32)
-
-    def ints53(self, purpose, subs, tick=0):
-        """-> (first, second) uint64[...]: the 53-bit integers of the two uniforms of calls `subs`"""
-        subs = np.asarray(subs, np.uint32)
-        ctr = np.empty(subs.shape + (4,), np.uint32)
-        ctr[..., 0], ctr[..., 1] = self.c01
-        ctr[..., 2] = subs
-        ctr[..., 3] = (int(purpose) & 0xFF) | (int(tick) << 8)
-        w = philox4x32_10(ctr, self.key).astype(np.uint64)
-        return ((w[..., 0] >> np.uint64(5)) << np.uint64(26)) | (w[..., 1] >> np.uint64(6)), \
-               ((w[..., 2] >> np.uint64(5)) << np.uint64(26)) | (w[..., 3] >> np.uint64(6))
-
-    def pairs(self, purpose, subs, tick=0):
-        a, b = self.ints53(purpose, subs, tick)
-        return a.astype(np.float64) * (1.0 / 9007199254740992.0), b.astype(np.float64) * (1.0 / 9007199254740992.0)
-
-    def block(self, purpose, n, tick=0):
-        """n uniforms: element q is half q & 1 of call q >> 1"""
-        q = np.arange(n)
-        a, b = self.pairs(purpose, q >> 1, tick)
-        return np.where(q & 1, b, a)
-
-
 def _randint(u, lo, hi):
-    return int(lo) + int(np.floor(u * (int(hi) - int(lo))))
-
-
-def _uniform(u, rng):
-    return float(rng[0]) + (float(rng[1]) - float(rng[0])) * u
+    return int(lo) + int(floor_int(u, int(hi) - int(lo)))
 
 
 # ---- rooms -------------------------------------------------------------------------------------------------------
@@ -132,14 +83,14 @@ def dig_rooms_host(d, n, n_rooms):
     for r in range(n_rooms):
         for t in range(ROOM_TRIES):
             (uh, uk), (uw, _) = d.pairs(P_ROOM, [2 * (ROOM_TRIES * r + t), 2 * (ROOM_TRIES * r + t) + 1])
-            h, w = 2 + int(np.floor(uh * 3)), 2 + int(np.floor(uw * 3))
+            h, w = 2 + int(floor_int(uh, 3)), 2 + int(floor_int(uw, 3))
             inner = occ[1:n - 1, 1:n - 1].astype(np.int64)
             c = np.cumsum(np.cumsum(np.pad(inner, ((1, 0), (1, 0))), 0), 1)
             win = c[h:, w:] - c[:-h, w:] - c[h:, :-w] + c[:-h, :-w]
             rows, cols = np.where(win == 0)
             if rows.shape[0] == 0:
                 continue
-            k = int(np.floor(uk * rows.shape[0]))
+            k = int(floor_int(uk, rows.shape[0]))
             r0, c0 = int(rows[k]), int(cols[k])
             occ[1 + max(0, r0 - 1):1 + min(m, r0 + h + 1), 1 + max(0, c0 - 1):1 + min(m, c0 + w + 1)] = 1
             walls[1 + r0:1 + r0 + h, 1 + c0:1 + c0 + w] = 0
@@ -272,8 +223,8 @@ def start_host(d, walls, cell_landmarks, purpose=P_START, tick=0):
 def commands_host(d, k, length, purpose=P_CMD, tick=0):
     """_sample_cmds: `length` draws below k, immediate repeats moved on by 1 + floor(u * (k - 1)), left to right"""
     ua, ub = d.pairs(purpose, np.arange(length), tick)
-    xs = np.floor(ua * k).astype(np.int64)
-    step = 1 + np.floor(ub * (k - 1)).astype(np.int64)
+    xs = floor_int(ua, k)
+    step = 1 + floor_int(ub, k - 1)
     for i in range(1, length):
         if xs[i] == xs[i - 1]:
             xs[i] = (xs[i] + step[i]) % k
@@ -287,24 +238,24 @@ def sample_candidate_host(seed, cand, on_pass=None, **kwargs):
     a = sampler_arguments(**kwargs)
     d = Draws(seed, cand)
     (u_cs, u_ah, u_lm, u_gt, u_fa), (u_wh, u_wd, u_n, u_ct, _) = d.pairs(P_HEAD, np.arange(5))
-    cell_size = _uniform(u_cs, a["cell_size_range"])
-    wall_height = _uniform(u_wh, a["wall_height_range"])
-    agent_height = _uniform(u_ah, a["agent_height_range"])
-    wall_density = _uniform(u_wd, a["wall_density_range"])
+    cell_size = uniform(u_cs, *a["cell_size_range"])
+    wall_height = uniform(u_wh, *a["wall_height_range"])
+    agent_height = uniform(u_ah, *a["agent_height_range"])
+    wall_density = uniform(u_wd, *a["wall_density_range"])
     k = min(_randint(u_lm, *a["landmarks_number_range"]), LMAX)
     n = _randint(u_n, *a["n_range"])
     if n % 2 == 0:
         n += 1
     ground_text = _randint(u_gt, 0, a["n_ground_textures"])
     ceiling_text = _randint(u_ct, 0, a["n_ceiling_textures"])
-    fol_angle = _uniform(u_fa, a["fol_angle_range"])
+    fol_angle = uniform(u_fa, *a["fol_angle_range"])
     walls, info = genmaze_host(d, n, bool(a["allow_loops"]), wall_density, on_pass=on_pass)
     info = dict(info, n=n, status=0)
     if walls is None:
         return None, dict(info, status=1)
     if int((walls < 1).sum()) < k + 1:
         return None, dict(info, status=2)
-    texts = np.floor(d.block(P_TEXT, n * n) * a["n_wall_textures"]).astype(np.int64).reshape(n, n)
+    texts = floor_int(d.block(P_TEXT, n * n), a["n_wall_textures"]).reshape(n, n)
     inner = np.zeros((n, n), bool)
     inner[1:-1, 1:-1] = True
     texts[inner & (walls < 1)] = 0
@@ -377,8 +328,7 @@ def resample_host(task, seed, index, episode, resample_cmd=True, resample_start=
     if resample_landmarks:
         landmarks, cl = targets_host(d, walls, k, P_LANDMARK | P_RESAMPLE, episode)
     elif resample_landmarks_color:
-        keys = d.ints53(P_SHUFFLE | P_RESAMPLE, np.arange(k) >> 1, episode)
-        keys = np.where(np.arange(k) & 1, keys[1], keys[0])
+        keys = interleave(np.arange(k), *d.ints53(P_SHUFFLE | P_RESAMPLE, np.arange(k) >> 1, episode))
         order = np.lexsort((np.arange(k), keys))          # new landmark r is the old landmark order[r]
         landmarks = [tuple(int(v) for v in task["landmarks_coordinates"][q]) for q in order]
         cl = np.full_like(np.asarray(task["cell_landmarks"], np.int8), -1)

@@ -11,54 +11,18 @@ and `candidate_host` runs the acceptance protocol with them over RandomLMHost.
 """
 import numpy as np
 
+from ..host_draws import box_muller, env_draw_sub_words, interleave, np_sum, pair
 from .lm_host import RandomLMHost
 from .stream_host import CHECK_T_HIGH, CHECK_T_LOW, _sub_step
 
-M32 = np.uint64(0xFFFFFFFF)
-TWO_PI = 6.283185307179586
 XV_DRAW_METALM, XV_DRAW_METALM_TASK = 9, 14                # csrc/metalm.hip, csrc/metalm_sampler.hip
 LM_QUERY, LM_POLICY, LM_LABEL, LM_GREEDY, LM_LOW = 0, 1, 2, 3, 4      # the pass kinds of csrc/metalm.hip
 
 STATUS = ("accepted", "nonfinite", "reward_low", "reward_high")
 
 
-def philox4x32_10(ctr, key):
-    """ctr uint32[..., 4], key uint32[..., 2] (broadcast against ctr's leading shape) -> uint32[..., 4]
-    (Salmon et al., SC'11; csrc/philox.h)"""
-    c = np.asarray(ctr, np.uint32).astype(np.uint64)
-    k = np.asarray(key, np.uint32).astype(np.uint64)
-    c0, c1, c2, c3 = c[..., 0], c[..., 1], c[..., 2], c[..., 3]
-    k0, k1 = k[..., 0], k[..., 1]
-    for _ in range(10):
-        p0 = np.uint64(0xD2511F53) * c0
-        p1 = np.uint64(0xCD9E8D57) * c2
-        c0, c1, c2, c3 = (p1 >> np.uint64(32)) ^ c1 ^ k0, p1 & M32, (p0 >> np.uint64(32)) ^ c3 ^ k1, p0 & M32
-        k0 = (k0 + np.uint64(0x9E3779B9)) & M32
-        k1 = (k1 + np.uint64(0xBB67AE85)) & M32
-    return np.stack(np.broadcast_arrays(c0, c1, c2, c3), axis=-1).astype(np.uint32)
-
-
-def env_draw_sub_words(seed, gid, tick, purpose, sub):
-    """xv_env_draw_sub (csrc/philox.h): counter {gid lo, gid hi, tick lo, purpose | tick hi << 8}, key {seed lo,
-    seed hi ^ (0x80000000 | sub)}.  sub: int array -> uint32[sub.shape + (4,)]"""
-    seed, gid, tick = int(seed) & (2**64 - 1), int(gid) & (2**64 - 1), int(tick) & (2**64 - 1)
-    sub = np.asarray(sub, np.uint32)
-    ctr = np.array([gid & 0xFFFFFFFF, gid >> 32, tick & 0xFFFFFFFF, (int(purpose) & 0xFF) | (((tick >> 32) << 8) & 0xFFFFFFFF)],
-                   np.uint32)
-    key = np.empty(sub.shape + (2,), np.uint32)
-    key[..., 0] = seed & 0xFFFFFFFF
-    key[..., 1] = np.uint32(seed >> 32) ^ (np.uint32(0x80000000) | sub)
-    return philox4x32_10(np.broadcast_to(ctr, sub.shape + (4,)), key)
-
-
-def _u53(a, b):
-    return ((a >> np.uint32(5)).astype(np.float64) * 67108864.0 + (b >> np.uint32(6)).astype(np.float64)) * \
-        (1.0 / 9007199254740992.0)
-
-
 def _pairs(seed, gid, tick, purpose, sub):
-    w = env_draw_sub_words(seed, gid, tick, purpose, sub)
-    return _u53(w[..., 0], w[..., 1]), _u53(w[..., 2], w[..., 3])
+    return pair(env_draw_sub_words(seed, gid, tick, purpose, sub))
 
 
 def n_normals(V, E, H):
@@ -68,12 +32,9 @@ def n_normals(V, E, H):
 
 def task_normals(seed, cand, n):
     """z[0 .. n) of candidate `cand`: z[i] is member i & 1 (cos, sin) of the fp64 Box-Muller pair of the call with
-    sub = i >> 1 (the constructions of linds/sampler_host.py:_Stream.normals)"""
+    sub = i >> 1"""
     i = np.arange(n)
-    ua, ub = _pairs(seed, cand, 0, XV_DRAW_METALM_TASK, i >> 1)
-    r = np.sqrt(-2.0 * np.log(1.0 - ua))
-    ang = TWO_PI * ub
-    return np.where(i & 1, r * np.sin(ang), r * np.cos(ang))
+    return interleave(i, *box_muller(*_pairs(seed, cand, 0, XV_DRAW_METALM_TASK, i >> 1)))
 
 
 def arrays_from_normals(z, V, E, H):
@@ -90,41 +51,19 @@ def arrays_from_normals(z, V, E, H):
                 dec_b=np.zeros(V))
 
 
-def np_sum_row(x):
-    """sum(x) of a contiguous float64 row of at most 128 elements in the order numpy's add.reduce takes: below 8 elements
-    left to right from 0; otherwise eight accumulators over the whole blocks of 8, combined pairwise, then the rest in
-    order.  Scalar fp64 arithmetic throughout (no numpy reduction is used)."""
-    x = [float(v) for v in x]
-    n = len(x)
-    if n > 128:
-        raise ValueError("rows of more than 128 elements are summed recursively: not restated")
-    if n < 8:
-        res = 0.0
-        for v in x:
-            res += v
-        return res
-    r = x[:8]
-    i = 8
-    while i < n - (n % 8):
-        for k in range(8):
-            r[k] += x[i + k]
-        i += 8
-    res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]))
-    for v in x[i:]:
-        res += v
-    return res
-
-
 def layer_norm_rows(x, eps=1e-8):
     """lm_host.layer_norm of a [rows, E] array with its sums in the stated order: mean = sum(x) / E, d = x - mean,
-    var = sum(d d) / E, d / (sqrt(var) + eps)"""
+    var = sum(d d) / E, d / (sqrt(var) + eps).  Rows of more than 128 elements are summed recursively, where the device's
+    lm_np_sum does not follow: they raise."""
     x = np.ascontiguousarray(x, np.float64)
+    if x.shape[1] > 128:
+        raise ValueError("rows of more than 128 elements are summed recursively: not restated on the device")
     out = np.empty_like(x)
     E = x.shape[1]
     for k, row in enumerate(x):
-        mean = np_sum_row(row) / E
+        mean = np_sum(row) / E
         d = row - mean
-        var = np_sum_row(d * d) / E
+        var = np_sum(d * d) / E
         out[k] = d / (np.sqrt(var) + eps)
     return out
 
@@ -133,8 +72,7 @@ def metalm_uniforms(seed, gid, tick, kind, n):
     """the free-running uniforms of positions 0 .. n - 1 of one pass (csrc/metalm_pass.h): position p is words 0,1 (p even)
     or 2,3 (p odd) of the call (seed, gid, tick, XV_DRAW_METALM, sub = kind << 16 | p >> 1)"""
     p = np.arange(n)
-    ua, ub = _pairs(seed, gid, tick, XV_DRAW_METALM, (int(kind) << 16) | (p >> 1))
-    return np.where(p & 1, ub, ua)
+    return interleave(p, *_pairs(seed, gid, tick, XV_DRAW_METALM, (int(kind) << 16) | (p >> 1)))
 
 
 def status_of(reward_low, reward_high, nonfinite=False):
