@@ -265,15 +265,23 @@ struct AnyMDPCoopLineN {
   static constexpr unsigned GM = (1u << LPE) - 1u;
   uint4 v[LPE][UPL];
   double ue[LPE];
+  int qa;      // byte address (ds_bpermute) of the first lane of the group that holds the owner lane's line: set by send()
+  static __device__ __forceinline__ int bperm(int addr, int x) { return __builtin_amdgcn_ds_bpermute(addr, x); }
   static __device__ __forceinline__ constexpr int unit_of(int jl, int k) { return CONTIG ? jl * UPL + k : jl + k * LPE; }
   static __device__ __forceinline__ int lane_of(int unit) { return CONTIG ? unit / UPL : unit % LPE; }   // within the group
   static __device__ __forceinline__ int slot_of(int unit) { return CONTIG ? unit % UPL : unit / LPE; }
   __device__ __forceinline__ void issue(const uint4* base, uint32_t line, int lane) {
     const int g = lane / LPE, jl = lane % LPE;
+    // every round's line index travels first, then the loads go out: the trips come back in order, so a counted wait per
+    // round separates them — ONE LDS round trip in front of the first request, not one per round (written as one loop,
+    // hipcc waits for each index before it sends the next)
+    uint32_t li[LPE];
+#pragma unroll
+    for (int it = 0; it < LPE; ++it) li[it] = LPE == 1 ? line : (uint32_t)__shfl((int)line, it * EPR + g);
+    if (LPE > 1) __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int it = 0; it < LPE; ++it) {
-      const uint32_t li = LPE == 1 ? line : (uint32_t)__shfl((int)line, it * EPR + g);
-      const uint4* lp = base + (size_t)li * 8;
+      const uint4* lp = base + (size_t)li[it] * 8;
 #pragma unroll
       for (int k = 0; k < UPL; ++k) v[it][k] = lp[unit_of(jl, k)];
     }
@@ -288,6 +296,7 @@ struct AnyMDPCoopLineN {
   // the env's uniform to the lanes that hold its line: call right after issue*()
   __device__ __forceinline__ void send(double u, int lane) {
     const int g = lane / LPE;
+    qa = (LPE * (lane % EPR)) << 2;
 #pragma unroll
     for (int it = 0; it < LPE; ++it) ue[it] = LPE == 1 ? u : xv_shfl_f64(u, it * EPR + g);
   }
@@ -335,10 +344,11 @@ struct AnyMDPCoopLineN {
         st16 = (sw >> (16 * (sg & 1))) & 0x1FFu;
       }
       const uint4 e = slot(it, slot_of(sg));          // group sg's entry, meaningful on lane lane_of(sg) of the group
-      const float px = __shfl(__uint_as_float(e.z), LPE * qo + lane_of(so));
-      const float py = __shfl(__uint_as_float(e.w), LPE * qo + lane_of(so));
-      uint32_t pm = (uint32_t)__shfl((int)packed, LPE * qo + LPE - 1);
-      if (FMT == 2) pm |= (uint32_t)__shfl((int)st16, LPE * qo + lane_of(6)) << 16;
+      // (the trips back to the owner lane, from addresses made with send(): lane LPE qo + x is qa + 4 x)
+      const float px = __int_as_float(bperm(qa + 4 * lane_of(so), (int)e.z));
+      const float py = __int_as_float(bperm(qa + 4 * lane_of(so), (int)e.w));
+      uint32_t pm = (uint32_t)bperm(qa + 4 * (LPE - 1), (int)packed);
+      if (FMT == 2) pm |= (uint32_t)bperm(qa + 4 * lane_of(6), (int)st16) << 16;
       { const bool own = ro == it; cnt = own ? co : cnt; rx = own ? px : rx; ry = own ? py : ry; meta = own ? pm : meta; }
     }
     beyond = cnt >= KC || ((meta >> 26) & 1u);
@@ -398,7 +408,8 @@ typedef AnyMDPCoopLineN<XV_ANYMDP_TOK_LPE, XV_ANYMDP_COOP_CONTIG != 0> AnyMDPTok
 // mixed-batch kernel of mixed.hip hands every family a contiguous range of its workgroups)
 // HAND: the launch may start while the launch of the step before it is still running (xv_anymdp_step_many, overlap mode:
 //     consecutive steps alternate between two HIP streams with no dependency between the streams).  Everything that does not
-//     depend on the env records is done first (action and reset-record loads, the transition uniform); then the wave waits
+//     depend on the env records is done first (action and reset-record loads, all three draws, the clamped action, the line
+//     index but for its state term, the uniforms' trips to the reader lanes, the outcome of a restart); then the wave waits
 //     until its envs' records carry this launch's tag — bits 18..31 of the record's first word = the low 14 bits of the tick
 //     of the step that may take the env next: the step before stores record and tag with ONE 8-byte agent-scope store, so
 //     the record IS the hand-off (a separate word costs a second round trip: 4.45 vs 3.95 us per step).  Every lane polls
@@ -408,10 +419,14 @@ typedef AnyMDPCoopLineN<XV_ANYMDP_TOK_LPE, XV_ANYMDP_COOP_CONTIG != 0> AnyMDPTok
 //     which its owner re-tags for the NEXT step — a late look would never see this step's tag.  The wait is bounded
 //     (xv_hand.h: polls AND wall clock): on expiry the wave goes on and sets XV_DEVERR_HANDOFF — wrong results, flagged,
 //     never a hang.
-template <bool INJECT, int G, bool ROLLOUT, bool TICKDEV = false, int BK = 0, bool HAND = false>
-__device__ __forceinline__ void anymdp_step_body(const AnyMDPArgs& P, const AnyMDPStepIO& io, int T_steps, int mode, int bid) {
+// MODE: the auto-reset mode as a compile-time value (XV_AUTORESET_*), or -1: the `mode` argument.  With it the tail behind the
+//     table line holds no kernel-argument load and only the selects of its mode (anymdp_select_variant lists what is built).
+template <bool INJECT, int G, bool ROLLOUT, bool TICKDEV = false, int BK = 0, bool HAND = false, int MODE = -1>
+__device__ __forceinline__ void anymdp_step_body(const AnyMDPArgs& P, const AnyMDPStepIO& io, int T_steps, int mode_arg, int bid) {
   constexpr bool FAST = G > 0;
   constexpr int GG = G > 0 ? G : 1;
+  static_assert(!HAND || (FAST && !ROLLOUT && !INJECT), "HAND: one free-running vector step on the fast tables");
+  const int mode = MODE >= 0 ? MODE : mode_arg;
   const int i = bid * blockDim.x + threadIdx.x;
   const bool valid = i < P.n_env;
   const int ic = valid ? i : P.n_env - 1;
@@ -451,10 +466,60 @@ __device__ __forceinline__ void anymdp_step_body(const AnyMDPArgs& P, const AnyM
   // the launch tick: a kernel argument, or — device tick mode of the engine (xv_engine_set_device_tick) and graph replays
   // of step_many — relative to the engine's / the graph's tick word in device memory
   const uint64_t tick0 = TICKDEV ? *P.tick_dev + P.tick : xv_launch_tick(P.tick, P.tick_dev);
-  xv_u32x4 w_pre{0u, 0u, 0u, 0u};
-  if (HAND) {
-    w_pre = xv_env_draw(P.seed, gid, tick0, XV_DRAW_STEP);      // the transition uniform does not need the env record
-    asm volatile("" : "+v"(w_pre.x), "+v"(w_pre.y), "+v"(w_pre.z), "+v"(w_pre.w));      // made here, in front of the wait
+  // HAND: everything that is a function of gid, tick, action, reset units and kernel arguments alone, made in front of the wait
+  // and pinned there (the empty asm: hipcc otherwise sinks a value to its first use, behind the wait) —
+  //   pre_u, pre_z, pre_ur    the step's three draws
+  //   pre_a, pre_abad         the clamped action, and whether it was out of range (whether that is an ERROR needs the record)
+  //   pre_line, pre_smul      the table line of inner state s is pre_line + s * pre_smul (bucket line; fence line without BK)
+  //   pre_row                 row index of state 0 under the action (the fall-back's rows: pre_row + s * A)
+  //   rst_s, rst_cterm, rst_obs   the complete outcome of a restart from the reset record
+  // and the uniforms are with the reader lanes of the line (L.send).  Behind the wait remain: the record's fields, one
+  // multiply-add, the line request.
+  double pre_u = 0.0, pre_ur = 0.0;
+  float pre_z = 0.0f;
+  int pre_a = 0, rst_s = 0, rst_cterm = 0, rst_obs = 0;
+  bool pre_abad = false;
+  uint32_t pre_line = 0u, pre_smul = 0u, pre_row = 0u;
+  AnyMDPStepLine L;
+  if constexpr (HAND) {
+    const xv_u32x4 w_pre = xv_env_draw(P.seed, gid, tick0, XV_DRAW_STEP);
+    const xv_u32x4 v_pre = xv_env_draw(P.seed, gid, tick0, XV_DRAW_RESET);
+    pre_u = xv_u53(w_pre.x, w_pre.y);
+    pre_z = xv_normal1(w_pre.z, w_pre.w);
+    pre_ur = xv_u53(v_pre.x, v_pre.y);
+    pre_abad = a_next < 0 || a_next >= A;      // reference: assert action < self.na (:97)
+    pre_a = a_next < 0 ? 0 : (a_next >= A ? A - 1 : a_next);
+    pre_row = ((uint32_t)t * S) * A + (uint32_t)pre_a;
+    if (BK) {
+      pre_line = pre_row * (uint32_t)P.NBK + (uint32_t)(int)(pre_u * (double)P.NBK);
+      pre_smul = (uint32_t)A * (uint32_t)P.NBK;
+    } else {
+      pre_line = pre_row * (uint32_t)P.RL;
+      pre_smul = (uint32_t)A * (uint32_t)P.RL;
+    }
+    const int k0 = (int)(rc01.x <= pre_ur) + (int)(rc01.y <= pre_ur) + (int)(rc2 <= pre_ur);
+    rst_s = (int)(((k0 < 2 ? rids.x : rids.y) >> (16 * (k0 & 1))) & 0xFFFFu);
+    rst_cterm = (int)((s0_term >> k0) & 1u);
+    rst_obs = (int)(((k0 < 2 ? robs.x : robs.y) >> (16 * (k0 & 1))) & 0xFFFFu);
+    if (BK) {
+      L.send(pre_u, lane);
+#pragma unroll
+      for (int it = 0; it < XV_ANYMDP_STEP_LPE; ++it) {
+        int lo = __double2loint(L.ue[it]), hi = __double2hiint(L.ue[it]);
+        asm volatile("" : "+v"(lo), "+v"(hi));
+        L.ue[it] = __hiloint2double(hi, lo);
+      }
+      asm volatile("" : "+v"(L.qa));
+    }
+    {
+      int ulo = __double2loint(pre_u), uhi = __double2hiint(pre_u);
+      int ab = pre_abad ? 1 : 0;
+      asm volatile("" : "+v"(ulo), "+v"(uhi), "+v"(pre_z), "+v"(pre_a), "+v"(ab), "+v"(pre_line), "+v"(pre_row));
+      asm volatile("" : "+v"(rst_s), "+v"(rst_cterm), "+v"(rst_obs), "+v"(max_steps));
+      pre_u = __hiloint2double(uhi, ulo);
+      pre_abad = ab != 0;
+    }
+    if (MODE < 0) asm volatile("" ::"s"(mode));      // a run-time mode is in a register here, not fetched behind the line
     const uint32_t want = XV_ANYMDP_SR_TAG(tick0);
     const uint64_t* rp = reinterpret_cast<const uint64_t*>(P.sr) + ic;
     const uint64_t t_begin = wall_clock64();
@@ -490,14 +555,18 @@ __device__ __forceinline__ void anymdp_step_body(const AnyMDPArgs& P, const AnyM
     double u, u_reset = 0.0;
     float z = 0.0f;
     xv_u32x4 w{0u, 0u, 0u, 0u};
-    if (INJECT) {
+    if (HAND) {
+      u = pre_u; z = pre_z; u_reset = pre_ur;
+    } else if (INJECT) {
       u = io.u[o];
     } else {
-      w = HAND ? w_pre : xv_env_draw(P.seed, gid, tick0 + (uint64_t)ts, XV_DRAW_STEP);
+      w = xv_env_draw(P.seed, gid, tick0 + (uint64_t)ts, XV_DRAW_STEP);
       u = xv_u53(w.x, w.y);
     }
     auto late_draws = [&]() {
-      if (INJECT) {
+      if (HAND) {
+        // made in front of the wait
+      } else if (INJECT) {
         z = io.z[o];
         u_reset = io.u_reset[o];
       } else {
@@ -521,28 +590,32 @@ __device__ __forceinline__ void anymdp_step_body(const AnyMDPArgs& P, const AnyM
       }
       if (valid) io.action_out[o] = a;
     }
-    if (a < 0 || a >= A) {  // reference: assert action < self.na (:97)
+    if (HAND) {
+      a = pre_a;      // (the range error is raised with the tail's selects: it needs the record's need_reset)
+    } else if (a < 0 || a >= A) {  // reference: assert action < self.na (:97)
       if (!(mode == XV_AUTORESET_NEXT_STEP && nr)) err |= XV_DEVERR_ACTION_RANGE;
       a = a < 0 ? 0 : A - 1;
     }
-    const uint32_t rowidx = ((uint32_t)t * S + s) * A + a;
+    // (HAND: the same value mod 2^32; used by the fall-back only, the line index below is one multiply-add)
+    const uint32_t rowidx = HAND ? pre_row + (uint32_t)s * (uint32_t)A : ((uint32_t)t * S + s) * A + a;
 
     // ---- s' = upper_bound(cdf[s,a,:], u)   (:99-100, numpy.random.choice), its reward pair (:103-104),
     //      observation id (:146-148) and terminal flag (:107-108) ----
-    int s2, obs2;
-    bool term2;
-    float2 rsv;
+    int s2 = 0, obs2 = 0;
+    bool term2 = false;
+    float2 rsv = make_float2(0.0f, 0.0f);
     bool need_fence = true;
     if (BK) {
       // the ONE line: bucket floor(u * NBK) of the row, read by the lanes of the env's group (AnyMDPCoopLineN)
-      const uint32_t bk = rowidx * (uint32_t)P.NBK + (uint32_t)(int)(u * (double)P.NBK);
-      AnyMDPStepLine L;
+      const uint32_t bk = HAND ? pre_line + (uint32_t)s * pre_smul : rowidx * (uint32_t)P.NBK + (uint32_t)(int)(u * (double)P.NBK);
       L.issue(P.bucket, bk, lane);
       if (ROLLOUT && io.action && ts + 1 < T) a_next = io.action[o + P.n_env];   // prefetch behind the line
-      __builtin_amdgcn_sched_barrier(0);
-      late_draws();
-      __builtin_amdgcn_sched_barrier(0);
-      L.send(u, lane);
+      if (!HAND) {      // (HAND: draws and uniforms are where they belong already)
+        __builtin_amdgcn_sched_barrier(0);
+        late_draws();
+        __builtin_amdgcn_sched_barrier(0);
+        L.send(u, lane);
+      }
       __builtin_amdgcn_sched_barrier(0);
       bool beyond_own;
       float rx, ry;
@@ -556,7 +629,8 @@ __device__ __forceinline__ void anymdp_step_body(const AnyMDPArgs& P, const AnyM
       need_fence = __ballot(beyond_own) != 0ull;
     }
     if (FAST && need_fence) {
-      const uint32_t fl = rowidx * (uint32_t)P.RL;   // fence line of the row
+      // fence line of the row
+      const uint32_t fl = (HAND && !BK) ? pre_line + (uint32_t)s * pre_smul : rowidx * (uint32_t)P.RL;
       // link 2: fence lines.  Iteration `it` serves envs 8*it .. 8*it+7: lanes 8q..8q+7 read the line of env 8*it+q.
       uint32_t li[8];
 #pragma unroll
@@ -673,7 +747,41 @@ __device__ __forceinline__ void anymdp_step_body(const AnyMDPArgs& P, const AnyM
     float o_r, o_rgt;
     bool o_term, o_trunc;
     bool do_reset = false;
-    if (mode == XV_AUTORESET_NEXT_STEP && nr) {
+    if constexpr (HAND) {
+      // the tail as selects: the record first (it is the hand-off), from values that were ready before the line came.
+      //   skip: NEXT_STEP, the call after a done — the action is ignored, the reset observation returned
+      //   stuck: DISABLED, stepping from a terminal state — env untouched, error bit set (reference :95-96)
+      //   otherwise the step proper (:99-114), restarted in the same step under SAME_STEP
+      const bool skip = mode == XV_AUTORESET_NEXT_STEP && nr != 0;
+      const bool stuck = mode == XV_AUTORESET_DISABLED && cterm != 0;
+      const bool norm = !skip && !stuck;
+      const int steps1 = steps + 1;
+      const bool done = term2 || steps1 >= max_steps;
+      const bool restart = norm && mode == XV_AUTORESET_SAME_STEP && done;
+      do_reset = skip || restart;
+      const int s_keep = s, steps_keep = steps;
+      s = do_reset ? rst_s : (norm ? s2 : s);
+      cterm = do_reset ? rst_cterm : (norm ? (term2 ? 1 : 0) : cterm);
+      nr = do_reset ? 0 : ((norm && mode == XV_AUTORESET_NEXT_STEP && done) ? 1 : nr);
+      steps = do_reset ? 0 : (norm ? steps1 : steps);
+      {
+        // hand the envs on BEFORE the outputs leave: record and tag of the next step in one 8-byte agent-scope store
+        const uint2 q = anymdp_sr_pack(s, steps, nr, cterm);
+        const uint32_t x = q.x | (XV_ANYMDP_SR_TAG(tick0 + 1u) << XV_ANYMDP_SR_TAG_SHIFT);
+        if (valid) __hip_atomic_store(reinterpret_cast<uint64_t*>(P.sr) + i, (uint64_t)x | ((uint64_t)q.y << 32), __ATOMIC_RELAXED,
+                                      __HIP_MEMORY_SCOPE_AGENT);
+      }
+      if (pre_abad && !skip) err |= XV_DEVERR_ACTION_RANGE;
+      if (stuck) err |= XV_DEVERR_STEP_TERMINAL;
+      o_rgt = norm ? rsv.x : 0.0f;
+      o_r = norm ? fmaf(rsv.y, z, rsv.x) : 0.0f;               // :105 normal(mu, sigma) = mu + sigma*z
+      o_term = norm ? term2 : stuck;
+      o_trunc = norm ? steps1 >= max_steps : (stuck && steps_keep >= max_steps);
+      o_obs = do_reset ? rst_obs : obs2;
+      if (MODE < 0 || MODE == XV_AUTORESET_DISABLED)
+        if (stuck) o_obs = P.state_map[(size_t)t * S + s_keep];
+      o_fobs = restart ? obs2 : -1;
+    } else if (mode == XV_AUTORESET_NEXT_STEP && nr) {
       // the call after a done ignores the action and returns the reset observation
       do_reset = true;
       o_r = 0.0f; o_rgt = 0.0f; o_term = false; o_trunc = false; o_obs = 0;
@@ -700,7 +808,7 @@ __device__ __forceinline__ void anymdp_step_body(const AnyMDPArgs& P, const AnyM
         }
       }
     }
-    if (do_reset) {                                            // reset(): :85-90
+    if (!HAND && do_reset) {                                   // reset(): :85-90 (HAND: rst_*, selected above)
       if (FAST) {
         // upper_bound over the 4 padded CDF entries; ids, terminal flags and observation ids come packed
         const int k0 = (int)(rc01.x <= u_reset) + (int)(rc01.y <= u_reset) + (int)(rc2 <= u_reset);
@@ -714,13 +822,6 @@ __device__ __forceinline__ void anymdp_step_body(const AnyMDPArgs& P, const AnyM
       }
       steps = 0;
       nr = 0;
-    }
-    if (HAND) {
-      // hand the envs on BEFORE the outputs leave: record and tag of the next step in one 8-byte agent-scope store
-      const uint2 q = anymdp_sr_pack(s, steps, nr, cterm);
-      const uint32_t x = q.x | (XV_ANYMDP_SR_TAG(tick0 + 1u) << XV_ANYMDP_SR_TAG_SHIFT);
-      if (valid) __hip_atomic_store(reinterpret_cast<uint64_t*>(P.sr) + i, (uint64_t)x | ((uint64_t)q.y << 32), __ATOMIC_RELAXED,
-                                    __HIP_MEMORY_SCOPE_AGENT);
     }
     if (valid) {
 #if XV_ANYMDP_NT_OUT
@@ -748,9 +849,9 @@ __device__ __forceinline__ void anymdp_step_body(const AnyMDPArgs& P, const AnyM
   if (err) atomicOr(P.err, err);
 }
 
-template <bool INJECT, int G, bool ROLLOUT, bool TICKDEV = false, int BK = 0, bool HAND = false>
+template <bool INJECT, int G, bool ROLLOUT, bool TICKDEV = false, int BK = 0, bool HAND = false, int MODE = -1>
 __global__ __launch_bounds__(256) void anymdp_step_kernel(AnyMDPArgs P, AnyMDPStepIO io, int T_steps, int mode) {
-  anymdp_step_body<INJECT, G, ROLLOUT, TICKDEV, BK, HAND>(P, io, T_steps, mode, (int)blockIdx.x);
+  anymdp_step_body<INJECT, G, ROLLOUT, TICKDEV, BK, HAND, MODE>(P, io, T_steps, mode, (int)blockIdx.x);
 }
 // An expired hand-off (XV_DEVERR_HANDOFF set during an overlapped call: a wave went on with a record nobody had handed it)
 // is REPAIRED: the call's opening kernel kept every env record and the error word as they were at entry (snap, w[0]); this
@@ -1911,15 +2012,23 @@ extern "C" int xv_anymdp_reset_injected(xv_anymdp* h, const uint8_t* mask, const
 // alike:  BK == 0: G = 0 .. 5;  BK == 1 (7 cuts per line: S <= 256, i.e. G <= 3): G = 1 .. 3;  BK == 2: G = 1 .. 5.  A larger G
 // takes the last of its row.  f gets the pair as a type with compile-time members g and bk.  (G = 0 has no HAND kernel and
 // no replay kernel: those callers leave it out with `if constexpr`.)
-template <int G, int BK> struct AnyMDPVariant { static constexpr int g = G, bk = BK; };
-template <class F>
-static auto anymdp_select_variant(int G, int bk, F&& f) {
-  if (bk == 1) return G == 1 ? f(AnyMDPVariant<1, 1>{}) : G == 2 ? f(AnyMDPVariant<2, 1>{}) : f(AnyMDPVariant<3, 1>{});
+// The third member, md, is the auto-reset mode the kernel is compiled for (anymdp_step_body's MODE): SAME_STEP — the default
+// and what training loops run — has kernels of its own for the single vector step and the step_many graph nodes; every other
+// mode, and every caller that passes -1 (roll-outs, the replay kernels), gets md = -1: the mode is the kernel's argument.
+template <int G, int BK, int MD = -1> struct AnyMDPVariant { static constexpr int g = G, bk = BK, md = MD; };
+template <int MD, class F>
+static auto anymdp_select_variant_md(int G, int bk, F&& f) {
+  if (bk == 1) return G == 1 ? f(AnyMDPVariant<1, 1, MD>{}) : G == 2 ? f(AnyMDPVariant<2, 1, MD>{}) : f(AnyMDPVariant<3, 1, MD>{});
   if (bk == 2)
-    return G == 1 ? f(AnyMDPVariant<1, 2>{}) : G == 2 ? f(AnyMDPVariant<2, 2>{}) : G == 3 ? f(AnyMDPVariant<3, 2>{})
-           : G == 4 ? f(AnyMDPVariant<4, 2>{}) : f(AnyMDPVariant<5, 2>{});
-  return G == 0 ? f(AnyMDPVariant<0, 0>{}) : G == 1 ? f(AnyMDPVariant<1, 0>{}) : G == 2 ? f(AnyMDPVariant<2, 0>{})
-         : G == 3 ? f(AnyMDPVariant<3, 0>{}) : G == 4 ? f(AnyMDPVariant<4, 0>{}) : f(AnyMDPVariant<5, 0>{});
+    return G == 1 ? f(AnyMDPVariant<1, 2, MD>{}) : G == 2 ? f(AnyMDPVariant<2, 2, MD>{}) : G == 3 ? f(AnyMDPVariant<3, 2, MD>{})
+           : G == 4 ? f(AnyMDPVariant<4, 2, MD>{}) : f(AnyMDPVariant<5, 2, MD>{});
+  return G == 0 ? f(AnyMDPVariant<0, 0, MD>{}) : G == 1 ? f(AnyMDPVariant<1, 0, MD>{}) : G == 2 ? f(AnyMDPVariant<2, 0, MD>{})
+         : G == 3 ? f(AnyMDPVariant<3, 0, MD>{}) : G == 4 ? f(AnyMDPVariant<4, 0, MD>{}) : f(AnyMDPVariant<5, 0, MD>{});
+}
+template <class F>
+static auto anymdp_select_variant(int G, int bk, int mode, F&& f) {
+  if (mode == XV_AUTORESET_SAME_STEP) return anymdp_select_variant_md<XV_AUTORESET_SAME_STEP>(G, bk, f);
+  return anymdp_select_variant_md<-1>(G, bk, f);
 }
 // (G, BK) of a handle under the search in effect, as anymdp_select_variant takes them
 static inline int anymdp_variant_g(const xv_anymdp* h, int eff) { return eff == XV_ANYMDP_SEARCH_BINARY ? 0 : h->a.G; }
@@ -1942,10 +2051,11 @@ static int anymdp_launch_step(xv_anymdp* h, const AnyMDPStepIO& io, int T, int m
   const int eff = anymdp_effective_search(h);
   // (bucket search: any packing but the 7-cut one is served by the 6-cut kernels here)
   const int bk = eff == XV_ANYMDP_SEARCH_BUCKET ? (h->a.bfmt == 1 ? 1 : 2) : 0;
-  anymdp_select_variant(anymdp_variant_g(h, eff), bk, [&](auto v) {
+  // (the roll-out keeps the mode as an argument: one kernel per layout)
+  anymdp_select_variant(anymdp_variant_g(h, eff), bk, roll ? -1 : mode, [&](auto v) {
     using V = decltype(v);
     if (roll) hipLaunchKernelGGL((anymdp_step_kernel<INJECT, V::g, true, false, V::bk>), grid, block, 0, h->eng->stream, h->a, io, T, mode);
-    else hipLaunchKernelGGL((anymdp_step_kernel<INJECT, V::g, false, false, V::bk>), grid, block, 0, h->eng->stream, h->a, io, T, mode);
+    else hipLaunchKernelGGL((anymdp_step_kernel<INJECT, V::g, false, false, V::bk, false, V::md>), grid, block, 0, h->eng->stream, h->a, io, T, mode);
   });
   XV_LAUNCH_CHECK();
   return XV_OK;

@@ -47,13 +47,13 @@ template <class K> static void anymdp_key_store(K* have, const K& want) { memcpy
 // One ring cycle of xv_anymdp_step_many as a graph: `period` step-kernel nodes in a chain (node j reads actions slot j,
 // writes output slot j, draws with tick *d_tick + j) and a node that advances *d_tick by `period`.  Back-to-back
 // dependent launches cost ~3.3 us each on a stream and ~1.6 us as graph nodes (scripts/devtools/graph_floor.hip).
-static void* anymdp_graph_step_fn(const xv_anymdp* h, int eff, bool hand = false) {
+static void* anymdp_graph_step_fn(const xv_anymdp* h, int eff, int mode, bool hand = false) {
   // the hand-off (HAND) kernels exist for the fence and bucket searches only: nullptr for the binary search
-  return anymdp_select_variant(anymdp_variant_g(h, eff), anymdp_variant_bk(h, eff), [&](auto v) -> void* {
+  return anymdp_select_variant(anymdp_variant_g(h, eff), anymdp_variant_bk(h, eff), mode, [&](auto v) -> void* {
     using V = decltype(v);
     if constexpr (V::g != 0)
-      if (hand) return reinterpret_cast<void*>(&anymdp_step_kernel<false, V::g, false, true, V::bk, true>);
-    return hand ? nullptr : reinterpret_cast<void*>(&anymdp_step_kernel<false, V::g, false, true, V::bk>);
+      if (hand) return reinterpret_cast<void*>(&anymdp_step_kernel<false, V::g, false, true, V::bk, true, V::md>);
+    return hand ? nullptr : reinterpret_cast<void*>(&anymdp_step_kernel<false, V::g, false, true, V::bk, false, V::md>);
   });
 }
 
@@ -78,7 +78,7 @@ struct AnyMDPStepNode {
 // the chain of `period` step nodes of handle `h` appended to `graph` behind `prev` (nullptr: a root); -> its last node
 static bool anymdp_add_chain(xv_anymdp* h, hipGraph_t graph, hipGraphNode_t* prev, uint64_t* d_tick, int eff, int period,
                              const AnyMDPRings& R, int mode) {
-  void* fn = anymdp_graph_step_fn(h, eff);
+  void* fn = anymdp_graph_step_fn(h, eff, mode);
   for (int j = 0; j < period; ++j) {
     hipKernelNodeParams np;
     memset(&np, 0, sizeof(np));
@@ -227,7 +227,7 @@ static bool anymdp_launch_replay(xv_anymdp* h, int eff, const AnyMDPStepIO& io, 
   a.seed = h->eng->seed; a.gid_base = h->eng->env_id_base; a.tick = t0; a.tick_dev = nullptr;
   const dim3 grid(xv_div_up(h->a.n_env, 256)), block(256);
   uint32_t* h_fell = h->gate.d_issued + 1;
-  anymdp_select_variant(h->a.G, anymdp_variant_bk(h, eff), [&](auto v) {
+  anymdp_select_variant(h->a.G, anymdp_variant_bk(h, eff), -1, [&](auto v) {
     using V = decltype(v);
     if constexpr (V::g != 0)
       hipLaunchKernelGGL((anymdp_replay_kernel<V::g, V::bk>), grid, block, 0, h->eng->stream, a, io, period, cycles, mode,
@@ -265,7 +265,7 @@ static int anymdp_pipe_graphs(xv_anymdp* h, int D, int period, int cycles, const
   want.period = period; want.mode = mode; want.search = eff; want.stride = R.stride;
   anymdp_ring_pointers(R, want.ptrs);
   want.bucket = (const void*)h->a.bucket; want.seed = h->eng->seed; want.gid_base = h->eng->env_id_base;
-  void* fn = anymdp_graph_step_fn(h, eff, true);
+  void* fn = anymdp_graph_step_fn(h, eff, mode, true);
   AnyMDPStepNode sn;
   return anymdp_pipe_graph_set(h, false, D, period, cycles, want, &h->pipe_key, [&](int g, int slot, int q, hipKernelNodeParams* np) {
     sn.fill(np, h, fn, h->d_ptick + q, g, slot, R, mode);
@@ -359,7 +359,7 @@ static int anymdp_pipe_call(xv_anymdp* h, int n_steps, int ring_period, int min_
 static int anymdp_pipe_run(xv_anymdp* h, int n_steps, int period, const AnyMDPRings& R, int mode, int* issued) {
   static const int min_steps = getenv("XV_ANYMDP_PIPE_MIN_STEPS") ? atoi(getenv("XV_ANYMDP_PIPE_MIN_STEPS")) : XV_ANYMDP_PIPE_GRAPH_MIN;
   const int eff = anymdp_effective_search(h);
-  return anymdp_pipe_call(h, n_steps, period, min_steps, anymdp_graph_step_fn(h, eff, true), false, R.obs, (size_t)period * (size_t)h->a.n_env,
+  return anymdp_pipe_call(h, n_steps, period, min_steps, anymdp_graph_step_fn(h, eff, mode, true), false, R.obs, (size_t)period * (size_t)h->a.n_env,
                           issued, [&](int D, int cycles) { return anymdp_pipe_graphs(h, D, period, cycles, R, mode); },
                           [&](int k, uint64_t t0) { return anymdp_launch_replay(h, eff, R.slot(0), period, k / period, mode, t0); });
 }
