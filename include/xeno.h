@@ -1183,6 +1183,45 @@ int xv_metalang1_generate(xv_metalang1* h, int L, double mask_ratio, const int32
                           const int32_t* noise_value, const double* u_noise, const double* u_mask, int32_t* features,
                           int32_t* labels, uint8_t* kinds, int32_t* n_segments);
 
+/* MetaLangV2 / MetaLangV1 tasks made on the device (task_sampler.py TaskSamplerV2 :22-50, TaskSamplerV1 :52-73), written in
+ * the layouts xv_metalang_set_task / xv_metalang1_set_task borrow.  The reference tests no task: every candidate is one.
+ * Pure functions of (seed, task index t in [task_base, task_base + n_task), the arguments): the calls neither read nor
+ * advance the engine's tick and never set its error word; a task does not depend on the launch it is made in.  Draws are
+ * Philox in the index layout — counter = {t lo, t hi, sub, purpose | tick << 8}, key = seed — with u53 the 53-bit uniform
+ * of two words (first: words 0,1; second: words 2,3):
+ *   purpose 0, tick 0, sub 0: n_gram of the task = n_gram_list[floor(first m)], m = n_list (HOST ints; an int is a list of one)
+ *   V2, purposes 1 .. 5 (word_emb, weights_inputlayer, bias_inputlayer, weights_outputlayer, bias_outputlayer), tick 0,
+ *     sub = q >> 1: element q of the array's flat [V][E], [n][E][H], [n][H], [H][V], [V] is half q & 1 of the fp64
+ *     Box-Muller pair r cos(a), r sin(a), r = sqrt(-2 log(1 - first)), a = 2 pi second.  The input layer is stored padded to
+ *     n_gram_max slots, exact zeros at and beyond the task's n; lambda_out [n_task] = lambda, n_gram int32[n_task].
+ *   V1, purpose 6, tick 0, sub = pattern j: length = max(3, k), k ~ Poisson(n_gram) by inversion on `first`: the smallest
+ *     k with first < sum_{i<=k} p_i, p_0 = exp_neg_n_gram (exp(-n_gram) per list entry, HOST doubles, formed once by the
+ *     caller), p_i = p_{i-1} n_gram / i, the search cut at k = 2 n_gram + 64: fp64 products, quotients and sums only.
+ *   V1, purpose 7, tick = pattern j, sub = pos >> 1: token pos = floor(u n_vocab), u half pos & 1 of the call.
+ * xv_metalang1_sample_lengths -> lengths int32[n_task n_patterns], n_gram int32[n_task]; xv_metalang1_sample_offsets (one
+ * call over ALL tasks) -> task_pattern_offset int32[n_task + 1] = t n_patterns, pattern_token_offset int32[n_task n_patterns
+ * + 1] = the exclusive prefix sum of lengths (saturated at 2^31 - 1), *n_token_total (device int64) the sum itself, which
+ * the caller reads to size `tokens` and to refuse more than 2^31 - 1; xv_metalang1_sample_tokens writes tokens[token_base ..
+ * token_base + n_token), the tokens of the n_task tasks whose offsets (n_task n_patterns + 1 entries, in the whole array's
+ * numbering) pattern_token_offset points at.  All buffers are device pointers unless marked HOST.
+ * Limits (XV_ERR_UNSUPPORTED beyond, the text names the limit): V2 as xv_metalang_create (n_vocab <= 1024, n_hidden <= 128,
+ * n_emb <= 64, n_gram <= n_gram_max <= 8); V1 1 <= n_gram <= 512 (exp(-n_gram) stays a normal double and the search
+ * short), n_patterns <= 2^20 (the tick field), n_task n_patterns <= 2^31 - 2; lists of 1 .. 16 entries. */
+#define XV_METALANG_SAMPLER_LIST_MAX 16
+#define XV_METALANG1_SAMPLER_NGRAM_MAX 512
+#define XV_METALANG1_SAMPLER_PATTERNS_MAX (1 << 20)
+int xv_metalang_sample_tasks(xv_engine* e, uint64_t seed, int64_t task_base, int n_task, int n_vocab, int n_emb, int n_hidden,
+                             const int32_t* n_gram_list, int n_list, int n_gram_max, double lambda, double* word_emb,
+                             double* weights_inputlayer, double* bias_inputlayer, double* weights_outputlayer,
+                             double* bias_outputlayer, double* lambda_out, int32_t* n_gram);
+int xv_metalang1_sample_lengths(xv_engine* e, uint64_t seed, int64_t task_base, int n_task, int n_patterns,
+                                const int32_t* n_gram_list, const double* exp_neg_n_gram, int n_list, int32_t* n_gram,
+                                int32_t* lengths);
+int xv_metalang1_sample_offsets(xv_engine* e, int n_task, int n_patterns, const int32_t* lengths,
+                                int32_t* task_pattern_offset, int32_t* pattern_token_offset, int64_t* n_token_total);
+int xv_metalang1_sample_tokens(xv_engine* e, uint64_t seed, int64_t task_base, int n_task, int n_patterns, int n_vocab,
+                               const int32_t* pattern_token_offset, int token_base, int n_token, int32_t* tokens);
+
 /* ------------------------------------------------------------------------------------------------
  * MetaLMV3 — reference: xenoverse/metalang/metalangv3.py (MetaLMV3Env :4-42) over xenoverse/utils/random_nn.py RandomLM
  * :218-344 and its decoders softmax_sampling :193-198, rnd_sampling :200-206, high_sampling :208-216; tasks from

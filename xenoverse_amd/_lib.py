@@ -151,6 +151,10 @@ SIGNATURES = {
     "xv_metalang1_destroy": [c_void_p],
     "xv_metalang1_set_task": [c_void_p, c_int, c_int, c_int] + [c_void_p] * 6,
     "xv_metalang1_generate": [c_void_p, c_int, C.c_double, c_void_p, c_int] + [c_void_p] * 7,
+    "xv_metalang_sample_tasks": [c_void_p, c_u64, c_i64] + [c_int] * 4 + [c_void_p, c_int, c_int, C.c_double] + [c_void_p] * 7,
+    "xv_metalang1_sample_lengths": [c_void_p, c_u64, c_i64, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p],
+    "xv_metalang1_sample_offsets": [c_void_p, c_int, c_int] + [c_void_p] * 4,
+    "xv_metalang1_sample_tokens": [c_void_p, c_u64, c_i64, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p],
     "xv_metalm_create": [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, C.POINTER(c_void_p)],
     "xv_metalm_destroy": [c_void_p],
     "xv_metalm_set_task": [c_void_p, c_int] + [c_void_p] * 6,

@@ -32,9 +32,18 @@ class MetaLangV2Batch(object):
 
     # ---- tasks ----------------------------------------------------------------------------------------------------
     def set_task(self, tasks, group_task_index=None):
-        """tasks: one task dict (TaskSamplerV2) or a list of them; group_task_index int[n_group]: the task of every group
+        """tasks: one task dict (TaskSamplerV2), a list of them, or the device tables of sample_tasks_v2_device (borrowed as
+        they are: keep them unchanged while the handle uses them); group_task_index int[n_group]: the task of every group
         (default: the only task; task g for group g when there are n_group tasks)"""
         import torch
+        from .device_sampler_v2 import TABLE_KEYS, check_tables_v2, is_tables_v2
+        if is_tables_v2(tasks):      # the device tables of sample_tasks_v2_device: borrowed as they are, no host copy
+            n_task, V, E, H, NG = check_tables_v2(tasks)
+            gti = self._group_task_index(n_task, group_task_index)
+            dev = [tasks[k] if tasks[k].is_contiguous() else tasks[k].contiguous() for k in TABLE_KEYS]
+            if dev[0].device != torch.device(self.device):
+                raise ValueError("the tables are on %s, this handle on %s" % (dev[0].device, self.device))
+            return self._set_tables(dev + [torch.from_numpy(gti).to(self.device)], n_task, V, E, H, NG)
         if isinstance(tasks, dict):
             tasks = [tasks]
         if not len(tasks):
@@ -46,16 +55,7 @@ class MetaLangV2Batch(object):
                 raise ValueError("task %d has (n_vocab, n_emb, n_hidden) = %s, task 0 has %s: one handle holds one size"
                                  % (k, s[:3], (V, E, H)))
         n_task, NG = len(tasks), max(s[3] for s in sizes)
-        if group_task_index is None:
-            if n_task == 1:
-                group_task_index = np.zeros(self.n_group, np.int32)
-            elif n_task == self.n_group:
-                group_task_index = np.arange(self.n_group, dtype=np.int32)
-            else:
-                raise ValueError("%d tasks for %d groups: give group_task_index" % (n_task, self.n_group))
-        gti = np.ascontiguousarray(group_task_index, dtype=np.int32)
-        if gti.shape != (self.n_group,) or gti.min() < 0 or gti.max() >= n_task:
-            raise ValueError("group_task_index must be int[n_group] with values in [0, %d)" % n_task)
+        gti = self._group_task_index(n_task, group_task_index)
         w_in = np.zeros((n_task, NG, E, H))
         b_in = np.zeros((n_task, NG, H))
         for k, (t, s) in enumerate(zip(tasks, sizes)):
@@ -66,7 +66,26 @@ class MetaLangV2Batch(object):
                 np.stack([np.asarray(t["bias_outputlayer"], np.float64).reshape(V) for t in tasks]),
                 np.array([float(t["_lambda"]) for t in tasks], np.float64),
                 np.array([s[3] for s in sizes], np.int32), gti]
-        dev = [torch.from_numpy(np.ascontiguousarray(a)).to(self.device) for a in host]
+        self._set_tables([torch.from_numpy(np.ascontiguousarray(a)).to(self.device) for a in host], n_task, V, E, H, NG)
+
+    def _group_task_index(self, n_task, group_task_index):
+        """the task of every group -> int32[n_group]; default: the only task, task g for group g when there are n_group"""
+        if group_task_index is None:
+            if n_task == 1:
+                group_task_index = np.zeros(self.n_group, np.int32)
+            elif n_task == self.n_group:
+                group_task_index = np.arange(self.n_group, dtype=np.int32)
+            else:
+                raise ValueError("%d tasks for %d groups: give group_task_index" % (n_task, self.n_group))
+        if hasattr(group_task_index, "detach"):
+            group_task_index = group_task_index.detach().cpu().numpy()
+        gti = np.ascontiguousarray(group_task_index, dtype=np.int32)
+        if gti.shape != (self.n_group,) or gti.min() < 0 or gti.max() >= n_task:
+            raise ValueError("group_task_index must be int[n_group] with values in [0, %d)" % n_task)
+        return gti
+
+    def _set_tables(self, dev, n_task, V, E, H, NG):
+        """dev: the eight device tensors of xv_metalang_set_task, in its order; the handle borrows them"""
         if self._h is not None and (V, E, H, NG) != (self.n_vocab, self.n_emb, self.n_hidden, self.n_gram_max):
             self._destroy()
         if self._h is None:

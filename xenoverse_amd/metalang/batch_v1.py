@@ -30,25 +30,25 @@ class MetaLangV1Batch(object):
 
     # ---- tasks ----------------------------------------------------------------------------------------------------
     def set_task(self, tasks, seq_task_index=None):
-        """tasks: one task dict (TaskSamplerV1) or a list of them; seq_task_index int[n_seq]: the task of every sequence
+        """tasks: one task dict (TaskSamplerV1), a list of them, or the device tables of sample_tasks_v1_device (borrowed as
+        they are: keep them unchanged while the handle uses them); seq_task_index int[n_seq]: the task of every sequence
         (default: the only task; task i for sequence i when there are n_seq tasks)"""
         import torch
+        from .device_sampler_v1 import TABLE_KEYS, check_tables_v1, is_tables_v1
+        if is_tables_v1(tasks):      # the device tables of sample_tasks_v1_device: no host copy
+            n_task, n_pattern, n_token = check_tables_v1(tasks)
+            sti = self._seq_task_index(n_task, seq_task_index)
+            dev = [tasks[k] if tasks[k].is_contiguous() else tasks[k].contiguous() for k in TABLE_KEYS]
+            if dev[0].device != torch.device(self.device):
+                raise ValueError("the tables are on %s, this handle on %s" % (dev[0].device, self.device))
+            return self._set_tables(dev + [torch.from_numpy(sti).to(self.device)], n_task, n_pattern, n_token)
         if isinstance(tasks, dict):
             tasks = [tasks]
         if not len(tasks):
             raise ValueError("set_task needs at least one task")
         checked = [check_task_v1(t, "task %d" % k) for k, t in enumerate(tasks)]
         n_task = len(tasks)
-        if seq_task_index is None:
-            if n_task == 1:
-                seq_task_index = np.zeros(self.n_seq, np.int32)
-            elif n_task == self.n_seq:
-                seq_task_index = np.arange(self.n_seq, dtype=np.int32)
-            else:
-                raise ValueError("%d tasks for %d sequences: give seq_task_index" % (n_task, self.n_seq))
-        sti = np.ascontiguousarray(seq_task_index, dtype=np.int32)
-        if sti.shape != (self.n_seq,) or sti.min() < 0 or sti.max() >= n_task:
-            raise ValueError("seq_task_index must be int[n_seq] with values in [0, %d)" % n_task)
+        sti = self._seq_task_index(n_task, seq_task_index)
         lens = np.array([len(p) for pats, _, _ in checked for p in pats], np.int64)
         if lens.sum() > 2 ** 31 - 1:
             raise _lib.XenoError("MetaLangV1: %d pattern tokens are more than the supported %d" % (lens.sum(), 2 ** 31 - 1))
@@ -56,9 +56,29 @@ class MetaLangV1Batch(object):
                 np.concatenate([[0], np.cumsum(lens)]).astype(np.int32),
                 np.concatenate([p for pats, _, _ in checked for p in pats]).astype(np.int32),
                 np.array([V for _, V, _ in checked], np.int32), np.array([e for _, _, e in checked], np.float64), sti]
-        dev = [torch.from_numpy(np.ascontiguousarray(a)).to(self.device) for a in host]
+        self._set_tables([torch.from_numpy(np.ascontiguousarray(a)).to(self.device) for a in host], n_task, len(lens),
+                         int(lens.sum()))
+
+    def _seq_task_index(self, n_task, seq_task_index):
+        """the task of every sequence -> int32[n_seq]; default: the only task, task i for sequence i when there are n_seq"""
+        if seq_task_index is None:
+            if n_task == 1:
+                seq_task_index = np.zeros(self.n_seq, np.int32)
+            elif n_task == self.n_seq:
+                seq_task_index = np.arange(self.n_seq, dtype=np.int32)
+            else:
+                raise ValueError("%d tasks for %d sequences: give seq_task_index" % (n_task, self.n_seq))
+        if hasattr(seq_task_index, "detach"):
+            seq_task_index = seq_task_index.detach().cpu().numpy()
+        sti = np.ascontiguousarray(seq_task_index, dtype=np.int32)
+        if sti.shape != (self.n_seq,) or sti.min() < 0 or sti.max() >= n_task:
+            raise ValueError("seq_task_index must be int[n_seq] with values in [0, %d)" % n_task)
+        return sti
+
+    def _set_tables(self, dev, n_task, n_pattern, n_token):
+        """dev: the six device tensors of xv_metalang1_set_task, in its order; the handle borrows them"""
         self.engine.sync()      # the tables a running call reads are let go below
-        _lib.check(self.lib.xv_metalang1_set_task(self._h, n_task, len(lens), int(lens.sum()), *(_lib.ptr(t) for t in dev)))
+        _lib.check(self.lib.xv_metalang1_set_task(self._h, n_task, n_pattern, n_token, *(_lib.ptr(t) for t in dev)))
         self._tables = dev      # borrowed by the handle
         self.n_task = n_task
 

@@ -20,32 +20,50 @@ def _sample_tasks(samples, seed_base, vocab_size, patterns_number, n_gram, error
                           error_ratio=error_rate) for i in range(samples)]
 
 
+def _sample_tables(samples, seed_base, device, vocab_size, patterns_number, n_gram, error_rate):
+    from .device_sampler_v1 import sample_tasks_v1_device
+    n_gram = list(n_gram) if isinstance(n_gram, (list, tuple)) else n_gram
+    return sample_tasks_v1_device(samples, n_vocab=vocab_size, n_patterns=patterns_number, n_gram=n_gram,
+                                  error_ratio=error_rate, seed=seed_base, device=device)
+
+
 def metalang_generator_v1(sample_type="sequences", vocab_size=64, patterns_number=10, n_gram=3, error_rate=0.15, samples=1000,
                           batch_size=1, task_file=None, sequence_length=4096, output_type="txt", output=None,
-                          device="cuda:0", seed=None):
+                          device="cuda:0", seed=None, sampler=None):
+    """sampler: None — tasks come from TaskSamplerV1 on numpy's stream, seeds seed .. seed + samples - 1, as ever; "device" —
+    from sample_tasks_v1_device(seed=seed): made on the GPU and handed to the generator as device tables (other tasks than
+    the former's for the same seed; they are drawn independently, so they are not shuffled)"""
     seed_base = int(time.time() * 1000 % 1000000) if seed is None else int(seed)
     sizes = dict(vocab_size=vocab_size, patterns_number=patterns_number, n_gram=n_gram, error_rate=error_rate)
     if sample_type == "tasks":
         if output is None:
             raise Exception("Must specify --output when sample_type is tasks")
         name = output if output.endswith(".pkl") else output + ".pkl"
+        if sampler == "device":
+            from .device_sampler_v1 import task_dicts_from_device_v1
+            tasks = task_dicts_from_device_v1(_sample_tables(samples, seed_base, device, **sizes))
+        else:
+            tasks = _sample_tasks(samples, seed_base, **sizes)
         with open(name, "wb") as f:
-            pickle.dump(_sample_tasks(samples, seed_base, **sizes), f)
+            pickle.dump(tasks, f)
         return None
     from .batch_v1 import MetaLangV1Batch
     if task_file is None:       # a task of its own for every sample
         batch_size = 1
-        tasks = _sample_tasks(samples, seed_base, **sizes)
+        tasks = _sample_tables(samples, seed_base, device, **sizes) if sampler == "device" else \
+            _sample_tasks(samples, seed_base, **sizes)
     else:
         with open(task_file, "rb") as f:
             tasks = pickle.load(f)
     n_batch = (samples - 1) // batch_size + 1
-    if len(tasks) < n_batch:
-        tasks = tasks * ((n_batch - 1) // len(tasks) + 1)
-    random.Random(seed_base).shuffle(tasks)
+    if isinstance(tasks, list):
+        if len(tasks) < n_batch:
+            tasks = tasks * ((n_batch - 1) // len(tasks) + 1)
+        random.Random(seed_base).shuffle(tasks)
+        tasks = tasks[:n_batch]
     n_seq = n_batch * batch_size
     gen = MetaLangV1Batch(n_seq, device=device, seed=seed_base)
-    gen.set_task(tasks[:n_batch], seq_task_index=numpy.repeat(numpy.arange(n_batch, dtype=numpy.int32), batch_size))
+    gen.set_task(tasks, seq_task_index=numpy.repeat(numpy.arange(n_batch, dtype=numpy.int32), batch_size))
     features, labels = (t.cpu().numpy() for t in gen.generate(sequence_length))
     flags = gen.check_errors()
     gen.close()
@@ -81,6 +99,8 @@ def main(argv=None):
     ap.add_argument("--output", type=str, default=None)
     ap.add_argument("--device", type=str, default="cuda:0")
     ap.add_argument("--seed", type=int, default=None, help="task seeds and the Philox key; default: from the clock, as the reference")
+    ap.add_argument("--sampler", type=str, choices=["device"], default=None,
+                    help="device: make the tasks on the GPU (metalang.sample_tasks_v1_device)")
     metalang_generator_v1(**vars(ap.parse_args(argv)))
 
 
