@@ -538,6 +538,31 @@ int xv_anymdp_sample_tasks(xv_engine* e, uint64_t seed, int64_t cand_base, int n
                            int32_t* max_steps, double* transition, double* reward, double* reward_noise,
                            xv_anymdp_cand_info* info, int32_t* status);
 
+/* Garnet and bandit tasks made on the device (additions within ABI 12; csrc/anymdp_garnet.hip) — reference:
+ * GarnetTaskSampler (task_sampler.py:120-160, task_sampler_utils.py:274-313) and the single-state task of AnyMDPTaskSampler
+ * (task_sampler_utils.py:258-272).  Counter-based draws, index = task (Garnet) or candidate (bandit): a pure function of
+ * (seed, arguments, index) whatever the launch batch, NOT NumPy's stream; the model and its counters are stated in
+ * xenoverse_amd/anymdp/sampler_host_garnet.py, which the kernels equal.
+ * xv_anymdp_sample_garnet: tasks task_base .. task_base + n_task - 1, each written to slot i of the step engine's tables
+ * exactly as build_tables forms them (fence line and block tails zero: xv_anymdp_create completes them) + n_real int32
+ * [n_task], the real state count (S when min_S <= 0, else drawn in min(min_S, S) .. S; states past it are padded: CDF 1.0,
+ * zero pairs, state_map 0).  transition / reward / reward_noise: fp64 [n_task][S][A][S], each nullable, zero outside the
+ * real states.  8 <= S <= 512, 2 <= A <= 64, min(min_S, S) >= 8, 2 <= b <= min(XV_ANYMDP_GARNET_B_MAX, smallest real
+ * state count).
+ * xv_anymdp_sample_bandits: candidates cand_base .. cand_base + n_cand - 1; status[i]: 0 accepted | 1 no round of
+ * max_rounds (1 .. XV_ANYMDP_BANDIT_ROUNDS_MAX) had std(reward) > 0.01.  Accepted candidates write slot i of the tables at
+ * S = 2 (build_tables' embedding of a single-state task in two inner states; rows nullable, then no table is written) and of
+ * reward / reward_noise fp64 [n_cand][A] (each nullable).  2 <= A <= 64.  New symbols only: no ABI bump. */
+#define XV_ANYMDP_GARNET_B_MAX 32
+#define XV_ANYMDP_BANDIT_ROUNDS_MAX (1 << 16)
+int xv_anymdp_sample_garnet(xv_engine* e, uint64_t seed, int64_t task_base, int n_task, int S, int A, int min_S, int b,
+                            double sigma, int s0_max, void* rows, int32_t* state_map, uint64_t* term_mask, double* s0_cdf,
+                            int32_t* s0_ids, int32_t* max_steps, int32_t* n_real, double* transition, double* reward,
+                            double* reward_noise);
+int xv_anymdp_sample_bandits(xv_engine* e, uint64_t seed, int64_t cand_base, int n_cand, int A, int max_rounds, int s0_max,
+                             void* rows, int32_t* state_map, uint64_t* term_mask, double* s0_cdf, int32_t* s0_ids,
+                             int32_t* max_steps, double* reward, double* reward_noise, int32_t* status);
+
 /* env.inner_state / env.steps accessors (anymdp_env.py:138-143); device int32[n_env] each, nullable */
 int xv_anymdp_get_state(xv_anymdp* h, int32_t* inner_state, int32_t* steps, uint8_t* need_reset);
 int xv_anymdp_set_state(xv_anymdp* h, const int32_t* inner_state, const int32_t* steps,

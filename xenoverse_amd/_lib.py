@@ -58,6 +58,8 @@ SIGNATURES = {
     "xv_anymdp_solve": [c_void_p, C.c_double, C.c_double, c_int, c_void_p, c_void_p, c_void_p],
     "xv_anymdp_step_many_graph_state": [c_void_p],
     "xv_anymdp_sample_tasks": [c_void_p, c_u64, c_i64, c_int, c_int, c_int, c_int] + [c_void_p] * 11,
+    "xv_anymdp_sample_garnet": [c_void_p, c_u64, c_i64, c_int, c_int, c_int, c_int, c_int, C.c_double, c_int] + [c_void_p] * 10,
+    "xv_anymdp_sample_bandits": [c_void_p, c_u64, c_i64, c_int, c_int, c_int, c_int] + [c_void_p] * 9,
     "xv_anymdp_value_iteration_set_summation": [c_int],
     "xv_anymdp_sample_observation_model": [c_void_p, c_u64, c_i64, c_int, c_int, c_int, c_int, C.c_double, C.c_double, c_void_p],
     "xv_anymdp_value_iteration_gs": [c_void_p, c_void_p, c_int, c_int, C.c_double, c_int, c_void_p, c_void_p],
