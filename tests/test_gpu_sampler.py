@@ -24,7 +24,9 @@ def _engine():
 
 
 @pytest.mark.parametrize("S,A,n", [(16, 4, 192), (8, 2, 64), (24, 5, 48), (32, 8, 40), (64, 8, 24), (64, 5, 16), (40, 12, 12),
-                                   (96, 4, 10), (128, 5, 8), (256, 5, 4), (64, 12, 8), (200, 20, 3)])
+                                   (96, 4, 10), (128, 5, 8), (256, 5, 4), (64, 12, 8), (200, 20, 3),
+                                   (72, 32, 4),      # three rows per thread, two term-mask words
+                                   (65, 8, 6)])      # the smallest two-word term mask
 def test_candidates_equal_the_oracle(S, A, n):
     """every candidate, accepted or not: status, start / terminal states, bands, sweep counts exact; tensors to 1e-9"""
     from xenoverse_amd.anymdp import device_sampler as ds

@@ -72,6 +72,14 @@ def sample_observation_model_device(engine, seed, n_tasks, state_space, observat
     return out
 
 
+def launch_batch(S, A, dense=False):
+    """candidates per launch that memory allows (6 GiB of outputs and scratch), 8192 at the most"""
+    per = S * A * row_lines(S) * 128 + (3 * S * A * S * 8 if dense else 0)
+    if S > 64 or S * A > 512:      # the candidate's scratch: transposed transition rows + two S x S matrices
+        per += ((S * A + 63) // 64 * 64 * S + 2 * S * S) * 8
+    return int(min(8192, (6 << 30) // per))
+
+
 def sample_tasks_device(n_tasks, state_space=64, action_space=5, seed=0, device="cuda:0", engine=None, batch=None,
                         s0_max=4, dense=False, max_candidates=None, task_type="MDP", observation_space=64,
                         observation_tokens=4, action_tokens=2, density=0.20, maximum_distribution=4):
@@ -93,10 +101,7 @@ def sample_tasks_device(n_tasks, state_space=64, action_space=5, seed=0, device=
         return sample_bandit_tasks_device(n_tasks, A, seed=seed, device=device, engine=engine, batch=batch, s0_max=s0_max,
                                           dense=dense, max_candidates=max_candidates)
     if batch is None:
-        per = S * A * row_lines(S) * 128 + (3 * S * A * S * 8 if dense else 0)
-        if S > 64 or S * A > 512:      # the candidate's scratch: transposed transition rows + two S x S matrices
-            per += ((S * A + 63) // 64 * 64 * S + 2 * S * S) * 8
-        batch = int(max(64, min(8192, (6 << 30) // per, 4 * n_tasks + 64)))
+        batch = max(64, min(launch_batch(S, A, dense), 4 * n_tasks + 64))
     keys = ["rows", "state_map", "term_mask", "s0_cdf", "s0_ids", "max_steps"] + \
         (["transition", "reward", "reward_noise"] if dense else [])
     with engine_scope(engine, device) as eng:

@@ -5,9 +5,10 @@
 // model: start / terminal states, banded transition kernel split over the actions, potential + position + state-action
 // rewards, terminal rewards repaired against the value function) and solver.py:57-148 (acceptance: value gap between
 // the optimal and the uniform policy, long-run occupancy of the greedy policy).  There the work is a Python triple loop
-// (518 s per 64x8 task without numba).  Here:
-//   * thread (s, a) of the workgroup owns row T[s, a, :] in registers for the whole life of the candidate (S <= 64):
-//     generation, 5 + 2 value iterations and the emission never move the transition tensor through memory;
+// (518 s per 64x8 task without numba).
+//
+// ONE MODEL: xs_candidate<Rows> states every stage once — head scalars, terminal redraws, bands, the split of a row over
+// the actions, rewards, the repair loop, the acceptance test and every output:
 //   * every random quantity is a counter-based draw, Philox4x32-10(counter = {candidate, index, purpose}, key = seed):
 //     a pure function of its coordinates, so the threads of a state simply recompute what they share (band, weights)
 //     instead of exchanging it, and a candidate is reproducible whatever the launch geometry.  Same distributions as the
@@ -15,9 +16,23 @@
 //   * value iteration is the synchronous sweep Q <- ER + gamma T V(Q) to rms update <= 1e-4 (the reference's stopping
 //     rule; same fixed point as its damped Gauss-Seidel): V through LDS broadcast reads, two barriers per sweep;
 //   * accepted candidates are emitted in the layout xv_anymdp_create reads (blocks of 7 {cdf, reward, noise}).
-// oracle/xeno_oracle_sampler.c (part 2) restates this file draw for draw; tests/test_gpu_sampler.py diffs them.
+// TWO STORAGES for the rows T[s, a, :] of the candidate's transition tensor, the `Rows` of the model:
+//   * RegRows<SP> (S <= 64, S * A <= 512): thread (s, a) owns its row in registers for the whole life of the candidate:
+//     generation, 5 + 2 value iterations and the emission never move the transition tensor through memory.  Every loop
+//     over a row is unrolled over SP = 16 / 32 / 64; a state's action centres are shared through LDS;
+//   * BigRows<R> (the rest up to S <= 256, S * A <= 4096: the reference's GarnetTaskSampler defaults to 128 states and its
+//     MultiTokensAnyPOMDPTaskSampler to 256, task_sampler.py:90-126): S * A rows of S doubles are 2.6 MB at 256 x 5, so
+//     they live in a per-candidate global scratch, TRANSPOSED in blocks of 64 rows — Tt[(row >> 6) * S + j][row & 63] — so
+//     that the 64 lanes of a wave, which own 64 consecutive rows, read element j of their rows as one coalesced 512-byte
+//     access.  Thread tid owns rows tid, tid + blockDim, ... (R <= 4 of them); the value iteration and the expected
+//     reward sweep the union of a wave's bands only; each thread recomputes its state's action centres.
+// A zero outside a row's band adds nothing to an fma over j ascending, so both storages give the same bits, and the file
+// is built with -ffp-contract=off: an expression evaluated as written is the same bits wherever it is instantiated.  The
+// Philox index strides (64 words per 256 states) were laid out for 256 states, so the coordinates are one set too.
+// oracle/xeno_oracle_sampler.c (part 2) restates the model draw for draw; tests/test_gpu_sampler.py diffs them.
 #include "philox.h"
 #include "xv_common.h"
+#include "xv_draws.h"
 
 namespace {
 
@@ -34,7 +49,7 @@ struct SamplerArgs {
   // table outputs, slot = candidate index within the launch (written for accepted candidates only)
   double* rows;          // [n_cand][S][A][row_lines][16]
   int32_t* state_map;    // [n_cand][S]
-  uint64_t* term_mask;   // [n_cand][1]
+  uint64_t* term_mask;   // [n_cand][ceil(S / 64)]
   double* s0_cdf;        // [n_cand][s0_max]
   int32_t* s0_ids;       // [n_cand][s0_max]
   int32_t* max_steps;    // [n_cand]
@@ -44,9 +59,7 @@ struct SamplerArgs {
   int32_t* status;                       // [n_cand]
 };
 
-__device__ __forceinline__ xv_u32x4 xs_draw(const SamplerArgs& P, uint64_t cand, uint32_t purpose, uint32_t idx) {
-  return xv_philox4x32_10((uint32_t)cand, (uint32_t)(cand >> 32), idx, purpose, (uint32_t)P.seed, (uint32_t)(P.seed >> 32));
-}
+// the 32-bit-word draws of this file (xv_draws.h builds its uniforms and normals from 53-bit pairs instead)
 __device__ __forceinline__ double xs_u32(uint32_t w) { return (double)w * (1.0 / 4294967296.0); }
 __device__ __forceinline__ void xs_normal2(uint32_t wa, uint32_t wb, double& z0, double& z1) {
   const double u1 = ((double)wa + 1.0) * (1.0 / 4294967296.0), u2 = xs_u32(wb);
@@ -64,81 +77,177 @@ __device__ __forceinline__ double xs_normal_of(const xv_u32x4& w, int k) {
   return (k & 1) ? z1 : z0;
 }
 __device__ __forceinline__ double xs_clip(double x, double lo, double hi) { return x < lo ? lo : (x > hi ? hi : x); }
-__device__ __forceinline__ double xs_expo(double u) { return -log(1.0 - u); }
+__device__ __forceinline__ double xs_row_max(const double* row, int A) {
+  double v = row[0];
+  for (int a = 1; a < A; ++a) v = row[a] > v ? row[a] : v;
+  return v;
+}
 
-// Synchronous value iteration on the candidate's rows.  q: this thread's Q[s, a] in/out.  Returns the sweep count
-// (uniform).  Qs[SA], Vs[SP], part[8]: LDS.  Each sweep: Q -> LDS | barrier | V = max / mean per state, and the
-// previous sweep's update norm is inspected (uniform decision) | barrier | 64 broadcast reads of V, one fma each.
+// One candidate as its workgroup sees it: its draws and its per-state arrays.  Each kernel carves the arrays its own way;
+// all are LDS, except that Pm / Pm2 are global scratch under BigRows.
+struct Cand {
+  const SamplerArgs& P;
+  uint64_t cand;
+  int S, A, SA;
+  double *Qs;                                  // [rows]  Q of every row (also: action centres, the state permutation)
+  double *Vs, *part;                           // [S] V of a sweep (first: band totals), [waves] update-norm partials
+  double *pot, *rpos, *npos, *bonus, *vstate;  // [S] reward pieces; V(s) = max_a Q after a value iteration
+  int *pitm, *bandlo, *bandhi;                 // [S] terminal flag, band [lo, hi)
+  double *Pm, *Pm2;                            // [S*S] band weights during generation, occupancy matrices at acceptance
+
+  __device__ __forceinline__ xv_u32x4 draw(uint32_t purpose, uint32_t idx) const {
+    return xv_philox4x32_10((uint32_t)cand, (uint32_t)(cand >> 32), idx, purpose, (uint32_t)P.seed, (uint32_t)(P.seed >> 32));
+  }
+  // centre of action b of live state s, uniform over the state's band
+  __device__ __forceinline__ double centre(int s, int b) const {
+    const int first = bandlo[s], last = bandhi[s];
+    const xv_u32x4 q4 = draw(XS_ACT, (uint32_t)s * 16u + (uint32_t)(b >> 2));
+    return (double)(first - 1) + xs_u32(xs_word(q4, b & 3)) * (double)(last - (first - 1));
+  }
+};
+
+// ---- row storage.  A storage names the rows of this thread (slot k < R is row `row(k)`; slots without storage are
+// skipped), visits their elements in ascending j — each(k, lo, hi, f) calls f(j, T[row][j]) for lo <= j < hi — and
+// chooses the inner range of the fma chains (each_inner) and how a thread gets the action centres of a row's state.
+
 template <int SP>
-__device__ __forceinline__ int xs_value_iteration(const double (&Trow)[SP], double er, double gamma, bool greedy, bool own, int S, int A,
-                                  double& q, double* Qs, double* Vs, double* part, int n_waves) {
-  const int tid = threadIdx.x, SA = S * A;
+struct RegRows {
+  static constexpr int R = 1;
+  double T[SP] = {};
+  __device__ __forceinline__ int row(int) const { return threadIdx.x; }
+  __device__ __forceinline__ bool stored(int) const { return true; }
+  template <class F>
+  __device__ __forceinline__ void each(int, int lo, int hi, F f) {
+#pragma unroll
+    for (int j = 0; j < SP; ++j)
+      if (j >= lo && j < hi) f(j, T[j]);
+  }
+  // all of the row, unrolled.  SP / 2 <= S (xv_anymdp_sample_tasks chooses the smallest SP that holds S), so the first half
+  // needs no test: each test is a wave-uniform branch per sweep and a mask held in scalar registers for the whole kernel
+  template <class F>
+  __device__ __forceinline__ void each_inner(int, int S, F f) {
+#pragma unroll
+    for (int j = 0; j < SP; ++j)
+      if (j < SP / 2 || j < S) f(j, T[j]);
+  }
+  __device__ __forceinline__ void set_inner(int, bool, int, int, int) {}
+  // the state's A centres are shared through LDS: every live row's thread draws its own
+  __device__ __forceinline__ void share_centres(const Cand& C) {
+    const int tid = threadIdx.x;
+    if (tid < C.SA) {
+      const int s = tid / C.A;
+      if (!C.pitm[s]) C.Qs[tid] = C.centre(s, tid - s * C.A);
+    }
+    __syncthreads();
+  }
+  __device__ __forceinline__ const double* centres(const Cand& C, int s, double (&)[64]) { return C.Qs + s * C.A; }
+};
+
+template <int R_>
+struct BigRows {
+  static constexpr int R = R_;
+  double* Tt;        // this candidate's [n_rb * S * 64]
+  int S, SAp;        // SAp = n_rb * 64 rows have storage
+  int wf[R_], wl[R_];
+  __device__ __forceinline__ int row(int k) const { return k * (int)blockDim.x + (int)threadIdx.x; }
+  __device__ __forceinline__ bool stored(int k) const { return row(k) < SAp; }
+  template <class F>
+  __device__ __forceinline__ void each(int k, int lo, int hi, F f) {
+    const int r = row(k);
+    double* col = Tt + ((size_t)(r >> 6) * S) * 64 + (r & 63);
+    for (int j = lo; j < hi; ++j) f(j, col[(size_t)j * 64]);
+  }
+  template <class F>
+  __device__ __forceinline__ void each_inner(int k, int, F f) { each(k, wf[k], wl[k], f); }
+  // the wave-uniform union of the bands of slot k's 64 rows (empty where none of them is live: nothing is read)
+  __device__ __forceinline__ void set_inner(int k, bool live, int first, int last, int S_) {
+    int lo = live ? first : S_, hi = live ? last : 0;
+    for (int o = 32; o > 0; o >>= 1) {
+      const int l2 = __shfl_xor(lo, o), h2 = __shfl_xor(hi, o);
+      lo = l2 < lo ? l2 : lo; hi = h2 > hi ? h2 : hi;
+    }
+    wf[k] = lo < hi ? lo : 0; wl[k] = lo < hi ? hi : 0;
+  }
+  __device__ __forceinline__ void share_centres(const Cand&) {}
+  // (the buffer is the caller's: a dynamically indexed member would keep the whole storage out of registers)
+  __device__ __forceinline__ const double* centres(const Cand& C, int s, double (&cen)[64]) {
+    for (int b = 0; b < C.A; ++b) cen[b] = C.centre(s, b);
+    return cen;
+  }
+};
+
+// Q of this thread's rows -> LDS
+template <class Rows>
+__device__ __forceinline__ void xs_publish(const Cand& C, const Rows& T, const double (&q)[Rows::R]) {
+#pragma unroll
+  for (int k = 0; k < Rows::R; ++k) {
+    const int r = T.row(k);
+    if (r < C.SA) C.Qs[r] = q[k];
+  }
+}
+
+// Synchronous value iteration on the candidate's rows.  q: Q of this thread's rows, in/out.  Returns the sweep count
+// (uniform).  Each sweep: Q -> LDS | barrier | V = max / mean per state, and the previous sweep's update norm is
+// inspected (uniform decision) | barrier | broadcast reads of V over the storage's inner range, one fma each.
+template <class Rows>
+__device__ __forceinline__ int xs_value_iteration(const Cand& C, Rows& T, double gamma, bool greedy,
+                                                  const double (&er)[Rows::R], double (&q)[Rows::R]) {
+  const int tid = threadIdx.x, S = C.S, A = C.A, n_waves = (int)(blockDim.x >> 6);
   double d2 = 0.0;
   int it = 0;
   for (;;) {
-    if (own) Qs[tid] = q;
+    xs_publish(C, T, q);
     {
       double x = d2;
       for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
-      if ((tid & 63) == 0) part[tid >> 6] = x;
+      if ((tid & 63) == 0) C.part[tid >> 6] = x;
     }
     __syncthreads();
     if (it > 0) {
       double tot = 0.0;
-      for (int w = 0; w < n_waves; ++w) tot += part[w];
-      if (sqrt(tot / (double)SA) <= 1.0e-4 || it >= XS_MAX_SWEEPS) break;
+      for (int w = 0; w < n_waves; ++w) tot += C.part[w];
+      if (sqrt(tot / (double)C.SA) <= 1.0e-4 || it >= XS_MAX_SWEEPS) break;
     }
     if (tid < S) {
-      const double* row = Qs + tid * A;
+      const double* row = C.Qs + tid * A;
       double v;
       if (greedy) {
-        v = row[0];
-        for (int a = 1; a < A; ++a) v = row[a] > v ? row[a] : v;
+        v = xs_row_max(row, A);
       } else {
         v = 0.0;
         for (int a = 0; a < A; ++a) v += row[a];
         v /= (double)A;
       }
-      Vs[tid] = v;
+      C.Vs[tid] = v;
     }
     __syncthreads();
-    double acc = 0.0;
+    d2 = 0.0;
 #pragma unroll
-    for (int j = 0; j < SP; ++j)
-      if (j < S) acc = fma(Trow[j], Vs[j], acc);
-    const double qn = fma(gamma, acc, er);
-    d2 = own ? (qn - q) * (qn - q) : 0.0;
-    q = qn;
+    for (int k = 0; k < Rows::R; ++k) {
+      double acc = 0.0;
+      T.each_inner(k, S, [&](int j, double& t) { acc = fma(t, C.Vs[j], acc); });
+      const double qn = fma(gamma, acc, er[k]);
+      if (T.row(k) < C.SA) d2 += (qn - q[k]) * (qn - q[k]);
+      q[k] = qn;
+    }
     ++it;
   }
   __syncthreads();
   return it;
 }
 
-template <int SP>
-__global__ __launch_bounds__(512) void anymdp_sampler_kernel(SamplerArgs P) {
-  extern __shared__ __attribute__((aligned(16))) double lds[];
-  const int S = P.S, A = P.A, SA = S * A, tid = threadIdx.x;
-  const int n_waves = (int)(blockDim.x >> 6);
-  const int ci = blockIdx.x;
-  const uint64_t cand = (uint64_t)(P.cand_base + ci);
-  // LDS carve-up
-  double* Qs = lds;                    // [SA]    (also: action centres during generation)
-  double* Vs = Qs + SA;                // [SP]
-  double* part = Vs + SP;              // [8]
-  double* pot = part + 8;              // [SP]
-  double* rpos = pot + SP;             // [SP]    (first: position-reward pdf)
-  double* npos = rpos + SP;            // [SP]
-  double* bonus = npos + SP;           // [SP]
-  double* vstate = bonus + SP;         // [SP]    V(s) = max_a Q after a value iteration
-  int* pitm = reinterpret_cast<int*>(vstate + SP);   // [SP]
-  double* Pm = reinterpret_cast<double*>(pitm + SP); // [2][SP*SP] occupancy matrices (acceptance only)
-
-  const bool own = tid < SA;
-  const int s = own ? tid / A : 0, a = own ? tid - s * A : 0;
+// The model: one candidate, by the whole workgroup.
+template <class Rows>
+__device__ __forceinline__ void xs_candidate(const Cand& C, Rows& T) {
+  constexpr int R = Rows::R;
+  const SamplerArgs& P = C.P;
+  const int S = C.S, A = C.A, SA = C.SA, tid = threadIdx.x, BD = blockDim.x, ci = blockIdx.x;
+  double *Qs = C.Qs, *Vs = C.Vs, *pot = C.pot, *rpos = C.rpos, *npos = C.npos, *bonus = C.bonus, *vstate = C.vstate;
+  int *pitm = C.pitm, *bandlo = C.bandlo, *bandhi = C.bandhi;
+  double* Pm = C.Pm;
 
   // ---- uniform scalars: every thread derives them from the same draws ----
-  xv_u32x4 w = xs_draw(P, cand, XS_HEAD, 0);
+  xv_u32x4 w = C.draw(XS_HEAD, 0);
   const double lower = 4.0 * S > 100 ? 4.0 * S : 100;
   double upper = 8.0 * S < 500 ? 8.0 * S : 500;
   if (upper < lower + 1) upper = lower + 1;
@@ -146,21 +255,30 @@ __global__ __launch_bounds__(512) void anymdp_sampler_kernel(SamplerArgs P) {
   // start states (task_sampler_utils.py:70-79)
   double w0[3] = {1.0, 0.0, 0.0};
   for (uint32_t r = 0; r < 16; ++r) {
-    const xv_u32x4 q4 = xs_draw(P, cand, XS_S0, r);
+    const xv_u32x4 q4 = C.draw(XS_S0, r);
     double z0, z1, z2, z3;
     xs_normal2(q4.x, q4.y, z0, z1);
     xs_normal2(q4.z, q4.w, z2, z3);
     const double c0 = z0 > 0.0 ? z0 : 0.0, c1 = z1 > 0.0 ? z1 : 0.0, c2 = z2 > 0.0 ? z2 : 0.0;
     if ((c0 + c1) + c2 >= XS_EPS) { w0[0] = c0; w0[1] = c1; w0[2] = c2; break; }
   }
-  int s0_id[3], n_s0 = 0;
-  double s0_p[3], s0sum = 0.0;
+  // the (at most three) start states, compacted.  Indexed through selects, never dynamically: a stack array indexed by a
+  // variable may be left in scratch memory
+  int s0_id[3] = {0, 0, 0}, n_s0 = 0;
+  double s0_p[3] = {0.0, 0.0, 0.0}, s0sum = 0.0;
+#pragma unroll
   for (int k = 0; k < 3; ++k)
-    if (w0[k] > XS_EPS) { s0_id[n_s0] = k; s0_p[n_s0] = w0[k]; s0sum += w0[k]; ++n_s0; }
-  for (int k = n_s0; k < 3; ++k) { s0_id[k] = 0; s0_p[k] = 0.0; }
-  for (int k = 0; k < n_s0; ++k) s0_p[k] /= s0sum;
+    if (w0[k] > XS_EPS) {
+#pragma unroll
+      for (int i = 0; i <= k; ++i) if (i == n_s0) { s0_id[i] = k; s0_p[i] = w0[k]; }
+      s0sum += w0[k]; ++n_s0;
+    }
+#pragma unroll
+  for (int k = 0; k < 3; ++k) if (k < n_s0) s0_p[k] /= s0sum;
+  auto s0i = [&](int k) { return k == 0 ? s0_id[0] : (k == 1 ? s0_id[1] : s0_id[2]); };
+  auto s0p = [&](int k) { return k == 0 ? s0_p[0] : (k == 1 ? s0_p[1] : s0_p[2]); };
   // terminal states (:81-93)
-  w = xs_draw(P, cand, XS_PIT, 0);
+  w = C.draw(XS_PIT, 0);
   double p_pit = -0.20 + 0.60 * xv_u53(w.x, w.y);
   if (p_pit < 0.0) p_pit = 0.0;
   const int goal = xs_u32(w.z) < 0.3 ? 1 : 0;
@@ -169,14 +287,14 @@ __global__ __launch_bounds__(512) void anymdp_sampler_kernel(SamplerArgs P) {
     for (uint32_t r = 0; r < 64; ++r) {
       mine = 0;
       if (tid < S) {
-        const xv_u32x4 q4 = xs_draw(P, cand, XS_PITS, r * 64u + (uint32_t)(tid >> 2));
+        const xv_u32x4 q4 = C.draw(XS_PITS, r * 64u + (uint32_t)(tid >> 2));
         mine = xs_u32(xs_word(q4, tid & 3)) < p_pit ? 1 : 0;
       }
       const int cnt = __syncthreads_count(mine);
       if ((double)cnt < (double)S * p_pit + 1.0) break;
     }
     if (tid < S) {
-      for (int k = 0; k < n_s0; ++k) if (tid == s0_id[k]) mine = 0;
+      for (int k = 0; k < n_s0; ++k) if (tid == s0i(k)) mine = 0;
       if (tid == S - 1) mine = goal;
       pitm[tid] = mine;
     }
@@ -184,11 +302,8 @@ __global__ __launch_bounds__(512) void anymdp_sampler_kernel(SamplerArgs P) {
   __syncthreads();
   int n_se = 0;
   for (int j = 0; j < S; ++j) n_se += pitm[j];
-  const bool live_row = own && !pitm[s];
 
   // ---- band of every live state (:95-124), by the state's own thread ----
-  int* bandlo = reinterpret_cast<int*>(Pm + 2 * SP * SP);   // [SP]
-  int* bandhi = bandlo + SP;                                  // [SP]
   if (tid < S) {
     int first = 0, last = 0;
     if (!pitm[tid]) {
@@ -200,7 +315,7 @@ __global__ __launch_bounds__(512) void anymdp_sampler_kernel(SamplerArgs P) {
       const int b_hi = S < st + fwd_max ? S : st + fwd_max;
       int b_lo = S - 1 < st + 1 ? S - 1 : st + 1;
       if (b_lo > b_hi - 1) b_lo = b_hi - 1;
-      w = xs_draw(P, cand, XS_BAND, (uint32_t)st);
+      w = C.draw(XS_BAND, (uint32_t)st);
       first = a_lo + (int)(w.x % (uint32_t)(a_hi - a_lo));
       last = b_lo + (int)(w.y % (uint32_t)(b_hi - b_lo));
       while (last < S) {          // widen until two live states lie ahead inside the band
@@ -215,11 +330,11 @@ __global__ __launch_bounds__(512) void anymdp_sampler_kernel(SamplerArgs P) {
   __syncthreads();
   // band weights clip(N(0,1), 0.1, 1) (:126-133), element (state, next state) by element over the whole workgroup,
   // staged in the (still unused) occupancy buffer
-  for (int el = tid; el < S * S; el += (int)blockDim.x) {
+  for (int el = tid; el < S * S; el += BD) {
     const int st = el / S, j = el - st * S;
     double v = 0.0;
     if (j >= bandlo[st] && j < bandhi[st]) {
-      const xv_u32x4 q4 = xs_draw(P, cand, XS_BANDW, ((uint32_t)st * 8u) * 64u + (uint32_t)(j >> 2));
+      const xv_u32x4 q4 = C.draw(XS_BANDW, ((uint32_t)st * 8u) * 64u + (uint32_t)(j >> 2));
       v = xs_clip(xs_normal_of(q4, j & 3), 0.10, 1.0);
     }
     Pm[el] = v;
@@ -233,30 +348,30 @@ __global__ __launch_bounds__(512) void anymdp_sampler_kernel(SamplerArgs P) {
   }
   __syncthreads();
 
-  // ---- this thread's row of the transition tensor (:154-175) ----
-  double Trow[SP];
+  // ---- the rows of the transition tensor (:154-175): the band weights of the state, split over its actions ----
+  T.share_centres(C);
 #pragma unroll
-  for (int j = 0; j < SP; ++j) Trow[j] = 0.0;
-  int first = 0, last = 0;
-  if (live_row) {
-    first = bandlo[s]; last = bandhi[s];
+  for (int k = 0; k < R; ++k) {
+    const int r = T.row(k);
+    const bool in = r < SA;
+    const int s = in ? r / A : 0, a = in ? r - s * A : 0;
+    const bool live = in && !pitm[s];
+    const int first = live ? bandlo[s] : 0, last = live ? bandhi[s] : 0;
+    T.set_inner(k, live, first, last, S);
+    if (!T.stored(k)) continue;
+    if (!live) {
+      T.each(k, 0, S, [](int, double& t) { t = 0.0; });
+      continue;
+    }
     const double tot = Vs[s];
-#pragma unroll
-    for (int j = 0; j < SP; ++j)
-      if (j >= first && j < last) Trow[j] = Pm[s * S + j] / tot;
-    // this action's centre; the state's A centres are shared through LDS
-    const xv_u32x4 q4 = xs_draw(P, cand, XS_ACT, (uint32_t)s * 16u + (uint32_t)(a >> 2));
-    Qs[tid] = (double)(first - 1) + xs_u32(xs_word(q4, a & 3)) * (double)(last - (first - 1));
-  }
-  __syncthreads();
-  if (live_row) {
-    w = xs_draw(P, cand, XS_ACTW, (uint32_t)s);
-    const double width = xs_clip(xs_expo(xv_u53(w.x, w.y)), 0.20, 1.6);
+    double cen_own[64];      // only a storage that recomputes the centres uses it
+    const double* cen = T.centres(C, s, cen_own);
+    w = C.draw(XS_ACTW, (uint32_t)s);
+    const double width = xs_clip(xv_expo(xv_u53(w.x, w.y)), 0.20, 1.6);
     const double inv_w2 = 1.0 / (width * width);
-    const double* cen = Qs + s * A;
     double rs = 0.0;
-#pragma unroll
-    for (int j = 0; j < SP; ++j) {
+    T.each(k, 0, S, [&](int j, double& t) {
+      double v = 0.0;
       if (j >= first && j < last) {
         double col = 0.0, dmin = 0.0, e_me = 0.0;
         int amin = 0;
@@ -275,29 +390,28 @@ __global__ __launch_bounds__(512) void anymdp_sampler_kernel(SamplerArgs P) {
           }
           if (a == amin) e_me = 1.0;
         }
-        Trow[j] = (e_me / col) * Trow[j];
-        rs += Trow[j];
+        v = (e_me / col) * (Pm[s * S + j] / tot);
+        rs += v;
       }
-    }
-#pragma unroll
-    for (int j = 0; j < SP; ++j)
-      if (j >= first && j < last) Trow[j] /= rs;
+      t = v;
+    });
+    T.each(k, first, last, [&](int, double& t) { t /= rs; });
   }
   __syncthreads();
 
-  // ---- rewards (:11-63, :193-207): per-state pieces in LDS, the state-action piece in registers ----
+  // ---- rewards (:11-63, :193-207): per-state pieces in LDS, the state-action pieces in registers ----
   double pbase, ub;
   {
-    w = xs_draw(P, cand, XS_POS, 0);
-    pbase = 0.2 * xs_expo(xv_u53(w.x, w.y));
+    w = C.draw(XS_POS, 0);
+    pbase = 0.2 * xv_expo(xv_u53(w.x, w.y));
     ub = xv_u53(w.z, w.w);
   }
   if (tid < S) {
     const int j = tid;
     // potential: a few Fourier terms over the state index (RandomFourier, utils/random_nn.py:346-368)
-    xv_u32x4 q4 = xs_draw(P, cand, XS_POT, 0);
-    const double base = xv_u53(q4.x, q4.y) < 0.5 ? 0.0 : xs_clip(xs_expo(xv_u53(q4.z, q4.w)), 0.20, 5.0);
-    q4 = xs_draw(P, cand, XS_POT, 1);
+    xv_u32x4 q4 = C.draw(XS_POT, 0);
+    const double base = xv_u53(q4.x, q4.y) < 0.5 ? 0.0 : xs_clip(xv_expo(xv_u53(q4.z, q4.w)), 0.20, 5.0);
+    q4 = C.draw(XS_POT, 1);
     double box = -base + 2.0 * base * xv_u53(q4.x, q4.y);
     if (box < 0.0) box = 0.0;
     const int n_items = 1 + (int)(q4.z % 3u);
@@ -306,24 +420,24 @@ __global__ __launch_bounds__(512) void anymdp_sampler_kernel(SamplerArgs P) {
     double pj = 0.0;
     for (int k = 0; k <= n_items; ++k) {
       double za, zb, order = 0.0;
-      q4 = xs_draw(P, cand, XS_POT, 2u + (uint32_t)k);
+      q4 = C.draw(XS_POT, 2u + (uint32_t)k);
       xs_normal2(q4.x, q4.y, za, zb);
-      const double ca = za * (xs_expo(xs_u32(q4.z)) * scale), cb = zb * (xs_expo(xs_u32(q4.w)) * scale);
+      const double ca = za * (xv_expo(xs_u32(q4.z)) * scale), cb = zb * (xv_expo(xs_u32(q4.w)) * scale);
       if (k > 0) {
         double zo, zd;
-        q4 = xs_draw(P, cand, XS_POT, 8u + (uint32_t)k);
+        q4 = C.draw(XS_POT, 8u + (uint32_t)k);
         xs_normal2(q4.y, q4.z, zo, zd);
         order = (double)(1 + (int)(q4.x % 5u)) + zo;
       }
       pj += ca * sin(order * x) + cb * cos(order * x);
     }
     pot[j] = pj;
-    q4 = xs_draw(P, cand, XS_POSN, (uint32_t)(j >> 2));
+    q4 = C.draw(XS_POSN, (uint32_t)(j >> 2));
     double pdf = xs_normal_of(q4, j & 3);
     pdf = pdf > 0.0 ? pdf : 0.0;
     if (j == S - 1) pdf += 0.20;
     rpos[j] = pdf * pbase;
-    q4 = xs_draw(P, cand, XS_POSU, (uint32_t)(j >> 2));
+    q4 = C.draw(XS_POSU, (uint32_t)(j >> 2));
     const double u = -0.30 + 0.60 * xs_u32(xs_word(q4, j & 3));
     npos[j] = pitm[j] ? 0.0 : (u > 0.0 ? u : 0.0) * pbase;
     bonus[j] = (j == S - 1) ? 1.0 : 0.0;
@@ -339,53 +453,72 @@ __global__ __launch_bounds__(512) void anymdp_sampler_kernel(SamplerArgs P) {
     const double baseline = 0.1 * c_all + ub * (0.9 * c_all - 0.1 * c_all);
     rpos[tid] = pitm[tid] ? 0.0 : cdf_j - baseline;
   }
-  double rsa = 0.0, nsa = 0.0, r_step = 0.0;
+  w = C.draw(XS_SA, 0);
+  const double sbase = xs_clip(0.05 * xv_expo(xv_u53(w.x, w.y)), 0.0, 0.10);
+  auto sa_pieces = [&](int r, double& rsa_r, double& nsa_r) {
+    double zr, zn;
+    const xv_u32x4 q4 = C.draw(XS_SAM, (uint32_t)r);
+    const double on = xs_u32(q4.x) > 0.7 ? 1.0 : 0.0;
+    xs_normal2(q4.y, q4.z, zr, zn);
+    rsa_r = sbase * zr * on;
+    nsa_r = 0.30 * sbase * (zn > 0.0 ? zn : 0.0) * on;
+  };
+  double r_step = 0.0, rsa[R], pot_s[R];
   {
-    w = xs_draw(P, cand, XS_SA, 0);
-    const double sbase = xs_clip(0.05 * xs_expo(xv_u53(w.x, w.y)), 0.0, 0.10);
-    if (own) {
-      double zr, zn;
-      const xv_u32x4 q4 = xs_draw(P, cand, XS_SAM, (uint32_t)tid);
-      const double on = xs_u32(q4.x) > 0.7 ? 1.0 : 0.0;
-      xs_normal2(q4.y, q4.z, zr, zn);
-      rsa = sbase * zr * on;
-      nsa = 0.30 * sbase * (zn > 0.0 ? zn : 0.0) * on;
+#pragma unroll
+    for (int k = 0; k < R; ++k) {
+      const int r = T.row(k);
+      double nsa;
+      rsa[k] = 0.0; pot_s[k] = 0.0;
+      if (r < SA) {
+        sa_pieces(r, rsa[k], nsa);
+        pot_s[k] = pot[r / A];
+      }
     }
     double zs, zd;
-    w = xs_draw(P, cand, XS_STEP, 0);
+    w = C.draw(XS_STEP, 0);
     xs_normal2(w.x, w.y, zs, zd);
     if (goal) r_step = (zs < 0.0 ? zs : 0.0) * 0.01;
     else if (n_se > 0) r_step = (zs > 0.0 ? zs : 0.0) * 0.01;
   }
   __syncthreads();
 
+  // reward of slot k's row -> next state j under the current terminal bonus, and a row's expectation of it: one fma per
+  // element of the storage's inner range, j ascending
+  auto reward = [&](int k, int j) {
+    const double r = (((pot_s[k] - pot[j]) + rpos[j]) + rsa[k]) + r_step;
+    return r + bonus[j];
+  };
+  auto expected = [&](double (&er)[R]) {
+#pragma unroll
+    for (int k = 0; k < R; ++k) {
+      double e = 0.0;
+      if (T.row(k) < SA) T.each_inner(k, S, [&](int j, double& t) { e = fma(t, reward(k, j), e); });
+      er[k] = e;
+    }
+  };
+  // V(s) = max_a Q(s, a) of this thread's q -> vstate, through Qs
+  auto state_values = [&](const double (&q)[R]) {
+    xs_publish(C, T, q);
+    __syncthreads();
+    if (tid < S) vstate[tid] = xs_row_max(Qs + tid * A, A);
+    __syncthreads();
+  };
+
   // ---- terminal rewards repaired against the value function (:209-256) ----
   const int last_live = goal ? S - 2 : S - 1;
   int status = 1, repair_rounds = 0;
   int sweeps[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  double q = 0.0, er = 0.0;
-  const double pot_s = own ? pot[s] : 0.0;
-  for (int tries = 0; tries < 5; ++tries) {
-    er = 0.0;
+  double q[R], er[R];
 #pragma unroll
-    for (int j = 0; j < SP; ++j)
-      if (j < S) {
-        double r = (((pot_s - pot[j]) + rpos[j]) + rsa) + r_step;
-        r += bonus[j];
-        er = fma(Trow[j], r, er);
-      }
-    const int sw = xs_value_iteration<SP>(Trow, er, 0.99, true, own, S, A, q, Qs, Vs, part, n_waves);
+  for (int k = 0; k < R; ++k) q[k] = 0.0;
+  for (int tries = 0; tries < 5; ++tries) {
+    expected(er);
+    const int sw = xs_value_iteration(C, T, 0.99, true, er, q);
     sweeps[tries] = sw;
     repair_rounds = tries + 1;
     if (sw >= XS_MAX_SWEEPS) { status = 4; break; }
-    if (own) Qs[tid] = q;
-    __syncthreads();
-    if (tid < S) {
-      double v = Qs[tid * A];
-      for (int b = 1; b < A; ++b) v = Qs[tid * A + b] > v ? Qs[tid * A + b] : v;
-      vstate[tid] = v;
-    }
-    __syncthreads();
+    state_values(q);
     double vmin_live = 0.0, vmax_s0 = 0.0, bmin = bonus[0];
     bool first_live = true;
     for (int j = 0; j < S; ++j) {
@@ -394,10 +527,10 @@ __global__ __launch_bounds__(512) void anymdp_sampler_kernel(SamplerArgs P) {
       if (bonus[j] < bmin) bmin = bonus[j];
     }
     for (int k = 0; k < n_s0; ++k) {
-      const double v = vstate[s0_id[k]];
+      const double v = vstate[s0i(k)];
       if (k == 0 || v > vmax_s0) vmax_s0 = v;
     }
-    w = xs_draw(P, cand, XS_REPAIR, (uint32_t)tries);
+    w = C.draw(XS_REPAIR, (uint32_t)tries);
     const double pit_gap = bmin - vmin_live + 1.0;
     const double goal_gap = vmax_s0 - vstate[last_live] + (2.0 + 3.0 * xv_u53(w.x, w.y));
     if (pit_gap <= 0.0 && goal_gap <= 0.0) { status = 0; break; }
@@ -419,654 +552,49 @@ __global__ __launch_bounds__(512) void anymdp_sampler_kernel(SamplerArgs P) {
   double gini = 0.0, ent = 0.0, gap_min = 0.0;
   if (status == 0) {
     const double g2 = exp2(-1.0 / (double)S);
-    er = 0.0;
+    expected(er);
+    double qo[R], qr[R];
 #pragma unroll
-    for (int j = 0; j < SP; ++j)
-      if (j < S) {
-        double r = (((pot_s - pot[j]) + rpos[j]) + rsa) + r_step;
-        r += bonus[j];
-        er = fma(Trow[j], r, er);
-      }
-    double qo = 0.0, qr = 0.0;
-    sweeps[5] = xs_value_iteration<SP>(Trow, er, g2, true, own, S, A, qo, Qs, Vs, part, n_waves);
-    if (own) Qs[tid] = qo;
-    __syncthreads();
-    int greedy_a = 0;
-    if (tid < S) {
-      double v = Qs[tid * A];
-      for (int b = 1; b < A; ++b) if (Qs[tid * A + b] > v) { v = Qs[tid * A + b]; greedy_a = b; }
-      vstate[tid] = v;
-    }
-    __syncthreads();
-    // occupancy matrix row of the greedy action: thread (s, a) with a == greedy(s) owns row s
-    {
-      int g_s = 0;
-      if (own) {
+    for (int k = 0; k < R; ++k) { qo[k] = 0.0; qr[k] = 0.0; }
+    sweeps[5] = xs_value_iteration(C, T, g2, true, er, qo);
+    state_values(qo);
+    // occupancy matrix: row s = the greedy action's row of T (first maximum), by the thread that owns it, or the start
+    // distribution for terminal states
+#pragma unroll
+    for (int k = 0; k < R; ++k) {
+      const int r = T.row(k);
+      if (r < SA) {
+        const int s = r / A, a = r - s * A;
+        int g_s = 0;
         double v = Qs[s * A];
         for (int b = 1; b < A; ++b) if (Qs[s * A + b] > v) { v = Qs[s * A + b]; g_s = b; }
-      }
-      if (own && a == g_s) {
-#pragma unroll
-        for (int j = 0; j < SP; ++j)
-          if (j < S) {
-            double pj = Trow[j];
+        if (a == g_s)
+          T.each(k, 0, S, [&](int j, double& t) {
+            double pj = t;
             if (pitm[s]) {
               pj = 0.0;
-              for (int k = 0; k < n_s0; ++k) if (j == s0_id[k]) pj = s0_p[k];
+              for (int kk = 0; kk < n_s0; ++kk) if (j == s0i(kk)) pj = s0p(kk);
             }
             Pm[s * S + j] = pj;
-          }
+          });
       }
     }
-    (void)greedy_a;
-    double vo_s0[3];
-    for (int k = 0; k < 3; ++k) vo_s0[k] = k < n_s0 ? vstate[s0_id[k]] : 0.0;
     __syncthreads();
-    sweeps[6] = xs_value_iteration<SP>(Trow, er, g2, false, own, S, A, qr, Qs, Vs, part, n_waves);
+    sweeps[6] = xs_value_iteration(C, T, g2, false, er, qr);
     if (sweeps[5] >= XS_MAX_SWEEPS || sweeps[6] >= XS_MAX_SWEEPS) status = 4;
-    if (own) Qs[tid] = qr;
+    xs_publish(C, T, qr);
     __syncthreads();
     const double scale = (1.0 - g2) * max_steps;
     for (int k = 0; k < n_s0; ++k) {
-      const int s0 = s0_id[k];
-      double vr = Qs[s0 * A];
-      for (int b = 1; b < A; ++b) vr = Qs[s0 * A + b] > vr ? Qs[s0 * A + b] : vr;
-      const double gap = vo_s0[k] * scale - vr * scale;
+      const double vr = xs_row_max(Qs + s0i(k) * A, A);
+      const double gap = vstate[s0i(k)] * scale - vr * scale;
       if (k == 0 || gap < gap_min) gap_min = gap;
     }
     if (status == 0 && gap_min < 2.0) status = 2;
     if (status == 0) {      // uniform
       const int K = (int)log2(max_steps) + 1;
       double* Pa = Pm;
-      double* Pb = Pm + SP * SP;
-      for (int rep = 0; rep < K; ++rep) {
-        __syncthreads();
-        for (int e = tid; e < S * S; e += blockDim.x) {
-          const int i = e / S, j = e - i * S;
-          double acc = 0.0;
-          for (int k = 0; k < S; ++k) acc = fma(Pa[i * S + k], Pa[k * S + j], acc);
-          Pb[e] = acc;
-        }
-        double* t = Pa; Pa = Pb; Pb = t;
-      }
-      __syncthreads();
-      for (int k = 0; k < n_s0; ++k) {
-        const double* row = Pa + s0_id[k] * S;
-        double s2 = 0.0, h = 0.0;
-        for (int j = 0; j < S; ++j) {
-          const double p = row[j] + 1.0e-12;
-          s2 += p * p;
-          h += p * log(p);
-        }
-        const double gk = 1.0 - s2, ek = -h / log((double)S);
-        if (k == 0 || gk < gini) gini = gk;
-        if (k == 0 || ek < ent) ent = ek;
-      }
-      if (!(gini > 0.70 && ent > 0.35)) status = 3;
-    }
-  }
-
-  // ---- outputs ----
-  if (tid == 0) {
-    P.status[ci] = status;
-    if (P.info) {
-      xv_anymdp_cand_info& o = P.info[ci];
-      o.status = status; o.goal = goal; o.n_s0 = n_s0; o.repair_rounds = repair_rounds;
-      for (int k = 0; k < 4; ++k) { o.s0[k] = k < n_s0 ? s0_id[k] : 0; o.s0_prob[k] = k < n_s0 ? s0_p[k] : 0.0; }
-      for (int k = 0; k < 8; ++k) o.sweeps[k] = sweeps[k];
-      o.max_steps = max_steps; o.gini = gini; o.ent = ent; o.gap_min = gap_min;
-    }
-  }
-  if (P.info && own && a == 0) {
-    P.info[ci].band_lo[s] = first;
-    P.info[ci].band_hi[s] = last;
-    P.info[ci].s_e[s] = (uint8_t)pitm[s];
-  }
-  if (own && (P.transition || P.reward || P.noise)) {
-    const size_t o = (((size_t)ci * S + s) * A + a) * S;
-#pragma unroll
-    for (int j = 0; j < SP; ++j)
-      if (j < S) {
-        if (P.transition) P.transition[o + j] = Trow[j];
-        if (P.reward) {
-          const double r = (((pot_s - pot[j]) + rpos[j]) + rsa) + r_step;
-          P.reward[o + j] = r + bonus[j];
-        }
-        if (P.noise) P.noise[o + j] = npos[j] + nsa;
-      }
-  }
-  // state_mapping: a Fisher-Yates permutation of the state ids (task_sampler.py:44), sequential by nature
-  if (tid == 0 && (P.state_map || P.info)) {
-    int* sm = reinterpret_cast<int*>(Qs);
-    for (int i = 0; i < S; ++i) sm[i] = i;
-    for (int i = S - 1; i >= 1; --i) {
-      const xv_u32x4 q4 = xs_draw(P, cand, XS_PERM, (uint32_t)(i >> 2));
-      const int j = (int)(xs_word(q4, i & 3) % (uint32_t)(i + 1));
-      const int t = sm[i]; sm[i] = sm[j]; sm[j] = t;
-    }
-    for (int i = 0; i < S; ++i) {
-      if (P.info) P.info[ci].state_map[i] = sm[i];
-      if (P.state_map && status == 0) P.state_map[(size_t)ci * S + i] = sm[i];
-    }
-  }
-  if (status != 0 || P.rows == nullptr) return;
-  // accepted: the step engine's tables.  Row record of (s, a): line 0 (fence) left zero — xv_anymdp_create completes
-  // it — then blocks of 7 entries {cdf fp64, reward fp32, noise fp32}; cdf = cumsum(row) / cumsum(row)[-1] as
-  // numpy.random.choice forms it, 1.0 for the all-zero rows of terminal states, 2.0 past the last state.
-  if (own) {
-    double* rec = P.rows + (((size_t)ci * S + s) * A + a) * (size_t)P.row_lines * 16;
-    for (int k = 0; k < P.row_lines * 16; ++k) rec[k] = 0.0;
-    double tot = 0.0;
-#pragma unroll
-    for (int j = 0; j < SP; ++j) if (j < S) tot += Trow[j];
-    const bool zero_row = tot == 0.0;
-    double c = 0.0;
-    const int n_ent = (P.row_lines - 1) * 7;
-    int j = 0;
-#pragma unroll
-    for (int jj = 0; jj < SP; ++jj)
-      if (jj < S) {
-        c += Trow[jj];
-        const double cdf = zero_row ? 1.0 : c / tot;
-        const double r = ((((pot_s - pot[jj]) + rpos[jj]) + rsa) + r_step) + bonus[jj];
-        const float rf = (float)r, nf = (float)(npos[jj] + nsa);
-        double* ent = rec + 16 * (1 + jj / 7) + 2 * (jj % 7);
-        ent[0] = cdf;
-        ent[1] = __hiloint2double((int)__float_as_uint(nf), (int)__float_as_uint(rf));
-        j = jj + 1;
-      }
-    for (; j < n_ent; ++j) rec[16 * (1 + j / 7) + 2 * (j % 7)] = 2.0;
-  }
-  if (tid == 0) {
-    uint64_t m = 0;
-    for (int j = 0; j < S; ++j) if (pitm[j]) m |= 1ull << j;
-    P.term_mask[ci] = m;
-    double c = 0.0, ctot = 0.0;
-    for (int k = 0; k < n_s0; ++k) ctot += s0_p[k];
-    for (int k = 0; k < P.s0_max; ++k) {
-      if (k < n_s0) {      // cumsum(p) / cumsum(p)[-1], as numpy.random.choice forms it (anymdp_env.py:89)
-        c += s0_p[k];
-        P.s0_cdf[(size_t)ci * P.s0_max + k] = c / ctot;
-        P.s0_ids[(size_t)ci * P.s0_max + k] = s0_id[k];
-      } else {
-        P.s0_cdf[(size_t)ci * P.s0_max + k] = 1.0;
-        P.s0_ids[(size_t)ci * P.s0_max + k] = s0_id[n_s0 - 1];
-      }
-    }
-    const double ms = ceil(max_steps);
-    P.max_steps[ci] = (int32_t)ms;
-  }
-}
-
-
-// ------------------------------------------------------------------------------------------------
-// The same sampler for 64 < S <= 256 (round 4; the reference's GarnetTaskSampler defaults to 128 states and its
-// MultiTokensAnyPOMDPTaskSampler to 256, task_sampler.py:90-126).  A candidate's transition tensor is S * A rows of S
-// doubles (2.6 MB at 256 x 5): it no longer lives in registers but in a per-candidate global scratch, TRANSPOSED in blocks
-// of 64 rows — Tt[(row >> 6) * S + j][row & 63] — so that the 64 lanes of a wave, which own 64 consecutive rows, read
-// element j of their rows as one coalesced 512-byte access.  Thread tid owns rows tid, tid + blockDim, ... (R <= 4 of them);
-// every chain keeps the order of the register kernel (fma over j ascending: a zero outside a row's band adds nothing), so
-// both kernels and the oracle restatement (oracle/xeno_oracle_sampler.c) agree to rounding, candidates draw for draw.
-// Same Philox coordinates as the register kernel: the index strides (64 words per 256 states) were laid out for 256 states.
-// ------------------------------------------------------------------------------------------------
-struct BigScratch {
-  double* Tt;        // [n_cand][n_rb * S * 64]
-  double* Pm;        // [n_cand][2 * S * S]   band weights during generation, occupancy matrices at acceptance
-  int n_rb;
-};
-
-__device__ __forceinline__ double xsb_t(const double* Tt, int S, int r, int j) { return Tt[((size_t)(r >> 6) * S + j) * 64 + (r & 63)]; }
-
-// reward of (row with potential pot_s and state-action piece rsa) -> next state j, without the terminal bonus
-__device__ __forceinline__ void xsb_sa_pieces(const SamplerArgs& P, uint64_t cand, double sbase, int r, double& rsa, double& nsa) {
-  double zr, zn;
-  const xv_u32x4 q4 = xs_draw(P, cand, XS_SAM, (uint32_t)r);
-  const double on = xs_u32(q4.x) > 0.7 ? 1.0 : 0.0;
-  xs_normal2(q4.y, q4.z, zr, zn);
-  rsa = sbase * zr * on;
-  nsa = 0.30 * sbase * (zn > 0.0 ? zn : 0.0) * on;
-}
-
-template <int R>
-__device__ __forceinline__ int xsb_value_iteration(const double* Tt, int S, int A, int SA, double gamma, bool greedy,
-                                                   const double (&er)[R], double (&q)[R], const int (&wf)[R], const int (&wl)[R],
-                                                   double* Qs, double* Vs, double* part, int n_waves) {
-  const int tid = threadIdx.x, BD = blockDim.x;
-  double d2 = 0.0;
-  int it = 0;
-  for (;;) {
-#pragma unroll
-    for (int k = 0; k < R; ++k) {
-      const int r = k * BD + tid;
-      if (r < SA) Qs[r] = q[k];
-    }
-    {
-      double x = d2;
-      for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
-      if ((tid & 63) == 0) part[tid >> 6] = x;
-    }
-    __syncthreads();
-    if (it > 0) {
-      double tot = 0.0;
-      for (int w = 0; w < n_waves; ++w) tot += part[w];
-      if (sqrt(tot / (double)SA) <= 1.0e-4 || it >= XS_MAX_SWEEPS) break;
-    }
-    if (tid < S) {
-      const double* row = Qs + tid * A;
-      double v;
-      if (greedy) {
-        v = row[0];
-        for (int a = 1; a < A; ++a) v = row[a] > v ? row[a] : v;
-      } else {
-        v = 0.0;
-        for (int a = 0; a < A; ++a) v += row[a];
-        v /= (double)A;
-      }
-      Vs[tid] = v;
-    }
-    __syncthreads();
-    d2 = 0.0;
-#pragma unroll
-    for (int k = 0; k < R; ++k) {
-      const int r = k * BD + tid;
-      const double* col = Tt + ((size_t)(r >> 6) * S) * 64 + (r & 63);
-      double acc = 0.0;
-      for (int j = wf[k]; j < wl[k]; ++j) acc = fma(col[(size_t)j * 64], Vs[j], acc);
-      const double qn = fma(gamma, acc, er[k]);
-      if (r < SA) d2 += (qn - q[k]) * (qn - q[k]);
-      q[k] = qn;
-    }
-    ++it;
-  }
-  __syncthreads();
-  return it;
-}
-
-template <int R>
-__global__ __launch_bounds__(1024) void anymdp_sampler_big_kernel(SamplerArgs P, BigScratch X) {
-  extern __shared__ __attribute__((aligned(16))) double lds[];
-  const int S = P.S, A = P.A, SA = S * A, tid = threadIdx.x, BD = blockDim.x;
-  const int n_waves = BD >> 6;
-  const int ci = blockIdx.x;
-  const uint64_t cand = (uint64_t)(P.cand_base + ci);
-  const int SAp = X.n_rb * 64;
-  double* Tt = X.Tt + (size_t)ci * SAp * S;
-  double* Pm = X.Pm + (size_t)ci * 2 * S * S;
-  double* Qs = lds;                    // [SAp]
-  double* Vs = Qs + SAp;               // [S]
-  double* part = Vs + S;               // [16]
-  double* pot = part + 16;             // [S]
-  double* rpos = pot + S;
-  double* npos = rpos + S;
-  double* bonus = npos + S;
-  double* vstate = bonus + S;
-  int* pitm = reinterpret_cast<int*>(vstate + S);
-  int* bandlo = pitm + S;
-  int* bandhi = bandlo + S;
-
-  // ---- uniform scalars (as the register kernel) ----
-  xv_u32x4 w = xs_draw(P, cand, XS_HEAD, 0);
-  const double lower = 4.0 * S > 100 ? 4.0 * S : 100;
-  double upper = 8.0 * S < 500 ? 8.0 * S : 500;
-  if (upper < lower + 1) upper = lower + 1;
-  const double max_steps = lower + xv_u53(w.x, w.y) * (upper - lower);
-  double w0[3] = {1.0, 0.0, 0.0};
-  for (uint32_t r = 0; r < 16; ++r) {
-    const xv_u32x4 q4 = xs_draw(P, cand, XS_S0, r);
-    double z0, z1, z2, z3;
-    xs_normal2(q4.x, q4.y, z0, z1);
-    xs_normal2(q4.z, q4.w, z2, z3);
-    const double c0 = z0 > 0.0 ? z0 : 0.0, c1 = z1 > 0.0 ? z1 : 0.0, c2 = z2 > 0.0 ? z2 : 0.0;
-    if ((c0 + c1) + c2 >= XS_EPS) { w0[0] = c0; w0[1] = c1; w0[2] = c2; break; }
-  }
-  int s0_id[3], n_s0 = 0;
-  double s0_p[3], s0sum = 0.0;
-  for (int k = 0; k < 3; ++k)
-    if (w0[k] > XS_EPS) { s0_id[n_s0] = k; s0_p[n_s0] = w0[k]; s0sum += w0[k]; ++n_s0; }
-  for (int k = n_s0; k < 3; ++k) { s0_id[k] = 0; s0_p[k] = 0.0; }
-  for (int k = 0; k < n_s0; ++k) s0_p[k] /= s0sum;
-  w = xs_draw(P, cand, XS_PIT, 0);
-  double p_pit = -0.20 + 0.60 * xv_u53(w.x, w.y);
-  if (p_pit < 0.0) p_pit = 0.0;
-  const int goal = xs_u32(w.z) < 0.3 ? 1 : 0;
-  {
-    int mine = 0;
-    for (uint32_t r = 0; r < 64; ++r) {
-      mine = 0;
-      if (tid < S) {
-        const xv_u32x4 q4 = xs_draw(P, cand, XS_PITS, r * 64u + (uint32_t)(tid >> 2));
-        mine = xs_u32(xs_word(q4, tid & 3)) < p_pit ? 1 : 0;
-      }
-      const int cnt = __syncthreads_count(mine);
-      if ((double)cnt < (double)S * p_pit + 1.0) break;
-    }
-    if (tid < S) {
-      for (int k = 0; k < n_s0; ++k) if (tid == s0_id[k]) mine = 0;
-      if (tid == S - 1) mine = goal;
-      pitm[tid] = mine;
-    }
-  }
-  __syncthreads();
-  int n_se = 0;
-  for (int j = 0; j < S; ++j) n_se += pitm[j];
-
-  // ---- bands ----
-  if (tid < S) {
-    int first = 0, last = 0;
-    if (!pitm[tid]) {
-      const int st = tid;
-      const int fwd_max = S / 4 + 1 > 2 ? S / 4 + 1 : 2, back_max = S / 2 + 1 > 2 ? S / 2 + 1 : 2;
-      const int a_lo = st - back_max > 0 ? st - back_max : 0;
-      int a_hi = st - 1 > 0 ? st - 1 : 0;
-      if (a_hi < a_lo + 1) a_hi = a_lo + 1;
-      const int b_hi = S < st + fwd_max ? S : st + fwd_max;
-      int b_lo = S - 1 < st + 1 ? S - 1 : st + 1;
-      if (b_lo > b_hi - 1) b_lo = b_hi - 1;
-      w = xs_draw(P, cand, XS_BAND, (uint32_t)st);
-      first = a_lo + (int)(w.x % (uint32_t)(a_hi - a_lo));
-      last = b_lo + (int)(w.y % (uint32_t)(b_hi - b_lo));
-      while (last < S) {
-        int ahead = 0;
-        for (int j = st + 1; j < last; ++j) ahead += !pitm[j];
-        if (ahead > 1) break;
-        ++last;
-      }
-    }
-    bandlo[tid] = first; bandhi[tid] = last;
-  }
-  __syncthreads();
-  for (int el = tid; el < S * S; el += BD) {
-    const int st = el / S, j = el - st * S;
-    double v = 0.0;
-    if (j >= bandlo[st] && j < bandhi[st]) {
-      const xv_u32x4 q4 = xs_draw(P, cand, XS_BANDW, ((uint32_t)st * 8u) * 64u + (uint32_t)(j >> 2));
-      v = xs_clip(xs_normal_of(q4, j & 3), 0.10, 1.0);
-    }
-    Pm[el] = v;
-  }
-  __syncthreads();
-  if (tid < S && !pitm[tid]) {
-    Pm[tid * S + tid] = (tid == S - 1) ? 0.0 : Pm[tid * S + tid] / 2.0;
-    double tot = 0.0;
-    for (int j = bandlo[tid]; j < bandhi[tid]; ++j) tot += Pm[tid * S + j];
-    Vs[tid] = tot;
-  }
-  __syncthreads();
-
-  // ---- the rows of the transition tensor, into the transposed scratch; wave-uniform column ranges of each row group ----
-  int wf[R], wl[R];
-#pragma unroll
-  for (int k = 0; k < R; ++k) {
-    const int r = k * BD + tid;
-    const bool in = r < SA;
-    const int s = in ? r / A : 0, a = in ? r - s * A : 0;
-    const bool live = in && !pitm[s];
-    const int first = live ? bandlo[s] : 0, last = live ? bandhi[s] : 0;
-    int lo = live ? first : S, hi = live ? last : 0;
-    for (int o = 32; o > 0; o >>= 1) {
-      const int l2 = __shfl_xor(lo, o), h2 = __shfl_xor(hi, o);
-      lo = l2 < lo ? l2 : lo; hi = h2 > hi ? h2 : hi;
-    }
-    wf[k] = lo < hi ? lo : 0; wl[k] = lo < hi ? hi : 0;
-    if (r >= SAp) continue;
-    double* col = Tt + ((size_t)(r >> 6) * S) * 64 + (r & 63);
-    if (!live) {
-      for (int j = 0; j < S; ++j) col[(size_t)j * 64] = 0.0;
-      continue;
-    }
-    const double tot = Vs[s];
-    double cen[64];
-    for (int b = 0; b < A; ++b) {
-      const xv_u32x4 q4 = xs_draw(P, cand, XS_ACT, (uint32_t)s * 16u + (uint32_t)(b >> 2));
-      cen[b] = (double)(first - 1) + xs_u32(xs_word(q4, b & 3)) * (double)(last - (first - 1));
-    }
-    w = xs_draw(P, cand, XS_ACTW, (uint32_t)s);
-    const double width = xs_clip(xs_expo(xv_u53(w.x, w.y)), 0.20, 1.6);
-    const double inv_w2 = 1.0 / (width * width);
-    double rs = 0.0;
-    for (int j = 0; j < S; ++j) {
-      double v = 0.0;
-      if (j >= first && j < last) {
-        double colsum = 0.0, dmin = 0.0, e_me = 0.0;
-        int amin = 0;
-        for (int b = 0; b < A; ++b) {
-          const double d = cen[b] - (double)j, d2 = d * d;
-          const double e = exp(-d2 * inv_w2);
-          colsum += e;
-          if (b == a) e_me = e;
-          if (b == 0 || d2 < dmin) { dmin = d2; amin = b; }
-        }
-        if (colsum < XS_EPS) {
-          colsum = 0.0;
-          for (int b = 0; b < A; ++b) {
-            const double d = cen[b] - (double)j;
-            colsum += (b == amin) ? 1.0 : exp(-(d * d) * inv_w2);
-          }
-          if (a == amin) e_me = 1.0;
-        }
-        v = (e_me / colsum) * (Pm[s * S + j] / tot);
-        rs += v;
-      }
-      col[(size_t)j * 64] = v;
-    }
-    for (int j = first; j < last; ++j) col[(size_t)j * 64] /= rs;
-  }
-  __syncthreads();
-
-  // ---- rewards: per-state pieces in LDS (as the register kernel) ----
-  double pbase, ub;
-  {
-    w = xs_draw(P, cand, XS_POS, 0);
-    pbase = 0.2 * xs_expo(xv_u53(w.x, w.y));
-    ub = xv_u53(w.z, w.w);
-  }
-  if (tid < S) {
-    const int j = tid;
-    xv_u32x4 q4 = xs_draw(P, cand, XS_POT, 0);
-    const double base = xv_u53(q4.x, q4.y) < 0.5 ? 0.0 : xs_clip(xs_expo(xv_u53(q4.z, q4.w)), 0.20, 5.0);
-    q4 = xs_draw(P, cand, XS_POT, 1);
-    double box = -base + 2.0 * base * xv_u53(q4.x, q4.y);
-    if (box < 0.0) box = 0.0;
-    const int n_items = 1 + (int)(q4.z % 3u);
-    const double scale = box / sqrt((double)n_items);
-    const double x = (double)j / (double)(2 * S);
-    double pj = 0.0;
-    for (int k = 0; k <= n_items; ++k) {
-      double za, zb, order = 0.0;
-      q4 = xs_draw(P, cand, XS_POT, 2u + (uint32_t)k);
-      xs_normal2(q4.x, q4.y, za, zb);
-      const double ca = za * (xs_expo(xs_u32(q4.z)) * scale), cb = zb * (xs_expo(xs_u32(q4.w)) * scale);
-      if (k > 0) {
-        double zo, zd;
-        q4 = xs_draw(P, cand, XS_POT, 8u + (uint32_t)k);
-        xs_normal2(q4.y, q4.z, zo, zd);
-        order = (double)(1 + (int)(q4.x % 5u)) + zo;
-      }
-      pj += ca * sin(order * x) + cb * cos(order * x);
-    }
-    pot[j] = pj;
-    q4 = xs_draw(P, cand, XS_POSN, (uint32_t)(j >> 2));
-    double pdf = xs_normal_of(q4, j & 3);
-    pdf = pdf > 0.0 ? pdf : 0.0;
-    if (j == S - 1) pdf += 0.20;
-    rpos[j] = pdf * pbase;
-    q4 = xs_draw(P, cand, XS_POSU, (uint32_t)(j >> 2));
-    const double u = -0.30 + 0.60 * xs_u32(xs_word(q4, j & 3));
-    npos[j] = pitm[j] ? 0.0 : (u > 0.0 ? u : 0.0) * pbase;
-    bonus[j] = (j == S - 1) ? 1.0 : 0.0;
-  }
-  __syncthreads();
-  double cdf_j = 0.0, c_all = 0.0;
-  for (int i = 0; i < S; ++i) {
-    c_all += rpos[i];
-    if (i == tid) cdf_j = c_all;
-  }
-  __syncthreads();
-  if (tid < S) {
-    const double baseline = 0.1 * c_all + ub * (0.9 * c_all - 0.1 * c_all);
-    rpos[tid] = pitm[tid] ? 0.0 : cdf_j - baseline;
-  }
-  double r_step = 0.0, sbase;
-  {
-    w = xs_draw(P, cand, XS_SA, 0);
-    sbase = xs_clip(0.05 * xs_expo(xv_u53(w.x, w.y)), 0.0, 0.10);
-    double zs, zd;
-    w = xs_draw(P, cand, XS_STEP, 0);
-    xs_normal2(w.x, w.y, zs, zd);
-    if (goal) r_step = (zs < 0.0 ? zs : 0.0) * 0.01;
-    else if (n_se > 0) r_step = (zs > 0.0 ? zs : 0.0) * 0.01;
-  }
-  double rsa[R], nsa[R], pot_s[R];
-#pragma unroll
-  for (int k = 0; k < R; ++k) {
-    const int r = k * BD + tid;
-    rsa[k] = 0.0; nsa[k] = 0.0; pot_s[k] = 0.0;
-    if (r < SA) {
-      xsb_sa_pieces(P, cand, sbase, r, rsa[k], nsa[k]);
-      pot_s[k] = pot[r / A];
-    }
-  }
-  __syncthreads();
-
-  // expected reward of this thread's rows under the current bonus: the chain of the register kernel over the row's band
-  auto expected = [&](double (&er)[R]) {
-#pragma unroll
-    for (int k = 0; k < R; ++k) {
-      const int r = k * BD + tid;
-      double e = 0.0;
-      if (r < SA) {
-        const double* col = Tt + ((size_t)(r >> 6) * S) * 64 + (r & 63);
-        for (int j = wf[k]; j < wl[k]; ++j) {
-          double rr = (((pot_s[k] - pot[j]) + rpos[j]) + rsa[k]) + r_step;
-          rr += bonus[j];
-          e = fma(col[(size_t)j * 64], rr, e);
-        }
-      }
-      er[k] = e;
-    }
-  };
-
-  // ---- terminal rewards repaired against the value function ----
-  const int last_live = goal ? S - 2 : S - 1;
-  int status = 1, repair_rounds = 0;
-  int sweeps[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  double q[R], er[R];
-#pragma unroll
-  for (int k = 0; k < R; ++k) q[k] = 0.0;
-  for (int tries = 0; tries < 5; ++tries) {
-    expected(er);
-    const int sw = xsb_value_iteration<R>(Tt, S, A, SA, 0.99, true, er, q, wf, wl, Qs, Vs, part, n_waves);
-    sweeps[tries] = sw;
-    repair_rounds = tries + 1;
-    if (sw >= XS_MAX_SWEEPS) { status = 4; break; }
-#pragma unroll
-    for (int k = 0; k < R; ++k) {
-      const int r = k * BD + tid;
-      if (r < SA) Qs[r] = q[k];
-    }
-    __syncthreads();
-    if (tid < S) {
-      double v = Qs[tid * A];
-      for (int b = 1; b < A; ++b) v = Qs[tid * A + b] > v ? Qs[tid * A + b] : v;
-      vstate[tid] = v;
-    }
-    __syncthreads();
-    double vmin_live = 0.0, vmax_s0 = 0.0, bmin = bonus[0];
-    bool first_live = true;
-    for (int j = 0; j < S; ++j) {
-      const double v = vstate[j];
-      if (!pitm[j] && (first_live || v < vmin_live)) { vmin_live = v; first_live = false; }
-      if (bonus[j] < bmin) bmin = bonus[j];
-    }
-    for (int k = 0; k < n_s0; ++k) {
-      const double v = vstate[s0_id[k]];
-      if (k == 0 || v > vmax_s0) vmax_s0 = v;
-    }
-    w = xs_draw(P, cand, XS_REPAIR, (uint32_t)tries);
-    const double pit_gap = bmin - vmin_live + 1.0;
-    const double goal_gap = vmax_s0 - vstate[last_live] + (2.0 + 3.0 * xv_u53(w.x, w.y));
-    if (pit_gap <= 0.0 && goal_gap <= 0.0) { status = 0; break; }
-    __syncthreads();
-    if (tid < S) {
-      double bj = bonus[tid];
-      if (pit_gap > 0.0 && pitm[tid] && !(goal && tid == S - 1)) bj -= pit_gap + (1.0 + 9.0 * xs_u32(w.z));
-      if (goal_gap > 0.0 && tid == S - 1) {
-        const double extra = 1.0 + 9.0 * xs_u32(w.w);
-        const double lift = 2.0 * goal_gap > extra ? 2.0 * goal_gap : extra;
-        bj += goal ? lift : (1.0 - 0.99) * lift;
-      }
-      bonus[tid] = bj;
-    }
-    __syncthreads();
-  }
-
-  // ---- acceptance ----
-  double gini = 0.0, ent = 0.0, gap_min = 0.0;
-  if (status == 0) {
-    const double g2 = exp2(-1.0 / (double)S);
-    expected(er);
-    double qo[R], qr[R];
-#pragma unroll
-    for (int k = 0; k < R; ++k) { qo[k] = 0.0; qr[k] = 0.0; }
-    sweeps[5] = xsb_value_iteration<R>(Tt, S, A, SA, g2, true, er, qo, wf, wl, Qs, Vs, part, n_waves);
-#pragma unroll
-    for (int k = 0; k < R; ++k) {
-      const int r = k * BD + tid;
-      if (r < SA) Qs[r] = qo[k];
-    }
-    __syncthreads();
-    if (tid < S) {
-      double v = Qs[tid * A];
-      for (int b = 1; b < A; ++b) if (Qs[tid * A + b] > v) v = Qs[tid * A + b];
-      vstate[tid] = v;
-    }
-    __syncthreads();
-    // occupancy matrix: row s = the greedy action's row of T (first maximum), or the start distribution for terminal states
-#pragma unroll
-    for (int k = 0; k < R; ++k) {
-      const int r = k * BD + tid;
-      if (r < SA) {
-        const int s = r / A, a = r - s * A;
-        int g_s = 0;
-        double v = Qs[s * A];
-        for (int b = 1; b < A; ++b) if (Qs[s * A + b] > v) { v = Qs[s * A + b]; g_s = b; }
-        if (a == g_s) {
-          const double* col = Tt + ((size_t)(r >> 6) * S) * 64 + (r & 63);
-          for (int j = 0; j < S; ++j) {
-            double pj = col[(size_t)j * 64];
-            if (pitm[s]) {
-              pj = 0.0;
-              for (int kk = 0; kk < n_s0; ++kk) if (j == s0_id[kk]) pj = s0_p[kk];
-            }
-            Pm[s * S + j] = pj;
-          }
-        }
-      }
-    }
-    double vo_s0[3];
-    for (int k = 0; k < 3; ++k) vo_s0[k] = k < n_s0 ? vstate[s0_id[k]] : 0.0;
-    __syncthreads();
-    sweeps[6] = xsb_value_iteration<R>(Tt, S, A, SA, g2, false, er, qr, wf, wl, Qs, Vs, part, n_waves);
-    if (sweeps[5] >= XS_MAX_SWEEPS || sweeps[6] >= XS_MAX_SWEEPS) status = 4;
-#pragma unroll
-    for (int k = 0; k < R; ++k) {
-      const int r = k * BD + tid;
-      if (r < SA) Qs[r] = qr[k];
-    }
-    __syncthreads();
-    const double scale = (1.0 - g2) * max_steps;
-    for (int k = 0; k < n_s0; ++k) {
-      const int s0 = s0_id[k];
-      double vr = Qs[s0 * A];
-      for (int b = 1; b < A; ++b) vr = Qs[s0 * A + b] > vr ? Qs[s0 * A + b] : vr;
-      const double gap = vo_s0[k] * scale - vr * scale;
-      if (k == 0 || gap < gap_min) gap_min = gap;
-    }
-    if (status == 0 && gap_min < 2.0) status = 2;
-    if (status == 0) {
-      const int K = (int)log2(max_steps) + 1;
-      double* Pa = Pm;
-      double* Pb = Pm + (size_t)S * S;
+      double* Pb = C.Pm2;
       for (int rep = 0; rep < K; ++rep) {
         __syncthreads();
         for (int e = tid; e < S * S; e += BD) {
@@ -1079,7 +607,7 @@ __global__ __launch_bounds__(1024) void anymdp_sampler_big_kernel(SamplerArgs P,
       }
       __syncthreads();
       for (int k = 0; k < n_s0; ++k) {
-        const double* row = Pa + s0_id[k] * S;
+        const double* row = Pa + s0i(k) * S;
         double s2 = 0.0, h = 0.0;
         for (int j = 0; j < S; ++j) {
           const double p = row[j] + 1.0e-12;
@@ -1095,12 +623,19 @@ __global__ __launch_bounds__(1024) void anymdp_sampler_big_kernel(SamplerArgs P,
   }
 
   // ---- outputs ----
+  double nsa[R];
+#pragma unroll
+  for (int k = 0; k < R; ++k) {
+    double again;
+    nsa[k] = 0.0;
+    if (T.row(k) < SA && (P.noise || (status == 0 && P.rows))) sa_pieces(T.row(k), again, nsa[k]);
+  }
   if (tid == 0) {
     P.status[ci] = status;
     if (P.info) {
       xv_anymdp_cand_info& o = P.info[ci];
       o.status = status; o.goal = goal; o.n_s0 = n_s0; o.repair_rounds = repair_rounds;
-      for (int k = 0; k < 4; ++k) { o.s0[k] = k < n_s0 ? s0_id[k] : 0; o.s0_prob[k] = k < n_s0 ? s0_p[k] : 0.0; }
+      for (int k = 0; k < 4; ++k) { o.s0[k] = k < n_s0 ? s0i(k) : 0; o.s0_prob[k] = k < n_s0 ? s0p(k) : 0.0; }
       for (int k = 0; k < 8; ++k) o.sweeps[k] = sweeps[k];
       o.max_steps = max_steps; o.gini = gini; o.ent = ent; o.gap_min = gap_min;
     }
@@ -1113,26 +648,23 @@ __global__ __launch_bounds__(1024) void anymdp_sampler_big_kernel(SamplerArgs P,
   if (P.transition || P.reward || P.noise) {
 #pragma unroll
     for (int k = 0; k < R; ++k) {
-      const int r = k * BD + tid;
+      const int r = T.row(k);
       if (r < SA) {
         const size_t o = ((size_t)ci * SA + r) * S;
-        const double* col = Tt + ((size_t)(r >> 6) * S) * 64 + (r & 63);
-        for (int j = 0; j < S; ++j) {
-          if (P.transition) P.transition[o + j] = col[(size_t)j * 64];
-          if (P.reward) {
-            const double rr = (((pot_s[k] - pot[j]) + rpos[j]) + rsa[k]) + r_step;
-            P.reward[o + j] = rr + bonus[j];
-          }
+        T.each(k, 0, S, [&](int j, double& t) {
+          if (P.transition) P.transition[o + j] = t;
+          if (P.reward) P.reward[o + j] = reward(k, j);
           if (P.noise) P.noise[o + j] = npos[j] + nsa[k];
-        }
+        });
       }
     }
   }
+  // state_mapping: a Fisher-Yates permutation of the state ids (task_sampler.py:44), sequential by nature
   if (tid == 0 && (P.state_map || P.info)) {
     int* sm = reinterpret_cast<int*>(Qs);
     for (int i = 0; i < S; ++i) sm[i] = i;
     for (int i = S - 1; i >= 1; --i) {
-      const xv_u32x4 q4 = xs_draw(P, cand, XS_PERM, (uint32_t)(i >> 2));
+      const xv_u32x4 q4 = C.draw(XS_PERM, (uint32_t)(i >> 2));
       const int j = (int)(xs_word(q4, i & 3) % (uint32_t)(i + 1));
       const int t = sm[i]; sm[i] = sm[j]; sm[j] = t;
     }
@@ -1142,49 +674,102 @@ __global__ __launch_bounds__(1024) void anymdp_sampler_big_kernel(SamplerArgs P,
     }
   }
   if (status != 0 || P.rows == nullptr) return;
+  // accepted: the step engine's tables.  Row record of (s, a): line 0 (fence) left zero — xv_anymdp_create completes
+  // it — then blocks of 7 entries {cdf fp64, reward fp32, noise fp32}; cdf = cumsum(row) / cumsum(row)[-1] as
+  // numpy.random.choice forms it, 1.0 for the all-zero rows of terminal states, 2.0 past the last state.
 #pragma unroll
   for (int k = 0; k < R; ++k) {
-    const int r = k * BD + tid;
+    const int r = T.row(k);
     if (r >= SA) continue;
-    const double* col = Tt + ((size_t)(r >> 6) * S) * 64 + (r & 63);
     double* rec = P.rows + ((size_t)ci * SA + r) * (size_t)P.row_lines * 16;
     for (int e = 0; e < P.row_lines * 16; ++e) rec[e] = 0.0;
     double tot = 0.0;
-    for (int j = 0; j < S; ++j) tot += col[(size_t)j * 64];
+    T.each(k, 0, S, [&](int, double& t) { tot += t; });
     const bool zero_row = tot == 0.0;
     double c = 0.0;
-    const int n_ent = (P.row_lines - 1) * 7;
-    for (int jj = 0; jj < S; ++jj) {
-      c += col[(size_t)jj * 64];
-      const double cdf = zero_row ? 1.0 : c / tot;
-      const double rr = ((((pot_s[k] - pot[jj]) + rpos[jj]) + rsa[k]) + r_step) + bonus[jj];
-      const float rf = (float)rr, nf = (float)(npos[jj] + nsa[k]);
-      double* ent2 = rec + 16 * (1 + jj / 7) + 2 * (jj % 7);
-      ent2[0] = cdf;
+    T.each(k, 0, S, [&](int j, double& t) {
+      c += t;
+      const float rf = (float)reward(k, j), nf = (float)(npos[j] + nsa[k]);
+      double* ent2 = rec + 16 * (1 + j / 7) + 2 * (j % 7);
+      ent2[0] = zero_row ? 1.0 : c / tot;
       ent2[1] = __hiloint2double((int)__float_as_uint(nf), (int)__float_as_uint(rf));
-    }
+    });
+    const int n_ent = (P.row_lines - 1) * 7;
     for (int j = S; j < n_ent; ++j) rec[16 * (1 + j / 7) + 2 * (j % 7)] = 2.0;
   }
-  if (tid < (S + 63) / 64) {
+  if (tid < (S + 63) / 64) {      // one mask word per 64 states
     uint64_t m = 0;
     for (int j = 0; j < 64 && 64 * tid + j < S; ++j) if (pitm[64 * tid + j]) m |= 1ull << j;
     P.term_mask[(size_t)ci * ((S + 63) / 64) + tid] = m;
   }
   if (tid == 0) {
     double c = 0.0, ctot = 0.0;
-    for (int k = 0; k < n_s0; ++k) ctot += s0_p[k];
+    for (int k = 0; k < n_s0; ++k) ctot += s0p(k);
     for (int k = 0; k < P.s0_max; ++k) {
-      if (k < n_s0) {
-        c += s0_p[k];
+      if (k < n_s0) {      // cumsum(p) / cumsum(p)[-1], as numpy.random.choice forms it (anymdp_env.py:89)
+        c += s0p(k);
         P.s0_cdf[(size_t)ci * P.s0_max + k] = c / ctot;
-        P.s0_ids[(size_t)ci * P.s0_max + k] = s0_id[k];
+        P.s0_ids[(size_t)ci * P.s0_max + k] = s0i(k);
       } else {
         P.s0_cdf[(size_t)ci * P.s0_max + k] = 1.0;
-        P.s0_ids[(size_t)ci * P.s0_max + k] = s0_id[n_s0 - 1];
+        P.s0_ids[(size_t)ci * P.s0_max + k] = s0i(n_s0 - 1);
       }
     }
     P.max_steps[ci] = (int32_t)ceil(max_steps);
   }
+}
+
+// ---- the two kernels: carve the candidate's arrays, name the storage, run the model ----
+
+template <int SP>
+__global__ __launch_bounds__(512) void anymdp_sampler_kernel(SamplerArgs P) {
+  extern __shared__ __attribute__((aligned(16))) double lds[];
+  Cand C{P, (uint64_t)(P.cand_base + blockIdx.x), P.S, P.A, P.S * P.A};
+  C.Qs = lds;                          // [SA]
+  C.Vs = C.Qs + C.SA;                  // [SP]
+  C.part = C.Vs + SP;                  // [8]
+  C.pot = C.part + 8;                  // [SP] each
+  C.rpos = C.pot + SP;
+  C.npos = C.rpos + SP;
+  C.bonus = C.npos + SP;
+  C.vstate = C.bonus + SP;
+  C.pitm = reinterpret_cast<int*>(C.vstate + SP);
+  C.Pm = reinterpret_cast<double*>(C.pitm + SP);     // [2][SP*SP]
+  C.Pm2 = C.Pm + SP * SP;
+  C.bandlo = reinterpret_cast<int*>(C.Pm + 2 * SP * SP);
+  C.bandhi = C.bandlo + SP;
+  RegRows<SP> T;
+  xs_candidate(C, T);
+}
+
+struct BigScratch {
+  double* Tt;        // [n_cand][n_rb * S * 64]
+  double* Pm;        // [n_cand][2 * S * S]
+  int n_rb;
+};
+
+template <int R>
+__global__ __launch_bounds__(1024) void anymdp_sampler_big_kernel(SamplerArgs P, BigScratch X) {
+  extern __shared__ __attribute__((aligned(16))) double lds[];
+  const int S = P.S, SAp = X.n_rb * 64;
+  Cand C{P, (uint64_t)(P.cand_base + blockIdx.x), S, P.A, S * P.A};
+  C.Qs = lds;                          // [SAp]
+  C.Vs = C.Qs + SAp;                   // [S]
+  C.part = C.Vs + S;                   // [16]
+  C.pot = C.part + 16;                 // [S] each
+  C.rpos = C.pot + S;
+  C.npos = C.rpos + S;
+  C.bonus = C.npos + S;
+  C.vstate = C.bonus + S;
+  C.pitm = reinterpret_cast<int*>(C.vstate + S);
+  C.bandlo = C.pitm + S;
+  C.bandhi = C.bandlo + S;
+  C.Pm = X.Pm + (size_t)blockIdx.x * 2 * S * S;
+  C.Pm2 = C.Pm + (size_t)S * S;
+  BigRows<R> T;
+  T.Tt = X.Tt + (size_t)blockIdx.x * SAp * S;
+  T.S = S; T.SAp = SAp;
+  xs_candidate(C, T);
 }
 
 }  // namespace
@@ -1252,7 +837,7 @@ extern "C" int xv_anymdp_sample_tasks(xv_engine* e, uint64_t seed, int64_t cand_
     return XV_OK;
   }
   const int threads = (S * A + 63) / 64 * 64;
-  const int SP = S <= 16 ? 16 : (S <= 32 ? 32 : 64);
+  const int SP = S <= 16 ? 16 : (S <= 32 ? 32 : 64);      // the smallest that holds S, and S >= 8: SP / 2 <= S (RegRows::each_inner)
   const size_t lds = sizeof(double) * ((size_t)S * A + 6 * SP + 8 + 2 * (size_t)SP * SP) + sizeof(int) * 3 * SP;
 #define XS_LAUNCH(SP_)                                                                                            \
   do {                                                                                                            \
