@@ -1621,6 +1621,93 @@ int xv_anyhvac_sampler_check(int64_t cand_base, int n_cand, int NW, int NL, int 
                              const xv_anyhvac_sampler_params* params, const double* table, const double* extras,
                              const int32_t* status);
 
+/* ------------------------------------------------------------------------------------------------
+ * ChemVerse — reference: xenoverse/chemverse/environment/simulator.py simulate_chain_reaction :639-880 with state_at :34-41,
+ * k_eq_at_T / rate_constant_at_T :44-54, _mixture_heat_capacity / _count_gas_moles / _process_phase_transitions :57-108,
+ * heterogeneous_rate_factor :111-149, phase_factor_for_reaction :152-167, solve_equilibrium_extent :170-205 (scipy's brentq,
+ * xtol 1e-10, 200 iterations, restated), catalyst_acceleration :208-216, _find_common_solvent :219-278, _dissolved_fraction
+ * :281-305, _find_applicable_reactions :308-335, _step_single_reaction :338-428, _update_vessel_state :431-499,
+ * _apply_gas_loss :614-636; worlds: world_gen/models.py :8-265.  The numeric chain-reaction simulator, for n_exp independent
+ * experiments in one launch, each under its own world; the tool-call shell around it (sessions, cost model, samplers) is not
+ * part of the library.  fp64 throughout.  Host restatement, which is the specification: xenoverse_amd/chemverse/host.py; the
+ * tables: xenoverse_amd/chemverse/tables.py (chemical and reaction indices in the world dicts' insertion order — reaction
+ * order is semantics).  New symbols only: no ABI bump.
+ *   xv_chem_set_worlds   the worlds' tables, concatenated, borrowed until the next set_worlds / destroy.  world_off int32
+ *                        [n_world + 1][4]: the first chemical, reaction, equipment entry and solubility entry of every world
+ *                        (world w has C_w = world_off[w + 1][0] - world_off[w][0] chemicals and C_w^2 solubility entries);
+ *                        c_stride >= every C_w and r_stride >= every R_w give the row widths of the per-experiment arrays.
+ *                        chem_f float64 [sum C][8]: molecular weight, melting point, boiling point, clausius_C, heat capacity,
+ *                        latent heat of fusion, of vaporisation, is_solvent (0 / 1).  sol_present uint8, sol_value float64
+ *                        [sum C^2], indexed [chemical][solvent]: `sid in chem.solubility` and its value (two different tests
+ *                        in the reference).  rxn_i int32 [sum R][36]: n_reactant, n_product, n_byproduct, n_catalyst,
+ *                        reactant[6], their coefficients[6], product[4], coefficients[4], byproduct[4], coefficients[4],
+ *                        catalyst[4] (chemical indices within the world; a byproduct outside the world is dropped by the
+ *                        table builder, :415).  rxn_f float64 [sum R][4]: delta_G_kJ, delta_H_kJ, activation_energy_kJ,
+ *                        log_A_factor.  rxn_solv int64 [sum R]: bit s set when every non-solvent reactant lists solvent s.
+ *                        eq_i int32 [sum E][2]: sealed (0 / 1), thermal mode (0 isothermal, 1 adiabatic, 2 open_air, 3
+ *                        heating, 4 cooling).  eq_f float64 [sum E][6]: max_temp_C, min_temp_C, max_pressure_atm,
+ *                        heat_transfer_coeff, max_heat_rate_W, gas retention (0.75 for reflux_condenser, else 0).
+ *   xv_chem_simulate     n_exp experiments, GROUPED by the caller: the 64 experiments of a workgroup, [64 k, 64 k + 64), belong
+ *                        to the world of the first of them; exp_world < 0 marks a padding entry (nothing is computed or
+ *                        written for it).  amounts float64 [n][c_stride] grams by chemical; order int32 [n][c_stride] with
+ *                        n_initial int32 [n]: the chemicals in the caller's order (the pool is a dict in insertion order, and
+ *                        sums run in it); an amount <= 1e-9 is not in the pool (:668-671).  temperature_C, pressure_atm,
+ *                        duration_s, heating_rate_C_per_s, vessel_volume_L float64 [n], equipment int32 [n] (index within the
+ *                        world), step_seconds a HOST double.  A pure function of its arguments: it neither reads nor
+ *                        advances the engine's tick, and an experiment's result does not depend on the batch it is in.
+ * Outputs (xv_chem_out; every pointer nullable, the history its four arrays or none, the log its seven or none):
+ *   final_pool, consumed, produced, byproduct, gas_lost float64 [n][c_stride]: the pool with entries <= 1e-9 zeroed
+ *   (pool_clean :845) and the run's totals, unfiltered; after an equipment failure during the run only `consumed` (the steps
+ *   before the failing one) is non-zero, after a failure of the initial check nothing is.  fired int32 [n][r_stride].
+ *   num_steps int32: max(1, ceil(duration / step_seconds)); steps_run int32: iterations of the step loop entered (the
+ *   reference breaks after three steps without progress).  converged uint8.  failure uint8: 0 none, 1 / 2 the initial
+ *   temperature / pressure, 3 / 4 temperature / pressure during the run; failure_step int32 (-1: none or initial).  final_T,
+ *   final_P float64, unrounded.  History (temperature_history[:30]): hist_step int32, hist_T, hist_P float64 [n][30],
+ *   hist_count int32 [n].  Log (reaction_log[:20]): log_step, log_active int32, log_T, log_P float64 [n][20], log_consumed,
+ *   log_produced float64 [n][20][c_stride] (the step's sums, unfiltered), log_count int32 [n].
+ * Limits (XV_ERR_UNSUPPORTED beyond, the text names the limit): the XV_CHEM_* below.  Bad inputs: world and equipment
+ * indices and non-finite inputs are the caller's to refuse before the launch; the kernel never indexes with them — a world,
+ * equipment or chemical index out of range, an experiment of another world than its workgroup's (skipped), a table size
+ * beyond the strides and more than XV_CHEM_STEPS_MAX steps (cut there) are clamped and set XV_DEVERR_ACTION_RANGE, a
+ * non-finite input sets XV_DEVERR_NONFINITE. */
+#define XV_CHEM_C_MAX 64          /* chemicals per world */
+#define XV_CHEM_R_MAX 128         /* reactions per world */
+#define XV_CHEM_E_MAX 16          /* equipment entries per world */
+#define XV_CHEM_REACTANTS_MAX 6   /* per reaction */
+#define XV_CHEM_PRODUCTS_MAX 4
+#define XV_CHEM_BYPRODUCTS_MAX 4
+#define XV_CHEM_CATALYSTS_MAX 4
+#define XV_CHEM_COEFF_MAX 8       /* largest stoichiometric coefficient */
+#define XV_CHEM_STEPS_MAX 4096    /* steps per experiment */
+#define XV_CHEM_WORLDS_MAX 65536  /* worlds per handle */
+#define XV_CHEM_EXP_MAX (1 << 22) /* experiments per handle */
+#define XV_CHEM_HISTORY_MAX 30
+#define XV_CHEM_LOG_MAX 20
+typedef struct xv_chem xv_chem;
+typedef struct xv_chem_out {
+  double *final_pool, *consumed, *produced, *byproduct, *gas_lost;
+  int32_t* fired;
+  int32_t *num_steps, *steps_run;
+  uint8_t *converged, *failure;
+  int32_t* failure_step;
+  double *final_T, *final_P;
+  int32_t* hist_step;
+  double *hist_T, *hist_P;
+  int32_t* hist_count;
+  int32_t *log_step, *log_active;
+  double *log_T, *log_P, *log_consumed, *log_produced;
+  int32_t* log_count;
+} xv_chem_out;
+int xv_chem_create(xv_engine* e, int n_exp_capacity, xv_chem** out);
+int xv_chem_destroy(xv_chem* h);
+int xv_chem_set_worlds(xv_chem* h, int n_world, int c_stride, int r_stride, const int32_t* world_off, const double* chem_f,
+                       const uint8_t* sol_present, const double* sol_value, const int32_t* rxn_i, const double* rxn_f,
+                       const int64_t* rxn_solv, const int32_t* eq_i, const double* eq_f);
+int xv_chem_simulate(xv_chem* h, int n_exp, const int32_t* exp_world, const double* amounts, const int32_t* order,
+                     const int32_t* n_initial, const double* temperature_C, const double* pressure_atm,
+                     const double* duration_s, const int32_t* equipment, const double* heating_rate_C_per_s,
+                     const double* vessel_volume_L, double step_seconds, const xv_chem_out* out);
+
 #ifdef __cplusplus
 }
 #endif

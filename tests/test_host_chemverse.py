@@ -1,0 +1,235 @@
+"""ChemVerse without a GPU: the tables, brentq_host against recorded scipy calls, the host restatement against the reference's
+recorded runs (tests/chemverse_util.py states the comparison), the reference-surface dict wrapper."""
+import copy
+
+import numpy as np
+import pytest
+
+import chemverse_util as cu
+from xenoverse_amd import _lib
+from xenoverse_amd.chemverse import build_tables, host, simulate_chain_reaction, simulate_chain_reactions
+from xenoverse_amd.chemverse import tables as T
+
+
+# ---- tables ---------------------------------------------------------------------------------------------------------------
+def small_world():
+    chem = lambda **k: dict(dict(molecular_weight=100.0, melting_point=0.0, boiling_point=100.0), **k)      # noqa: E731
+    return dict(
+        chemicals={"Z": chem(is_solvent=True), "B": chem(solubility={"Z": 0.0}), "A": chem(solubility={"Z": 12.5, "Q": 3.0}),
+                   "P": chem(molecular_weight=200.0)},
+        reactions={"r9": dict(reactants=[["A", 2], ["B", 1]], catalysts=["Z"], products=[["P", 1]],
+                              byproducts=[["ghost", 1], ["Z", 3]], delta_G_kJ=-10.0, delta_H_kJ=-20.0, activation_energy_kJ=30.0,
+                              log_A_factor=5.0),
+                   "r1": dict(reactants=[["P", 1]], catalysts=[], products=[["A", 1]], byproducts=[], delta_G_kJ=1.0,
+                              delta_H_kJ=2.0, activation_energy_kJ=3.0, log_A_factor=4.0)},
+        equipment={"reflux_condenser": dict(vessel_type="open", thermal_mode="open_air", max_temp_C=400.0),
+                   "open_beaker": dict(vessel_type="open", thermal_mode="open_air", heat_transfer_coeff=0.05),
+                   "bomb": dict(vessel_type="sealed", thermal_mode="isothermal", max_pressure_atm=50.0, max_heat_rate_W=500.0)})
+
+
+def test_tables_follow_dict_order():
+    t = build_tables(small_world())
+    assert t["chem_ids"] == ["Z", "B", "A", "P"] and t["rxn_ids"] == ["r9", "r1"]
+    assert t["equip_names"] == ["reflux_condenser", "open_beaker", "bomb"]
+    row = t["rxn_i"][0]
+    assert row[:4].tolist() == [2, 1, 1, 1]      # the byproduct outside the world is dropped
+    assert row[T.RX_REAC:T.RX_REAC + 2].tolist() == [2, 1] and row[T.RX_REAC_COEFF:T.RX_REAC_COEFF + 2].tolist() == [2, 1]
+    assert row[T.RX_PROD] == 3 and row[T.RX_BYP] == 0 and row[T.RX_BYP_COEFF] == 3 and row[T.RX_CAT] == 0
+    assert t["rxn_f"][0].tolist() == [-10.0, -20.0, 30.0, 5.0]
+    assert t["chem_f"][3, T.CH_MW] == 200.0 and t["chem_f"][0, T.CH_SOLVENT] == 1.0 and t["chem_f"][1, T.CH_CP] == 2.0
+    assert t["eq_i"].tolist() == [[0, 2], [0, 2], [1, 0]]
+    assert t["eq_f"][0].tolist() == [400.0, -273.0, 1000.0, 0.0, 0.0, 0.75]
+    assert t["eq_f"][1].tolist() == [5000.0, -273.0, 1000.0, 0.05, 0.0, 0.0]
+    assert t["eq_f"][2].tolist() == [5000.0, -273.0, 50.0, 0.0, 500.0, 0.0]
+
+
+def test_tables_keep_solubility_presence_and_value_apart():
+    t = build_tables(small_world())
+    # B lists Z with the value 0: present (the solvent search accepts it), value 0 (the dissolved fraction is 0)
+    assert t["sol_present"][1, 0] == 1 and t["sol_value"][1, 0] == 0.0
+    assert t["sol_present"][2, 0] == 1 and t["sol_value"][2, 0] == 12.5
+    assert t["sol_present"].sum() == 2      # Q is not a chemical of the world
+    assert int(t["rxn_solv"][0]) == 1       # A and B both list Z, and only Z
+    assert int(t["rxn_solv"][1]) == 0       # P lists nothing
+    # a World-like object is accepted too
+    class W(object):
+        pass
+    w, d = W(), small_world()
+    w.chemicals, w.reactions, w.equipment = d["chemicals"], d["reactions"], d["equipment"]
+    t2 = build_tables(w)
+    assert all(np.array_equal(t[k], t2[k]) for k in ("chem_f", "sol_present", "sol_value", "rxn_i", "rxn_f", "eq_i", "eq_f"))
+
+
+def _refused(world, name):
+    with pytest.raises(_lib.XenoError) as ex:
+        build_tables(world)
+    assert ex.value.code == _lib.XV_ERR_UNSUPPORTED and name in str(ex.value), str(ex.value)
+
+
+def test_tables_refuse_beyond_the_limits_by_name():
+    w = small_world()
+    for i in range(T.C_MAX):
+        w["chemicals"]["X%d" % i] = dict(molecular_weight=10.0, melting_point=0.0, boiling_point=1.0)
+    _refused(w, "C_MAX")
+    w = small_world()
+    for i in range(T.R_MAX):
+        w["reactions"]["x%d" % i] = copy.deepcopy(w["reactions"]["r1"])
+    _refused(w, "R_MAX")
+    for key, name, n in (("reactants", "REACTANTS_MAX", T.REACTANTS_MAX), ("products", "PRODUCTS_MAX", T.PRODUCTS_MAX),
+                         ("byproducts", "BYPRODUCTS_MAX", T.BYPRODUCTS_MAX)):
+        w = small_world()
+        for i in range(n + 1):
+            w["chemicals"]["X%d" % i] = dict(molecular_weight=10.0, melting_point=0.0, boiling_point=1.0)
+        w["reactions"]["r1"][key] = [["X%d" % i, 1] for i in range(n + 1)]
+        _refused(w, name)
+    w = small_world()
+    for i in range(T.CATALYSTS_MAX + 1):
+        w["chemicals"]["X%d" % i] = dict(molecular_weight=10.0, melting_point=0.0, boiling_point=1.0)
+    w["reactions"]["r1"]["catalysts"] = ["X%d" % i for i in range(T.CATALYSTS_MAX + 1)]
+    _refused(w, "CATALYSTS_MAX")
+    w = small_world()
+    w["reactions"]["r1"]["products"] = [["A", T.COEFF_MAX + 1]]
+    _refused(w, "COEFF_MAX")
+    with pytest.raises(_lib.XenoError) as ex:
+        T.num_steps_of(5.0 * T.STEPS_MAX + 1.0, 5.0)
+    assert ex.value.code == _lib.XV_ERR_UNSUPPORTED and "STEPS_MAX" in str(ex.value)
+    assert T.num_steps_of(5.0 * T.STEPS_MAX, 5.0) == T.STEPS_MAX
+
+
+def test_limits_agree_with_the_header():
+    import os
+    import re
+    text = open(os.path.join(os.path.dirname(cu.GOLD), "..", "include", "xeno.h")).read()
+    for name, value in (("C_MAX", T.C_MAX), ("R_MAX", T.R_MAX), ("E_MAX", T.E_MAX), ("REACTANTS_MAX", T.REACTANTS_MAX),
+                        ("PRODUCTS_MAX", T.PRODUCTS_MAX), ("BYPRODUCTS_MAX", T.BYPRODUCTS_MAX),
+                        ("CATALYSTS_MAX", T.CATALYSTS_MAX), ("COEFF_MAX", T.COEFF_MAX), ("STEPS_MAX", T.STEPS_MAX),
+                        ("HISTORY_MAX", host.HISTORY_MAX), ("LOG_MAX", host.LOG_MAX)):
+        m = re.search(r"#define XV_CHEM_%s (\d+)" % name, text)
+        assert m and int(m.group(1)) == value, name
+
+
+def test_fixture_worlds_fit_the_limits():
+    sizes = [(cu.fixture(t)["tab"]["C"], cu.fixture(t)["tab"]["R"]) for t in cu.TAGS]
+    assert sizes[0][1] < sizes[1][1] < sizes[2][1]      # fewest, middle, most reactions
+    assert all(cu.fixture(t)["tab"]["E"] == 7 for t in cu.TAGS)
+
+
+# ---- brentq ---------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("tag", cu.TAGS)
+def test_brentq_host_equals_scipy_bit_for_bit(tag):
+    r = cu.fixture(tag)["runs"]
+    n = len(r["brent_root"])
+    assert n >= 100
+    most = 0
+    for i in range(n):
+        nr, npr = int(r["brent_n_r"][i]), int(r["brent_n_p"][i])
+        f = host.equilibrium_objective(float(r["brent_K_eq"][i]), r["brent_r_mol"][i, :nr].tolist(),
+                                       r["brent_r_coeff"][i, :nr].tolist(), r["brent_p_mol"][i, :npr].tolist(),
+                                       r["brent_p_coeff"][i, :npr].tolist())
+        root, calls = host.brentq_host(f, 0.0, float(r["brent_max_extent"][i]))
+        assert np.float64(root).view(np.uint64) == r["brent_root"][i].view(np.uint64), (i, root, r["brent_root"][i])
+        assert calls == r["brent_calls"][i], (i, calls, int(r["brent_calls"][i]))
+        most = max(most, calls)
+    assert most > 6      # the recorded calls include ones that iterate
+
+
+def test_brentq_host_raises_where_scipy_does():
+    with pytest.raises(host.BrentError):
+        host.brentq_host(lambda x: float("nan") if x > 0.5 else x - 2.0, 0.0, 1.0)
+    with pytest.raises(host.BrentError):      # |x|-like kink at an irrational point, two iterations allowed
+        host.brentq_host(lambda x: x ** 3 - 0.3, 0.0, 1.0, maxiter=2)
+    out = []
+    xi = host.solve_equilibrium_extent_host(1.0, [1.0], [1], [0.0], [1], out)
+    assert out == ["root"] and abs(xi - 0.5) < 1e-9
+
+
+# ---- the host restatement against the reference's recorded runs ---------------------------------------------------------------
+_host_runs = {}
+
+
+def host_runs(tag):
+    if tag not in _host_runs:
+        fx = cu.fixture(tag)
+        res = host.simulate_chain_host(fx["tab"], [cu.host_experiment(fx, i) for i in range(fx["n"])], record="log")
+        for v in res.values():
+            v.setflags(write=False)
+        _host_runs[tag] = res
+    return _host_runs[tag]
+
+
+@pytest.mark.parametrize("tag", cu.TAGS)
+def test_host_equals_the_reference_bit_for_bit(tag):
+    fx = cu.fixture(tag)
+    assert cu.unstable_fraction(fx) <= 0.02
+    res = host_runs(tag)
+    r = fx["runs"]
+    for key in cu.DISCRETE:      # discrete outcomes: every experiment, the unstable ones included
+        m = cu.rows(key, fx["n"])
+        assert np.array_equal(res[key][:m], r[key]), key
+    worst = cu.compare(fx, res, exact=True, label="host %s: " % tag)
+    assert worst <= 1.0
+
+
+def test_fixtures_hold_the_smallest_shapes_that_can_go_wrong():
+    seen = set()
+    for tag in cu.TAGS:
+        fx = cu.fixture(tag)
+        r = fx["runs"]
+        fired = r["fired"].sum(axis=1)
+        dt = r["duration_s"] / r["num_steps"]
+        if ((r["num_steps"] == 1) & (fired > 0)).any():
+            seen.add("one step")
+        if ((r["num_steps"] == 3) & (dt == 4.0) & (fired > 0)).any():
+            seen.add("three steps of 4 s")
+        if ((r["num_steps"] == 120) & (r["steps_run"] == 120)).any():
+            seen.add("120 steps")
+        if ((fired == 0) & (r["failure"] == 0) & (r["steps_run"] == 3) & (r["num_steps"] > 3) & (r["converged"] == 1)).any():
+            seen.add("idle break")
+        if np.isin(r["failure"], (1, 2)).any():
+            seen.add("initial failure")
+        if (np.isin(r["failure"], (3, 4)) & (r["failure_step"] > 0)).any():
+            seen.add("failure mid-run")
+        started = r["grams"] > 1e-9
+        if ((r["final_pool"] > 1e-9) & ~started).any():
+            seen.add("order list grows")
+    assert seen == {"one step", "three steps of 4 s", "120 steps", "idle break", "initial failure", "failure mid-run",
+                    "order list grows"}
+
+
+# ---- the reference-surface wrapper ------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("tag", cu.TAGS)
+def test_dict_wrapper_equals_the_recorded_dicts(tag):
+    fx = cu.fixture(tag)
+    recorded = cu.recorded_dicts(fx)
+    picked = [(i, d) for i, d in recorded if fx["runs"]["order_free"][i]]
+    assert len(picked) >= 32
+    kinds = set()
+    for i, want in picked:
+        got = simulate_chain_reaction(fx["world"], backend="host", **cu.call_args(fx, i))
+        assert list(sorted(got)) == list(sorted(want)), i
+        assert got == want, (i, [k for k in want if got[k] != want[k]])
+        kinds.add(want.get("failure_reason", "")[:12])
+        if len(want["temperature_history"]) == 30:
+            kinds.add("history cut at 30")
+        if want["reaction_log"]:
+            kinds.add("log")
+    assert {"", "log"} <= kinds
+    if tag == "a":
+        assert len(kinds) >= 4, kinds      # both kinds of failure text among the recorded ones
+
+
+def test_wrapper_surface():
+    fx = cu.fixture("a")
+    args = [dict(cu.call_args(fx, i), world=0) for i in (0, 1, 2)]
+    many = simulate_chain_reactions([fx["world"]], args, backend="host")
+    assert many == [simulate_chain_reaction(fx["world"], backend="host", **cu.call_args(fx, i)) for i in (0, 1, 2)]
+    # equipment None is the open beaker; an id outside the world is carried through the pool untouched
+    a = dict(cu.call_args(fx, 0), equipment=None, temperature_C=25.0, pressure_atm=0.5)
+    a["initial_amounts_g"] = dict(a["initial_amounts_g"], NOT_A_CHEMICAL=3.0)
+    d = simulate_chain_reaction(fx["world"], backend="host", **a)
+    assert "equipment_failure" not in d
+    assert d["equipment"] == "open_beaker" and d["final_pool_g"].get("NOT_A_CHEMICAL") == 3.0
+    with pytest.raises(ValueError):
+        simulate_chain_reaction(fx["world"], backend="numpy", **cu.call_args(fx, 0))
+    with pytest.raises(ValueError):
+        simulate_chain_reaction(fx["world"], backend="host", **dict(cu.call_args(fx, 0), temperature_C=float("nan")))

@@ -194,6 +194,10 @@ SIGNATURES = {
     "xv_anyhvac_start_get_state": [c_void_p, c_void_p, c_void_p, c_void_p],     # (handle, last_fail, ring, count)
     "xv_anyhvac_start_set_state": [c_void_p, c_void_p, c_void_p, c_void_p],
     "xv_anyhvac_sample_tasks": [c_void_p, c_u64, c_i64] + [c_int] * 8 + [c_void_p] * 5,
+    "xv_chem_create": [c_void_p, c_int, C.POINTER(c_void_p)],
+    "xv_chem_destroy": [c_void_p],
+    "xv_chem_set_worlds": [c_void_p, c_int, c_int, c_int] + [c_void_p] * 9,
+    "xv_chem_simulate": [c_void_p, c_int] + [c_void_p] * 10 + [C.c_double, c_void_p],
     "xv_anyhvac_sampler_check": [c_i64] + [c_int] * 8 + [c_void_p] * 4,
 }
 for _p in ("xv_cartpole", "xv_acrobot"):      # the control families share one set of entry points (csrc/xv_control.h)
@@ -245,6 +249,14 @@ class AnyHVACState(C.Structure):
 class AnyHVACActIO(C.Structure):
     """xv_anyhvac_act_io (include/xeno.h)"""
     FIELDS = ("action_index", "applied_value", "delta", "action_cost", "stat_counts")
+    _fields_ = [(k, C.c_void_p) for k in FIELDS]
+
+
+class ChemOut(C.Structure):
+    """xv_chem_out (include/xeno.h): device pointers of what a ChemVerse launch writes, each nullable"""
+    FIELDS = ("final_pool", "consumed", "produced", "byproduct", "gas_lost", "fired", "num_steps", "steps_run", "converged",
+              "failure", "failure_step", "final_T", "final_P", "hist_step", "hist_T", "hist_P", "hist_count", "log_step",
+              "log_active", "log_T", "log_P", "log_consumed", "log_produced", "log_count")
     _fields_ = [(k, C.c_void_p) for k in FIELDS]
 
 
