@@ -115,7 +115,7 @@ def test_fixture_worlds_fit_the_limits():
 
 
 # ---- brentq ---------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("tag", cu.TAGS)
+@pytest.mark.parametrize("tag", cu.TAGS + cu.WIDE_TAGS)
 def test_brentq_host_equals_scipy_bit_for_bit(tag):
     r = cu.fixture(tag)["runs"]
     n = len(r["brent_root"])
@@ -157,7 +157,7 @@ def host_runs(tag):
     return _host_runs[tag]
 
 
-@pytest.mark.parametrize("tag", cu.TAGS)
+@pytest.mark.parametrize("tag", cu.TAGS + cu.WIDE_TAGS)
 def test_host_equals_the_reference_bit_for_bit(tag):
     fx = cu.fixture(tag)
     assert cu.unstable_fraction(fx) <= 0.02
@@ -196,8 +196,105 @@ def test_fixtures_hold_the_smallest_shapes_that_can_go_wrong():
                     "order list grows"}
 
 
+# ---- the wide fixtures: a sampled hard world, a world at every table limit, one run of STEPS_MAX steps -----------------------------
+SIZE_CAP = 811543      # the cap tests/test_host_metalm.py applies to its family's fixtures
+WIDE_BRANCHES = ("solvent_self", "reaction_index_ge_64_fired", "chemical_index_ge_32_in_pool", "chemical_63_in_pool",
+                 "reactants_6", "products_4", "byproducts_2_or_more", "byproducts_4", "catalysts_2_or_more", "catalysts_4",
+                 "coeff_4_to_7", "coeff_8", "external_solvent_index_ge_32", "rescaled_with_byproducts")
+
+
+def test_wide_fixtures_are_at_the_limits_and_small():
+    import os
+    x, h = cu.fixture("x")["tab"], cu.fixture("h")["tab"]
+    assert x["C"] == T.C_MAX and x["R"] == T.R_MAX
+    ri = x["rxn_i"]
+    assert ri[:, T.RX_NREAC].max() == T.REACTANTS_MAX and ri[:, T.RX_NPROD].max() == T.PRODUCTS_MAX
+    assert ri[:, T.RX_NBYP].max() == T.BYPRODUCTS_MAX and ri[:, T.RX_NCAT].max() == T.CATALYSTS_MAX
+    coeffs = np.concatenate([ri[:, T.RX_REAC_COEFF:T.RX_PROD].ravel(), ri[:, T.RX_PROD_COEFF:T.RX_BYP].ravel(),
+                             ri[:, T.RX_BYP_COEFF:T.RX_CAT].ravel()])
+    assert coeffs.max() == T.COEFF_MAX
+    full = (ri[:, :4] == (T.REACTANTS_MAX, T.PRODUCTS_MAX, T.BYPRODUCTS_MAX, T.CATALYSTS_MAX)).all(axis=1)
+    assert full[64:].sum() >= 2 and not full[:64].any()      # the widened reactions lie in the second word of the applicable set
+    assert h["R"] > 64 and h["C"] > 32
+    for tag in cu.WIDE_TAGS + (cu.LONG,):
+        fx = cu.fixture(tag)
+        assert cu.unstable_fraction(fx) <= 0.02
+        assert os.path.getsize(os.path.join(cu.GOLD, "chemverse_runs_%s.npz" % tag)) <= SIZE_CAP
+        if tag != cu.LONG:
+            assert fx["n"] == cu.fixture("a")["n"]      # tests/test_gpu_chemverse_wide.py interleaves x, h and a
+            assert os.path.getsize(os.path.join(cu.GOLD, "chemverse_world_%s.json" % tag)) <= SIZE_CAP
+
+
+def test_wide_fixtures_reach_the_branches_beyond_the_evaluation_worlds():
+    """what the reference took while it recorded (branch_hits), and, where the arrays can show it, the arrays themselves"""
+    total = dict((b, 0) for b in WIDE_BRANCHES)
+    in_arrays = set()
+    for tag in cu.WIDE_TAGS:
+        fx = cu.fixture(tag)
+        hits = cu.branch_hits(fx)
+        for b in WIDE_BRANCHES:
+            total[b] += int((hits[b] & fx["runs"]["stable"]).sum())
+        r, ri = fx["runs"], fx["tab"]["rxn_i"]
+        fired = r["fired"] > 0
+        held = (r["final_pool"] > 1e-9) | (r["grams"] > 1e-9)
+        solvent = fx["tab"]["chem_f"][:, T.CH_SOLVENT] != 0
+        all_solvent = np.array([solvent[row[T.RX_REAC:T.RX_REAC + row[T.RX_NREAC]]].all() for row in ri])
+        coeff = np.concatenate([ri[:, T.RX_REAC_COEFF:T.RX_PROD], ri[:, T.RX_PROD_COEFF:T.RX_BYP]], axis=1).max(axis=1)
+        for name, mask in (("reaction_index_ge_64_fired", fired[:, 64:].any(axis=1)),
+                           ("chemical_index_ge_32_in_pool", held[:, 32:].any(axis=1)),
+                           ("chemical_63_in_pool", held[:, 63:].any(axis=1)),
+                           ("solvent_self", fired[:, all_solvent].any(axis=1)),
+                           ("reactants_6", fired[:, ri[:, T.RX_NREAC] == 6].any(axis=1)),
+                           ("products_4", fired[:, ri[:, T.RX_NPROD] == 4].any(axis=1)),
+                           ("catalysts_2_or_more", fired[:, ri[:, T.RX_NCAT] >= 2].any(axis=1)),
+                           ("catalysts_4", fired[:, ri[:, T.RX_NCAT] == 4].any(axis=1)),
+                           ("coeff_8", fired[:, coeff == 8].any(axis=1))):
+            assert not (mask & ~hits[name]).any(), (tag, name)
+            if (mask & fx["runs"]["stable"]).any():
+                in_arrays.add(name)
+        # a fired reaction past 63 and a chemical past 31 in the recorded log rows too
+        assert (r["log_produced"][..., 32:] > 0).any(), tag
+    assert all(total[b] > 0 for b in WIDE_BRANCHES), total
+    assert len(in_arrays) == 9, in_arrays
+    x = cu.fixture("x")
+    hx = cu.branch_hits(x)
+    for b in ("solvent_self", "chemical_63_in_pool", "reactants_6", "byproducts_4", "catalysts_4", "coeff_8",
+              "rescaled_with_byproducts", "external_solvent_index_ge_32"):
+        assert (hx[b] & x["runs"]["stable"]).any(), b
+    assert ((x["runs"]["final_pool"][:, 63] > 1e-9) & (x["runs"]["grams"][:, 63] == 0)).any()      # chemical 63 was MADE
+    assert x["runs"]["order"].max() >= 32      # the order list's entries, uint8 on the device, beyond 31
+
+
+def test_solvent_masks_keep_bit_63_through_the_int64_view():
+    x = cu.fixture("x")["tab"]
+    top = (x["rxn_solv"] >> np.uint64(63)) & np.uint64(1)
+    assert x["rxn_solv"].dtype == np.uint64 and top.any() and not top.all()
+    p = T.pack_worlds([cu.fixture("a")["tab"], x])
+    assert p["c_stride"] == T.C_MAX and p["r_stride"] == T.R_MAX and p["rxn_solv"].dtype == np.int64
+    R_a = cu.fixture("a")["tab"]["R"]
+    carried = p["rxn_solv"][R_a:]
+    assert (carried < 0).sum() == int(top.sum())      # bit 63 is the sign of the int64 the C interface takes
+    assert np.array_equal(carried.view(np.uint64), x["rxn_solv"])
+    assert np.array_equal(np.ascontiguousarray(carried).tobytes(), x["rxn_solv"].tobytes())
+
+
+def test_host_equals_the_reference_on_the_longest_run():
+    """STEPS_MAX steps: the history is sampled every 204th step (25 entries: steps 0..4, then 204 .. 4080), the log cut at 20"""
+    fx = cu.fixture(cu.LONG)
+    r = fx["runs"]
+    assert fx["n"] == 1 and r["num_steps"][0] == T.STEPS_MAX and r["steps_run"][0] == T.STEPS_MAX
+    assert r["hist_count"][0] == 25 and r["log_count"][0] == host.LOG_MAX and r["fired"].sum() >= T.STEPS_MAX
+    assert r["hist_step"][0, :25].tolist() == [0, 1, 2, 3, 4] + list(range(204, T.STEPS_MAX, 204))
+    res = host.simulate_chain_host(fx["tab"], [cu.host_experiment(fx, 0)], record="log")
+    for key in cu.DISCRETE:
+        assert np.array_equal(res[key], r[key]), key
+    for key in cu.FLOATS:
+        assert np.array_equal(res[key].view(np.uint64), r[key].view(np.uint64)) or not r["order_free"][0], key
+    assert cu.compare(fx, res, exact=True, label="host long: ") <= 1.0
+
+
 # ---- the reference-surface wrapper ------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("tag", cu.TAGS)
+@pytest.mark.parametrize("tag", cu.TAGS + cu.WIDE_TAGS)
 def test_dict_wrapper_equals_the_recorded_dicts(tag):
     fx = cu.fixture(tag)
     recorded = cu.recorded_dicts(fx)
