@@ -1154,6 +1154,8 @@ int xv_mixed_step_many_overlap_state(xv_anymdp* a);
  * [0, n_vocab) handed to log_prob, a task index or n_gram outside its range: XV_DEVERR_ACTION_RANGE; a standard deviation
  * or a sum of exponentials that is not finite and positive: XV_DEVERR_NONFINITE. */
 typedef struct xv_metalang xv_metalang;
+/* e may be NULL: the handle then needs no GPU and only answers xv_metalang_describe (and set_task, destroy);
+ * xv_metalang_generate and xv_metalang_log_prob refuse it with XV_ERR_INVALID. */
 int xv_metalang_create(xv_engine* e, int n_group, int seqs_per_group, int n_vocab, int n_emb, int n_hidden, int n_gram_max,
                        xv_metalang** out);
 int xv_metalang_destroy(xv_metalang* h);
@@ -1165,6 +1167,16 @@ int xv_metalang_set_task(xv_metalang* h, int n_task, const double* word_emb, con
                          const double* lambda, const int32_t* n_gram, const int32_t* group_task);
 int xv_metalang_generate(xv_metalang* h, int L, const double* u, int32_t* tokens, double* logp);
 int xv_metalang_log_prob(xv_metalang* h, int L, const int32_t* tokens, double* logp);
+/* What xv_metalang_generate (teacher = 0) or xv_metalang_log_prob (teacher = 1) launches for this handle, from the code
+ * that launches it; read-only, no GPU work (new symbol, no ABI bump).  out: [0] threads per workgroup (64, 256, 1024);
+ * [1] doubles of the W_out column held in registers (16, 32, 64; 0: read through L2); [2] 1: seqs_per_group == 1, the
+ * logit is a register; [3] 1: the input tables are copied to LDS, 0: read through L2 (XV_METALANG_TABLES=l2 in the
+ * environment of xv_metalang_create forces 0); [4] steps between two rounds of global I/O; [5] where a group's logits
+ * live: 0 a register, 1 LDS, 2 HBM scratch; [6] sequences per pass of the hidden layer; [7] bytes of dynamic LDS per
+ * workgroup; [8] 1: [7] is above 65536 (the launch raises the kernel's limit first); [9] positions per workgroup
+ * (0: the whole call).  For this call alone xv_metalang_create accepts e == NULL: such a handle describes and is
+ * destroyed, generate and log_prob refuse it with XV_ERR_INVALID. */
+int xv_metalang_describe(const xv_metalang* h, int teacher, int32_t out[10]);
 
 /* ------------------------------------------------------------------------------------------------
  * MetaLangV1 — reference: xenoverse/metalang/metalangv1.py (add_noise :39-50, data_generator :57-74), tasks from

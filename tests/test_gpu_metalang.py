@@ -8,7 +8,7 @@ its own draws first, so every token must be equal.  Probabilities are compared a
 import numpy as np
 import pytest
 
-from metalang_util import FILES, PPL_TOL, TAU, by_name, fixture_id, load
+from metalang_util import FILES, PPL_TOL, TAU, _philox_uniforms, by_name, fixture_id, load
 from util import to_np as _np
 from xenoverse_amd.metalang import MetaLangV2, MetaLangV2Batch, MetaLangV2Host, TaskSamplerV2
 
@@ -112,25 +112,6 @@ def test_device_equals_host_at_scale(name):
     assert np.abs(np.exp(_np(gen.log_prob(tokens))) / h_prob - 1.0).max() <= RTOL_P
     assert gen.check_errors() == 0
     gen.close()
-
-
-def _philox_uniforms(engine, seed, first_seq, n_seq, tick, L):
-    """the uniforms a free-running call draws, from the documented counter layout (csrc/metalang.hip, csrc/philox.h):
-    counter = {id lo, id hi, tick lo, 8 | tick hi << 8}, key = {seed lo, seed hi ^ (0x80000000 | t >> 1)}; words 0,1 (t even)
-    or 2,3 (t odd); u = ((a >> 5) * 2^26 + (b >> 6)) / 2^53 (xv_u53)"""
-    ids = first_seq + np.arange(n_seq, dtype=np.uint64)
-    ctr = np.stack([ids & 0xFFFFFFFF, ids >> np.uint64(32), np.full(n_seq, tick & 0xFFFFFFFF, np.uint64),
-                    np.full(n_seq, 8 | ((tick >> 32) << 8), np.uint64)], axis=1).astype(np.int64)
-    u = np.zeros((n_seq, L))
-    for sub in range((L + 1) // 2):
-        key = [seed & 0xFFFFFFFF, ((seed >> 32) & 0xFFFFFFFF) ^ (0x80000000 | sub)]
-        w = _np(engine.philox(ctr, key)).astype(np.int64) & 0xFFFFFFFF
-        for odd in (0, 1):
-            t = 2 * sub + odd
-            if t < L:
-                a, b = w[:, 2 * odd], w[:, 2 * odd + 1]
-                u[:, t] = ((a >> 5) * 67108864.0 + (b >> 6)) / 9007199254740992.0
-    return u
 
 
 def test_free_running_draws():

@@ -92,6 +92,45 @@ def test_too_many_sequences_per_group_is_refused():
         MetaLangV2Batch(1, 65)
 
 
+def test_describe_reports_the_dispatch_without_a_gpu():
+    """xv_metalang_describe on a handle made without an engine: the keys, and four sizes whose variant is plain"""
+    from xenoverse_amd.metalang import describe_dispatch
+    from xenoverse_amd.metalang.batch import DESCRIBE_KEYS
+    d = describe_dispatch(1, 256, 16, 64, 3)      # the sampler's defaults: DESIGN.md §3.6 kernel (a)
+    assert tuple(d) == DESCRIBE_KEYS and set(d) == {"block", "w_out_regs", "single_seq", "tables_in_lds", "steps_per_io",
+                                                    "logits", "act_seqs", "lds_bytes", "lds_opt_in", "teacher_chunk"}
+    assert d == dict(block=256, w_out_regs=64, single_seq=True, tables_in_lds=True, steps_per_io=64, logits="register",
+                     act_seqs=1, lds_bytes=d["lds_bytes"], lds_opt_in=False, teacher_chunk=0)
+    assert 8 * (256 * 16 + 2 * (16 * 64 + 64)) < d["lds_bytes"] <= 65536      # the tables and a little more
+    t = describe_dispatch(1, 256, 16, 64, 3, teacher=True)
+    assert t == dict(d, teacher_chunk=128)
+    d = describe_dispatch(16, 64, 16, 16, 6)
+    assert (d["block"], d["w_out_regs"], d["single_seq"], d["steps_per_io"], d["logits"]) == (64, 16, False, 8, "lds")
+    d = describe_dispatch(64, 1024, 8, 32, 2)
+    assert (d["block"], d["w_out_regs"], d["logits"], d["lds_opt_in"]) == (1024, 0, "scratch", False)
+    # looks like a tables-in-LDS case (784 doubles of tables); hs alone is 64 sequences x 128 doubles = 64 KiB
+    d = describe_dispatch(64, 48, 16, 128, 1)
+    assert (d["block"], d["tables_in_lds"], d["logits"], d["lds_opt_in"]) == (64, False, "lds", True)
+    assert d["lds_bytes"] > 65536
+    with pytest.raises(XenoError, match=r"n_vocab = 1025 is outside the supported range 1 \.\. 1024"):
+        describe_dispatch(1, 1025, 16, 64, 3)
+
+
+def test_the_tables_switch_keeps_the_tables_out_of_lds(monkeypatch):
+    """XV_METALANG_TABLES=l2 is read when the handle is made"""
+    from xenoverse_amd.metalang import describe_dispatch
+    monkeypatch.delenv("XV_METALANG_TABLES", raising=False)
+    lds = describe_dispatch(4, 64, 16, 16, 3)
+    assert lds["tables_in_lds"]
+    monkeypatch.setenv("XV_METALANG_TABLES", "l2")
+    l2 = describe_dispatch(4, 64, 16, 16, 3)
+    assert not l2["tables_in_lds"]
+    tab = 64 * 16 + 2 * (16 * 16 + 16)
+    assert l2 == dict(lds, tables_in_lds=False, lds_bytes=lds["lds_bytes"] - 8 * tab)
+    monkeypatch.setenv("XV_METALANG_TABLES", "lds")
+    assert describe_dispatch(4, 64, 16, 16, 3) == lds
+
+
 def test_no_task_set_raises_the_reference_text():
     env = MetaLangV2(L=16)
     with pytest.raises(Exception, match="Please set task before using data generator"):

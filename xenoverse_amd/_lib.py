@@ -149,6 +149,7 @@ SIGNATURES = {
     "xv_metalang_set_task": [c_void_p, c_int] + [c_void_p] * 8,
     "xv_metalang_generate": [c_void_p, c_int, c_void_p, c_void_p, c_void_p],
     "xv_metalang_log_prob": [c_void_p, c_int, c_void_p, c_void_p],
+    "xv_metalang_describe": [c_void_p, c_int, c_void_p],
     "xv_metalang1_create": [c_void_p, c_int, C.POINTER(c_void_p)],
     "xv_metalang1_destroy": [c_void_p],
     "xv_metalang1_set_task": [c_void_p, c_int, c_int, c_int] + [c_void_p] * 6,

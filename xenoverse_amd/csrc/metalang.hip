@@ -369,7 +369,7 @@ extern "C" int xv_metalang_create(xv_engine* e, int n_group, int seqs_per_group,
                                   int n_gram_max, xv_metalang** out) {
   XV_CHECK_ARG(out != nullptr);
   *out = nullptr;
-  XV_CHECK_ARG(e != nullptr && n_group >= 1);
+  XV_CHECK_ARG(n_group >= 1);      // e == nullptr: a handle that only describes (xv_metalang_describe), no GPU needed
   const struct { const char* name; int v, hi; } lim[5] = {{"n_vocab", n_vocab, ML_V_MAX}, {"n_hidden", n_hidden, ML_H_MAX},
                                                          {"n_emb", n_emb, ML_E_MAX}, {"n_gram", n_gram_max, ML_NG_MAX},
                                                          {"seqs_per_group", seqs_per_group, ML_B_MAX}};
@@ -403,15 +403,17 @@ extern "C" int xv_metalang_create(xv_engine* e, int n_group, int seqs_per_group,
   a.o_lds = seqs_per_group > 1 && ob <= ML_O_LDS_CAP ? ob : 0;
   // the tables go to LDS where the workgroup then stays within 64 KiB (two and more workgroups per CU)
   if (tab <= ML_TAB_CAP && !(where && where[0] == 'l' && where[1] == '2') && ml_lds_bytes(a, tab) <= 65536) a.tab_n = tab;
-  a.err = e->d_err;
+  a.err = e ? e->d_err : nullptr;
   *out = h;
   return XV_OK;
 }
 
 extern "C" int xv_metalang_destroy(xv_metalang* h) {
   if (!h) return XV_OK;
-  (void)hipSetDevice(h->eng->device);
-  (void)hipStreamSynchronize(h->eng->stream);
+  if (h->eng) {
+    (void)hipSetDevice(h->eng->device);
+    (void)hipStreamSynchronize(h->eng->stream);
+  }
   if (h->scratch) (void)hipFree(h->scratch);
   delete h;
   return XV_OK;
@@ -432,45 +434,82 @@ extern "C" int xv_metalang_set_task(xv_metalang* h, int n_task, const double* wo
   return XV_OK;
 }
 
+// What a call launches: the template parameters of metalang_kernel and the run-time layouts, all of them a function of the
+// handle's sizes and of which call it is.  ml_run launches from it and xv_metalang_describe reports it.
+struct MLPlan {
+  int block;       // threads: 64, 256, 1024
+  int hr;          // doubles of the W_out column in registers, 0: read through L2
+  bool b1;         // B == 1: the logit is a register
+  bool teacher;
+  bool tl;         // the input tables are copied to LDS
+  int K;           // steps between two rounds of I/O
+  int o_where;     // the logits of a group: 0 a register, 1 LDS, 2 HBM scratch
+  int act_b;       // sequences per pass of the hidden layer
+  size_t lds;      // dynamic LDS of a workgroup; above 65536 the kernel needs hipFuncSetAttribute
+  int chunk;       // positions per workgroup, 0: the whole call
+};
+
+// the W_out column lives in registers (HR = 16, 32, 64 doubles) for V <= 256 and H <= 64; a 1024-thread block has 128
+// VGPRs per lane and a column of H > 64 takes more than 128: those read W_out through L2
+static MLPlan ml_plan(const MLArgs& a, bool teacher) {
+  MLPlan p;
+  p.block = ml_block(a.V);
+  p.hr = p.block == 1024 || a.H > 64 ? 0 : a.H <= 16 ? 16 : a.H <= 32 ? 32 : 64;
+  p.b1 = a.B == 1;
+  p.teacher = teacher;
+  p.tl = a.tab_n != 0;
+  p.K = a.K;
+  p.o_where = a.B == 1 ? 0 : a.o_lds ? 1 : 2;
+  p.act_b = a.act_b;
+  p.lds = ml_lds_bytes(a, a.tab_n);
+  p.chunk = teacher ? ML_TEACHER_CHUNK : 0;
+  return p;
+}
+
+struct MLCall {
+  xv_metalang* h;
+  const MLArgs& a;
+  const MLPlan& p;
+  dim3 grid;
+  int L, chunk;
+  const double* u;
+  int32_t* tokens;
+  double* logp;
+};
+
 template <int BLOCK, int HR, bool B1, bool TEACHER, bool TL>
-static int ml_launch_k(xv_metalang* h, const MLArgs& a, dim3 grid, size_t lds, int L, int chunk, const double* u,
-                       int32_t* tokens, double* logp) {
+static int ml_launch_k(const MLCall& c) {
   auto k = metalang_kernel<BLOCK, HR, B1, TEACHER, TL>;
-  if (lds > 65536) XV_HIP(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(k, grid, dim3(BLOCK), lds, h->eng->stream, a, L, chunk, u, tokens, logp);
+  if (c.p.lds > 65536) XV_HIP(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c.p.lds));
+  hipLaunchKernelGGL(k, c.grid, dim3(BLOCK), c.p.lds, c.h->eng->stream, c.a, c.L, c.chunk, c.u, c.tokens, c.logp);
   XV_LAUNCH_CHECK();
   return XV_OK;
 }
 
 template <int BLOCK, int HR, bool B1>
-static int ml_launch_t(xv_metalang* h, const MLArgs& a, bool teacher, dim3 grid, size_t lds, int L, int chunk,
-                       const double* u, int32_t* tokens, double* logp) {
-  if (a.tab_n)
-    return teacher ? ml_launch_k<BLOCK, HR, B1, true, true>(h, a, grid, lds, L, chunk, u, tokens, logp)
-                   : ml_launch_k<BLOCK, HR, B1, false, true>(h, a, grid, lds, L, chunk, u, tokens, logp);
-  return teacher ? ml_launch_k<BLOCK, HR, B1, true, false>(h, a, grid, lds, L, chunk, u, tokens, logp)
-                 : ml_launch_k<BLOCK, HR, B1, false, false>(h, a, grid, lds, L, chunk, u, tokens, logp);
+static int ml_launch_t(const MLCall& c) {
+  if (c.p.tl) return c.p.teacher ? ml_launch_k<BLOCK, HR, B1, true, true>(c) : ml_launch_k<BLOCK, HR, B1, false, true>(c);
+  return c.p.teacher ? ml_launch_k<BLOCK, HR, B1, true, false>(c) : ml_launch_k<BLOCK, HR, B1, false, false>(c);
 }
 
 template <int BLOCK, int HR>
-static int ml_launch_b(xv_metalang* h, const MLArgs& a, bool teacher, dim3 grid, size_t lds, int L, int chunk,
-                       const double* u, int32_t* tokens, double* logp) {
-  return a.B == 1 ? ml_launch_t<BLOCK, HR, true>(h, a, teacher, grid, lds, L, chunk, u, tokens, logp)
-                  : ml_launch_t<BLOCK, HR, false>(h, a, teacher, grid, lds, L, chunk, u, tokens, logp);
+static int ml_launch_b(const MLCall& c) {
+  return c.p.b1 ? ml_launch_t<BLOCK, HR, true>(c) : ml_launch_t<BLOCK, HR, false>(c);
 }
 
-// the W_out column lives in registers (HR = 16, 32, 64 doubles) for V <= 256 and H <= 64; a 1024-thread block has 128
-// VGPRs per lane and a column of H > 64 takes more than 128: those read W_out through L2
 template <int BLOCK>
-static int ml_launch_h(xv_metalang* h, const MLArgs& a, bool teacher, dim3 grid, size_t lds, int L, int chunk,
-                       const double* u, int32_t* tokens, double* logp) {
-  if (a.H <= 16) return ml_launch_b<BLOCK, 16>(h, a, teacher, grid, lds, L, chunk, u, tokens, logp);
-  if (a.H <= 32) return ml_launch_b<BLOCK, 32>(h, a, teacher, grid, lds, L, chunk, u, tokens, logp);
-  if (a.H <= 64) return ml_launch_b<BLOCK, 64>(h, a, teacher, grid, lds, L, chunk, u, tokens, logp);
-  return ml_launch_b<BLOCK, 0>(h, a, teacher, grid, lds, L, chunk, u, tokens, logp);
+static int ml_launch_h(const MLCall& c) {
+  if (c.p.hr == 16) return ml_launch_b<BLOCK, 16>(c);
+  if (c.p.hr == 32) return ml_launch_b<BLOCK, 32>(c);
+  if (c.p.hr == 64) return ml_launch_b<BLOCK, 64>(c);
+  return ml_launch_b<BLOCK, 0>(c);
 }
 
 static int ml_run(xv_metalang* h, const char* who, bool teacher, int L, const double* u, int32_t* tokens, double* logp) {
+  if (!h->eng) {
+    xv_set_error("%s: the handle was made without an engine: it only describes (xv_metalang_describe)", who);
+    return XV_ERR_INVALID;
+  }
   if (!h->task_set) {
     xv_set_error("%s: no task set (xv_metalang_set_task)", who);
     return XV_ERR_INVALID;
@@ -478,11 +517,11 @@ static int ml_run(xv_metalang* h, const char* who, bool teacher, int L, const do
   xv_engine* e = h->eng;
   XV_HIP(hipSetDevice(e->device));
   MLArgs a = h->a;
-  const int block = ml_block(a.V);
-  const int chunk = teacher ? ML_TEACHER_CHUNK : L;
+  const MLPlan p = ml_plan(a, teacher);
+  const int chunk = p.chunk ? p.chunk : L;
   const dim3 grid((unsigned)a.G, (unsigned)((L + chunk - 1) / chunk));
-  if (a.B > 1 && a.o_lds == 0) {
-    const size_t need = sizeof(double) * (size_t)grid.x * grid.y * a.B * block;
+  if (p.o_where == 2) {
+    const size_t need = sizeof(double) * (size_t)grid.x * grid.y * a.B * p.block;
     if (need > h->scratch_bytes) {
       XV_HIP(hipStreamSynchronize(e->stream));
       if (h->scratch) (void)hipFree(h->scratch);
@@ -505,10 +544,18 @@ static int ml_run(xv_metalang* h, const char* who, bool teacher, int L, const do
     a.seed = e->seed;
     a.gid_base = e->env_id_base;
   }
-  const size_t lds = ml_lds_bytes(a, a.tab_n);
-  if (block == 64) return ml_launch_h<64>(h, a, teacher, grid, lds, L, chunk, u, tokens, logp);
-  if (block == 256) return ml_launch_h<256>(h, a, teacher, grid, lds, L, chunk, u, tokens, logp);
-  return ml_launch_b<1024, 0>(h, a, teacher, grid, lds, L, chunk, u, tokens, logp);
+  const MLCall c = {h, a, p, grid, L, chunk, u, tokens, logp};
+  if (p.block == 64) return ml_launch_h<64>(c);
+  if (p.block == 256) return ml_launch_h<256>(c);
+  return ml_launch_b<1024, 0>(c);
+}
+
+extern "C" int xv_metalang_describe(const xv_metalang* h, int teacher, int32_t out[10]) {
+  XV_CHECK_ARG(h != nullptr && out != nullptr && (teacher == 0 || teacher == 1));
+  const MLPlan p = ml_plan(h->a, teacher != 0);
+  out[0] = p.block; out[1] = p.hr; out[2] = p.b1; out[3] = p.tl; out[4] = p.K; out[5] = p.o_where; out[6] = p.act_b;
+  out[7] = (int32_t)p.lds; out[8] = p.lds > 65536; out[9] = p.chunk;
+  return XV_OK;
 }
 
 extern "C" int xv_metalang_generate(xv_metalang* h, int L, const double* u, int32_t* tokens, double* logp) {

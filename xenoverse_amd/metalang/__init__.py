@@ -9,7 +9,7 @@ sample_tasks_v1_device; the unqualified sample_tasks_device is MetaLMV3's."""
 from .task_sampler import LIMITS, TaskSamplerV1, TaskSamplerV2  # noqa: F401
 from .host import MetaLangV2Host  # noqa: F401
 from .host_v1 import LIMITS_V1, MetaLangV1Host  # noqa: F401
-from .batch import MetaLangV2, MetaLangV2Batch  # noqa: F401
+from .batch import MetaLangV2, MetaLangV2Batch, describe_dispatch  # noqa: F401
 from .batch_v1 import MetaLangV1, MetaLangV1Batch  # noqa: F401
 from .lm_host import FUNCTION_VOCABULARY, LM_LIMITS, RandomLMHost, TaskSamplerV3  # noqa: F401
 from .lm_env import MetaLMV3Env, MetaLMV3VecEnv  # noqa: F401

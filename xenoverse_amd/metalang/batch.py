@@ -9,6 +9,34 @@ from .. import _lib
 from .task_sampler import TASK_ARRAYS, check_limit, check_task
 
 
+DESCRIBE_KEYS = ("block", "w_out_regs", "single_seq", "tables_in_lds", "steps_per_io", "logits", "act_seqs", "lds_bytes",
+                 "lds_opt_in", "teacher_chunk")      # xv_metalang_describe's out[0 .. 9] (include/xeno.h)
+LOGITS_WHERE = ("register", "lds", "scratch")
+
+
+def _describe(lib, h, teacher):
+    out = (C.c_int32 * len(DESCRIBE_KEYS))()
+    _lib.check(lib.xv_metalang_describe(h, 1 if teacher else 0, out))
+    d = dict(zip(DESCRIBE_KEYS, (int(v) for v in out)))
+    for k in ("single_seq", "tables_in_lds", "lds_opt_in"):
+        d[k] = bool(d[k])
+    d["logits"] = LOGITS_WHERE[d["logits"]]
+    return d
+
+
+def describe_dispatch(seqs_per_group, n_vocab, n_emb, n_hidden, n_gram_max, teacher=False):
+    """what a MetaLangV2Batch of these sizes would launch (MetaLangV2Batch.describe), from the library's own selection, without
+    a GPU: the handle is made without an engine and can do nothing else"""
+    lib = _lib.load()
+    h = C.c_void_p()
+    _lib.check(lib.xv_metalang_create(None, 1, int(seqs_per_group), int(n_vocab), int(n_emb), int(n_hidden), int(n_gram_max),
+                                      C.byref(h)))
+    try:
+        return _describe(lib, h, teacher)
+    finally:
+        lib.xv_metalang_destroy(h)
+
+
 class MetaLangV2Batch(object):
     """n_group groups of seqs_per_group sequences.  A group is one call of the reference's forward(L, batch=seqs_per_group)
     under one task: its sequences share the mean and the standard deviation of the logits at every step.  Every task of a
@@ -138,6 +166,14 @@ class MetaLangV2Batch(object):
         _lib.check(self.lib.xv_metalang_log_prob(self._h, L, _lib.ptr(t), _lib.ptr(logp)))
         self.engine.sync()
         return logp
+
+    def describe(self, teacher=False):
+        """which kernel variant and layouts generate (teacher=False) or log_prob (teacher=True) launches for the task set
+        (xv_metalang_describe) -> dict with DESCRIBE_KEYS: block 64 / 256 / 1024; w_out_regs 16 / 32 / 64, 0: W_out through
+        L2; single_seq; tables_in_lds; steps_per_io; logits "register" / "lds" / "scratch"; act_seqs; lds_bytes; lds_opt_in
+        (above 64 KiB); teacher_chunk (0: one workgroup runs the whole call)"""
+        self._live()
+        return _describe(self.lib, self._h, teacher)
 
     @staticmethod
     def perplexity(logp):
