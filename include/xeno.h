@@ -1640,8 +1640,8 @@ int xv_anyhvac_sampler_check(int64_t cand_base, int n_cand, int NW, int NL, int 
  * xtol 1e-10, 200 iterations, restated), catalyst_acceleration :208-216, _find_common_solvent :219-278, _dissolved_fraction
  * :281-305, _find_applicable_reactions :308-335, _step_single_reaction :338-428, _update_vessel_state :431-499,
  * _apply_gas_loss :614-636; worlds: world_gen/models.py :8-265.  The numeric chain-reaction simulator, for n_exp independent
- * experiments in one launch, each under its own world; the tool-call shell around it (sessions, cost model, samplers) is not
- * part of the library.  fp64 throughout.  Host restatement, which is the specification: xenoverse_amd/chemverse/host.py; the
+ * experiments in one launch, each under its own world; the tool-call shell around it (sessions, samplers) is not part of
+ * the library; of the cost model, what the ground-truth cost oracle needs is (xv_chem_optimal below).  fp64 throughout.  Host restatement, which is the specification: xenoverse_amd/chemverse/host.py; the
  * tables: xenoverse_amd/chemverse/tables.py (chemical and reaction indices in the world dicts' insertion order — reaction
  * order is semantics).  New symbols only: no ABI bump.
  *   xv_chem_set_worlds   the worlds' tables, concatenated, borrowed until the next set_worlds / destroy.  world_off int32
@@ -1719,6 +1719,44 @@ int xv_chem_simulate(xv_chem* h, int n_exp, const int32_t* exp_world, const doub
                      const int32_t* n_initial, const double* temperature_C, const double* pressure_atm,
                      const double* duration_s, const int32_t* equipment, const double* heating_rate_C_per_s,
                      const double* vessel_volume_L, double step_seconds, const xv_chem_out* out);
+
+/* ChemVerse's cost oracle — reference: environment/api.py compute_optimal_cost :1777-1901, _compute_chain_cost :1903-1942,
+ * _simulate_chain :1944-2109, _compute_one_pot_cost :2111-2266.  The device runs the bisections on the scale of the layer-1
+ * charge, for n_cand candidates at once; route search, the optimal (temperature, duration) of a reaction, every decimal
+ * rounding and the prices are host work (xenoverse_amd/chemverse/optimal_host.py, which is also the specification).  New
+ * symbols only: no ABI bump.
+ *   xv_chem_optimal   on a handle with worlds set.  Candidates GROUPED as xv_chem_simulate's experiments (64 of one world
+ *                     per workgroup, cand_world < 0 pads).  A candidate is n_step <= l_stride <= XV_CHEM_CHAIN_MAX
+ *                     experiments in a row, all in `equipment` at 1 atm: step s runs at step_T, step_duration [n][l_stride]
+ *                     on the charge charge int32 [n][l_stride][k_stride] (n_charge [n][l_stride] entries, in pool order):
+ *                     chemical | kind << 8, kind 0 scale, 1 0.1 * scale, 2 5 * scale grams, 3 max(virtual pool, 0.01);
+ *                     a chemical named twice is summed.  After a step, what it consumed (above 1e-9) leaves the virtual
+ *                     pool (not below 0) and what it produced or made as byproduct (0.001 g or more) joins it.  The yield
+ *                     is the virtual pool's entry of `target` (mode 0) or the last step's final pool's (mode 1), and passes
+ *                     when yield >= threshold.  Pass p < n_iter (<= XV_CHEM_BISECT_MAX) tries (lo + hi) / 2 from scale_lo,
+ *                     scale_hi; a candidate nothing passed then tries hi; the last pass runs at best_scale and writes the
+ *                     rows.  n_pass: the largest n_iter; n_pass + 2 launches on the engine's stream, no host round trip.
+ *                     launch_ms (HOST float [n_pass + 2], nullable): each launch's time, which makes the call synchronous.
+ * Outputs (xv_chem_opt_out, every pointer nullable): best_scale float64 [n] (0 when not found), found uint8 [n], bits
+ * uint32 [n] (bit p: pass p passed; bit 31: the pass at scale_hi did), yield float64 [n] unrounded, at best_scale; of that
+ * last pass charged float64 [n][l_stride][k_stride] (grams per charge entry), consumed, produced, byproduct float64
+ * [n][l_stride][c_stride] (a step's totals as xv_chem_simulate reports them), failure uint8 [n][l_stride], final_pool float64
+ * [n][c_stride] (mode 1 only).  Rows of candidates not found and of padding are not written.  Bad inputs are clamped and
+ * flagged as in xv_chem_simulate. */
+#define XV_CHEM_CHAIN_MAX 16      /* reactions per route */
+#define XV_CHEM_BISECT_MAX 30     /* bisection passes per candidate */
+typedef struct xv_chem_opt_out {
+  double* best_scale;
+  uint8_t* found;
+  uint32_t* bits;
+  double *yield, *charged, *consumed, *produced, *byproduct, *final_pool;
+  uint8_t* failure;
+} xv_chem_opt_out;
+int xv_chem_optimal(xv_chem* h, int n_cand, int l_stride, int k_stride, int n_pass, const int32_t* cand_world,
+                    const int32_t* n_step, const int32_t* equipment, const int32_t* target, const int32_t* mode,
+                    const int32_t* n_iter, const double* threshold, const double* scale_lo, const double* scale_hi,
+                    const double* step_T, const double* step_duration, const int32_t* n_charge, const int32_t* charge,
+                    double step_seconds, const xv_chem_opt_out* out, float* launch_ms);
 
 #ifdef __cplusplus
 }

@@ -199,6 +199,7 @@ SIGNATURES = {
     "xv_chem_destroy": [c_void_p],
     "xv_chem_set_worlds": [c_void_p, c_int, c_int, c_int] + [c_void_p] * 9,
     "xv_chem_simulate": [c_void_p, c_int] + [c_void_p] * 10 + [C.c_double, c_void_p],
+    "xv_chem_optimal": [c_void_p] + [c_int] * 4 + [c_void_p] * 13 + [C.c_double, c_void_p, c_void_p],
     "xv_anyhvac_sampler_check": [c_i64] + [c_int] * 8 + [c_void_p] * 4,
 }
 for _p in ("xv_cartpole", "xv_acrobot"):      # the control families share one set of entry points (csrc/xv_control.h)
@@ -258,6 +259,12 @@ class ChemOut(C.Structure):
     FIELDS = ("final_pool", "consumed", "produced", "byproduct", "gas_lost", "fired", "num_steps", "steps_run", "converged",
               "failure", "failure_step", "final_T", "final_P", "hist_step", "hist_T", "hist_P", "hist_count", "log_step",
               "log_active", "log_T", "log_P", "log_consumed", "log_produced", "log_count")
+    _fields_ = [(k, C.c_void_p) for k in FIELDS]
+
+
+class ChemOptOut(C.Structure):
+    """xv_chem_opt_out (include/xeno.h): device pointers of what xv_chem_optimal writes, each nullable"""
+    FIELDS = ("best_scale", "found", "bits", "yield", "charged", "consumed", "produced", "byproduct", "final_pool", "failure")
     _fields_ = [(k, C.c_void_p) for k in FIELDS]
 
 

@@ -5,12 +5,19 @@
   simulate_chain_reactions(worlds, experiments)    a list of such calls from one launch
   scan(world, amounts, temperatures, durations, equipment, scales)   a Cartesian grid of conditions as one batch
 
-The tool-call shell of the reference (sessions, cost and purification models, world samplers) is not part of this package.
+  compute_optimal_cost(world, ...)                 the reference's ground-truth cost oracle (optimal.py): its signature and dict
+  compute_optimal_costs(worlds, requests), chain_costs, one_pot_costs, ChemVerseOptimal   batches of it and its parts
+
+The tool-call shell of the reference (sessions, perform_reaction, pathway evaluation, world samplers) is not part of this
+package; of its cost and purification models, what the cost oracle calls is (optimal_host.py).
 """
 import numpy as np
 
 from . import tables as T
 from .batch import ChemVerseBatch, prepare_experiments  # noqa: F401
+from .optimal import (ChemVerseOptimal, chain_costs, compute_optimal_cost, compute_optimal_costs,  # noqa: F401
+                      one_pot_costs)
+from .optimal_host import find_reaction_chains, optimal_conditions, yield_threshold  # noqa: F401
 from .host import (FAIL_INIT_P, FAIL_INIT_T, FAIL_NONE, FAIL_RUN_P, FAIL_RUN_T, HISTORY_MAX, LOG_MAX,  # noqa: F401
                    brentq_host, simulate_chain_host, simulate_one)
 from .tables import build_tables  # noqa: F401

@@ -22,6 +22,7 @@ BYPRODUCTS_MAX = 4
 CATALYSTS_MAX = 4
 COEFF_MAX = 8         # largest stoichiometric coefficient
 STEPS_MAX = 4096      # steps per experiment: ceil(duration / step_seconds)
+CHAIN_MAX = 16        # reactions per route of the cost oracle (optimal_host.py, csrc/chemverse_optimal.hip)
 
 # columns of chem_f
 CH_MW, CH_MP, CH_BP, CH_CLAUSIUS, CH_CP, CH_LFUS, CH_LVAP, CH_SOLVENT = range(8)
@@ -44,6 +45,11 @@ EI_SEALED, EI_MODE = range(2)
 EQ_I = 2
 EF_MAX_T, EF_MIN_T, EF_MAX_P, EF_HTC, EF_MAX_HEAT_W, EF_RETENTION = range(6)
 EQ_F = 6
+
+# world_gen/models.py:199-211: a world file's cost_params are laid over these
+DEFAULT_COST_PARAMS = dict(heating_coeff=0.8, cooling_coeff=1.2, heating_exponent=1.5, cooling_exponent=1.3,
+                           pressure_high_coeff=1.5, pressure_low_coeff=1.5, pressure_high_exp=0.7, pressure_low_exp=0.6,
+                           equipment_base=5.0, equipment_pressure_coeff=0.3, duration_coeff=0.05)
 
 THERMAL_MODES = ("isothermal", "adiabatic", "open_air", "heating", "cooling")
 GAS_RETENTION_RATES = {"open_beaker": 0.0, "reflux_condenser": 0.75}      # simulator.py:608-611
@@ -177,7 +183,25 @@ def build_tables(world):
                    GAS_RETENTION_RATES.get(name, 0.0))
     if not np.isfinite(eq_f).all():
         raise ValueError("a ChemVerse world's equipment limits must be finite")
-    return dict(C=C, R=R, E=E, chem_ids=chem_ids, rxn_ids=rxn_ids, equip_names=equip_names,
+    # what the cost oracle reads (optimal_host.py); xv_chem_set_worlds takes none of it.  A missing layer counts as 1, a
+    # missing price is NaN (the reference's None: only layer-1 chemicals are bought)
+    num = lambda v, d: d if v is None else float(v)      # noqa: E731
+    layer = np.array([int(_get(chemicals[c], "layer", 1) or 1) for c in chem_ids], np.int32)
+    price = np.array([num(_get(chemicals[c], "price_per_gram", None), np.nan) for c in chem_ids], np.float64)
+    medicinal = np.array([num(_get(chemicals[c], "medicinal_value", None), np.nan) for c in chem_ids], np.float64)
+    for i, c in enumerate(chem_ids):      # models.py:28: a property of the object, a product of two fields in the JSON
+        if np.isnan(medicinal[i]):
+            medicinal[i] = num(_get(chemicals[c], "medicinal_expected", None), 0.0) * \
+                num(_get(chemicals[c], "medicinal_efficacy", None), 0.0)
+    toxicity = np.array([num(_get(chemicals[c], "base_toxicity", None), 0.0) for c in chem_ids], np.float64)
+    cost_params = dict(DEFAULT_COST_PARAMS)
+    cost_params.update(_get(world, "cost_params", None) or {})
+    eq_cost = np.array([(equipment[n].get("base_cost_per_hour", 0.0), equipment[n].get("cost_multiplier", 1.0))
+                        for n in equip_names], np.float64).reshape(E, 2)
+    return dict(layer=layer, price_per_gram=price, medicinal_value=medicinal, base_toxicity=toxicity,
+                num_layers=int(layer.max()), cost_params=cost_params, base_cost_per_hour=eq_cost[:, 0].copy(),
+                cost_multiplier=eq_cost[:, 1].copy(), chem_names=[str(_get(chemicals[c], "name", c)) for c in chem_ids],
+                C=C, R=R, E=E, chem_ids=chem_ids, rxn_ids=rxn_ids, equip_names=equip_names,
                 equip_specs=[dict(vessel_type=equipment[n]["vessel_type"], thermal_mode=equipment[n]["thermal_mode"],
                                   max_temp_C=equipment[n].get("max_temp_C", 5000.0),
                                   min_temp_C=equipment[n].get("min_temp_C", -273.0),

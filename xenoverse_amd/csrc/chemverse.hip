@@ -257,97 +257,87 @@ __device__ __forceinline__ double chem_phase_heat(const ChemLane& L, double old_
   return heat;
 }
 
-__global__ __launch_bounds__(CHEM_LANES) void chem_simulate_kernel(ChemWorlds W, ChemExp X, ChemOut O, double* __restrict__ ws_acc,
-                                                                   int32_t* __restrict__ ws_fired, uint32_t* err_word) {
-  extern __shared__ double chem_smem[];
-  const int lane = threadIdx.x;
-  const int cs = W.c_stride, rs = W.r_stride;
-  double* s_pool = chem_smem;                                   // [cs][64]
-  double* s_chem = chem_smem + (size_t)cs * CHEM_LANES;         // [8][cs]
-  uint8_t* s_order = reinterpret_cast<uint8_t*>(s_chem + CHEM_F * cs);      // [cs][64]
-  const int exp0 = blockIdx.x * CHEM_LANES;
-  const int e = exp0 + lane;
-  uint32_t err = 0u;
+// ---- one experiment, in the pieces the simulator kernel and the cost oracle's kernel (chemverse_optimal.hip) share ----------
+struct ChemWorldAt {      // a world's place in the concatenated tables
+  int c0, r0, e0, s0, C, R, E;
+};
 
-  // the workgroup's world: that of its first experiment
-  int wb = X.exp_world[exp0];
-  if ((unsigned)wb >= (unsigned)W.n_world) { wb = 0; if (lane == 0) err |= XV_DEVERR_ACTION_RANGE; }
+// the workgroup's world wb: its offsets and sizes, kept inside the strides (else *err is set on lane 0), and its
+// per-chemical table staged into s_chem.  Holds the one barrier: every lane of the workgroup calls it.
+__device__ __forceinline__ ChemWorldAt chem_stage_world(const ChemWorlds& W, int wb, int lane, double* s_chem, uint32_t* err) {
+  const int cs = W.c_stride, rs = W.r_stride;
   const int32_t* wo = W.world_off + 4 * wb;
-  const int c0 = wo[0], r0 = wo[1], e0 = wo[2], s0 = wo[3];
-  int C = wo[4] - c0, R = wo[5] - r0, E = wo[6] - e0;
+  ChemWorldAt A;
+  A.c0 = wo[0]; A.r0 = wo[1]; A.e0 = wo[2]; A.s0 = wo[3];
+  int C = wo[4] - A.c0, R = wo[5] - A.r0, E = wo[6] - A.e0;
   if (C < 1 || C > cs || C > XV_CHEM_C_MAX || R < 0 || R > rs || E < 1) {
-    if (lane == 0) err |= XV_DEVERR_ACTION_RANGE;
+    if (lane == 0) *err |= XV_DEVERR_ACTION_RANGE;
     C = C < 1 ? 1 : (C > cs ? cs : C);
     if (C > XV_CHEM_C_MAX) C = XV_CHEM_C_MAX;
     R = R < 0 ? 0 : (R > rs ? rs : R);
     if (E < 1) E = 1;
   }
+  A.C = C; A.R = R; A.E = E;
   for (int i = lane; i < CHEM_F * cs; i += CHEM_LANES) {
     const int k = i / cs, c = i - k * cs;
-    s_chem[i] = c < C ? W.chem_f[(size_t)(c0 + c) * CHEM_F + k] : 0.0;
+    s_chem[i] = c < C ? W.chem_f[(size_t)(A.c0 + c) * CHEM_F + k] : 0.0;
   }
   __syncthreads();
+  return A;
+}
 
-  bool active = e < X.n_exp;
-  if (active) {
-    const int w = X.exp_world[e];
-    if (w < 0) active = false;      // a padding lane
-    else if (w != wb) { active = false; err |= XV_DEVERR_ACTION_RANGE; }      // the caller groups experiments by world
-  }
-  if (!active) {
-    if (err) atomicOr(err_word, err);
-    return;      // no barrier follows
-  }
+#define CHEM_ACCUM(a, c) acc[((size_t)(a) * cs + (c)) * CHEM_LANES]      // of the names acc and cs where it is used
 
-  ChemLane L;
-  L.pool = s_pool + lane;
-  L.order = s_order + lane;
-  L.chem = s_chem;
-  L.cs = cs;
-  L.C = C;
+// an empty pool and zeroed accumulators
+__device__ __forceinline__ void chem_lane_clear(ChemLane& L, uint64_t* member, double* acc, int32_t* fired, int R) {
+  const int cs = L.cs;
   L.n_order = 0;
-  double* acc = ws_acc + (size_t)blockIdx.x * CHEM_ACC * cs * CHEM_LANES + lane;      // array a, chemical c: acc[(a * cs + c) * 64]
-  int32_t* fired = ws_fired + (size_t)blockIdx.x * rs * CHEM_LANES + lane;
-#define CHEM_ACCUM(a, c) acc[((size_t)(a) * cs + (c)) * CHEM_LANES]
-  for (int c = 0; c < C; ++c) {
+  *member = 0ull;
+  for (int c = 0; c < L.C; ++c) {
     CHEM_POOL(L, c) = 0.0;
 #pragma unroll
     for (int a = 0; a < CHEM_ACC; ++a) CHEM_ACCUM(a, c) = 0.0;
   }
   for (int r = 0; r < R; ++r) fired[r * CHEM_LANES] = 0;
+}
 
-  // the experiment
-  double T = X.T[e], P = X.P[e];
-  const double duration = X.duration[e], rate = X.heating_rate[e], volume = X.volume[e];
+// one entry of the initial amounts (:668-671): c is inside the world, g finite
+__device__ __forceinline__ void chem_lane_charge(ChemLane& L, uint64_t* member, int c, double g) {
+  if (((*member >> c) & 1ull) || !(g > 1e-9)) return;
+  CHEM_POOL(L, c) = g;
+  L.order[L.n_order * CHEM_LANES] = (uint8_t)c;
+  ++L.n_order;
+  *member |= 1ull << c;
+}
+
+struct ChemRun {      // in: the conditions; out: the run's scalars (T, P become the final ones)
+  double T, P, duration, rate, volume;
+  int eq;
+  int num_steps, steps_run, failure, failure_step, converged_steps, hist_count, log_count;
+};
+
+// simulate_chain_reaction :673-843 for the charged lane.  The totals are left in the accumulators 3..6 and the pool in L;
+// history and log rows go to O at experiment e where O has them.
+__device__ __forceinline__ void chem_lane_run(const ChemWorlds& W, const ChemWorldAt& A, ChemLane& L, uint64_t member,
+                                              double* acc, int32_t* fired, double step_seconds, ChemRun& X, const ChemOut& O,
+                                              int e, uint32_t* errp) {
+  const int cs = L.cs, C = A.C, R = A.R, r0 = A.r0, e0 = A.e0, s0 = A.s0;
+  uint32_t err = 0u;
+  double T = X.T, P = X.P;
+  const double duration = X.duration, rate = X.rate, volume = X.volume;
   if (!(isfinite(T) && isfinite(P) && isfinite(duration) && isfinite(rate) && isfinite(volume))) err |= XV_DEVERR_NONFINITE;
-  int eq = X.equipment[e];
-  if ((unsigned)eq >= (unsigned)E) { err |= XV_DEVERR_ACTION_RANGE; eq = 0; }
+  int eq = X.eq;
+  if ((unsigned)eq >= (unsigned)A.E) { err |= XV_DEVERR_ACTION_RANGE; eq = 0; }
   const int sealed = W.eq_i[(size_t)(e0 + eq) * 2], mode = W.eq_i[(size_t)(e0 + eq) * 2 + 1];
   const double* ef = W.eq_f + (size_t)(e0 + eq) * 6;
   const double max_T = ef[0], min_T = ef[1], max_P = ef[2], htc = ef[3], max_heat_W = ef[4], retention = ef[5];
   const double T_init = T, P_init = P;
 
-  uint64_t member = 0ull;
-  int n_init = X.n_initial[e];
-  if (n_init < 0 || n_init > cs) { err |= XV_DEVERR_ACTION_RANGE; n_init = n_init < 0 ? 0 : cs; }
-  for (int i = 0; i < n_init; ++i) {      // :668-671
-    const int c = X.order[(size_t)e * cs + i];
-    if ((unsigned)c >= (unsigned)C) { err |= XV_DEVERR_ACTION_RANGE; continue; }
-    if ((member >> c) & 1ull) continue;
-    const double g = X.amounts[(size_t)e * cs + c];
-    if (!isfinite(g)) { err |= XV_DEVERR_NONFINITE; continue; }
-    if (g > 1e-9) {
-      CHEM_POOL(L, c) = g;
-      L.order[L.n_order * CHEM_LANES] = (uint8_t)c;
-      ++L.n_order;
-      member |= 1ull << c;
-    }
-  }
   L.T = T;
   L.logP = log(fmax(0.01, P));
   const double initial_gas_moles = chem_gas_moles(L);
 
-  double steps_f = ceil(duration / X.step_seconds);      // :683-684
+  double steps_f = ceil(duration / step_seconds);      // :683-684
   int num_steps = steps_f >= 1.0 ? (steps_f <= (double)XV_CHEM_STEPS_MAX ? (int)steps_f : XV_CHEM_STEPS_MAX + 1) : 1;
   if (num_steps > XV_CHEM_STEPS_MAX) { err |= XV_DEVERR_ACTION_RANGE; num_steps = XV_CHEM_STEPS_MAX; }
   const double dt = duration / (double)num_steps;
@@ -654,6 +644,71 @@ __global__ __launch_bounds__(CHEM_LANES) void chem_simulate_kernel(ChemWorlds W,
       ++log_count;
     }
   }
+  X.T = T; X.P = P;
+  X.num_steps = num_steps; X.steps_run = steps_run; X.failure = failure; X.failure_step = failure_step;
+  X.converged_steps = converged_steps; X.hist_count = hist_count; X.log_count = log_count;
+  *errp |= err;
+}
+
+// static: chemverse_optimal.hip includes this file, and the kernel is no template
+static __global__ __launch_bounds__(CHEM_LANES) void chem_simulate_kernel(ChemWorlds W, ChemExp X, ChemOut O,
+                                                                          double* __restrict__ ws_acc,
+                                                                          int32_t* __restrict__ ws_fired, uint32_t* err_word) {
+  extern __shared__ double chem_smem[];
+  const int lane = threadIdx.x;
+  const int cs = W.c_stride, rs = W.r_stride;
+  double* s_pool = chem_smem;                                   // [cs][64]
+  double* s_chem = chem_smem + (size_t)cs * CHEM_LANES;         // [8][cs]
+  uint8_t* s_order = reinterpret_cast<uint8_t*>(s_chem + CHEM_F * cs);      // [cs][64]
+  const int exp0 = blockIdx.x * CHEM_LANES;
+  const int e = exp0 + lane;
+  uint32_t err = 0u;
+
+  // the workgroup's world: that of its first experiment
+  int wb = X.exp_world[exp0];
+  if ((unsigned)wb >= (unsigned)W.n_world) { wb = 0; if (lane == 0) err |= XV_DEVERR_ACTION_RANGE; }
+  const ChemWorldAt A = chem_stage_world(W, wb, lane, s_chem, &err);
+  const int C = A.C, R = A.R;
+
+  bool active = e < X.n_exp;
+  if (active) {
+    const int w = X.exp_world[e];
+    if (w < 0) active = false;      // a padding lane
+    else if (w != wb) { active = false; err |= XV_DEVERR_ACTION_RANGE; }      // the caller groups experiments by world
+  }
+  if (!active) {
+    if (err) atomicOr(err_word, err);
+    return;      // no barrier follows
+  }
+
+  ChemLane L;
+  L.pool = s_pool + lane;
+  L.order = s_order + lane;
+  L.chem = s_chem;
+  L.cs = cs;
+  L.C = C;
+  double* acc = ws_acc + (size_t)blockIdx.x * CHEM_ACC * cs * CHEM_LANES + lane;      // array a, chemical c: acc[(a * cs + c) * 64]
+  int32_t* fired = ws_fired + (size_t)blockIdx.x * rs * CHEM_LANES + lane;
+  uint64_t member;
+  chem_lane_clear(L, &member, acc, fired, R);
+
+  int n_init = X.n_initial[e];
+  if (n_init < 0 || n_init > cs) { err |= XV_DEVERR_ACTION_RANGE; n_init = n_init < 0 ? 0 : cs; }
+  for (int i = 0; i < n_init; ++i) {      // :668-671
+    const int c = X.order[(size_t)e * cs + i];
+    if ((unsigned)c >= (unsigned)C) { err |= XV_DEVERR_ACTION_RANGE; continue; }
+    if ((member >> c) & 1ull) continue;
+    const double g = X.amounts[(size_t)e * cs + c];
+    if (!isfinite(g)) { err |= XV_DEVERR_NONFINITE; continue; }
+    chem_lane_charge(L, &member, c, g);
+  }
+  ChemRun run;
+  run.T = X.T[e]; run.P = X.P[e]; run.duration = X.duration[e]; run.rate = X.heating_rate[e]; run.volume = X.volume[e];
+  run.eq = X.equipment[e];
+  chem_lane_run(W, A, L, member, acc, fired, X.step_seconds, run, O, e, &err);
+  const double T = run.T, P = run.P;
+  const int num_steps = run.num_steps, steps_run = run.steps_run, failure = run.failure, failure_step = run.failure_step,
+            converged_steps = run.converged_steps, hist_count = run.hist_count, log_count = run.log_count;
 
   // results
   const bool destroyed = failure != 0;
@@ -705,11 +760,7 @@ __global__ __launch_bounds__(CHEM_LANES) void chem_simulate_kernel(ChemWorlds W,
     O.log_count[e] = log_count;
   }
   if (err) atomicOr(err_word, err);
-#undef CHEM_ACCUM
 }
-
-#ifndef XV_KERNELS_ONLY
-#include <new>
 
 struct xv_chem {
   xv_engine* eng;
@@ -719,7 +770,13 @@ struct xv_chem {
   int blocks;          // workgroups the workspace serves
   double* ws_acc;      // [blocks][7][c_stride][64]
   int32_t* ws_fired;   // [blocks][r_stride][64]
+  double* ws_opt;      // the cost oracle's (chemverse_optimal.hip), made by its first call: the virtual pool
+                       // [blocks][c_stride][64], then lo, hi, best [blocks * 64] each
+  uint32_t* ws_opt_bits;      // [blocks * 64][2]: the decision bits, found
 };
+
+#ifndef XV_KERNELS_ONLY      // chemverse_optimal.hip includes this file for its kernels and handle type only
+#include <new>
 
 extern "C" int xv_chem_create(xv_engine* e, int n_exp_capacity, xv_chem** out) {
   XV_CHECK_ARG(out != nullptr);
@@ -742,6 +799,8 @@ extern "C" int xv_chem_create(xv_engine* e, int n_exp_capacity, xv_chem** out) {
   h->blocks = 0;
   h->ws_acc = nullptr;
   h->ws_fired = nullptr;
+  h->ws_opt = nullptr;
+  h->ws_opt_bits = nullptr;
   *out = h;
   return XV_OK;
 }
@@ -749,8 +808,12 @@ extern "C" int xv_chem_create(xv_engine* e, int n_exp_capacity, xv_chem** out) {
 static void chem_free_workspace(xv_chem* h) {
   if (h->ws_acc) (void)hipFree(h->ws_acc);
   if (h->ws_fired) (void)hipFree(h->ws_fired);
+  if (h->ws_opt) (void)hipFree(h->ws_opt);
+  if (h->ws_opt_bits) (void)hipFree(h->ws_opt_bits);
   h->ws_acc = nullptr;
   h->ws_fired = nullptr;
+  h->ws_opt = nullptr;
+  h->ws_opt_bits = nullptr;
   h->blocks = 0;
 }
 
